@@ -26,8 +26,12 @@ steady state; a FIXED, untimed prologue of ``--prewarm`` launches of the same ke
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline     — algorithmic fp64 flops per launch / measured kernel duration vs the fp64 MFMA peak
-  cpu_baseline — the CPU oracle (oracle/gp_oracle.py, the reference's op sequence in torch fp64)
-                 timed on this box's host cores on a bounded sample of the same workload.
+                 (from the timed region's own events: no run of its own)
+  cpu_baseline — only with ``--full``: the CPU oracle (oracle/gp_oracle.py, the reference's op sequence in
+                 torch fp64) timed on this box's host cores on a bounded sample of the same workload (~25 s).
+A plain run (no ``--full``) does only what the headline figure needs: set-up, prologue, warm-up, the timed steps,
+the result line.  ``--dump-outputs DIR`` writes what the last timed step returned to its caller as .npy files
+(``dump_outputs``); the inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -95,6 +99,35 @@ def make_inputs(rank: int, device, T: int = T_PER_GPU):
     y = torch.from_numpy(ys)
     th = torch.from_numpy(theta)
     return (X, y, th), (X.to(device), y.to(device), th.to(device))
+
+
+DUMP_L_TASKS = 64   # L is T x N x N doubles (128 MiB at T = N = 256): the factors of a fixed, seeded sample of tasks are written
+
+
+def dump_tasks(T: int):
+    """The tasks whose dense factor ``dump_outputs`` writes: DUMP_L_TASKS of the T, drawn with a fixed seed, in increasing order."""
+    import numpy as np
+
+    return np.sort(np.random.default_rng(0).choice(T, min(T, DUMP_L_TASKS), replace=False))
+
+
+def dump_outputs(path: str, o, grad=None) -> None:
+    """Write what one step returned to its caller (``o``: the dict of ops.gp_fit_fused; ``grad``: ops.mll_backward's
+    per-task gradient with --step fit+grad) as float64 .npy files under ``path``: mll, quad, logdet, jitter, info,
+    alpha for every task; L (and Linv_diag with a gradient) for the tasks of ``dump_tasks`` as L_sample
+    (Linv_diag_sample); grad.  At the bench shape ~34 MB (~36 MB with a gradient)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    idx = torch.from_numpy(dump_tasks(int(o["mll"].shape[0]))).to(o["L"].device)
+    arrays = {k: o[k] for k in ("mll", "quad", "logdet", "jitter", "info", "alpha")}
+    arrays["L_sample"] = o["L"].index_select(0, idx)
+    if grad is not None:
+        arrays["Linv_diag_sample"] = o["Linv_diag"].index_select(0, idx)
+        arrays["grad"] = grad
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.detach().cpu().numpy().astype(np.float64))
 
 
 # ---- CPU baseline ------------------------------------------------------------------------------------
@@ -237,6 +270,10 @@ def launch_ranks(args) -> int:
            "--prewarm", str(args.prewarm), "--total-tasks", str(args.total_tasks)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
     line = None
     for ln in res.stdout.splitlines():
@@ -263,8 +300,14 @@ def main():
     ap.add_argument("--total-tasks", type=int, default=0,
                     help="strong scaling: this many tasks IN ALL, sharded over the ranks (1024 = BASELINE configs[3]); "
                          "0 = weak scaling, 256 tasks per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (cpu_baseline, ~25 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's tasks) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.prewarm < 0:
+        ap.error("--steps must be >= 1, --warmup and --prewarm >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -325,13 +368,15 @@ def main():
     fused = torch.zeros(rows + DIM + 2, dtype=torch.float64, device=device)
     grad_acc = fused[rows:]
     works = []
+    last_grad = [None]   # the per-task gradient of the latest step (--dump-outputs)
 
     def step(i):
         o = out_g if with_grad else out
         o["mll"] = mll_rows[i]
         ops.gp_fit_fused(X, y, th, kind, out=o, zero_upper=True, want_linv=with_grad)   # the full dense L, zeros included, every step
         if with_grad:
-            grad_acc.add_(ops.mll_backward(X, th, kind, o["L"], o["Linv_diag"], o["alpha"], workspace=gws).sum(0))
+            last_grad[0] = ops.mll_backward(X, th, kind, o["L"], o["Linv_diag"], o["alpha"], workspace=gws)
+            grad_acc.add_(last_grad[0].sum(0))
 
     def reduce_region(k):
         """The region's exchange step: the per-step MLL sums go next to the gradient sums, the fused buffer goes through
@@ -394,6 +439,9 @@ def main():
         elapsed = float(tmax.item())
     ok = not bool(out["info"].any().item())
     reduced = fused.cpu()
+    if args.dump_outputs and rank == 0:
+        # after the timed region: its reduce reads the MLL rows only, so these buffers hold the last step's outputs
+        dump_outputs(args.dump_outputs, out_g if with_grad else out, last_grad[0] if with_grad else None)
 
     if rank == 0:
         flops = algorithmic_flops_per_task(N_POINTS, DIM, True) * T_loc
@@ -439,7 +487,7 @@ def main():
                 "algorithmic_bytes_per_launch": algorithmic_bytes_per_task(N_POINTS, DIM) * T_loc,
             },
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(host_inputs)
         print(json.dumps(res), flush=True)
     if distributed:

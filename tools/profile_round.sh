@@ -7,7 +7,7 @@ R=${1:-r03}
 OUT=$PWD/gpurun_out/$R
 mkdir -p $OUT
 export TMPDIR=/tmp
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"; cat $OUT/bench.json
 stats() {   # name, program args...
   local name=$1; shift
