@@ -281,6 +281,25 @@ int scaml_target_posterior_grad_f64(const double* cov_g, const double* mu_g, con
                                     int Mq, int D, int kind, double* dmu, double* dvar, void* stream);
 
 /*
+ * (7f) The acquisition function of a FANTASY model (ScaMLGP.fantasize: the target GP conditioned on p pending points with F sampled
+ * outcomes each; Monte-Carlo integration over the pending evaluations) in place of (7)'s finish and (5d)'s target gradient:
+ *   mu_f[q]  = m + s (mean_q[q] + Knq[:, q] . alpha[:, f])             f = 0 .. F-1, alpha (n, F) = Knn^-1 [r_0 .. r_{F-1}]
+ *   v[q]     = s^2 (var_q[q] - Knq[:, q] . Z[:, q] + noise_add)         (shared by all fantasies)
+ *   value[q] = (1/F) sum_f A(mu_f[q], v[q])
+ * acqf 0: UCB, A = -mu + sqrt(beta max(v, 0)), acqf_param = beta; acqf 1: EI (minimisation), sigma = sqrt(max(v, 1e-9)),
+ * u = -(mu - best_f) / sigma, A = sigma (phi(u) + u Phi(u)), acqf_param = best_f.  Knq, Z (n, M), mean_q, var_q (M) as in (7).
+ * grad (M, D) or NULL: d value / d x_q from the GRAD pass's weighted sums (cov_g (n, M * 16), mu_g / var_g (M * 16)), the training
+ * inputs Xt (n, D), the queries Xq (M, D) and the target kernel theta (D + 2) of family `kind`, as (5d) takes them; the gradient
+ * contracts over the training points once per query with abar = sum_f dA/dmu_f alpha[:, f].  info (1) int32 or NULL: a factorisation
+ * that failed even with jitter turns every output into NaN.  One wave per query point, no host synchronisation.
+ * Limits: F <= 64, n <= scaml_fit_max_n(); with grad also n <= 96 and D <= 15.  SCAML_E_TOOLARGE beyond them.
+ */
+int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q,
+                                  double m_all, double s_all, double noise_add, const int32_t* info, int acqf, double acqf_param,
+                                  const double* cov_g, const double* mu_g, const double* var_g, const double* Xt, const double* Xq,
+                                  const double* theta, int n, int M, int F, int D, int kind, double* value, double* grad, void* stream);
+
+/*
  * (8) The target GP's training objective with its analytic gradient, and the whole refit, in ONE launch.
  * Replaces what the reference runs on every report(): scamlgp/optimizer.py:176-185 rebuilds ScaMLGP and calls
  * optimize_marginal_likelihood (scamlgp/utils.py:139-212), which drives scipy L-BFGS-B through torch autograd over

@@ -17,6 +17,7 @@
 #include "gp_fit_params.h"
 #include "gp_posterior_params.h"
 #include "gp_target_params.h"
+#include "gp_fantasy_params.h"
 #include <math.h>
 
 extern "C" const unsigned char scaml_hsaco_blob[];   // generated: lib/hsaco_blob.c
@@ -59,6 +60,7 @@ struct Module {
   hipFunction_t tgt_finish = nullptr;
   hipFunction_t tgt_fit = nullptr;
   hipFunction_t tgt_grad[2] = {nullptr, nullptr};
+  hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {nullptr, nullptr};   // value only; value + gradient per kind
   hipFunction_t blk_round = nullptr, blk_finish = nullptr;
   hipFunction_t coop[2] = {nullptr, nullptr};
   hipFunction_t blk_solve[2][2] = {}, blk_syrk[2] = {nullptr, nullptr};   // solve: [kind][D <= 8]
@@ -134,6 +136,9 @@ struct Module {
       if ((e = hipModuleGetFunction(&tgt_grad[kind], mod, name)) != hipSuccess) return e;
     }
     if ((e = hipModuleGetFunction(&tgt_finish, mod, "scaml_target_finish_kernel")) != hipSuccess) return e;
+    if ((e = hipModuleGetFunction(&tgt_fantasy, mod, "scaml_target_fantasy_acqf_kernel")) != hipSuccess) return e;
+    if ((e = hipModuleGetFunction(&tgt_fantasy_grad[0], mod, "scaml_target_fantasy_acqf_grad_rbf_kernel")) != hipSuccess) return e;
+    if ((e = hipModuleGetFunction(&tgt_fantasy_grad[1], mod, "scaml_target_fantasy_acqf_grad_matern_kernel")) != hipSuccess) return e;
     if ((e = hipModuleGetFunction(&tgt_fit, mod, "scaml_target_fit_kernel")) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)tgt_fit, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     for (int kind = 0; kind < 2; ++kind) {
@@ -798,6 +803,35 @@ int scaml_target_posterior_grad_f64(const double* cov_g, const double* mu_g, con
   if (D > 15) return SCAML_E_TOOLARGE;
   e = hipModuleLaunchKernel(m.tgt_grad[kind], (unsigned)Mq, 1, 1, 64, 1, 1, 0, (hipStream_t)stream, args, nullptr);   // one wave per query point
   if (e != hipSuccess) { set_error("hipModuleLaunchKernel(target_grad)", e); return SCAML_E_LAUNCH; }
+  return SCAML_OK;
+}
+
+// ---- (7f) fantasy model: acquisition value (+ input gradient) averaged over the fantasies (csrc/gp_fantasy.hip) ---------------
+int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q,
+                                  double m_all, double s_all, double noise_add, const int32_t* info, int acqf, double acqf_param,
+                                  const double* cov_g, const double* mu_g, const double* var_g, const double* Xt, const double* Xq,
+                                  const double* theta, int n, int M, int F, int D, int kind, double* value, double* grad, void* stream) {
+  if (n < 1 || M < 0 || F < 1) return SCAML_E_BADARG;
+  if (!Knq || !Z || !alpha || !mean_q || !var_q || !value) return SCAML_E_BADARG;
+  if (acqf != 0 && acqf != 1) return SCAML_E_BADARG;
+  if (!(s_all > 0.0)) return SCAML_E_BADARG;
+  if (grad) {
+    if (D < 1 || !cov_g || !mu_g || !var_g || !Xt || !Xq || !theta) return SCAML_E_BADARG;
+    if (kind != SCAML_KIND_RBF && kind != SCAML_KIND_MATERN52) return SCAML_E_BADARG;
+  }
+  if (F > scaml::FANTASY_MAX_F || n > scaml::FANTASY_MAX_N) return SCAML_E_TOOLARGE;
+  if (grad && (n > scaml::FANTASY_GRAD_MAX_N || D > scaml::FANTASY_GRAD_MAX_D)) return SCAML_E_TOOLARGE;
+  if (M == 0) return SCAML_OK;
+  Module& m = module();
+  hipError_t e = m.load();
+  if (e != hipSuccess) { set_error("loading the gfx950 code object", e); return SCAML_E_LAUNCH; }
+  scaml::FantasyAcqfParams p{Knq, Z, alpha, mean_q, var_q, m_all, s_all, noise_add, info, acqf_param, cov_g, mu_g, var_g, Xt, Xq, theta,
+                             value, grad, n, M, F, grad ? D : 0, acqf, 0};
+  size_t psize = sizeof(p);
+  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &psize, HIP_LAUNCH_PARAM_END};
+  // one wave per query point
+  e = hipModuleLaunchKernel(grad ? m.tgt_fantasy_grad[kind] : m.tgt_fantasy, (unsigned)M, 1, 1, 64, 1, 1, 0, (hipStream_t)stream, nullptr, config);
+  if (e != hipSuccess) { set_error("hipModuleLaunchKernel(target_fantasy_acqf)", e); return SCAML_E_LAUNCH; }
   return SCAML_OK;
 }
 

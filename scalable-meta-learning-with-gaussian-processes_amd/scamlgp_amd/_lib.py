@@ -123,6 +123,9 @@ def _load() -> ctypes.CDLL:
     lib.scaml_posterior_linv_grad_f64.argtypes = [_dp] * 10 + [c_int] * 6 + [_dp, _dp, _dp, ctypes.c_uint, c_void_p]
     lib.scaml_target_posterior_grad_f64.restype = c_int
     lib.scaml_target_posterior_grad_f64.argtypes = [_dp] * 8 + [c_double, _dp, c_int, c_int, c_int, c_int, _dp, _dp, c_void_p]
+    lib.scaml_target_fantasy_acqf_f64.restype = c_int
+    lib.scaml_target_fantasy_acqf_f64.argtypes = ([_dp] * 5 + [c_double, c_double, c_double, _dp, c_int, c_double] + [_dp] * 6
+                                                  + [c_int] * 5 + [_dp, _dp, c_void_p])
     lib.scaml_target_fit_max_n.restype = c_int
     lib.scaml_target_fit_max_n.argtypes = [c_int, c_int]
     lib.scaml_target_fit_max_d.restype = c_int
@@ -178,6 +181,7 @@ EXPORTED_SYMBOLS = (
     "scaml_target_finish_f64",
     "scaml_posterior_linv_grad_f64",
     "scaml_target_posterior_grad_f64",
+    "scaml_target_fantasy_acqf_f64",
     "scaml_target_fit_max_n",
     "scaml_target_fit_max_d",
     "scaml_target_fit_workspace_doubles",

@@ -10,10 +10,15 @@ two things ``scamlgp/optimizer.py`` does with the model:
 The acquisition optimiser follows botorch's ``optimize_acqf`` recipe -- ``raw_samples`` random candidates, ``num_restarts``
 initial conditions drawn from them (the best one plus a Boltzmann sample of the rest), box-constrained L-BFGS-B over all
 starts jointly, best end point wins -- with exact gradients from the posterior's input-gradient kernels (round 3;
-central differences where they do not apply)."""
+central differences where they do not apply).
+
+Parallel evaluations (``max_pending_evaluations``, scamlgp/optimizer.py:41, 106, 149): points handed out by ``suggest()`` and not yet
+reported are pending; the acquisition function is then built on ``model.fantasize(pending, num_fantasies)`` and averages over the
+fantasised outcomes.  A ``report()`` without an objective value (None / NaN) keeps the point in ``X`` / ``Y`` and out of the fit
+(scamlgp/optimizer.py:169-173)."""
 from __future__ import annotations
 
-from typing import Callable, Dict, Hashable, Optional, Tuple
+from typing import Callable, Dict, Hashable, Optional, Sequence, Tuple, Union
 
 import math
 
@@ -24,6 +29,11 @@ import torch
 from . import hyper
 from .model import ScaMLGP, SourceGP
 from .utils import ExpectedImprovement, UpperConfidenceBound, optimize_marginal_likelihood
+
+
+class OptimizerNotReady(RuntimeError):
+    """``suggest()`` while ``max_pending_evaluations`` points are pending (blackboxopt's exception of the same name): report one
+    first."""
 
 
 class GraphedAcquisition:
@@ -125,7 +135,16 @@ class ScaMLGPBOLoop:
     def __init__(self, source_gps: Dict[Hashable, SourceGP], dim: int, acquisition: str = "ucb", beta: float = 9.0,
                  num_restarts_log_likelihood: int = 5, raw_samples: int = 1024, num_restarts: int = 10, af_max_iter: int = 50,
                  gp_likelihood: Optional[hyper.GaussianLikelihood] = None, gp_kernel: Optional[hyper.ScaleKernel] = None,
-                 seed: Optional[int] = None, use_graph: bool = True):
+                 seed: Optional[int] = None, use_graph: bool = True, max_pending_evaluations: Optional[int] = None,
+                 num_fantasies: int = 16):
+        """``max_pending_evaluations``: None (default) -- strictly suggest -> report, no bookkeeping; an integer k -- ``suggest()``
+        records its point in ``pending`` until it is reported, raises OptimizerNotReady while k points are pending, and builds the
+        acquisition function on ``num_fantasies`` fantasies of the pending outcomes (ScaMLGP.fantasize, base samples from ``gen``)."""
+        if max_pending_evaluations is not None and int(max_pending_evaluations) < 1:
+            raise ValueError("max_pending_evaluations must be None or a positive integer")
+        self.max_pending_evaluations = None if max_pending_evaluations is None else int(max_pending_evaluations)
+        self.num_fantasies = int(num_fantasies)
+        self.pending = torch.empty(0, dim, dtype=torch.float64)
         self.source_gps, self.dim = source_gps, dim
         self.acquisition, self.beta = acquisition, beta
         self.num_restarts_log_likelihood = num_restarts_log_likelihood
@@ -137,13 +156,34 @@ class ScaMLGPBOLoop:
         # scamlgp/optimizer.py:142-148: the model before any evaluation (prior only)
         self.model = ScaMLGP(self.X, self.Y, source_gps, likelihood=gp_likelihood, covar_module=gp_kernel)
 
-    def report(self, x: torch.Tensor, y: float) -> None:
-        self.X = torch.cat([self.X, torch.as_tensor(x, dtype=torch.float64).reshape(1, -1)], 0)
-        self.Y = torch.cat([self.Y, torch.tensor([[float(y)]], dtype=torch.float64)], 0)
+    def report(self, x: torch.Tensor, y: Union[float, None, Sequence[Optional[float]], torch.Tensor]) -> None:
+        """Record evaluations and refit once: x (D,) with y a float, or x (q, D) with y (q,).  A y of None or NaN keeps the point in
+        ``X`` / ``Y`` (as NaN) and out of the model's training set.  A reported point leaves ``pending`` (its first equal row, if any);
+        reporting a point that was never suggested is allowed."""
+        xs = torch.as_tensor(x, dtype=torch.float64).reshape(-1, self.dim)
+        if y is None or np.ndim(y) == 0:
+            ys = [y]
+        elif isinstance(y, torch.Tensor):
+            ys = y.detach().cpu().reshape(-1).tolist()
+        else:
+            ys = list(np.asarray(y, dtype=object).reshape(-1))
+        if len(ys) != xs.shape[0]:
+            raise ValueError(f"report() got {xs.shape[0]} points and {len(ys)} objective values")
+        yv = torch.tensor([[float("nan") if v is None else float(v)] for v in ys], dtype=torch.float64)
+        for row in xs:
+            hit = torch.nonzero((self.pending == row).all(-1)).flatten()
+            if hit.numel():
+                keep = torch.ones(self.pending.shape[0], dtype=torch.bool)
+                keep[int(hit[0])] = False
+                self.pending = self.pending[keep]
+        self.X = torch.cat([self.X, xs], 0)
+        self.Y = torch.cat([self.Y, yv], 0)
+        ok = torch.isfinite(self.Y).squeeze(-1)
         # scamlgp/optimizer.py:176-185, same call sequence: the fitted modules go back in, the weights restart at 1/T
+        # (evaluations without an objective value stay out of the fit, scamlgp/optimizer.py:169-173)
         self.model = ScaMLGP(
-            self.X,
-            self.Y,
+            self.X if bool(ok.all()) else self.X[ok],
+            self.Y if bool(ok.all()) else self.Y[ok],
             self.source_gps,
             likelihood=self.model.likelihood,
             covar_module=self.model.covar_module,
@@ -151,18 +191,27 @@ class ScaMLGPBOLoop:
         optimize_marginal_likelihood(self.model, self.num_restarts_log_likelihood)
 
     def acquisition_function(self) -> Callable[[torch.Tensor], torch.Tensor]:
+        model = self.model
+        if self.max_pending_evaluations is not None and self.pending.shape[0] > 0:
+            model = self.model.eval().fantasize(self.pending, self.num_fantasies, generator=self.gen)
         if self.acquisition == "ei":
-            if self.Y.numel() == 0:
+            Yf = self.Y[torch.isfinite(self.Y)]
+            if Yf.numel() == 0:
                 raise ValueError("EI needs at least one evaluation")
-            return ExpectedImprovement(self.model, float(self.Y.min()))
-        return UpperConfidenceBound(self.model, self.beta)
+            return ExpectedImprovement(model, float(Yf.min()))
+        return UpperConfidenceBound(model, self.beta)
 
     def suggest(self) -> torch.Tensor:
+        k = self.max_pending_evaluations
+        if k is not None and self.pending.shape[0] >= k:
+            raise OptimizerNotReady(f"{self.pending.shape[0]} evaluations are pending (max_pending_evaluations={k}): report one first")
         self.model.eval()
+        af = self.acquisition_function()
         # (the graph path needs training data on the model: the prior-only model takes the torch branch of posterior())
-        dev = self.model.device if (self.use_graph and self.model.n >= 1) else None
-        x, _ = optimize_acqf(self.acquisition_function(), self.dim, self.raw_samples, self.num_restarts, self.af_max_iter, self.gen,
-                             graph_device=dev)
+        dev = af.model.device if (self.use_graph and af.model.n >= 1) else None
+        x, _ = optimize_acqf(af, self.dim, self.raw_samples, self.num_restarts, self.af_max_iter, self.gen, graph_device=dev)
+        if k is not None:
+            self.pending = torch.cat([self.pending, x.reshape(1, -1)], 0)
         return x
 
     def run(self, objective: Callable[[torch.Tensor], float], n_steps: int):

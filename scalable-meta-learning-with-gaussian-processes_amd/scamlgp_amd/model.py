@@ -15,6 +15,7 @@ by the eval-mode value the reference happens to compute (``scamlgp/utils.py:176-
 """
 from __future__ import annotations
 
+import copy
 import math
 import warnings
 from dataclasses import dataclass
@@ -455,6 +456,16 @@ class TargetPosterior:
     mean = property(lambda self: self.mvn.mean.unsqueeze(-1))
     variance = property(lambda self: self.mvn.variance.unsqueeze(-1))
 
+    def rsample(self, sample_shape: torch.Size = torch.Size(), generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """Joint samples ``(*sample_shape, *batch, M, 1)``: mean + L eps with L the jittered Cholesky of ``.mvn.covariance_matrix``
+        (psd_safe_cholesky) and eps standard normal base samples drawn from ``generator`` (on the generator's device; default:
+        torch's global one on the CPU), so that a seeded generator reproduces the samples."""
+        mean = self.mvn.mean
+        L = psd_safe_cholesky(self.mvn.covariance_matrix)
+        gdev = generator.device if generator is not None else torch.device("cpu")
+        eps = torch.randn(*torch.Size(sample_shape), *mean.shape, dtype=torch.float64, generator=generator, device=gdev).to(mean.device)
+        return (mean + (L @ eps.unsqueeze(-1)).squeeze(-1)).unsqueeze(-1)
+
 
 class ScaMLGP:
     """Scalable meta-learning GP (scamlgp/model.py:218-384): target prior
@@ -468,7 +479,7 @@ class ScaMLGP:
 
     def __init__(self, train_X: torch.Tensor, train_Y: torch.Tensor, source_gps: Dict[Hashable, SourceGP],
                  likelihood: Optional[hyper.GaussianLikelihood] = None, covar_module: Optional[hyper.ScaleKernel] = None,
-                 weight_pruning_threshold: float = 1e-3) -> None:
+                 weight_pruning_threshold: float = 1e-3, _fixed_transform: Optional[tuple] = None) -> None:
         self._weight_pruning_threshold = weight_pruning_threshold
         self.source_gps = source_gps
         gps = list(source_gps.values())
@@ -486,13 +497,17 @@ class ScaMLGP:
         self.likelihood, self.covar_module = lik.to(dev), cov.to(dev)
         self.kind = cov.kind
         self.spec = hyper.spec_from_modules(lik, cov)
-        # standardise w.r.t. ALL meta + target observations (scamlgp/model.py:264-276)
-        self.has_transform = self.train_Y.numel() > 0
-        if self._shard is None:
-            m, s = standardize_fit(torch.cat([self._stack.raw_targets(), self.train_Y], dim=-2))
-        else:   # the same statistics from all-reduced sums: no rank ever holds the other shards' observations
-            m, s = sdist.standardize_fit_sharded(self._stack.raw_targets(), self.train_Y, self._shard)
-        self.m_all, self.s_all = (m.squeeze(), s.squeeze()) if self.has_transform else (self.train_Y.new_zeros(()), self.train_Y.new_ones(()))
+        if _fixed_transform is None:
+            # standardise w.r.t. ALL meta + target observations (scamlgp/model.py:264-276)
+            self.has_transform = self.train_Y.numel() > 0
+            if self._shard is None:
+                m, s = standardize_fit(torch.cat([self._stack.raw_targets(), self.train_Y], dim=-2))
+            else:   # the same statistics from all-reduced sums: no rank ever holds the other shards' observations
+                m, s = sdist.standardize_fit_sharded(self._stack.raw_targets(), self.train_Y, self._shard)
+            self.m_all, self.s_all = (m.squeeze(), s.squeeze()) if self.has_transform else (self.train_Y.new_zeros(()), self.train_Y.new_ones(()))
+        else:   # condition_on_observations: the parent's transform, kept fixed (botorch's convention)
+            self.has_transform = bool(_fixed_transform[2])
+            self.m_all, self.s_all = _fixed_transform[0].clone(), _fixed_transform[1].clone()
         self._m_all_f, self._s_all_f = float(self.m_all), float(self.s_all)   # (one sync here instead of one per posterior call)
         self.outcome_transform = _OutcomeTransform(self.m_all, self.s_all) if self.has_transform else None
         self.train_inputs = (self.train_X,)
@@ -509,6 +524,56 @@ class ScaMLGP:
         self.weights_prior = hyper.GammaPrior(1.0, 1.0)
         self.weights_lower_bound = 1e-10   # GreaterThan(1e-10, transform=None): a box bound for the optimiser
         self.training = True
+        self.num_fantasies: Optional[int] = None   # F of a fantasy model (condition_on_observations with (F, p, 1) targets)
+
+    @property
+    def batch_shape(self) -> torch.Size:
+        return torch.Size([self.num_fantasies]) if self.num_fantasies is not None else torch.Size()
+
+    # -- conditioning on new observations and fantasies (pending evaluations) ----------------------------------------------
+    def condition_on_observations(self, X: torch.Tensor, Y: torch.Tensor) -> "ScaMLGP":
+        """The model with (X (p, D), Y) appended to its target training set, Y (p, 1) or (F, p, 1) in original units: same
+        hyper-parameters (copied modules), same weights, same source stack, the parent's outcome transform kept fixed (m_all / s_all
+        are not refitted: botorch's convention), no refit.  Y (p, 1): an ordinary ScaMLGP.  Y (F, p, 1): a fantasy model of batch
+        shape (F,) -- ``posterior(Xq)`` gives ``.mean`` / ``.variance`` (F, M, 1), the variance the same for every f; the acquisition
+        functions average over the F fantasies (``fantasy_acqf``); ``mll`` and refitting raise."""
+        if self._shard is not None:
+            raise NotImplementedError("conditioning / fantasies are not implemented for a task-sharded source stack (shard=True)")
+        if self.num_fantasies is not None:
+            raise NotImplementedError("a fantasy model cannot be conditioned further")
+        D = self._stack.D
+        X = torch.as_tensor(X, dtype=torch.float64).to(self.device).reshape(-1, D)
+        Y = torch.as_tensor(Y, dtype=torch.float64).to(self.device)
+        p = X.shape[0]
+        if Y.dim() == 1:
+            Y = Y.unsqueeze(-1)
+        if Y.dim() not in (2, 3) or tuple(Y.shape[-2:]) != (p, 1):
+            raise ValueError(f"Y must be (p, 1) or (F, p, 1) with p = {p}, got {tuple(Y.shape)}")
+        Y0 = Y[0] if Y.dim() == 3 else Y
+        new = ScaMLGP(torch.cat([self.train_X, X]), torch.cat([self.train_Y, Y0]), self.source_gps,
+                      likelihood=copy.deepcopy(self.likelihood), covar_module=copy.deepcopy(self.covar_module),
+                      weight_pruning_threshold=self._weight_pruning_threshold, _fixed_transform=(self.m_all, self.s_all, self.has_transform))
+        new.raw_weights = self.raw_weights.detach().clone()
+        new.training = self.training
+        if Y.dim() == 3:
+            F = Y.shape[0]
+            new.num_fantasies = int(F)
+            new.train_Y = torch.cat([self.train_Y.unsqueeze(0).expand(F, -1, -1), Y], 1)            # (F, n + p, 1)
+            new.train_targets = ((new.train_Y - new.m_all) / new.s_all).squeeze(-1).contiguous()   # (F, n + p)
+        return new
+
+    def fantasize(self, X: torch.Tensor, num_fantasies: int, generator: Optional[torch.Generator] = None,
+                  observation_noise: bool = True) -> "ScaMLGP":
+        """A fantasy model for pending evaluations at X (p, D): ``num_fantasies`` joint samples of the posterior at X (the (p, p)
+        covariance of ``posterior(X).mvn.covariance_matrix``, plus the noise on its diagonal with ``observation_noise``), base samples
+        from ``generator``, then ``condition_on_observations(X, samples)``.  Monte-Carlo integration over the pending outcomes inside
+        the acquisition function (the "integrated acquisition" of Snoek et al., 2012, what botorch's ``fantasize`` serves).  The
+        reference hands this step to blackboxopt, which is not available here, so which strategy it applies is not checked."""
+        if self._shard is not None:
+            raise NotImplementedError("fantasies are not implemented for a task-sharded source stack (shard=True)")
+        X = torch.as_tensor(X, dtype=torch.float64).to(self.device).reshape(-1, self._stack.D)
+        samples = self.posterior(X, observation_noise=observation_noise).rsample(torch.Size([int(num_fantasies)]), generator=generator)
+        return self.condition_on_observations(X, samples)
 
     # -- parameters -------------------------------------------------------------------------
     @property
@@ -630,6 +695,8 @@ class ScaMLGP:
 
     def mll(self, raw_theta: Optional[torch.Tensor] = None, raw_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Training objective (A9): [log N(y~ | mean, cov + sigma^2 I) + log priors] / n, differentiable in torch."""
+        if self.num_fantasies is not None:
+            raise NotImplementedError("a fantasy model is not fitted: it keeps its parent's hyper-parameters")
         rt = self.raw_theta if raw_theta is None else raw_theta
         w = self.raw_weights if raw_weights is None else raw_weights
         theta = self.spec.to_theta(rt)
@@ -652,6 +719,8 @@ class ScaMLGP:
         """The training set in the layouts of the library's target-fit kernel (built once; None if the kernel does not take
         this shape -- more target points than its LDS holds, D > 16 -- and the torch objective ``mll`` is all there is)."""
         if getattr(self, "_tprob", None) is None:
+            if self.num_fantasies is not None:
+                raise NotImplementedError("a fantasy model is not fitted: it keeps its parent's hyper-parameters")
             if self.n < 1 or not ops.TargetFitProblem.supported(self.n, self.T, self._stack.D):
                 return None
             self._tprob = ops.TargetFitProblem(self.source_means, self.source_covs, self.train_X, self.train_targets, self._m_all_f,
@@ -689,7 +758,8 @@ class ScaMLGP:
     def supports_posterior_grad(self) -> bool:
         """The analytic input-gradient path needs training data within the fused covariance block (n <= 96), D <= 15 and the
         explicit inverse factors of the source stack (SourceGPStack.refresh caches them)."""
-        return 1 <= self.n <= 96 and self._stack.D <= 15 and self._stack.N <= 512 and self.device.type == "cuda"
+        return (1 <= self.n <= 96 and self._stack.D <= 15 and self._stack.N <= 512 and self.device.type == "cuda"
+                and (self.num_fantasies is None or self.num_fantasies <= 64))
 
     def _train_VA(self) -> torch.Tensor:
         """V = L^-1 K(X_t, train_X) of every source task (T, N, n): fixed for the model's lifetime (sources and training inputs are)."""
@@ -730,7 +800,21 @@ class ScaMLGP:
         central-difference stencil, with exact gradients."""
         if not self.supports_posterior_grad():
             raise NotImplementedError("analytic posterior gradients need 1 <= n <= 96 training points and D <= 15")
+        if self.num_fantasies is not None:
+            raise NotImplementedError("a fantasy model's acquisition gradient comes from fantasy_acqf (the acquisition-function classes)")
         Xq = torch.as_tensor(X, dtype=torch.float64).reshape(-1, self._stack.D).to(self.device).contiguous()
+        cov_s, mean_s, var_s, xall, cov_g, mu_g, var_g = self._grad_pass(Xq)
+        theta = self.theta
+        full = ops.target_posterior_full(cov_s, mean_s, var_s, xall, theta, self.train_targets, self._m_all_f, self._s_all_f, self.kind,
+                                         factor=self._target_factor())
+        self._keep_target_factor(full["factor"])
+        dmu, dvar = ops.target_posterior_grad(cov_g, mu_g, var_g, self.train_X, Xq, theta, full["alpha"], full["Z"], self._s_all_f,
+                                              full["info"], self.kind)
+        return full["mu"], full["var"], dmu, dvar
+
+    def _grad_pass(self, Xq: torch.Tensor):
+        """The source pass of ``posterior_with_grad`` at Xq (Mq, D): the joint prior over cat(train_X, Xq) for the target GP's value
+        path (cov_s (n, n + Mq), mean_s, var_s (n + Mq,), xall) and the weighted GRAD-pass sums (cov_g (n, Mq * 16), mu_g, var_g)."""
         Mq, n = Xq.shape[0], self.n
         st, f = self._stack, self._stack.fit
         w_full, active = self._active_tasks()
@@ -745,13 +829,69 @@ class ScaMLGP:
         mean_s = torch.cat([mu_t, mu_g.reshape(Mq, 16)[:, 0]])
         var_s = torch.cat([var_t, var_g.reshape(Mq, 16)[:, 0]])
         xall = torch.cat([self.train_X, Xq], 0)
+        return cov_s, mean_s, var_s, xall, cov_g, mu_g, var_g
+
+    def fantasy_acqf(self, X: torch.Tensor, acqf: int, acqf_param: float, want_grad: bool = False):
+        """The acquisition function of a fantasy model, averaged over its fantasies, at X (M, D): (value (M,), d value / d X (M, D) or
+        None).  ``acqf``: ops.ACQF_UCB (acqf_param = beta) or ops.ACQF_EI (acqf_param = best_f).  The source pass at cat(X', Xq), the
+        assemble and Z = Knn^-1 Knq are those of an ordinary model (the training block's factor and the F columns of alpha are computed
+        once per parameter state and cached); then ONE launch of scaml_target_fantasy_acqf_f64 in place of the finish and gradient
+        kernels: no per-fantasy work outside it."""
+        if self.num_fantasies is None:
+            raise ValueError("fantasy_acqf needs a fantasy model (ScaMLGP.fantasize)")
+        if self.num_fantasies > 64:
+            raise NotImplementedError("the fantasy acquisition kernel takes at most 64 fantasies")
+        Xq = torch.as_tensor(X, dtype=torch.float64).reshape(-1, self._stack.D).to(self.device).contiguous()
+        n = self.n
+        grad_inputs = None
+        if want_grad:
+            if not self.supports_posterior_grad():
+                raise NotImplementedError("analytic acquisition gradients need 1 <= n <= 96 training points and D <= 15")
+            cov_s, mean_s, var_s, xall, cov_g, mu_g, var_g = self._grad_pass(Xq)
+            grad_inputs = dict(cov_g=cov_g, mu_g=mu_g, var_g=var_g, Xt=self.train_X, Xq=Xq, theta=self.theta)
+        else:
+            if not 1 <= n <= ops.fit_max_n():
+                raise NotImplementedError(f"the fantasy acquisition path takes 1 <= n <= {ops.fit_max_n()} training points")
+            xall = torch.cat([self.train_X, Xq], 0)
+            mean_s, cov_s, var_s = self._source_prior(xall, n, train_first=True)
+        blk = ops.target_fantasy_block(cov_s, mean_s, var_s, xall, self.theta, self.train_targets, self._m_all_f, self._s_all_f, self.kind,
+                                       factor=self._target_factor())
+        self._keep_target_factor(blk["factor"])
+        if Xq.shape[0] == 0:
+            return Xq.new_empty((0,)), (Xq.new_empty((0, self._stack.D)) if want_grad else None)
+        return ops.target_fantasy_acqf(blk["Knq"], blk["Z"], blk["alpha"], blk["mean_q"], blk["var_q"], self._m_all_f, self._s_all_f,
+                                       blk["info"], acqf, acqf_param, 0.0, grad_inputs, self.kind)
+
+    def _fantasy_posterior(self, Xq: torch.Tensor, batch, observation_noise: bool) -> TargetPosterior:
+        """posterior() of a fantasy model at Xq (M, D): mean (F, M) from one product alpha^T Knq over all fantasies, the shared
+        variance from scaml_target_finish_f64, the joint covariance (it does not depend on the targets either) only when read."""
+        if batch is not None:
+            raise ValueError("the posterior of a fantasy model takes X (M, D)")
+        n, F = self.n, self.num_fantasies
+        if not 1 <= n <= ops.fit_max_n():
+            raise NotImplementedError(f"the fantasy posterior takes 1 <= n <= {ops.fit_max_n()} training points")
+        xall = torch.cat([self.train_X, Xq], 0)
+        mu_s, cov_s, var_s = self._source_prior(xall, n, train_first=True)
         theta = self.theta
-        full = ops.target_posterior_full(cov_s, mean_s, var_s, xall, theta, self.train_targets, self._m_all_f, self._s_all_f, self.kind,
-                                         factor=self._target_factor())
-        self._keep_target_factor(full["factor"])
-        dmu, dvar = ops.target_posterior_grad(cov_g, mu_g, var_g, self.train_X, Xq, theta, full["alpha"], full["Z"], self._s_all_f,
-                                              full["info"], self.kind)
-        return full["mu"], full["var"], dmu, dvar
+        noise = float(theta[-1]) if observation_noise else 0.0
+        blk = ops.target_fantasy_block(cov_s, mu_s, var_s, xall, theta, self.train_targets, self._m_all_f, self._s_all_f, self.kind,
+                                       factor=self._target_factor(), var_noise_add=noise)
+        self._keep_target_factor(blk["factor"])
+        M = Xq.shape[0]
+        mu = self.m_all + self.s_all * (blk["mean_q"] + blk["alpha"].transpose(0, 1) @ blk["Knq"])   # (F, M)
+        mu = torch.where(blk["info"][0] > 0, torch.full_like(mu, float("nan")), mu)
+        var = blk["var"].unsqueeze(0).expand(F, M)
+
+        def full_cov() -> torch.Tensor:
+            _, cj, _, th = self._joint(Xq, full=True)
+            Lc2 = psd_safe_cholesky(cj[:n, :n] + th[-1] * torch.eye(n, dtype=torch.float64, device=self.device))
+            V2 = torch.linalg.solve_triangular(Lc2, cj[:n, n:], upper=False)
+            S = cj[n:, n:] - V2.transpose(0, 1) @ V2
+            if observation_noise:
+                S = S + th[-1] * torch.eye(M, dtype=torch.float64, device=self.device)
+            return (self.s_all ** 2 * S).unsqueeze(0).expand(F, M, M)
+
+        return TargetPosterior(mu, var, full_cov)
 
     def posterior(self, X: torch.Tensor, observation_noise: bool = False) -> TargetPosterior:
         """Target posterior at X (M, D) in original units (A10).  The source prior is evaluated ONCE at
@@ -761,6 +901,8 @@ class ScaMLGP:
         covariance.  X (*batch, q, D): ``.mean`` / ``.variance`` (*batch, q, 1), ``.mvn.covariance_matrix`` (*batch, q, q)."""
         Xq, batch, q = _split_batch(torch.as_tensor(X, dtype=torch.float64).to(self.device), self._stack.D)
         n = self.n
+        if self.num_fantasies is not None:
+            return self._fantasy_posterior(Xq, batch, observation_noise)
         if 1 <= n <= ops.fit_max_n():
             # the library's target-GP path: weighted source sums at cat(train_X, Xq), then assemble -> jittered Cholesky
             # (T = 1) -> solve -> finish: four launches, no host synchronisation, no torch arithmetic

@@ -573,6 +573,93 @@ def target_posterior_grad(cov_g: Optional[torch.Tensor], mu_g: torch.Tensor, var
     return dmu, dvar
 
 
+ACQF_UCB = 0
+ACQF_EI = 1
+
+
+def target_fantasy_block(cov_s: torch.Tensor, mean_s: torch.Tensor, var_s: torch.Tensor, Xall: torch.Tensor, theta: torch.Tensor,
+                         targets: torch.Tensor, m_all: float, s_all: float, kind: int,
+                         factor: Optional[Dict[str, torch.Tensor]] = None, var_noise_add: Optional[float] = None) -> Dict[str, torch.Tensor]:
+    """The value path of ``target_posterior_full`` for a fantasy model: the n training points of ``Xall`` carry F target vectors
+    ``targets`` (F, n) (standardised; they differ only in the conditioned rows).  scaml_target_assemble_f64 (with targets[0]) and
+    scaml_cho_solve_batched_f64 for Z = Knn^-1 Knq, as in (7); ``factor``: that of an earlier call with the same training block, else
+    scaml_potrf_batched_f64 (jitter ladder) and ONE scaml_cho_solve_batched_f64 with R = F right-hand sides for alpha (n, F).
+    ``var_noise_add`` (not None): also the posterior variance (M,) in original units, + that noise, from scaml_target_finish_f64 (it
+    does not depend on the targets).  Returns dict(Knq (n, M), Z (n, M), mean_q, var_q (M,), alpha (n, F), info, factor, var)."""
+    F, n = targets.shape
+    W, D = Xall.shape
+    M = W - n
+    if not 1 <= n <= _lib.lib.scaml_fit_max_n():
+        raise ValueError(f"target_fantasy_block takes 1 <= n <= {_lib.lib.scaml_fit_max_n()} training points")
+    cov_s = _check(cov_s, "cov_s", (n, W))
+    mean_s = _check(mean_s, "mean_s", (W,))
+    var_s = _check(var_s, "var_s", (W,))
+    Xall = _check(Xall, "Xall")
+    theta = _check(theta, "theta", (D + 2,))
+    targets = _check(targets, "targets", (F, n))
+    dev = Xall.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        Knn, resid = torch.empty((1, n, n), **f64), torch.empty((1, n), **f64)
+        Knq, mean_q, var_q = torch.empty((1, n, M), **f64), torch.empty((M,), **f64), torch.empty((M,), **f64)
+        rc = _lib.lib.scaml_target_assemble_f64(_ptr(cov_s), _ptr(mean_s), _ptr(var_s), _ptr(Xall), _ptr(theta), _ptr(targets[0]),
+                                                float(m_all), float(s_all), n, M, D, int(kind), _ptr(Knn), _ptr(resid), _ptr(Knq),
+                                                _ptr(mean_q), _ptr(var_q), _stream_handle())
+        _lib.check_rc(rc, "scaml_target_assemble_f64")
+        f = factor
+        if f is None:
+            f = potrf_batched(Knn, resid, want_linv=True)
+            # r_f = r_0 + (y~_f - y~_0): the training rows are shared, only the conditioned rows differ per fantasy
+            R = (resid[0].unsqueeze(-1) + (targets - targets[0]).transpose(0, 1)).unsqueeze(0).contiguous()
+            f["alpha_f"] = cho_solve(f["L"], f["Linv_diag"], R)[0]
+        Z = cho_solve(f["L"], f["Linv_diag"], Knq)[0] if M > 0 else None
+        var = None
+        if var_noise_add is not None:
+            mu0, var = torch.empty((M,), **f64), torch.empty((M,), **f64)
+            if M > 0:
+                rc = _lib.lib.scaml_target_finish_f64(_ptr(Knq), _ptr(Z), _ptr(f["alpha"]), _ptr(mean_q), _ptr(var_q), float(m_all), float(s_all),
+                                                      float(var_noise_add), _ptr(f["info"]), n, M, _ptr(mu0), _ptr(var), _stream_handle())
+                _lib.check_rc(rc, "scaml_target_finish_f64")
+    return dict(Knq=Knq[0], Z=Z, mean_q=mean_q, var_q=var_q, alpha=f["alpha_f"], info=f["info"], factor=f, var=var)
+
+
+def target_fantasy_acqf(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor, mean_q: torch.Tensor, var_q: torch.Tensor, m_all: float,
+                        s_all: float, info: Optional[torch.Tensor], acqf: int, acqf_param: float, noise_add: float = 0.0,
+                        grad_inputs: Optional[Dict[str, torch.Tensor]] = None, kind: int = KIND_RBF):
+    """(1/F) sum_f A(mu_f, v) at M query points, A = UCB (``acqf`` ACQF_UCB, acqf_param = beta) or EI (ACQF_EI, acqf_param = best_f),
+    from the fantasy block (``target_fantasy_block``: Knq, Z (n, M), alpha (n, F), mean_q, var_q (M,)).  ``grad_inputs``:
+    dict(cov_g (n, M * 16), mu_g, var_g (M * 16), Xt (n, D), Xq (M, D), theta (D + 2)) of the GRAD pass -- then also d value / d x
+    (M, D).  One launch of scaml_target_fantasy_acqf_f64.  Returns (value (M,), grad (M, D) or None)."""
+    n, M = Knq.shape
+    F = int(alpha.shape[1])
+    Knq = _check(Knq, "Knq", (n, M))
+    Z = _check(Z, "Z", (n, M))
+    alpha = _check(alpha, "alpha", (n, F))
+    mean_q = _check(mean_q, "mean_q", (M,))
+    var_q = _check(var_q, "var_q", (M,))
+    if info is not None:
+        info = _check(info.reshape(-1)[:1], "info", (1,), torch.int32)
+    dev = Knq.device
+    g, D = None, 0
+    if grad_inputs is not None:
+        Xq = _check(grad_inputs["Xq"], "Xq")
+        D = int(Xq.shape[1])
+        g = dict(cov_g=_check(grad_inputs["cov_g"].reshape(n, -1), "cov_g", (n, M * 16)),
+                 mu_g=_check(grad_inputs["mu_g"].reshape(-1), "mu_g", (M * 16,)),
+                 var_g=_check(grad_inputs["var_g"].reshape(-1), "var_g", (M * 16,)),
+                 Xt=_check(grad_inputs["Xt"], "Xt", (n, D)), Xq=_check(Xq, "Xq", (M, D)),
+                 theta=_check(grad_inputs["theta"], "theta", (D + 2,)))
+    with torch.cuda.device(dev):
+        value = torch.empty((M,), dtype=torch.float64, device=dev)
+        grad = torch.empty((M, D), dtype=torch.float64, device=dev) if g is not None else None
+        rc = _lib.lib.scaml_target_fantasy_acqf_f64(
+            _ptr(Knq), _ptr(Z), _ptr(alpha), _ptr(mean_q), _ptr(var_q), float(m_all), float(s_all), float(noise_add), _ptr(info),
+            int(acqf), float(acqf_param), *([_ptr(g[k]) for k in ("cov_g", "mu_g", "var_g", "Xt", "Xq", "theta")] if g else [None] * 6),
+            n, M, F, D, int(kind), _ptr(value), _ptr(grad), _stream_handle())
+    _lib.check_rc(rc, "scaml_target_fantasy_acqf_f64")
+    return value, grad
+
+
 def mll_backward_workspace(T: int, N: int, D: int, device) -> Dict[str, torch.Tensor]:
     """Reusable buffers of ``mll_backward`` for a (T, N, D) stack: the explicit inverse factors (T N^2 doubles) and
     the per-tile partial sums.  An optimiser loop allocates them once (scaml_mll_backward_workspace_doubles)."""

@@ -223,6 +223,8 @@ def optimize_marginal_likelihood(model: Union[SourceGPStack, ScaMLGP, Dict, Sour
     if isinstance(model, SourceGPStack):
         return _fit_stack(model, num_restarts, **fit_options)
     if isinstance(model, ScaMLGP):
+        if model.num_fantasies is not None:
+            raise NotImplementedError("a fantasy model is not refitted: it keeps its parent's hyper-parameters")
         return _fit_target(model, num_restarts, **fit_options)
     raise TypeError(f"cannot fit a {type(model).__name__}")
 
@@ -240,20 +242,32 @@ def _drop_q(X: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     return v.squeeze(-1) if X.dim() > 2 else v
 
 
+def _fantasy_value(model: ScaMLGP, X: torch.Tensor, acqf: int, param: float) -> torch.Tensor:
+    """A fantasy model's acquisition value at X (M, D) or (*batch, 1, D), averaged over its fantasies."""
+    v, _ = model.fantasy_acqf(X.reshape(-1, X.shape[-1]), acqf, param)
+    return _drop_q(X, v.reshape(X.shape[:-1]))
+
+
 
 class UpperConfidenceBound:
     """botorch UpperConfidenceBound(model, beta=9.0, maximize=False) (scamlgp/utils.py:215-224):
-    value = -mu + sqrt(beta * var) per query point; X (M, D) -> (M,)."""
+    value = -mu + sqrt(beta * var) per query point; X (M, D) -> (M,).  On a fantasy model (ScaMLGP.fantasize) the value is the
+    mean over the fantasies of the per-fantasy value (``ScaMLGP.fantasy_acqf``)."""
 
     def __init__(self, model: ScaMLGP, beta: float = 9.0):
         self.model, self.beta = model, beta
 
     def __call__(self, X: torch.Tensor) -> torch.Tensor:
+        if self.model.num_fantasies is not None:
+            return _fantasy_value(self.model, _single_q(X), ops.ACQF_UCB, self.beta)
         mvn = self.model.posterior(_single_q(X)).mvn
         return _drop_q(X, -mvn.mean + torch.sqrt(self.beta * mvn.variance.clamp_min(0.0)))
 
     def value_and_grad(self, X: torch.Tensor):
-        """(value (M,), d value / d X (M, D)) from the model's analytic posterior gradients (ScaMLGP.posterior_with_grad)."""
+        """(value (M,), d value / d X (M, D)) from the model's analytic posterior gradients (ScaMLGP.posterior_with_grad); on a fantasy
+        model the mean over the fantasies and its exact gradient."""
+        if self.model.num_fantasies is not None:
+            return self.model.fantasy_acqf(X, ops.ACQF_UCB, self.beta, want_grad=True)
         mu, var, dmu, dvar = self.model.posterior_with_grad(X)
         sd = torch.sqrt(self.beta * var.clamp_min(0.0))
         # d sqrt(beta var) = beta dvar / (2 sqrt(beta var)); zero where the variance is clamped
@@ -263,12 +277,15 @@ class UpperConfidenceBound:
 
 class ExpectedImprovement:
     """botorch analytic ExpectedImprovement(model, best_f, maximize=False) (scamlgp/optimizer.py:96-98):
-    sigma = sqrt(max(var, 1e-9)), u = -(mu - best_f) / sigma, EI = sigma (phi(u) + u Phi(u))."""
+    sigma = sqrt(max(var, 1e-9)), u = -(mu - best_f) / sigma, EI = sigma (phi(u) + u Phi(u)).  On a fantasy model: the mean over the
+    fantasies of the per-fantasy EI, best_f still the caller's incumbent over observed data."""
 
     def __init__(self, model: ScaMLGP, best_f: float):
         self.model, self.best_f = model, best_f
 
     def __call__(self, X: torch.Tensor) -> torch.Tensor:
+        if self.model.num_fantasies is not None:
+            return _fantasy_value(self.model, _single_q(X), ops.ACQF_EI, self.best_f)
         mvn = self.model.posterior(_single_q(X)).mvn
         sigma = mvn.variance.clamp_min(1e-9).sqrt()
         u = -(mvn.mean - self.best_f) / sigma
@@ -278,7 +295,9 @@ class ExpectedImprovement:
 
     def value_and_grad(self, X: torch.Tensor):
         """(EI (M,), d EI / d X (M, D)): d EI = -Phi(u) d mu + phi(u) d sigma, d sigma = d var / (2 sigma) (zero where the variance
-        sits on the 1e-9 floor), from the model's analytic posterior gradients."""
+        sits on the 1e-9 floor), from the model's analytic posterior gradients; on a fantasy model the mean over the fantasies."""
+        if self.model.num_fantasies is not None:
+            return self.model.fantasy_acqf(X, ops.ACQF_EI, self.best_f, want_grad=True)
         mu, var, dmu, dvar = self.model.posterior_with_grad(X)
         sigma = var.clamp_min(1e-9).sqrt()
         u = -(mu - self.best_f) / sigma
