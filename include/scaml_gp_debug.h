@@ -1,0 +1,44 @@
+/*
+ * scaml_gp_debug.h — developer switches of libscaml_hip.so.
+ *
+ * These functions are NOT part of the stable ABI of scaml_gp.h.  They flip process-global
+ * switches that route an entry point through one of its implementations regardless of the
+ * problem shape, for A/B timing and for testing one path against the other; each switch
+ * starts from an environment variable read when the library is loaded.  A switch applies to
+ * every thread and every device of the process; setting one while another thread is inside
+ * an entry point is free of data races, and that call takes either the old or the new path.
+ * They may change or disappear in any release.
+ */
+#ifndef SCAML_GP_DEBUG_H
+#define SCAML_GP_DEBUG_H
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* scaml_mll_backward_f64: 1 the two-launch path (L^-1 in the workspace, then the K^-1 tile kernel) even where the
+ * single-launch kernel applies, 2 the single-launch kernel even for the small stacks the two launches serve by default,
+ * anything else the choice by shape.  Starts from SCAML_GRAD_LEGACY (1) / SCAML_GRAD_FUSED (2).  Returns the previous mode. */
+int scaml_debug_force_two_launch_grad(int mode);
+
+/* scaml_gp_fit_blocked_f64: 0 by shape, 1 the 2 x 2 sequence of launches only, 2 the several-CUs-per-task kernel whenever
+ * it is launchable; any other value changes nothing.  Starts from SCAML_BLOCKED_FIT_PATH.  Returns the previous mode, or,
+ * for mode == -1, the path the last call took (1 / 2). */
+int scaml_debug_blocked_fit_path(int mode);
+
+/* Several-CUs-per-task fit: 1 write-through payload stores even when a task's workgroups share an XCD, 0 by placement;
+ * any other value changes nothing.  Starts from SCAML_COOP_FAR (set: 1).  Returns the previous value. */
+int scaml_debug_coop_far(int on);
+
+/* scaml_target_mll_f64 / scaml_target_fit_f64: 1 the column-by-column elimination where the matrix-core factorisation
+ * would apply, anything else the choice by shape.  Starts from SCAML_TARGET_FIT_NO_MFMA (set: 1).  Returns the previous mode. */
+int scaml_debug_target_fit_path(int mode);
+
+/* Diagnostic builds only (SCAML_STAMPS): point the device-side stamp buffer at caller memory.  0 ok, SCAML_E_BADARG
+ * when the code object has no stamp buffer, SCAML_E_LAUNCH on a HIP error. */
+int scaml_debug_set_stamp_buffer(long long* buf);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SCAML_GP_DEBUG_H */

@@ -137,6 +137,8 @@ __global__ __launch_bounds__(512) void gp_blocked_solve_kernel(BlockedFitParams 
   double* a1s = X2s + 64 * DP;           // [NP] v1 = L11^-1 y1
   double* exptab = a1s + NP;             // [64]
   double* invl = exptab + 64;            // [DS]
+  // End of the carve, invl + DS: blocked_solve_lds_doubles(D) (gp_fit_params.h; one spare double) -- change both together
+  // (D is a run-time extent here and in the rank update below: nothing constant to assert on).
 
   int task, sg;
   if (!bk_task_part((N - BK_N1 + 63) / 64, p.T, task, sg)) return;
@@ -333,6 +335,7 @@ __global__ __launch_bounds__(512, 4) void gp_blocked_syrk_kernel(BlockedFitParam
   double* Xc = Xr + 64 * DP;        // [64][DP] column points
   double* exptab = Xc + 64 * DP;    // [64]
   double* invl = exptab + 64;       // [D]
+  // End of the carve, invl + D: blocked_syrk_lds_doubles(D) (gp_fit_params.h; one spare double) -- change both together.
   const int nt = (N2 + 63) / 64;
   int task, tile;
   if (!bk_task_part(nt * (nt + 1) / 2, p.T, task, tile)) return;

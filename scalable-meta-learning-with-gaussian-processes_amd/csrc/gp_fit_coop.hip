@@ -396,6 +396,8 @@ __global__ __launch_bounds__(512) void gp_fit_coop_kernel(CoopFitParams p) {
   double* Dg = Cb + 4 * CF_BS;           // L_jj
   double* Wb = Dg + CF_BS;               // L_jj^-1
   double* Xs = Wb + CF_BS;               // [N][DP] x / lengthscale
+  static_assert(64 + 16 + 32 + 32 + 16 + 8 + 6 * CF_BS == coop_fit_lds_doubles(0, 0), "carve up to Xs and gp_fit_params.h disagree");
+  // End of the carve, Xs + N * DP: coop_fit_lds_doubles(N, D) (N, D are run-time extents: the part before Xs is asserted)
 
   const double* Xg = p.X + (size_t)task * N * D;
   const double* yg = p.y + (size_t)task * N;

@@ -83,6 +83,7 @@ namespace scaml {
 // (lane -> row 16t + (lane & 15), column 4m + (lane >> 4)), the C/D-layout tile spills/reloads
 // (lane -> row (lane >> 4) + 4g, column lane & 15) and the per-row reads are all bank-conflict free.
 constexpr int PP = 17;
+static_assert(PP == FIT_PP, "gp_fit_params.h sizes the LDS with this pitch");
 
 __device__ __forceinline__ int opaque_s(int v) {
   asm volatile("" : "+s"(v));  // keeps per-slot address arithmetic from being hoisted out of the panel loop
@@ -386,6 +387,9 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   int* cntY = cntS + NB;         // [NB] update waves done folding column k into the right-hand side
   int* cntU = cntY + NB;         // [NB] update waves done with U2(k): nobody reads column k any more
   int* cntB = cntU + NB;         // [NB] back-substitution: tiles (i, k), i > k, already folded into w_k
+  // End of the carve, cntB + NB: the launcher asks for fit_lds_doubles(NB, WU, D) (gp_fit_params.h) -- change both together.
+  // (D is a run-time extent, so the end is no constant to assert on, and taking the offsets from the header would alter
+  // the address arithmetic of a kernel whose instruction stream is kept as it is.)
 
   const int task = blockIdx.x;
   const int tid = threadIdx.x;

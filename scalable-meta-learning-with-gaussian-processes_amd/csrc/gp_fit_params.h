@@ -1,5 +1,6 @@
 // Kernel-argument block of gp_fit_fused_kernel, shared by the device source and the host launcher.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace scaml {
@@ -93,5 +94,42 @@ struct CoopFitParams {
   unsigned flags;
   int parts;                // workgroups per task
 };
+
+// ---- dynamic LDS footprints, in doubles -----------------------------------------------------------------------------------
+// The one definition of how much LDS each kernel's carve of `lds[]` needs: the host launcher requests exactly these, and a
+// kernel whose carve changes has to change the function here with it (the carve's last line names it).
+constexpr int FIT_PP = 17;   // LDS panel pitch of the fused fit (PP in csrc/gp_fit_fused.hip)
+
+// gp_fit_fused_kernel / gp_fit_blocked_kernel <NB = nb, WU = wu>, carve at the top of gp_fit_attempt
+constexpr size_t fit_lds_doubles(int nb, int wu, int D) {
+  const size_t np = (size_t)nb * 16;
+  const size_t regionA = 3 * np * FIT_PP + (size_t)(nb + 2) * 16 * FIT_PP + 4 * 256;   // PT[3], WAll[nb], LT[2], DG[2], CR[2]
+  const size_t buildA = (size_t)(((D + 3) & ~3) + 4) * np + (nb == 16 ? 24 * 256 : 0);   // staged points (+ tail rows) + the panel wave's tile images (N > 128 only)
+  // + vectors, trash/exp table, row lists, 1/l, fail flag + 6 nb hand-off counters (ints)
+  return (buildA > regionA ? buildA : regionA) + 3 * np + 160 + (size_t)wu * nb * 4 + D + (D & 1) + 2 + 3 * (size_t)nb;
+}
+
+// largest D whose staged point stack fits `lds_doubles` next to the vectors, for the padded order np = 32, 64, 128, 256
+// (fit_lds_doubles solved for D with the row lists and counters of the largest variant: nb = 16, wu = 7)
+constexpr int fit_max_d(int np, int lds_doubles) {
+  const int budget = lds_doubles - 3 * np - 160 - 7 * 16 * 4 - 3 * 16 - 4 - (np == 256 ? 24 * 256 : 0);
+  return ((budget / (np + 1)) & ~3) - 4;   // rows: D rounded up to 4, + 4 tail rows; + 1/l per dimension
+}
+
+// gp_fit_coop_kernel: exp table, 1/l, tv, rvs, red, ctrl, six 32 x 33 blocks (Cb[4], Dg, Wb), the task's points [N][D | 1]
+constexpr size_t coop_fit_lds_doubles(int N, int D) {
+  return 64 + 16 + 32 + 32 + 16 + 8 + 6 * 32 * 33 + (size_t)N * (D | 1);
+}
+
+// gp_blocked_solve_kernel <SMALLD = D <= 8> (D <= 8: points staged zero-padded to 8 dimensions, pitch 9)
+constexpr size_t blocked_solve_lds_doubles(int D) {
+  const size_t dp = D <= 8 ? 9 : (size_t)(D | 1);
+  return 3 * 16 * 258 + 2 * 4 * 256 + 256 * dp + 64 * dp + 256 + 64 + (D <= 8 ? 8 : (size_t)D) + 1;
+}
+
+// gp_blocked_syrk_kernel
+constexpr size_t blocked_syrk_lds_doubles(int D) {
+  return (size_t)(8 * 512 + 128 * (D | 1) + 64 + D + 1);
+}
 
 }  // namespace scaml

@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256) void gp_linv_kernel(LinvParams p) {
   const int lc = lane & 15, lq = lane >> 4;
   int n = p.n_points ? p.n_points[task] : N;
   n = n < 0 ? 0 : (n > N ? N : n);
-  double* Vs = lds + (size_t)wave * NP * 16;
+  double* Vs = lds + (size_t)wave * NP * 16;   // one strip per wave: strip_solve_lds_doubles(NP, waves) (gp_posterior_params.h)
   const double* Lg = p.L + (size_t)task * N * N;
   const double* Wg = p.Linv_diag + (size_t)task * NB * 256;
   double* Og = p.Linv + (size_t)task * N * N;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void gp_cho_solve_kernel(ChoSolveParams p) {
   const int lc = lane & 15, lq = lane >> 4;
   int n = p.n_points ? p.n_points[task] : N;
   n = n < 0 ? 0 : (n > N ? N : n);
-  double* Vs = lds + (size_t)wave * NP * 16;
+  double* Vs = lds + (size_t)wave * NP * 16;   // one strip per wave: strip_solve_lds_doubles(NP, waves) (gp_posterior_params.h)
   const double* Lg = p.L + (size_t)task * N * N;
   const double* Wg = p.Linv_diag + (size_t)task * NB * 256;
   const double* Bg = p.B + (size_t)task * N * R;
@@ -294,7 +294,7 @@ template <int KIND>
 __global__ __launch_bounds__(256) void gp_mll_grad_kernel(MllGradParams p) {
   __shared__ double exptab[64];
   __shared__ double invl_s[64];   // 1 / lengthscale (D <= 64: larger D take the division)
-  extern __shared__ double xstage[];   // [waves][64][D | 1] scaled points of the four blocks of a super-tile
+  extern __shared__ double xstage[];   // [4 waves][64][DP] scaled points (+ alpha) of the four blocks of a super-tile: mll_grad_lds_doubles(D) (gp_posterior_params.h)
   const int N = p.N, D = p.D, NB = (N + 15) / 16;
   const int NT = NB * (NB + 1) / 2;
   // XCD-aware block -> (task, tile group) map.  Workgroups go to the 8 XCDs round-robin by linear id, and

@@ -221,6 +221,8 @@ __global__ __launch_bounds__(NBT * 32 / SPLIT) void gp_mll_grad_fused_kernel(Mll
   double* exptab = zs_all + NW * 512;    // [64]
   double* invl = exptab + 64;            // [8]
   double* red = invl + 8;                // [NW][10]
+  static_assert(2 * BUF + 2 * NP * GF_DP + 16 + NP + NW * 512 + 64 + 8 + NW * 10 == mll_grad_fused_lds_doubles(NBT, NW),
+                "carve (end: red + NW * 10) and gp_posterior_params.h disagree");
 
   const int N = p.N, D = p.D;
   const int NB = (N + 15) / 16;

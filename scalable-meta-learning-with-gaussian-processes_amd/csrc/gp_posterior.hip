@@ -40,6 +40,8 @@ __global__ __launch_bounds__(256) void gp_posterior_kernel(PosteriorParams p) {
   double* wbase = xsT + (p.x_in_lds ? D * NP : 0);
   double* xqs = wbase + wave * (16 * D + NP * 16);
   double* Vs = xqs + 16 * D;
+  // End of the carve, the last wave's Vs + NP * 16: posterior_lds_doubles(N, D, waves, x_in_lds) (gp_posterior_params.h) --
+  // change both together (all extents are run-time values: nothing constant to assert on).
 
   const double* Xg = p.X + (size_t)task * N * D;
   const double* th = p.theta + (size_t)task * (D + 2);
@@ -173,6 +175,7 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(PosteriorParams 
   double* nq = red + 32;
   double* nr = nq + 16;
   double* Ks = nr + NP;
+  // End of the carve, Ks + NP * 16: posterior_linv_lds_doubles(N, D) (gp_posterior_params.h) -- change both together.
 
   const double* Xg = p.X + (size_t)task * N * D;
   const double* th = p.theta + (size_t)task * (D + 2);

@@ -1,5 +1,6 @@
 // Kernel-argument blocks of the posterior kernels, shared by device source and host launcher.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace scaml {
@@ -106,5 +107,32 @@ struct MllGradFusedParams {
   double* partials;         // (T, tiles, D+2): the task's totals go into tile slot 0, zeros into the others
   int T, N, D;
 };
+
+// ---- dynamic LDS footprints, in doubles (see csrc/gp_fit_params.h: one definition for the host launcher and the kernels) ----
+// gp_posterior_kernel: exp table | alpha [np] | 1/l (+ pad) | X^T [D][np] when x_in_lds | per wave: xq [D][16], V strip [np][16]
+constexpr size_t posterior_lds_doubles(int N, int D, int waves, bool x_in_lds) {
+  const size_t np = (size_t)((N + 15) / 16) * 16;
+  return 64 + np + D + (D & 1) + (x_in_lds ? (size_t)D * np : 0) + (size_t)waves * (16 * D + np * 16);
+}
+
+// gp_posterior_linv_kernel: exp table | alpha [np] | 1/l [d4] | xq [d4][16] | red [32] | |xq|^2 [16] | |x|^2 [np] | K_*^T strip [np][16]
+constexpr size_t posterior_linv_lds_doubles(int N, int D) {
+  const size_t np = (size_t)((N + 15) / 16) * 16;
+  const size_t d4 = (size_t)((D + 3) & ~3);   // query points, 1 / lengthscale zero-padded to the MFMA k-step
+  return 64 + np + d4 + 16 * d4 + 32 + 16 + np + np * 16;
+}
+
+// gp_linv_kernel, gp_cho_solve_kernel: one [np][16] strip per wave
+constexpr size_t strip_solve_lds_doubles(int np, int waves) { return (size_t)waves * np * 16; }
+
+// gp_mll_grad_kernel: [4 waves][64][(D + 1) | 1] scaled points + alpha of a super-tile (next to 1 KiB of static LDS)
+constexpr size_t mll_grad_lds_doubles(int D) { return (size_t)4 * 64 * ((D + 1) | 1); }
+
+// gp_mll_grad_fused_kernel <NBT = nbt>: buf [2][16][np + 2] | Xs [np][9] + 16 | Xq [np][9] | alpha [np] | per wave 2 x 256 |
+// exp table | 1/l [8] | per wave 10.  The launcher sizes every instance for waves = nbt / 2, split workgroups included.
+constexpr size_t mll_grad_fused_lds_doubles(int nbt, int waves) {
+  const size_t np = (size_t)16 * nbt;
+  return 2 * 16 * (np + 2) + 2 * np * 9 + 16 + np + (size_t)waves * 512 + 64 + 8 + (size_t)waves * 10;
+}
 
 }  // namespace scaml

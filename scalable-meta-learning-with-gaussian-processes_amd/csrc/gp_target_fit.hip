@@ -952,7 +952,9 @@ TF_DEV void tf_run(const TfCtx& c, const TargetFitParams& p, int prob) {
   }
 }
 
-TF_DEV void tf_carve(TfCtx& c, double* lds, int n, int T, int D, int nwave, int mfma) {
+// Returns the end of the carve: lds + target_fit_lds_doubles(n, T, D, mfma, nwave) (gp_target_params.h, what the launcher asks
+// for; tests/test_target_fit_emul.py compares the two).
+TF_DEV double* tf_carve(TfCtx& c, double* lds, int n, int T, int D, int nwave, int mfma) {
   double* q = lds;
   c.nb = (n + 15) / 16;
   c.mfma = mfma;
@@ -982,6 +984,7 @@ TF_DEV void tf_carve(TfCtx& c, double* lds, int n, int T, int D, int nwave, int 
   c.part = q; q += nwave * (TARGET_FIT_DMAX + 2);
   c.red = q; q += nwave;
   c.sc = q; q += 8 + 2 * TARGET_FIT_HMAX;
+  return q;
 }
 
 TF_DEV void tf_main(TfCtx& c, const TargetFitParams& p, int prob) {

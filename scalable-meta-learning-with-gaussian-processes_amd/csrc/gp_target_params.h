@@ -1,5 +1,6 @@
 // Kernel-argument block of the target-GP fit kernel (csrc/gp_target_fit.hip), shared by device source and host launcher.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace scaml {
@@ -45,5 +46,14 @@ struct TargetFitParams {
 
 constexpr int TARGET_FIT_DMAX = 16;
 constexpr int TARGET_FIT_HMAX = 16;
+
+// Dynamic LDS footprint of scaml_target_fit_kernel in doubles: what tf_carve (csrc/gp_target_fit.hip) hands out for a workgroup
+// of `waves` waves -- the one definition the host launcher and scaml_target_fit_max_n use (see csrc/gp_fit_params.h).
+constexpr size_t target_fit_lds_doubles(int n, int T, int D, bool mfma, int waves) {
+  const size_t nw = (size_t)waves, nb = (size_t)(n + 15) / 16;
+  const size_t mats = mfma ? 2 * (nb * (nb + 1) / 2) * 16 * 17 : (size_t)(n + 1) * (n + 2) / 2 + (size_t)n * (n + 1) / 2;
+  return mats + (size_t)n * D + 2 * (size_t)(n + 1) + 4 * (size_t)n + 16 + 2 * (size_t)T +
+         2 * (size_t)(D + 2) + D + nw * (TARGET_FIT_DMAX + 2) + nw + 8 + 2 * TARGET_FIT_HMAX;
+}
 
 }  // namespace scaml

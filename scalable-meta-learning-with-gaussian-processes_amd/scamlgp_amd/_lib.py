@@ -40,6 +40,76 @@ class ScamlLibraryError(RuntimeError):
     pass
 
 
+_i, _u, _ll, _f = c_int, c_uint, ctypes.c_longlong, ctypes.c_double
+_host_spec = ctypes.POINTER(_f)   # (the one host pointer of the ABI: 19 doubles read during the call)
+
+# The C ABI, once: name -> (restype, argtypes).  include/scaml_gp.h declares the entry points, include/scaml_gp_debug.h the
+# scaml_debug_* developer switches.
+SIGNATURES = {
+    "scaml_version": (_i, []),
+    "scaml_last_error": (c_char_p, []),
+    "scaml_fit_max_n": (_i, []),
+    "scaml_fit_max_d": (_i, [_i]),
+    "scaml_gp_fit_fused_f64": (_i, [
+        _dp, _dp, _dp, _dp, _dp,  # X, y, theta, n_points, jitter_in
+        _i, _i, _i, _i,  # T, N, D, kind
+        _dp, _dp, _dp, _dp, _dp,  # L, alpha, quad, logdet, mll
+        _dp, _dp, _dp, _u, c_void_p,  # info, jitter_used, Linv_diag, flags, stream
+    ]),
+    "scaml_fit_blocked_max_n": (_i, []),
+    "scaml_fit_blocked_max_d": (_i, []),
+    "scaml_gp_fit_blocked_workspace_bytes": (_ll, [_i, _i]),
+    "scaml_gp_fit_blocked_f64": (_i, [
+        _dp, _dp, _dp, _dp, _dp,  # X, y, theta, n_points, jitter_in
+        _i, _i, _i, _i,  # T, N, D, kind
+        _dp, _dp, _dp, _dp, _dp,  # L, alpha, quad, logdet, mll
+        _dp, _dp, _dp, _u,  # info, jitter_used, Linv_diag, flags
+        _dp, _ll, _dp,  # workspace, workspace_bytes, stream
+    ]),
+    "scaml_kernel_matrix_f64": (_i, [_dp, _dp, _dp, _i, _i, _i, _i, _i, _i, _i, _dp, c_void_p]),
+    "scaml_potrf_batched_f64": (_i, [_dp, _dp, _dp, _dp, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u, c_void_p]),
+    "scaml_posterior_max_n": (_i, []),
+    "scaml_posterior_batched_f64": (_i, [
+        _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,  # Xq, X, theta, L, Linv_diag, alpha, y_mean, y_std, n_points
+        _i, _i, _i, _i, _i,  # T, N, M, D, kind
+        _dp, _dp, _dp, _u, c_void_p,  # mu, var, V, flags, stream
+    ]),
+    "scaml_posterior_cov_f64": (_i, [_dp, _dp, _dp, _dp, _i, _i, _i, _i, _i, _i, _dp, _u, c_void_p]),
+    "scaml_linv_batched_f64": (_i, [_dp, _dp, _dp, _i, _i, _dp, c_void_p]),
+    "scaml_linv_batched_lower_f64": (_i, [_dp, _dp, _dp, _i, _i, _dp, c_void_p]),
+    "scaml_posterior_linv_f64": (_i, [
+        _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,  # Xq, X, theta, Linv, alpha, y_mean, y_std, n_points
+        _i, _i, _i, _i, _i,  # T, N, M, D, kind
+        _dp, _dp, _dp, _u, c_void_p,  # mu, var, V, flags, stream
+    ]),
+    "scaml_cho_solve_batched_f64": (_i, [_dp, _dp, _dp, _dp, _i, _i, _i, _dp, c_void_p]),
+    "scaml_solve_lt_batched_f64": (_i, [_dp, _dp, _dp, _dp, _i, _i, _i, _dp, c_void_p]),
+    "scaml_weighted_task_sum_f64": (_i, [_dp, _dp, _dp, _i, _ll, _i, _dp, c_void_p]),
+    "scaml_weighted_prior_reduce_f64": (_i, [_dp, _dp, _dp, _dp, _i, _i, _i, _dp, _dp, c_void_p]),
+    "scaml_mll_backward_workspace_doubles": (_ll, [_i, _i, _i]),
+    "scaml_mll_backward_f64": (_i, [_dp, _dp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _dp, _dp, c_void_p]),
+    "scaml_posterior_linv_cov_f64": (_i, [_dp] * 9 + [_i] * 6 + [_dp, _dp, _dp, _u, c_void_p]),
+    "scaml_target_assemble_f64": (_i, [_dp] * 6 + [_f, _f, _i, _i, _i, _i] + [_dp] * 5 + [c_void_p]),
+    "scaml_target_finish_f64": (_i, [_dp] * 5 + [_f, _f, _f, _dp, _i, _i, _dp, _dp, c_void_p]),
+    "scaml_posterior_linv_grad_f64": (_i, [_dp] * 10 + [_i] * 6 + [_dp, _dp, _dp, _u, c_void_p]),
+    "scaml_target_posterior_grad_f64": (_i, [_dp] * 8 + [_f, _dp, _i, _i, _i, _i, _dp, _dp, c_void_p]),
+    "scaml_target_fantasy_acqf_f64": (_i, [_dp] * 5 + [_f, _f, _f, _dp, _i, _f] + [_dp] * 6 + [_i] * 5 + [_dp, _dp, c_void_p]),
+    "scaml_target_fit_max_n": (_i, [_i, _i]),
+    "scaml_target_fit_max_d": (_i, []),
+    "scaml_target_fit_workspace_doubles": (_ll, [_i, _i, _i, _i]),
+    "scaml_target_mll_f64": (_i, [_dp] * 4 + [_f, _f, _host_spec, _dp] + [_i] * 5 + [_dp] * 4 + [c_void_p]),
+    "scaml_target_fit_f64": (_i, [_dp] * 4 + [_f, _f, _host_spec, _dp] + [_i] * 7 + [_f, _f] + [_dp] * 5 + [_ll, c_void_p]),
+    "scaml_debug_target_fit_path": (_i, [_i]),
+    "scaml_debug_blocked_fit_path": (_i, [_i]),
+    "scaml_debug_coop_far": (_i, [_i]),
+    "scaml_debug_force_two_launch_grad": (_i, [_i]),
+    "scaml_debug_set_stamp_buffer": (_i, [c_void_p]),
+}
+
+# Every symbol include/scaml_gp.h declares; tests check the built library exports them all.
+EXPORTED_SYMBOLS = tuple(name for name in SIGNATURES if not name.startswith("scaml_debug_"))
+
+
 def _load() -> ctypes.CDLL:
     if not os.path.exists(LIB_PATH):
         raise ScamlLibraryError(
@@ -47,147 +117,13 @@ def _load() -> ctypes.CDLL:
             "(run __graft_entry__.build()); there is no CPU fallback for the GP hot path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    lib.scaml_version.restype = c_int
-    lib.scaml_version.argtypes = []
-    lib.scaml_last_error.restype = c_char_p
-    lib.scaml_last_error.argtypes = []
-    lib.scaml_fit_max_n.restype = c_int
-    lib.scaml_fit_max_n.argtypes = []
-    lib.scaml_fit_max_d.restype = c_int
-    lib.scaml_fit_max_d.argtypes = [c_int]
-    lib.scaml_fit_blocked_max_n.restype = c_int
-    lib.scaml_fit_blocked_max_n.argtypes = []
-    lib.scaml_fit_blocked_max_d.restype = c_int
-    lib.scaml_fit_blocked_max_d.argtypes = []
-    lib.scaml_gp_fit_blocked_workspace_bytes.restype = ctypes.c_longlong
-    lib.scaml_gp_fit_blocked_workspace_bytes.argtypes = [c_int, c_int]
-    lib.scaml_gp_fit_blocked_f64.restype = c_int
-    lib.scaml_gp_fit_blocked_f64.argtypes = [
-        _dp, _dp, _dp, _dp, _dp,  # X, y, theta, n_points, jitter_in
-        c_int, c_int, c_int, c_int,  # T, N, D, kind
-        _dp, _dp, _dp, _dp, _dp,  # L, alpha, quad, logdet, mll
-        _dp, _dp, _dp, ctypes.c_uint,  # info, jitter_used, Linv_diag, flags
-        _dp, ctypes.c_longlong, _dp,  # workspace, workspace_bytes, stream
-    ]
-    lib.scaml_gp_fit_fused_f64.restype = c_int
-    lib.scaml_gp_fit_fused_f64.argtypes = [
-        _dp, _dp, _dp, _dp, _dp,  # X, y, theta, n_points, jitter_in
-        c_int, c_int, c_int, c_int,  # T, N, D, kind
-        _dp, _dp, _dp, _dp, _dp,  # L, alpha, quad, logdet, mll
-        _dp, _dp, _dp, c_uint, c_void_p,  # info, jitter_used, Linv_diag, flags, stream
-    ]
-    lib.scaml_kernel_matrix_f64.restype = c_int
-    lib.scaml_kernel_matrix_f64.argtypes = [_dp, _dp, _dp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _dp, c_void_p]
-    lib.scaml_potrf_batched_f64.restype = c_int
-    lib.scaml_potrf_batched_f64.argtypes = [_dp, _dp, _dp, _dp, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, c_uint, c_void_p]
-    lib.scaml_posterior_max_n.restype = c_int
-    lib.scaml_posterior_max_n.argtypes = []
-    lib.scaml_posterior_batched_f64.restype = c_int
-    lib.scaml_posterior_batched_f64.argtypes = [
-        _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,  # Xq, X, theta, L, Linv_diag, alpha, y_mean, y_std, n_points
-        c_int, c_int, c_int, c_int, c_int,  # T, N, M, D, kind
-        _dp, _dp, _dp, ctypes.c_uint, c_void_p,  # mu, var, V, flags, stream
-    ]
-    lib.scaml_posterior_cov_f64.restype = c_int
-    lib.scaml_posterior_cov_f64.argtypes = [_dp, _dp, _dp, _dp, c_int, c_int, c_int, c_int, c_int, c_int, _dp, ctypes.c_uint, c_void_p]
-    lib.scaml_linv_batched_f64.restype = c_int
-    lib.scaml_linv_batched_f64.argtypes = [_dp, _dp, _dp, c_int, c_int, _dp, c_void_p]
-    lib.scaml_linv_batched_lower_f64.restype = c_int
-    lib.scaml_linv_batched_lower_f64.argtypes = [_dp, _dp, _dp, c_int, c_int, _dp, c_void_p]
-    lib.scaml_posterior_linv_f64.restype = c_int
-    lib.scaml_posterior_linv_f64.argtypes = [
-        _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,  # Xq, X, theta, Linv, alpha, y_mean, y_std, n_points
-        c_int, c_int, c_int, c_int, c_int,  # T, N, M, D, kind
-        _dp, _dp, _dp, ctypes.c_uint, c_void_p,  # mu, var, V, flags, stream
-    ]
-    lib.scaml_cho_solve_batched_f64.restype = c_int
-    lib.scaml_cho_solve_batched_f64.argtypes = [_dp, _dp, _dp, _dp, c_int, c_int, c_int, _dp, c_void_p]
-    lib.scaml_solve_lt_batched_f64.restype = c_int
-    lib.scaml_solve_lt_batched_f64.argtypes = [_dp, _dp, _dp, _dp, c_int, c_int, c_int, _dp, c_void_p]
-    lib.scaml_weighted_task_sum_f64.restype = c_int
-    lib.scaml_weighted_task_sum_f64.argtypes = [_dp, _dp, _dp, c_int, ctypes.c_longlong, c_int, _dp, c_void_p]
-    lib.scaml_weighted_prior_reduce_f64.restype = c_int
-    lib.scaml_weighted_prior_reduce_f64.argtypes = [_dp, _dp, _dp, _dp, c_int, c_int, c_int, _dp, _dp, c_void_p]
-    lib.scaml_mll_backward_workspace_doubles.restype = ctypes.c_longlong
-    lib.scaml_mll_backward_workspace_doubles.argtypes = [c_int, c_int, c_int]
-    lib.scaml_mll_backward_f64.restype = c_int
-    lib.scaml_mll_backward_f64.argtypes = [_dp, _dp, _dp, _dp, _dp, _dp, c_int, c_int, c_int, c_int, _dp, _dp, c_void_p]
-    lib.scaml_posterior_linv_cov_f64.restype = c_int
-    lib.scaml_posterior_linv_cov_f64.argtypes = [_dp] * 9 + [c_int] * 6 + [_dp, _dp, _dp, ctypes.c_uint, c_void_p]
-    c_double = ctypes.c_double
-    lib.scaml_target_assemble_f64.restype = c_int
-    lib.scaml_target_assemble_f64.argtypes = [_dp] * 6 + [c_double, c_double, c_int, c_int, c_int, c_int] + [_dp] * 5 + [c_void_p]
-    lib.scaml_target_finish_f64.restype = c_int
-    lib.scaml_target_finish_f64.argtypes = [_dp] * 5 + [c_double, c_double, c_double, _dp, c_int, c_int, _dp, _dp, c_void_p]
-    lib.scaml_posterior_linv_grad_f64.restype = c_int
-    lib.scaml_posterior_linv_grad_f64.argtypes = [_dp] * 10 + [c_int] * 6 + [_dp, _dp, _dp, ctypes.c_uint, c_void_p]
-    lib.scaml_target_posterior_grad_f64.restype = c_int
-    lib.scaml_target_posterior_grad_f64.argtypes = [_dp] * 8 + [c_double, _dp, c_int, c_int, c_int, c_int, _dp, _dp, c_void_p]
-    lib.scaml_target_fantasy_acqf_f64.restype = c_int
-    lib.scaml_target_fantasy_acqf_f64.argtypes = ([_dp] * 5 + [c_double, c_double, c_double, _dp, c_int, c_double] + [_dp] * 6
-                                                  + [c_int] * 5 + [_dp, _dp, c_void_p])
-    lib.scaml_target_fit_max_n.restype = c_int
-    lib.scaml_target_fit_max_n.argtypes = [c_int, c_int]
-    lib.scaml_target_fit_max_d.restype = c_int
-    lib.scaml_target_fit_max_d.argtypes = []
-    lib.scaml_target_fit_workspace_doubles.restype = ctypes.c_longlong
-    lib.scaml_target_fit_workspace_doubles.argtypes = [c_int, c_int, c_int, c_int]
-    host_spec = ctypes.POINTER(c_double)   # (the one host pointer of the ABI: 19 doubles read during the call)
-    lib.scaml_target_mll_f64.restype = c_int
-    lib.scaml_target_mll_f64.argtypes = [_dp] * 4 + [c_double, c_double, host_spec, _dp] + [c_int] * 5 + [_dp] * 4 + [c_void_p]
-    lib.scaml_target_fit_f64.restype = c_int
-    lib.scaml_target_fit_f64.argtypes = ([_dp] * 4 + [c_double, c_double, host_spec, _dp] + [c_int] * 7 + [c_double, c_double] + [_dp] * 5
-                                         + [ctypes.c_longlong, c_void_p])
-    lib.scaml_debug_target_fit_path.restype = c_int
-    lib.scaml_debug_target_fit_path.argtypes = [c_int]
-    lib.scaml_debug_blocked_fit_path.restype = c_int
-    lib.scaml_debug_blocked_fit_path.argtypes = [c_int]
-    lib.scaml_debug_coop_far.restype = c_int
-    lib.scaml_debug_coop_far.argtypes = [c_int]
-    lib.scaml_debug_force_two_launch_grad.restype = c_int
-    lib.scaml_debug_force_two_launch_grad.argtypes = [c_int]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 
 lib = _load()
-
-# Every symbol include/scaml_gp.h declares; tests check the built library exports them all.
-EXPORTED_SYMBOLS = (
-    "scaml_version",
-    "scaml_last_error",
-    "scaml_fit_max_n",
-    "scaml_fit_max_d",
-    "scaml_gp_fit_fused_f64",
-    "scaml_fit_blocked_max_n",
-    "scaml_fit_blocked_max_d",
-    "scaml_gp_fit_blocked_workspace_bytes",
-    "scaml_gp_fit_blocked_f64",
-    "scaml_kernel_matrix_f64",
-    "scaml_potrf_batched_f64",
-    "scaml_posterior_max_n",
-    "scaml_posterior_batched_f64",
-    "scaml_posterior_cov_f64",
-    "scaml_linv_batched_f64",
-    "scaml_linv_batched_lower_f64",
-    "scaml_posterior_linv_f64",
-    "scaml_cho_solve_batched_f64",
-    "scaml_solve_lt_batched_f64",
-    "scaml_weighted_task_sum_f64",
-    "scaml_weighted_prior_reduce_f64",
-    "scaml_mll_backward_workspace_doubles",
-    "scaml_mll_backward_f64",
-    "scaml_posterior_linv_cov_f64",
-    "scaml_target_assemble_f64",
-    "scaml_target_finish_f64",
-    "scaml_posterior_linv_grad_f64",
-    "scaml_target_posterior_grad_f64",
-    "scaml_target_fantasy_acqf_f64",
-    "scaml_target_fit_max_n",
-    "scaml_target_fit_max_d",
-    "scaml_target_fit_workspace_doubles",
-    "scaml_target_mll_f64",
-    "scaml_target_fit_f64",
-)
 
 
 def check_rc(rc: int, what: str) -> None:

@@ -31,13 +31,23 @@ extern "C" int emul_target_fit(const double* means_t, const double* covs_p, cons
   p.z = z; p.value = value; p.grad = grad; p.info = info; p.jitter = jitter; p.workspace = ws.data(); p.stats = stats;
   p.B = B; p.n = n; p.T = T; p.D = D; p.kind = kind; p.mode = mode; p.max_iter = max_iter; p.history = history; p.max_ls = 20;
   p.gtol = gtol; p.ftol = ftol;
-  std::vector<double> lds((size_t)(n + 1) * (n + 2) + n * D + 8 * n + 2 * T + 3 * D + 200);
+  std::vector<double> lds(target_fit_lds_doubles(n, T, D, false, 1));
   for (int b = 0; b < B; ++b) {
     TfCtx c;
     c.tid = 0; c.nthr = 1; c.lane = 0; c.wave = 0; c.nwave = 1; c.solo = 0;
     c.n = n; c.T = T; c.D = D; c.P = P; c.E = n * (n + 1) / 2; c.kind = kind;
-    tf_carve(c, lds.data(), n, T, D, 1, 0);
+    if (tf_carve(c, lds.data(), n, T, D, 1, 0) != lds.data() + lds.size()) return -1;
     tf_main(c, p, b);
   }
   return 0;
+}
+
+// The LDS footprint twice: where the kernel's carve ends, and what the host launcher asks for (csrc/gp_target_params.h).
+extern "C" long long emul_target_fit_carve_doubles(int n, int T, int D, int waves, int mfma) {
+  std::vector<double> lds(scaml::target_fit_lds_doubles(n, T, D, mfma != 0, waves) + 4096);
+  scaml::TfCtx c;
+  return (long long)(scaml::tf_carve(c, lds.data(), n, T, D, waves, mfma) - lds.data());
+}
+extern "C" long long emul_target_fit_lds_doubles(int n, int T, int D, int waves, int mfma) {
+  return (long long)scaml::target_fit_lds_doubles(n, T, D, mfma != 0, waves);
 }

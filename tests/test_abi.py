@@ -3,14 +3,15 @@ include/scaml_gp.h declares; argument validation happens before any HIP call."""
 import ctypes
 import os
 import re
+import subprocess
 
 from scamlgp_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared_symbols():
-    text = open(os.path.join(ROOT, "include", "scaml_gp.h")).read()
+def _declared_symbols(header="scaml_gp.h"):
+    text = open(os.path.join(ROOT, "include", header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(scaml_[a-z0-9_]+)\s*\(", text)))
 
@@ -22,6 +23,19 @@ def test_header_symbols_are_exported():
     for name in declared:
         assert hasattr(dll, name), f"{name} declared in scaml_gp.h but not exported"
     assert sorted(_lib.EXPORTED_SYMBOLS) == declared
+
+
+def test_exported_functions_are_exactly_the_two_headers():
+    """No more and no fewer: every scaml_* function the library exports is declared in scaml_gp.h or scaml_gp_debug.h.
+    (The only other scaml_* exports are the two data objects of the embedded code object, which the build emits.)"""
+    debug = _declared_symbols("scaml_gp_debug.h")
+    assert len(debug) == 5 and all(name.startswith("scaml_debug_") for name in debug)
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {(kind, name) for _, kind, name in (line.split() for line in out.splitlines() if len(line.split()) == 3)
+                if name.startswith("scaml_")}
+    data = {("R", "scaml_hsaco_blob"), ("R", "scaml_hsaco_blob_len")}
+    assert exported - data == {("T", name) for name in _declared_symbols() + debug}
+    assert sorted(_lib.SIGNATURES) == sorted(_declared_symbols() + debug)
 
 
 def test_version_and_limits():

@@ -33,6 +33,17 @@ def emul(tmp_path_factory):
     return lib
 
 
+def test_carve_ends_at_the_footprint_the_launcher_requests(emul):
+    """tf_carve (device side) and target_fit_lds_doubles (what the host asks for) are the same number of doubles."""
+    for f in (emul.emul_target_fit_carve_doubles, emul.emul_target_fit_lds_doubles):
+        f.restype, f.argtypes = ctypes.c_longlong, [ctypes.c_int] * 5
+    for mfma, n_max in ((0, 144), (1, 112)):
+        for n in range(1, n_max + 1):
+            for T, D, waves in ((1, 1, 8), (32, 7, 8), (512, 16, 8), (5, 3, 1), (5, 3, 4)):
+                args = (n, T, D, waves, mfma)
+                assert emul.emul_target_fit_carve_doubles(*args) == emul.emul_target_fit_lds_doubles(*args), args
+
+
 def _call(lib, prob, z, mode, max_iter=200, history=10):
     dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
     B, P = z.shape

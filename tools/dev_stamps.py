@@ -12,9 +12,10 @@ if PER_PANEL:
     sys.argv.remove("--per-panel")
 _name = ("libscaml_hip_onepanel%s.so" % ONE[0][len("--one-panel"):]) if ONE else ("libscaml_hip_perpanel.so" if PER_PANEL else "libscaml_hip_stamps%s.so" % os.environ.get("STAMP_WAVE", "0"))
 lib = ctypes.CDLL(os.path.join(ROOT, "scalable-meta-learning-with-gaussian-processes_amd", "lib", _name))
+from scamlgp_amd._lib import SIGNATURES
 vp = ctypes.c_void_p
 lib.scaml_gp_fit_fused_f64.argtypes = [vp]*5 + [ctypes.c_int]*4 + [vp]*8 + [ctypes.c_uint, vp]
-lib.scaml_debug_set_stamp_buffer.argtypes = [vp]
+lib.scaml_debug_set_stamp_buffer.restype, lib.scaml_debug_set_stamp_buffer.argtypes = SIGNATURES["scaml_debug_set_stamp_buffer"]
 T, N, D = int(sys.argv[1]) if len(sys.argv) > 1 else 256, int(sys.argv[2]) if len(sys.argv) > 2 else 256, int(sys.argv[3]) if len(sys.argv) > 3 else 8
 kind = int(sys.argv[4]) if len(sys.argv) > 4 else 1
 dev = torch.device("cuda:0")
