@@ -338,6 +338,37 @@ int scaml_target_fit_f64(const double* means_t, const double* covs_packed, const
                          double ftol, double* value, int32_t* info, double* jitter_used, int32_t* stats, double* workspace,
                          long long workspace_doubles, void* stream);
 
+/*
+ * (9) Training the source GPs on the device: the hyper-parameter fit of a whole stack, B = tasks x starts problems side by side
+ * (scamlgp/model.py:176-188 -> scamlgp/utils.py:139-212: L-BFGS on -(mll + sum log p(theta) / n) over the raw parameters of the
+ * sigmoid Interval constraints, from the warm start and from every prior-sampled restart).
+ * One call enqueues n_evals rounds of { fit at the trial point ((3) / (3b)), MLL gradient (4), optimiser step } on `stream` and
+ * returns; nothing is synchronised.  The step kernel (csrc/gp_stack_fit.hip, one wave per problem) runs the per-problem state
+ * machine of a backtracking L-BFGS: Armijo test with halving (c1 = 1e-4, 20 trials), curvature pairs (`history` <= 16 of them),
+ * stopping rules max|g| <= gtol, relative decrease <= ftol, max_iter iterations.  Problems do not wait for each other; a finished
+ * problem is still evaluated (at its accepted point) until the caller stops calling.
+ *   X (B, N, D), y (B, N), n_points (B) or NULL: the data, replicated per start by the caller (problem b = start * T + task).
+ *   spec_host: HOST pointer to 15 doubles, the first 15 of (8)'s block: Interval bounds and (kind, p1, p2) of the lengthscale,
+ *       outputscale and noise priors.
+ *   z (B, D + 2): raw start points in; after every call the accepted point of each problem.
+ *   value (B): mll + sum log p(theta) / n at z.   stats (B, 4) int32: [iterations, evaluations, status, 0], status 0 still running,
+ *       1 / 2 converged (gradient / decrease), 3 line search failed, 4 objective not finite at the start point, 5 max_iter.
+ *   flags: SCAML_STACK_FIT_CONTINUE resumes from the state the previous call left in `workspace` (same arguments otherwise);
+ *       without it the first round evaluates z and initialises the state.  The caller reads stats and calls again while any
+ *       problem is still running.  Chunking does not change the result.
+ *   workspace: scaml_stack_fit_workspace_bytes(B, N, D, history) bytes, 16-byte aligned; it starts with the per-problem state,
+ *       (4 + 2 history) (D + 2) + history + 16 doubles each: accepted point, its gradient (d objective / d raw, objective =
+ *       -value), direction, trial point, the pairs, scalars.
+ * Shapes: what (3) / (3b) and (4) take (N <= 512, a multiple of 16 beyond 256; their D limits) and D <= scaml_stack_fit_max_d();
+ * SCAML_E_TOOLARGE otherwise.  B == 0 or n_evals == 0: nothing is enqueued.
+ */
+#define SCAML_STACK_FIT_CONTINUE 1u
+int scaml_stack_fit_max_d(void);
+long long scaml_stack_fit_workspace_bytes(int B, int N, int D, int history);
+int scaml_stack_fit_f64(const double* X, const double* y, const int32_t* n_points, const double* spec_host, double* z, int B, int N,
+                        int D, int kind, int n_evals, unsigned flags, int max_iter, int history, double gtol, double ftol,
+                        double* value, int32_t* stats, void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@
 #include "gp_posterior_params.h"
 #include "gp_target_params.h"
 #include "gp_fantasy_params.h"
+#include "gp_stack_fit_params.h"
 #include <math.h>
 
 extern "C" const unsigned char scaml_hsaco_blob[];   // generated: lib/hsaco_blob.c
@@ -66,7 +67,7 @@ struct Module {
   hipFunction_t wsum = nullptr, linv = nullptr, chosolve = nullptr, kmat[2] = {}, mllgrad[2] = {};
   hipFunction_t tgt_assemble[2] = {}, tgt_finish = nullptr, tgt_fit = nullptr, tgt_grad[2] = {};
   hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {};   // value only; value + gradient per kind
-  hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {};
+  hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {}, stack_step = nullptr;
   hipFunction_t blk_solve[2][2] = {}, blk_syrk[2] = {};   // solve: [kind][D <= 8]
   hipFunction_t mllgrad_fused[4][2][2] = {};   // [size class NBT = 2, 4, 8, 16][kind][LDS-DMA staging]
   hipFunction_t mllgrad_split[2][2][2] = {};   // LDS-DMA staging, [N <= 128 | N <= 256 class][kind][2 | 4 workgroups per task]
@@ -102,6 +103,7 @@ struct Module {
         {&tgt_fantasy_grad[1], "scaml_target_fantasy_acqf_grad_matern_kernel", 0, {}},
         {&tgt_fit, "scaml_target_fit_kernel", kLdsLimit, {}},
         {coop, "_ZN5scaml18gp_fit_coop_kernelILi%dEEEvNS_13CoopFitParamsE", kLdsLimit, {K}},
+        {&stack_step, "scaml_stack_fit_step_kernel", 0, {}},
         {&blk_round, "scaml_blocked_round_kernel", 0, {}},
         {&blk_finish, "scaml_blocked_finish_kernel", 0, {}},
         {&blk_solve[0][0], "_ZN5scaml23gp_blocked_solve_kernelILi%dELb%dEEEvNS_16BlockedFitParamsE", kLdsLimit, {K, B}},
@@ -737,18 +739,23 @@ size_t target_fit_lds_bytes(int n, int T, int D, bool mfma) {
 bool target_fit_use_mfma(int n, int T, int D) {
   return g_dev.target_fit_path.load(kRelaxed) == 0 && n <= 112 && target_fit_lds_bytes(n, T, D, true) <= kLdsLimit;
 }
+// one (kind, p1, p2) triple of a constraint / prior block
+int prior_from_host(const double* t, scaml::TargetPrior& pr) {
+  const int kind = (int)t[0];
+  const double p1 = t[1], p2 = t[2];
+  if (kind < 0 || kind > 2) return SCAML_E_BADARG;
+  if (kind == 1 && !(p1 > 0.0 && p2 > 0.0)) return SCAML_E_BADARG;
+  if (kind == 2 && !(p2 > 0.0)) return SCAML_E_BADARG;
+  pr.kind = kind; pr.pad_ = 0; pr.p1 = p1; pr.p2 = p2;
+  pr.c0 = kind == 1 ? p1 * log(p2) - lgamma(p1) : (kind == 2 ? -log(p2) - 0.9189385332046727 : 0.0);
+  return SCAML_OK;
+}
 int target_spec_from_host(const double* spec, scaml::TargetSpec& sp) {
   sp.ls_lo = spec[0]; sp.ls_hi = spec[1]; sp.os_lo = spec[2]; sp.os_hi = spec[3]; sp.nz_lo = spec[4]; sp.nz_hi = spec[5];
   if (!(sp.ls_hi > sp.ls_lo) || !(sp.os_hi > sp.os_lo) || !(sp.nz_hi > sp.nz_lo)) return SCAML_E_BADARG;
   scaml::TargetPrior* pr[4] = {&sp.ls_prior, &sp.os_prior, &sp.nz_prior, &sp.w_prior};
   for (int q = 0; q < 4; ++q) {
-    const int kind = (int)spec[6 + 3 * q];
-    const double p1 = spec[7 + 3 * q], p2 = spec[8 + 3 * q];
-    if (kind < 0 || kind > 2) return SCAML_E_BADARG;
-    if (kind == 1 && !(p1 > 0.0 && p2 > 0.0)) return SCAML_E_BADARG;
-    if (kind == 2 && !(p2 > 0.0)) return SCAML_E_BADARG;
-    pr[q]->kind = kind; pr[q]->pad_ = 0; pr[q]->p1 = p1; pr[q]->p2 = p2;
-    pr[q]->c0 = kind == 1 ? p1 * log(p2) - lgamma(p1) : (kind == 2 ? -log(p2) - 0.9189385332046727 : 0.0);
+    if (prior_from_host(spec + 6 + 3 * q, *pr[q]) != SCAML_OK) return SCAML_E_BADARG;
   }
   sp.w_lower = spec[18];
   return SCAML_OK;
@@ -811,6 +818,98 @@ int scaml_target_fit_f64(const double* means_t, const double* covs_packed, const
   p.B = B; p.n = n; p.T = T; p.D = D; p.kind = kind; p.mode = 1; p.max_iter = max_iter; p.history = history; p.max_ls = 20;
   p.gtol = gtol; p.ftol = ftol;
   return target_fit_launch(p, stream);
+}
+
+// ---- (9) source stack: the whole hyper-parameter fit as rounds of { fit, MLL gradient, optimiser step } (csrc/gp_stack_fit.hip) ----
+namespace {
+struct StackFitLayout {
+  size_t state, theta, L, alpha, linv, quad, logdet, mll, jitter, info, grad, blocked, total;
+};
+StackFitLayout stack_fit_layout(int B, int N, int D, int history) {
+  const size_t b = (size_t)B, n = (size_t)N, P = (size_t)D + 2, nb = (n + 15) / 16;
+  StackFitLayout l{};
+  size_t o = 0;
+  auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  l.state = take(b * scaml::stack_fit_state_doubles((int)P, history) * 8);   // (first: the caller may read the state, include/scaml_gp.h)
+  l.theta = take(b * P * 8);
+  l.L = take(b * n * n * 8);
+  l.alpha = take(b * n * 8);
+  l.linv = take(b * nb * 256 * 8);
+  l.quad = take(b * 8);
+  l.logdet = take(b * 8);
+  l.mll = take(b * 8);
+  l.jitter = take(b * 8);
+  l.info = take(b * 4);
+  l.grad = take((size_t)scaml_mll_backward_workspace_doubles(B, N, D) * 8);
+  l.blocked = take(N > 256 ? (size_t)scaml_gp_fit_blocked_workspace_bytes(B, N) : 0);
+  l.total = o;
+  return l;
+}
+}  // namespace
+
+int scaml_stack_fit_max_d(void) { return scaml::STACK_FIT_PMAX - 2; }
+
+long long scaml_stack_fit_workspace_bytes(int B, int N, int D, int history) {
+  if (B < 0 || N < 1 || N > scaml_fit_blocked_max_n() || D < 1 || D > scaml_stack_fit_max_d() || history < 1 || history > scaml::STACK_FIT_HMAX) return 0;
+  return (long long)stack_fit_layout(B, N, D, history).total;
+}
+
+int scaml_stack_fit_f64(const double* X, const double* y, const int32_t* n_points, const double* spec_host, double* z, int B, int N,
+                        int D, int kind, int n_evals, unsigned flags, int max_iter, int history, double gtol, double ftol,
+                        double* value, int32_t* stats, void* workspace, long long workspace_bytes, void* stream) {
+  if (B < 0 || N < 1 || D < 1 || n_evals < 0 || max_iter < 0) return SCAML_E_BADARG;
+  if (!X || !y || !spec_host || !z || !value || !stats || !workspace) return SCAML_E_BADARG;
+  if (!valid_kind(kind) || (flags & ~SCAML_STACK_FIT_CONTINUE)) return SCAML_E_BADARG;
+  if (history < 1 || history > scaml::STACK_FIT_HMAX) return SCAML_E_BADARG;
+  scaml::StackFitSpec sp{spec_host[0], spec_host[1], spec_host[2], spec_host[3], spec_host[4], spec_host[5], {}, {}, {}};
+  if (!(sp.ls_hi > sp.ls_lo) || !(sp.os_hi > sp.os_lo) || !(sp.nz_hi > sp.nz_lo)) return SCAML_E_BADARG;
+  scaml::TargetPrior* pr[3] = {&sp.ls_prior, &sp.os_prior, &sp.nz_prior};
+  for (int q = 0; q < 3; ++q) {
+    if (prior_from_host(spec_host + 6 + 3 * q, *pr[q]) != SCAML_OK) return SCAML_E_BADARG;
+  }
+  // the shapes the fit and gradient paths take
+  const bool blocked = N > scaml_fit_max_n();
+  if (N > scaml_fit_blocked_max_n() || (blocked && (N & 15))) return SCAML_E_TOOLARGE;
+  if (D > scaml_stack_fit_max_d() || D > (blocked ? scaml_fit_blocked_max_d() : scaml_fit_max_d(N))) return SCAML_E_TOOLARGE;
+  if (scaml::mll_grad_lds_doubles(D) * sizeof(double) > kLdsLimit - 2048) return SCAML_E_TOOLARGE;
+  const StackFitLayout lay = stack_fit_layout(B, N, D, history);
+  if (workspace_bytes < (long long)lay.total || ((uintptr_t)workspace & 15)) return SCAML_E_BADARG;
+  if (B == 0 || n_evals == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  char* ws = (char*)workspace;
+  double *theta = (double*)(ws + lay.theta), *L = (double*)(ws + lay.L), *alpha = (double*)(ws + lay.alpha), *linv = (double*)(ws + lay.linv);
+  double *quad = (double*)(ws + lay.quad), *logdet = (double*)(ws + lay.logdet), *mll = (double*)(ws + lay.mll), *jit = (double*)(ws + lay.jitter);
+  int32_t* info = (int32_t*)(ws + lay.info);
+  double* gwork = (double*)(ws + lay.grad);
+  const int nb = (N + 15) / 16, tiles = nb * (nb + 1) / 2;
+  double* partials = gwork + (size_t)B * N * N;
+  scaml::StackFitParams p{mll, info, partials, n_points, sp, z, theta, value, stats, (double*)(ws + lay.state), B, N, D, tiles, 1,
+                          max_iter, history, 20, gtol, ftol, 1e-4};
+  int rc = SCAML_OK;
+  if (!(flags & SCAML_STACK_FIT_CONTINUE)) {
+    if (n_points) {   // ragged stacks: rows past n_t are never written by the fit but read by the solves
+      hipError_t e = hipMemsetAsync(L, 0, (size_t)B * N * N * 8, (hipStream_t)stream);
+      if (e == hipSuccess) e = hipMemsetAsync(alpha, 0, (size_t)B * N * 8, (hipStream_t)stream);
+      if (e != hipSuccess) { set_error("hipMemsetAsync(stack fit factors)", e); return SCAML_E_LAUNCH; }
+    }
+    p.mode = 0;
+    if ((rc = launch(m->stack_step, dim3((unsigned)B), 64, 0, stream, "stack_fit_step", p)) != SCAML_OK) return rc;
+    p.mode = 1;
+  }
+  for (int r = 0; r < n_evals; ++r) {
+    if (blocked) {
+      rc = scaml_gp_fit_blocked_f64(X, y, theta, n_points, nullptr, B, N, D, kind, L, alpha, quad, logdet, mll, info, jit, linv, SCAML_FIT_STORE_L,
+                                    ws + lay.blocked, (long long)(lay.total - lay.blocked), stream);
+    } else {
+      scaml::FitParams f{X, y, theta, n_points, nullptr, nullptr, L, alpha, quad, logdet, mll, info, jit, linv, B, N, D, SCAML_FIT_STORE_L};
+      rc = fit_common(f, kind, stream);
+    }
+    if (rc != SCAML_OK) return rc;
+    if ((rc = scaml_mll_backward_f64(X, theta, L, linv, alpha, n_points, B, N, D, kind, gwork, partials, stream)) != SCAML_OK) return rc;
+    if ((rc = launch(m->stack_step, dim3((unsigned)B), 64, 0, stream, "stack_fit_step", p)) != SCAML_OK) return rc;
+  }
+  return SCAML_OK;
 }
 
 }  // extern "C"

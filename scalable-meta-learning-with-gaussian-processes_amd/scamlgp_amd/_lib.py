@@ -28,6 +28,7 @@ FIT_ZERO_UPPER = 2
 FIT_NO_RETRY = 4
 POST_XQ_PER_TASK = 1
 POST_MEAN_ONLY = 2
+STACK_FIT_CONTINUE = 1
 
 E_BADARG = -1
 E_TOOLARGE = -2
@@ -41,7 +42,7 @@ class ScamlLibraryError(RuntimeError):
 
 
 _i, _u, _ll, _f = c_int, c_uint, ctypes.c_longlong, ctypes.c_double
-_host_spec = ctypes.POINTER(_f)   # (the one host pointer of the ABI: 19 doubles read during the call)
+_host_spec = ctypes.POINTER(_f)   # (the one host pointer of the ABI: 19 doubles -- stack fit: 15 -- read during the call)
 
 # The C ABI, once: name -> (restype, argtypes).  include/scaml_gp.h declares the entry points, include/scaml_gp_debug.h the
 # scaml_debug_* developer switches.
@@ -99,6 +100,9 @@ SIGNATURES = {
     "scaml_target_fit_workspace_doubles": (_ll, [_i, _i, _i, _i]),
     "scaml_target_mll_f64": (_i, [_dp] * 4 + [_f, _f, _host_spec, _dp] + [_i] * 5 + [_dp] * 4 + [c_void_p]),
     "scaml_target_fit_f64": (_i, [_dp] * 4 + [_f, _f, _host_spec, _dp] + [_i] * 7 + [_f, _f] + [_dp] * 5 + [_ll, c_void_p]),
+    "scaml_stack_fit_max_d": (_i, []),
+    "scaml_stack_fit_workspace_bytes": (_ll, [_i, _i, _i, _i]),
+    "scaml_stack_fit_f64": (_i, [_dp, _dp, _dp, _host_spec, _dp] + [_i] * 5 + [_u, _i, _i, _f, _f, _dp, _dp, _dp, _ll, c_void_p]),
     "scaml_debug_target_fit_path": (_i, [_i]),
     "scaml_debug_blocked_fit_path": (_i, [_i]),
     "scaml_debug_coop_far": (_i, [_i]),

@@ -316,8 +316,12 @@ def meta_fit_scamlgp(
     device: Optional[torch.device] = None,
     shard: bool = False,
     group=None,
+    fit_options: Optional[dict] = None,
 ) -> Dict[Hashable, SourceGP]:
     """Train the source GPs on the given meta-data (scamlgp/model.py:138-189).
+
+    ``fit_options`` is forwarded to ``optimize_marginal_likelihood`` (the reference forwards ``fit_gpytorch_options`` the same
+    way, scamlgp/utils.py:139-175), e.g. ``{"driver": "device"}`` for the optimiser on the device.
 
     ``shard=True`` under an initialised torch.distributed group (one process per GPU): every rank is handed the SAME
     ``meta_data`` and keeps, fits and returns only its contiguous shard of the tasks (``dist.shard_range``); the
@@ -347,7 +351,7 @@ def meta_fit_scamlgp(
     Xs, Ys = zip(*[_canonical_order(d.X(), d.Y()) for d in data])
     stack = SourceGPStack(task_ids, Xs, Ys, kind=cov.kind, spec=hyper.spec_from_modules(lik, cov), device=device)
     stack.shard = ts if ts is not None and ts.world > 1 else None
-    optimize_marginal_likelihood(stack, num_restarts=num_restarts_log_likelihood)
+    optimize_marginal_likelihood(stack, num_restarts=num_restarts_log_likelihood, **(fit_options or {}))
     return {tid: SourceGP(stack, i) for i, tid in enumerate(stack.task_ids)}
 
 

@@ -874,6 +874,81 @@ def target_fit(prob: TargetFitProblem, z0: torch.Tensor, max_iter: int = 200, hi
     return dict(z=z, value=value, info=info, jitter=jit, stats=stats)
 
 
+# ---- (9) source stack: the whole hyper-parameter fit enqueued on the device ---------------------------------------------------
+# rounds enqueued between two reads of the status.  Measured (tools/dev_stackfit_time.py, profiles/stack_fit_timings.txt): the cost per
+# evaluation is flat from 4 on (the rounds are GPU-bound), and every round past the last problem's stop is a wasted evaluation of the
+# whole batch, so the smallest value past the knee is the default.
+STACK_FIT_EVALS_PER_CALL = 4
+_STACK_FIT_MAX_LS = 20          # trials per line search inside scaml_stack_fit_f64
+
+
+def stack_spec_host(spec):
+    """The 15 host doubles ``scaml_stack_fit_f64`` reads: Interval bounds and (kind, p1, p2) of the three hyper-priors."""
+    import ctypes
+
+    from . import hyper
+
+    def prior(pr):
+        if pr is None:
+            return [0.0, 0.0, 0.0]
+        if isinstance(pr, hyper.GammaPrior):
+            return [1.0, pr.concentration, pr.rate]
+        if isinstance(pr, hyper.LogNormalPrior):
+            return [2.0, pr.loc, pr.scale]
+        raise TypeError(f"prior {type(pr).__name__} is not supported by the stack-fit kernel")
+
+    vals = [spec.ls_constraint.lower, spec.ls_constraint.upper, spec.os_constraint.lower, spec.os_constraint.upper,
+            spec.noise_constraint.lower, spec.noise_constraint.upper, *prior(spec.ls_prior), *prior(spec.os_prior), *prior(spec.noise_prior)]
+    return (ctypes.c_double * 15)(*[float(v) for v in vals])
+
+
+def stack_fit(X: torch.Tensor, y: torch.Tensor, n_points: Optional[torch.Tensor], spec, z0: torch.Tensor, kind: int, *,
+              max_iter: int = 200, history: int = 10, gtol: float = 1e-5, ftol: float = 2.2e-9,
+              evals_per_call: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """Minimise -(mll + sum log p(theta) / n) from every row of z0 (B, D + 2) (raw parameters; problem b uses X[b], y[b]) with
+    ``scaml_stack_fit_f64``: every call enqueues ``evals_per_call`` rounds of fit + MLL gradient + optimiser step for all B problems,
+    then the status column is read -- the only synchronisation -- and the fit continues while a problem is still running (at most
+    ``1 + max_iter * 20`` evaluations: then every problem has stopped).  ``hyper.batched_lbfgs`` per problem, without the host.
+    Returns dict(z (B, D+2) accepted points, value (B,) mll + prior term there, grad (B, D+2) gradient of -value there,
+    stats (B, 4) int32 [iterations, evaluations, status, 0] on the host, n_eval rounds enqueued, n_calls)."""
+    if X.dim() != 3:
+        raise ValueError("X must be (B, N, D)")
+    B, N, D = X.shape
+    P = D + 2
+    X = _check(X, "X")
+    y = _check(y, "y", (B, N))
+    z = _check(z0, "z0", (B, P)).clone()
+    if n_points is not None:
+        n_points = _check(n_points, "n_points", (B,), torch.int32)
+    per_call = int(evals_per_call or STACK_FIT_EVALS_PER_CALL)
+    if per_call < 1:
+        raise ValueError("evals_per_call must be positive")
+    spec_host = stack_spec_host(spec)
+    dev = X.device
+    budget = 1 + int(max_iter) * _STACK_FIT_MAX_LS
+    n_eval = n_calls = 0
+    with torch.cuda.device(dev):
+        value = torch.empty((B,), dtype=torch.float64, device=dev)
+        stats = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+        nbytes = int(_lib.lib.scaml_stack_fit_workspace_bytes(B, N, D, int(history)))
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        host = stats.cpu()
+        while B > 0:
+            k = min(per_call, budget - n_eval)
+            rc = _lib.lib.scaml_stack_fit_f64(_ptr(X), _ptr(y), _ptr(n_points), spec_host, _ptr(z), B, N, D, int(kind), k,
+                                              _lib.STACK_FIT_CONTINUE if n_calls else 0, int(max_iter), int(history), float(gtol),
+                                              float(ftol), _ptr(value), _ptr(stats), _ptr(ws), nbytes, _stream_handle())
+            _lib.check_rc(rc, "scaml_stack_fit_f64")
+            n_eval += k
+            n_calls += 1
+            host = stats.cpu()
+            if not bool((host[:, 2] == 0).any()) or n_eval >= budget:
+                break
+        stride = (4 + 2 * int(history)) * P + int(history) + 16   # the per-problem state opens the workspace (include/scaml_gp.h)
+        grad = ws[: B * stride * 8].view(torch.float64).reshape(B, stride)[:, P:2 * P].clone()
+    return dict(z=z, value=value, grad=grad, stats=host, n_eval=n_eval, n_calls=n_calls)
+
+
 def raise_if_not_psd(info: torch.Tensor) -> None:
     """Host-side check of the per-task status (one device->host sync)."""
     if bool((info < 0).any()):

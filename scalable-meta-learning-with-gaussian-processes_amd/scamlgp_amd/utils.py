@@ -58,9 +58,57 @@ class _GraphedBatchObjective:
         return self.f.clone(), self.g.clone()
 
 
-def _fit_stack(stack: SourceGPStack, num_restarts: int, max_iter: int = 200, use_graph: bool = True) -> None:
+def _stack_starts(stack: SourceGPStack, num_restarts: int) -> torch.Tensor:
+    """Warm start + ``num_restarts`` prior samples per task, problem b = rep * T + task."""
+    starts = [stack.raw.clone()]
+    for _ in range(num_restarts):
+        starts.append(stack.spec.to_raw(stack.spec.sample_prior((stack.T,), stack.D, device=stack.device)))
+    return torch.cat(starts, 0)
+
+
+def _keep_best(stack: SourceGPStack, x: torch.Tensor, f: torch.Tensor, reps: int, info: dict) -> None:
+    """Best-of-starts per task (f (reps * T,), inf = failed attempt), then the stack's factors at the chosen parameters."""
+    T, D = stack.T, stack.D
+    f = f.reshape(reps, T)
+    best = f.argmin(0)
+    if bool(torch.isinf(f.min(0).values).any()):
+        bad = torch.nonzero(torch.isinf(f.min(0).values)).flatten().tolist()
+        raise ModelFittingError(
+            "Hyperparameter optimization failed for all attempts. Usually this indicates a problem with model's "
+            f"input data or hyperparameter priors definitions. (tasks {[stack.task_ids[i] for i in bad][:8]})")
+    n_failed = int(torch.isinf(f).sum())
+    if n_failed:
+        logger.warning("%d of %d hyper-parameter optimisation attempts failed and were skipped.", n_failed, f.numel())
+    stack.raw = x.reshape(reps, T, D + 2)[best, torch.arange(T, device=stack.device)].contiguous()
+    stack.refresh()
+    obj = -f.min(0).values
+    # (a sharded stack also reports the objective summed over every rank's tasks: the fit's one collective)
+    total = sdist.fused_allreduce([obj.sum().reshape(1)], stack.shard)[0]
+    stack.last_fit_info = dict(objective=obj, objective_sum=total.squeeze(0), **info)
+
+
+def _fit_stack_device(stack: SourceGPStack, num_restarts: int, max_iter: int, evals_per_call=None) -> None:
+    """``_fit_stack`` with the optimiser on the device: ``ops.stack_fit`` enqueues fit + gradient + L-BFGS step for all problems and
+    reads only the status column back, once per chunk of evaluations."""
+    reps = 1 + num_restarts
+    x0 = _stack_starts(stack, num_restarts)
+    c = stack._replicated(reps)
+    res = ops.stack_fit(c["X"], c["y"], c["npts"], stack.spec, x0, stack.kind, max_iter=max_iter, evals_per_call=evals_per_call)
+    status = res["stats"][:, 2].to(stack.device)
+    f = -res["value"]
+    f = torch.where((status == 4) | ~torch.isfinite(f), torch.full_like(f, float("inf")), f)
+    _keep_best(stack, res["z"], f, reps, dict(n_iter=int(res["stats"][:, 0].max()), n_eval=res["n_eval"], stats=res["stats"]))
+
+
+def _fit_stack(stack: SourceGPStack, num_restarts: int, max_iter: int = 200, use_graph: bool = True, driver: str = "host",
+               evals_per_call=None) -> None:
     """All T tasks x (1 + num_restarts) starts as ONE batch: every L-BFGS iteration is one fused-fit
-    launch + one gradient launch over (1 + R) * T problems."""
+    launch + one gradient launch over (1 + R) * T problems.  ``driver="device"`` keeps the optimiser itself on the device as well
+    (``scaml_stack_fit_f64``: same starts, same algorithm per problem, no host round trip per evaluation)."""
+    if driver == "device":
+        return _fit_stack_device(stack, num_restarts, max_iter, evals_per_call)
+    if driver != "host":
+        raise ValueError(f"driver must be 'host' or 'device', got {driver!r}")
     T, D = stack.T, stack.D
     reps = 1 + num_restarts
     starts = [stack.raw.clone()]
