@@ -9,14 +9,13 @@ namespace scaml {
 // C++ values hipcc shuffled all 136 registers through copies at every merge of the unrolled step code (and, like in
 // the fused fit, spilled).  Every access is an asm statement naming the physical registers (csrc/tile_regs.inc); the
 // build sets "amdgpu-agpr-alloc"="0" so the compiler keeps out of the AGPR half, and caps the arch VGPRs so that
-// VGPRs + block AGPRs <= 256 (two waves per SIMD).  Hazards hipcc cannot see inside asm: GF_DRAIN (19 wait states)
+// VGPRs + block AGPRs <= 256 (two waves per SIMD).  Hazards hipcc cannot see inside asm: MFMA_DRAIN (scaml_common.hpp)
 // separates the last MFMA writing a register from any non-accumulating read of it (as MFMA A/B operand,
 // v_accvgpr_read, VALU); dependent accumulation into the same registers issues back to back (interlocked).
 #include "tile_regs.inc"
 #ifdef GF_NO_DRAIN   // (timing experiments only: the results are wrong without the wait states)
-#define GF_DRAIN() asm volatile("" ::: "memory")
-#else
-#define GF_DRAIN() asm volatile("s_nop 15\n\ts_nop 2" ::: "memory")
+#undef MFMA_DRAIN
+#define MFMA_DRAIN() asm volatile("" ::: "memory")
 #endif
 #ifdef GF_NO_MFMA    // (timing experiments only: everything but the matrix instructions)
 #define GF_MFMA(txt) "; " txt
@@ -168,14 +167,6 @@ __device__ __forceinline__ void gf_bwd_chain(GfOps& cur, int last, const double*
   }
 }
 #undef GF_BWD_CASE
-
-// value of an MFMA result for the VALU: 19 wait states behind the instruction (hipcc pads for the 8-pass gfx942
-// instruction; on gfx950 the last result pair is not interlocked), and the data dependency keeps the uses behind it
-__device__ __forceinline__ d4_t gf_settle(d4_t v) {
-  asm volatile("s_nop 15\n\ts_nop 2" : "+v"(v));
-  return v;
-}
-
 
 // ACC <- four doubles (element g = row lq + 4 g, column lc)
 __device__ __forceinline__ void gf_acc_set(double d0, double d1, double d2, double d3) {

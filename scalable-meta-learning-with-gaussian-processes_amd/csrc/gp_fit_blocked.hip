@@ -89,7 +89,7 @@ template <int KB>
 __device__ __forceinline__ void bk_solve_step(const double* pa) {
   GfOps cur = gf_load_ops(pa, 4);
   gf_fwd_chain<KB, BK_NB1, false>(cur, 0, pa);
-  GF_DRAIN();
+  MFMA_DRAIN();
   GfTile<gf_slot<BK_NB1, false>(KB)>::set_prod_acc(cur.a0, cur.a1, cur.a2, cur.a3);
 }
 
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(512) void gp_blocked_solve_kernel(BlockedFitParams 
       d2v = __builtin_amdgcn_mfma_f64_16x16x4f64(-2.0 * xa[lq], xb0, d2v, 0, 0, 0);
       d2v = __builtin_amdgcn_mfma_f64_16x16x4f64(-2.0 * xa[lq + 4], xb1, d2v, 0, 0, 0);
       d2v = __builtin_amdgcn_mfma_f64_16x16x4f64(lq == 0 ? xa[8] : (lq == 1 ? 1.0 : 0.0), xb2, d2v, 0, 0, 0);
-      d2v = gf_settle(d2v);
+      d2v = mfma_settled(d2v);
       if (strip_full && 16 * kb + 16 <= n1) {   // wave-uniform: nothing to mask
 #pragma unroll
         for (int g = 0; g < 4; ++g) out[64 * g] = kernel_from_sqdist_scaled<KIND>(KIND == 0 ? vmax_f64(d2v[g], 0.0) : d2v[g], kc0, kc1, kc2, exptab);
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(512) void gp_blocked_solve_kernel(BlockedFitParams 
     } else {
       const double* kin = kbuf + ((kb & 1) * 4 + sw) * 256 + lane;
       const double k0 = kin[0], k1 = kin[64], k2 = kin[128], k3 = kin[192];
-      GF_DRAIN();   // (the previous step's closing product may still be reading ACC)
+      MFMA_DRAIN();   // (the previous step's closing product may still be reading ACC)
       gf_acc_set(k0, k1, k2, k3);
       const double* pa = buf + (kb % 3) * BUF + lc * PA + lq;   // A operand: L[16 kb + lc][16 j + lq + 4 m]
       switch (kb) {
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(512) void gp_blocked_solve_kernel(BlockedFitParams 
     BK_STAMP(4 + 4 * kb);   // barrier passed
   }
   if (helper) return;
-  GF_DRAIN();
+  MFMA_DRAIN();
   // the strip goes to memory as rows of L21 (and, on request, zeros into the mirrored block of the upper triangle)
   const int N2 = N - BK_N1;
   const bool in_matrix = colpt < N2;
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(512, 4) void gp_blocked_syrk_kernel(BlockedFitParam
   }
   // half ks finishes row blocks 2 ks, 2 ks + 1; the other two go to the partner wave (w, 1 - ks)
 #pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = gf_settle(acc[r]);
+  for (int r = 0; r < 4; ++r) acc[r] = mfma_settled(acc[r]);
   {
     double* out = xch + wave * 512 + lane;
 #pragma unroll

@@ -48,7 +48,6 @@ constexpr unsigned CF_DEAD = 255u;      // failure count that stops every attemp
 #endif
 #define CF_FSTAMP(k) do { const int j = part + 30 * P; CF_STAMP(k); } while (0)   // (slot 30: inside the finish)
 
-__device__ __forceinline__ void cf_settle(d4_t& v) { asm volatile("s_nop 15\n\ts_nop 2" : "+v"(v)); }   // gfx950: last MFMA result pair not interlocked
 // workgroup barrier for LDS traffic only: __syncthreads() also waits for every global load in flight (its fences), which undoes a prefetch
 __device__ __forceinline__ void cf_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // payload store: write-through (sc1) in general; a plain store where every workgroup of the task sits on the same XCD (`near`): the line
@@ -192,7 +191,7 @@ __device__ __forceinline__ int cf_potf2_32(double* C, double* Dg, double* Wb, in
   d4_t acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int m = 0; m < 4; ++m) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(C[(16 + lc) * CF_BP + 4 * m + lq], Wb[lc * CF_BP + 4 * m + lq], acc, 0, 0, 0);
-  cf_settle(acc);
+  mfma_settle(acc);
 #pragma unroll
   for (int g = 0; g < 4; ++g) Dg[(16 + lq + 4 * g) * CF_BP + lc] = acc[g];
   // S = C22 - L21 L21^T
@@ -204,7 +203,7 @@ __device__ __forceinline__ int cf_potf2_32(double* C, double* Dg, double* Wb, in
     const double l = Dg[(16 + lc) * CF_BP + 4 * m + lq];
     s = __builtin_amdgcn_mfma_f64_16x16x4f64(-l, l, s, 0, 0, 0);
   }
-  cf_settle(s);
+  mfma_settle(s);
 #pragma unroll
   for (int g = 0; g < 4; ++g) C[(16 + lq + 4 * g) * CF_BP + 16 + lc] = s[g];
   if (stamps && lane == 0) stamps[9] = (double)wall_clock64();
@@ -220,11 +219,11 @@ __device__ __forceinline__ int cf_potf2_32(double* C, double* Dg, double* Wb, in
   d4_t t = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int m = 0; m < 4; ++m) t = __builtin_amdgcn_mfma_f64_16x16x4f64(Dg[(16 + lc) * CF_BP + 4 * m + lq], Wb[(4 * m + lq) * CF_BP + lc], t, 0, 0, 0);
-  cf_settle(t);
+  mfma_settle(t);
   d4_t w = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int m = 0; m < 4; ++m) w = __builtin_amdgcn_mfma_f64_16x16x4f64(-Wb[(16 + lc) * CF_BP + 16 + 4 * m + lq], t[m], w, 0, 0, 0);
-  cf_settle(w);
+  mfma_settle(w);
 #pragma unroll
   for (int g = 0; g < 4; ++g) Wb[(16 + lq + 4 * g) * CF_BP + lc] = w[g];
   return 0;
@@ -293,7 +292,7 @@ __device__ __forceinline__ d4_t cf_accumulate(d4_t acc, __amdgpu_buffer_rsrc_t r
   }
   // (settled here, not at the use: the registers of one slot's tile are reused for the next slot's, and a VALU write into the last
   //  result pair 17 wait states behind the MFMA is as unprotected as a read -- found by the build's hazard audit)
-  cf_settle(acc);
+  mfma_settle(acc);
   return acc;
 }
 
@@ -330,8 +329,8 @@ __device__ __forceinline__ void cf_accumulate_v(d4_t& r0, d4_t& r1, __amdgpu_buf
     b1 = cf_loadv(rsV, rs, baseV, baseB, rowskip, s + 4, s_hi);
     if (s + 2 < s_hi) cf_mmav(b2, r0, r1);
   }
-  cf_settle(r0);
-  cf_settle(r1);
+  mfma_settle(r0);
+  mfma_settle(r1);
 }
 
 // Two tiles with the same B rows (the same tile position in two consecutive block rows) in ONE pipeline: B is loaded once, and the two
@@ -368,8 +367,8 @@ __device__ __forceinline__ void cf_accumulate_a2(d4_t& r0, d4_t& r1, __amdgpu_bu
     b1 = cf_loada2(rs, baseA, baseC, baseB, s + 4, s_hi);
     if (s + 2 < s_hi) cf_mmaa2(b2, r0, r1);
   }
-  cf_settle(r0);
-  cf_settle(r1);
+  mfma_settle(r0);
+  mfma_settle(r1);
 }
 
 template <int KIND>
@@ -541,9 +540,9 @@ __global__ __launch_bounds__(512) void gp_fit_coop_kernel(CoopFitParams p) {
     };
     // C = K - sums of a finished slot into the chunk buffer (or, mode 2, L_j,0:j v into rvs)
     auto put = [&](Slot& sl, d4_t kt, double* Cdst) {
-      cf_settle(sl.acc);
+      mfma_settle(sl.acc);
       if (sl.mode == 2) {
-        cf_settle(rv1);
+        mfma_settle(rv1);
         if (lq == 0) {   // row 0 of the two products: (L_j,0:j v)[16 tj + lc]
           rvs[lc] = sl.acc[0];
           rvs[16 + lc] = rv1[0];
@@ -568,7 +567,7 @@ __global__ __launch_bounds__(512) void gp_fit_coop_kernel(CoopFitParams p) {
         for (int m = 0; m < 4; ++m)
           out = __builtin_amdgcn_mfma_f64_16x16x4f64(Cs[(16 * ti + lc) * CF_BP + 16 * tk + 4 * m + lq], Wb[(16 * tj + lc) * CF_BP + 16 * tk + 4 * m + lq], out, 0, 0, 0);
       }
-      cf_settle(out);
+      mfma_settle(out);
       const int col = 32 * j + 16 * tj + lc;
       if (col < n) {
 #pragma unroll
@@ -644,7 +643,7 @@ __global__ __launch_bounds__(512) void gp_fit_coop_kernel(CoopFitParams p) {
           if (!gone) {
             if (four) {
               const d4_t kt1b = kvals(j, s1.row + 1);
-              cf_settle(rv1);
+              mfma_settle(rv1);
 #pragma unroll
               for (int g = 0; g < 4; ++g) Cb[3 * CF_BS + (16 * ti + lq + 4 * g) * CF_BP + 16 * tj + lc] = kt1b[g] - rv1[g];
             }

@@ -314,7 +314,6 @@ __device__ __forceinline__ int potf2_inv_block(d4_t a, double* LT, double* Wt, d
                : "=&v"(out)                                                                        \
                : "v"(w0), "v"(w1), "v"(w2), "v"(w3))
 
-#define MFMA_DRAIN() asm volatile("s_nop 15\n\ts_nop 2" ::: "memory")
 
 // switch-dispatch of one runtime slot index onto the code for the matching physical tile
 #define SCAML_CASE_(S, r0, r1, r2, r3, r4, r5, r6, r7) \

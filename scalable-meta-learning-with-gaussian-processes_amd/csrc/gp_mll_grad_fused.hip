@@ -45,10 +45,10 @@ __device__ __forceinline__ void gf_fwd_strip(int c, const double* pa, int PA, in
     return;
   }
   GfOps cur = gf_load_ops(pa + 16 * c, 4);
-  GF_DRAIN();        // (the previous strip step's last MFMA may still be reading ACC)
+  MFMA_DRAIN();      // (the previous strip step's last MFMA may still be reading ACC)
   gf_acc_zero();
   gf_fwd_chain<KB, NBT, SB>(cur, c, pa);
-  GF_DRAIN();
+  MFMA_DRAIN();
   Dst::set_prod_acc(cur.a0, cur.a1, cur.a2, cur.a3);   // (W_KB sits in the staged row block's last 16 columns)
 }
 
@@ -58,12 +58,12 @@ template <int KB, int NBT, bool SB>
 __device__ __forceinline__ void gf_bwd_strip(int last, const double* pb, double* zout, int lane) {
   using Dst = GfTile<gf_slot<NBT, SB>(KB)>;
   GfOps cur = gf_load_ops(pb + 16 * (last > KB ? last : KB) * 16, 64);
-  GF_DRAIN();
+  MFMA_DRAIN();
   Dst::copy_to_acc();   // V_KB: written by the forward pass, many steps (and barriers) ago
   gf_bwd_chain<KB, NBT, SB>(cur, last, pb);
-  GF_DRAIN();
+  MFMA_DRAIN();
   Dst::set_prod_acc(cur.a0, cur.a1, cur.a2, cur.a3);
-  GF_DRAIN();
+  MFMA_DRAIN();
   const d4_t z = Dst::get();
   zout[lane] = z[0]; zout[64 + lane] = z[1]; zout[128 + lane] = z[2]; zout[192 + lane] = z[3];
 }
@@ -95,11 +95,7 @@ __device__ __forceinline__ void gf_kernel_and_dfactor(double d2, const double* e
     k = exp_neg_t<true>(-0.5 * d2, exptab);
     h = k;
   } else {
-    const double dd = vmin_f64(vmax_f64(d2, 1e-30), 1e5);   // (bare v_max / v_min: one instruction each)
-    const double y = (double)__builtin_amdgcn_rsqf((float)dd);
-    const double g = dd * y;
-    const double e = __builtin_fma(-g, y, 1.0);
-    const double r = __builtin_fma(g * e, __builtin_fma(e, 0.375, 0.5), g);
+    const double r = sqrt_clamped_seeded(d2);
     const double s5 = 2.2360679774997896964;
     const double ex = exp_neg_t<false>(-s5 * r, exptab);
     const double p1 = __builtin_fma(s5, r, 1.0);
@@ -143,7 +139,7 @@ __device__ __forceinline__ void gf_epilogue(GfStrip& st, const double* zt, int k
   d2v = __builtin_amdgcn_mfma_f64_16x16x4f64(-2.0 * xap[lq], xc0, d2v, 0, 0, 0);
   d2v = __builtin_amdgcn_mfma_f64_16x16x4f64(-2.0 * xap[lq + 4], xc1, d2v, 0, 0, 0);
   d2v = __builtin_amdgcn_mfma_f64_16x16x4f64(lq == 0 ? na : (lq == 1 ? 1.0 : 0.0), lq == 0 ? 1.0 : (lq == 1 ? nc : 0.0), d2v, 0, 0, 0);
-  d2v = gf_settle(d2v);
+  d2v = mfma_settled(d2v);
   const double ac = als[col];
   const double hs = os * gf_hscale<KIND>();
   d4_t GH;
@@ -189,10 +185,10 @@ __device__ __forceinline__ void gf_epilogue(GfStrip& st, const double* zt, int k
   for (int m = 0; m < 4; ++m) T = __builtin_amdgcn_mfma_f64_16x16x4f64(xk[4 * m * GF_DP], GH[m], T, 0, 0, 0);
   // (register-staged variants spill: hipcc once placed a scratch reload into the accumulator 16 wait states behind the last MFMA --
   //  the build's hazard audit refused the code object; those variants pay 19 idle cycles per block for a guaranteed distance)
-  if constexpr (SETTLE_T) T = gf_settle(T);
+  if constexpr (SETTLE_T) T = mfma_settled(T);
   st.T = T;
   if (kb == c) {
-    const d4_t Tf = gf_settle(T);
+    const d4_t Tf = mfma_settled(T);
     const double cscol = sum_lane_groups(st.cs);   // column sum over all rows of the strip
     // lane (lc, lq): rows lq, lq + 4 of Q (registers 0, 1) and of Q2 (registers 2, 3)
     pd0 += Tf[2] - 2.0 * xc0 * Tf[0] + xc0 * xc0 * cscol;

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(PosteriorParams 
         d2v = __builtin_amdgcn_mfma_f64_16x16x4f64(av, xb[s4 * 16], d2v, 0, 0, 0);
       }
       d2v = __builtin_amdgcn_mfma_f64_16x16x4f64(lq == 0 ? nr[arow] : (lq == 1 ? 1.0 : 0.0), bn, d2v, 0, 0, 0);
-      asm volatile("s_nop 15\n\ts_nop 2" : "+v"(d2v));   // (gfx950: the last result pair is not interlocked for VALU reads)
+      mfma_settle(d2v);
       const int row0 = 16 * kb + lq;
       if (GRAD) {
         // column 0: the kernel value; column c = 1 + d: os dk/d(d2) * 2 (x'_d - a'_d) / l_d with primes = coordinates / l_d
@@ -353,9 +353,7 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(PosteriorParams 
         for (int as = 0; as < MAXAS; ++as) {
           if (as < nas) {
             d4_t v = cacc[as];
-            {   // gfx950: the last result pair of an fp64 MFMA is not interlocked for VALU / LDS reads -- settle first
-              asm volatile("s_nop 15\n\ts_nop 2" : "+v"(v));
-            }
+            mfma_settle(v);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
               double* dst = cb + as * 256 + g * 64 + lane;

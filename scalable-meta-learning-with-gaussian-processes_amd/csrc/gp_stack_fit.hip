@@ -51,21 +51,6 @@ SF_DEV double sf_max(double x) {
 }
 SF_DEV bool sf_finite(double x) { return x - x == 0.0; }
 
-SF_DEV double sf_prior_logp(const TargetPrior& p, double x) {
-  if (p.kind == 1) return p.c0 + (p.p1 - 1.0) * log(x) - p.p2 * x;
-  if (p.kind == 2) {
-    const double lx = log(x), u = (lx - p.p1) / p.p2;
-    return p.c0 - lx - 0.5 * u * u;
-  }
-  return 0.0;
-}
-SF_DEV double sf_prior_dlogp(const TargetPrior& p, double x) {
-  if (p.kind == 1) return (p.p1 - 1.0) / x - p.p2;
-  if (p.kind == 2) return -(1.0 + (log(x) - p.p1) / (p.p2 * p.p2)) / x;
-  return 0.0;
-}
-SF_DEV double sf_sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
-
 // sum over the tile axis of part (tiles, P), variable by variable.  Device: the wave's 64 lanes are 64 / PP streams of PP >= P
 // lanes (PP a power of two); stream j adds tiles j, j + 64 / PP, ... and the streams are folded by a butterfly -- a fixed order.
 SF_DEV void sf_tile_sums(const double* part, int tiles, int P, int lane, double* ts) {
@@ -90,7 +75,7 @@ SF_DEV void sf_tile_sums(const double* part, int tiles, int P, int lane, double*
 
 // Objective of one problem at the point (theta, raw) the fit was run at; returns f, the lane's components of df / d raw in g.
 // A fit that did not succeed (info != 0) has no value: f is NaN and the gradient zero.
-SF_DEV double sf_objective(const StackFitSpec& sp, double mll, int info, const double* part, int tiles, const double* theta,
+SF_DEV double sf_objective(const HyperSpec& sp, double mll, int info, const double* part, int tiles, const double* theta,
                            const double* raw, int n, int D, int lane, double* g) {
   const int P = D + 2;
   const double nf = n < 1 ? 1.0 : (double)n;
@@ -98,12 +83,11 @@ SF_DEV double sf_objective(const StackFitSpec& sp, double mll, int info, const d
   sf_tile_sums(part, tiles, P, lane, ts);
   double lp = 0.0;
   SF_FOR(i) {
-    const TargetPrior& pr = i < D ? sp.ls_prior : (i == D ? sp.os_prior : sp.nz_prior);
-    const double lo = i < D ? sp.ls_lo : (i == D ? sp.os_lo : sp.nz_lo), hi = i < D ? sp.ls_hi : (i == D ? sp.os_hi : sp.nz_hi);
-    const double th = theta[i], s = sf_sigmoid(raw[i]);
-    lp += sf_prior_logp(pr, th);
+    const HyperVar v = hyper_var(sp, i, D);
+    const double th = theta[i], s = interval_sigmoid(raw[i]);
+    lp += prior_logp(v.prior, th);
     const double dmll = ts[SF_AT(i)] / (2.0 * nf);
-    g[SF_AT(i)] = -(dmll + sf_prior_dlogp(pr, th) / nf) * ((hi - lo) * s * (1.0 - s));
+    g[SF_AT(i)] = -(dmll + prior_dlogp(v.prior, th) / nf) * interval_slope(v, s);
   }
   lp = sf_sum(lp);
   if (info != 0) {
@@ -280,9 +264,10 @@ SF_DEV void sf_step(const StackFitParams& p, int b, int lane) {
     r = sf_advance(st, P, H, p.max_iter, p.max_ls, p.gtol, p.ftol, p.c1, lane, ft, gt);
   }
   SF_FOR(i) {
+    // (spelled out, not hyper_var(p.spec, ...): through a reference to p.spec the compiler orders this loop differently)
     const double lo = i < p.D ? p.spec.ls_lo : (i == p.D ? p.spec.os_lo : p.spec.nz_lo);
     const double hi = i < p.D ? p.spec.ls_hi : (i == p.D ? p.spec.os_hi : p.spec.nz_hi);
-    theta[i] = lo + (hi - lo) * sf_sigmoid(xt[i]);
+    theta[i] = lo + (hi - lo) * interval_sigmoid(xt[i]);
     z[i] = x[i];
   }
   if (lane == 0) {

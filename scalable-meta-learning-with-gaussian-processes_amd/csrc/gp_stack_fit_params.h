@@ -3,15 +3,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "gp_target_params.h"   // TargetPrior
+#include "gp_hyper_spec.h"   // HyperSpec
 
 namespace scaml {
-
-// Constraints and priors of the source GPs (scamlgp/model.py:25-33, 36-70): sigmoid Interval and a hyper-prior per group.
-struct StackFitSpec {
-  double ls_lo, ls_hi, os_lo, os_hi, nz_lo, nz_hi;
-  TargetPrior ls_prior, os_prior, nz_prior;
-};
 
 constexpr int STACK_FIT_HMAX = 16;   // curvature pairs kept at most
 constexpr int STACK_FIT_PMAX = 64;   // one lane per variable: D + 2 <= 64
@@ -29,7 +23,7 @@ struct StackFitParams {
   const int32_t* info;       // (B)  status of that fit (anything but 0: the evaluation failed)
   const double* partials;    // (B, tiles, D+2) of scaml_mll_backward_f64
   const int32_t* n_points;   // (B) or NULL
-  StackFitSpec spec;
+  HyperSpec spec;
   double* z;                 // (B, D+2) raw: start points in (mode 0), accepted points out
   double* theta;             // (B, D+2) constrained: the point the next fit launch evaluates
   double* value;             // (B)  mll + prior term at the accepted point

@@ -118,20 +118,6 @@ TF_DEV double tf_block_max(const TfCtx& c, double x) {
   return t;
 }
 
-TF_DEV double tf_prior_logp(const TargetPrior& p, double x) {
-  if (p.kind == 1) return p.c0 + (p.p1 - 1.0) * log(x) - p.p2 * x;
-  if (p.kind == 2) {
-    const double lx = log(x), u = (lx - p.p1) / p.p2;
-    return p.c0 - lx - 0.5 * u * u;
-  }
-  return 0.0;
-}
-TF_DEV double tf_prior_dlogp(const TargetPrior& p, double x) {
-  if (p.kind == 1) return (p.p1 - 1.0) / x - p.p2;
-  if (p.kind == 2) return -(1.0 + (log(x) - p.p1) / (p.p2 * p.p2)) / x;
-  return 0.0;
-}
-
 // 1 / x for a pivot: f32 seed + two Newton steps (error 2^-22 -> 2^-44 -> 2^-88, then rounding) instead of the ~40-instruction
 // fp64 division, which sat on every column's critical path; outside the f32 range the plain division
 TF_DEV double tf_rcp(double x) {
@@ -171,7 +157,6 @@ TF_DEV void tf_kernel(int kind, double d2, double& kk, double& dk) {
 //                        B-operand layout of the next (lane (lc, lq) register m = element [4 m + lq][lc])
 //   v = X r, alpha = X^T v, K^-1 = X^T X by tiles, G = (alpha alpha^T - K^-1) / 2 packed into the (then free) L region.
 // Three barriers per BLOCK column instead of one per column.  Returns 0 or the 1-based index of the failing pivot.
-TF_DEV void tf_settle(d4_t& v) { asm volatile("s_nop 15\n\ts_nop 2" : "+v"(v)); }   // gfx950: an MFMA's last result pair is not interlocked
 TF_DEV int tf_tile(int i, int j) { return (i * (i + 1) / 2 + j) * TF_TS; }
 
 TF_DEV int tf_factor_mfma(const TfCtx& c, const TargetFitParams& p, double os, double noise, double jit, double& quad, double& logdet) {
@@ -308,7 +293,7 @@ TF_DEV int tf_factor_mfma(const TfCtx& c, const TargetFitParams& p, double os, d
         d4_t acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int m = 0; m < 4; ++m) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(At[lc * TF_TP + 4 * m + lq], wb[m], acc, 0, 0, 0);
-        tf_settle(acc);
+        mfma_settle(acc);
 #pragma unroll
         for (int g = 0; g < 4; ++g) At[(lq + 4 * g) * TF_TP + lc] = acc[g];
       }
@@ -329,7 +314,7 @@ TF_DEV int tf_factor_mfma(const TfCtx& c, const TargetFitParams& p, double os, d
         for (int g = 0; g < 4; ++g) acc[g] = At[(lq + 4 * g) * TF_TP + lc];
 #pragma unroll
         for (int m = 0; m < 4; ++m) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-Li[lc * TF_TP + 4 * m + lq], Lj[lc * TF_TP + 4 * m + lq], acc, 0, 0, 0);
-        tf_settle(acc);
+        mfma_settle(acc);
 #pragma unroll
         for (int g = 0; g < 4; ++g) At[(lq + 4 * g) * TF_TP + lc] = acc[g];
       }
@@ -347,12 +332,12 @@ TF_DEV int tf_factor_mfma(const TfCtx& c, const TargetFitParams& p, double os, d
 #pragma unroll
         for (int m = 0; m < 4; ++m) sacc = __builtin_amdgcn_mfma_f64_16x16x4f64(Lij[lc * TF_TP + 4 * m + lq], Xjk[(4 * m + lq) * TF_TP + lc], sacc, 0, 0, 0);
       }
-      tf_settle(sacc);
+      mfma_settle(sacc);
       const double* Wi = c.Xt + tf_tile(i, i);
       d4_t x = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int m = 0; m < 4; ++m) x = __builtin_amdgcn_mfma_f64_16x16x4f64(-Wi[lc * TF_TP + 4 * m + lq], sacc[m], x, 0, 0, 0);
-      tf_settle(x);
+      mfma_settle(x);
       double* Xik = c.Xt + tf_tile(i, k);
 #pragma unroll
       for (int g = 0; g < 4; ++g) Xik[(lq + 4 * g) * TF_TP + lc] = x[g];
@@ -394,7 +379,7 @@ TF_DEV int tf_factor_mfma(const TfCtx& c, const TargetFitParams& p, double os, d
 #pragma unroll
         for (int m = 0; m < 4; ++m) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Xa[(4 * m + lq) * TF_TP + lc], Xb[(4 * m + lq) * TF_TP + lc], acc, 0, 0, 0);
       }
-      tf_settle(acc);
+      mfma_settle(acc);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int a = 16 * ta + lq + 4 * g, b = 16 * tb + lc;
@@ -418,6 +403,8 @@ TF_DEV double tf_eval(const TfCtx& c, const TargetFitParams& p, const double* z,
   const TargetSpec& sp = p.spec;
   const double inv_s = 1.0 / p.s_all, inv_s2 = inv_s * inv_s;
   // ---- parameters ----
+  // (the Interval and the group ladders stay spelled out in this kernel: routed through hyper_var / interval_* of gp_hyper_spec.h
+  //  the register allocation of the whole evaluation shifts -- 6 more instructions, two more SGPR spills)
   for (int i = c.tid; i < D + 2; i += c.nthr) {
     const double lo = i < D ? sp.ls_lo : (i == D ? sp.os_lo : sp.nz_lo), hi = i < D ? sp.ls_hi : (i == D ? sp.os_hi : sp.nz_hi);
     const double s = 1.0 / (1.0 + exp(-z[i]));
@@ -594,8 +581,8 @@ TF_DEV double tf_eval(const TfCtx& c, const TargetFitParams& p, const double* z,
   }
   // log priors ride in the same reduction
   double lp = 0.0;
-  for (int i = c.tid; i < D + 2; i += c.nthr) lp += tf_prior_logp(i < D ? sp.ls_prior : (i == D ? sp.os_prior : sp.nz_prior), c.theta[i]);
-  for (int i = c.tid; i < T; i += c.nthr) lp += tf_prior_logp(sp.w_prior, c.w[i]);
+  for (int i = c.tid; i < D + 2; i += c.nthr) lp += prior_logp(i < D ? sp.ls_prior : (i == D ? sp.os_prior : sp.nz_prior), c.theta[i]);
+  for (int i = c.tid; i < T; i += c.nthr) lp += prior_logp(sp.w_prior, c.w[i]);
   const double quad = c.mfma ? quad_m : -c.Ap[tf_idxL(n, n)];
   double logdet = tf_block_sum(c, ld);
   if (c.mfma) logdet = logdet_m;
@@ -673,8 +660,8 @@ TF_DEV double tf_eval(const TfCtx& c, const TargetFitParams& p, const double* z,
     const double t0 = tf_wave_sum(((a0 + a1) + (a2 + a3)) * (2.0 * w0 * inv_s2) + am * inv_s);
     const double t1 = tf_wave_sum(((b0 + b1) + (b2 + b3)) * (2.0 * w1 * inv_s2) + bm * inv_s);
     if (tf_last_lane(c)) {
-      gz[D + 2 + i0] = (t0 + tf_prior_dlogp(sp.w_prior, w0)) * inv_n;
-      if (i1 != i0) gz[D + 2 + i1] = (t1 + tf_prior_dlogp(sp.w_prior, w1)) * inv_n;
+      gz[D + 2 + i0] = (t0 + prior_dlogp(sp.w_prior, w0)) * inv_n;
+      if (i1 != i0) gz[D + 2 + i1] = (t1 + prior_dlogp(sp.w_prior, w1)) * inv_n;
     }
   }
   // ---- d / d (lengthscales, outputscale, noise) ----
@@ -731,8 +718,8 @@ TF_DEV double tf_eval(const TfCtx& c, const TargetFitParams& p, const double* z,
     for (int v = 0; v < c.nwave; ++v) s += c.part[v * (TARGET_FIT_DMAX + 2) + slot];
     const double th = c.theta[q];
     if (q < D) s *= c.invl[q];   // (the 1 / l_d of d d2 / d l_d)
-    const TargetPrior& pr = q < D ? sp.ls_prior : (q == D ? sp.os_prior : sp.nz_prior);
-    gz[q] = (s + tf_prior_dlogp(pr, th)) * c.dth[q] * inv_n;
+    const HyperPrior& pr = q < D ? sp.ls_prior : (q == D ? sp.os_prior : sp.nz_prior);
+    gz[q] = (s + prior_dlogp(pr, th)) * c.dth[q] * inv_n;
   }
   TF_SYNC();
   TF_STAMP(7);

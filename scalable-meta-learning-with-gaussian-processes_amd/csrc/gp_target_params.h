@@ -3,24 +3,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gp_hyper_spec.h"   // TargetSpec
+
 namespace scaml {
-
-// One hyper-prior: log-density on the CONSTRAINED value, evaluated as gpytorch does.
-//   kind 0: none;  1: Gamma(concentration = p1, rate = p2);  2: LogNormal(loc = p1, scale = p2)
-// c0 is the additive constant of the log-density (host: Gamma c ln r - lgamma(c); LogNormal -ln scale - ln(2 pi) / 2).
-struct TargetPrior {
-  int kind;
-  int pad_;
-  double p1, p2, c0;
-};
-
-// Constraints and priors of the target GP (scamlgp/model.py:25-33, 73-105, 318-338): sigmoid Interval on
-// lengthscales / outputscale / noise, a plain box bound on the weights.
-struct TargetSpec {
-  double ls_lo, ls_hi, os_lo, os_hi, nz_lo, nz_hi;
-  TargetPrior ls_prior, os_prior, nz_prior, w_prior;
-  double w_lower;   // optimiser only: w >= w_lower (GreaterThan(1e-10, transform=None), model.py:334)
-};
 
 struct TargetFitParams {
   const double* means_t;   // (T, n)            source posterior means at the target inputs, original units

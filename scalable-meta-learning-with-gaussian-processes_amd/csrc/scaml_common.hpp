@@ -9,6 +9,13 @@
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
 
+// gfx950: the last result pair of an fp64 MFMA is not interlocked, and hipcc pads with the wait states of the 8-pass gfx942
+// instruction (tools/mfma_hazard_probe.hip measures it, tools/mfma_hazard_audit.py gates the build).  19 wait states behind the last
+// MFMA: mfma_settle(v) / v = mfma_settled(v) for a compiler-visible result (the data dependency keeps the uses behind the wait),
+// MFMA_DRAIN() for results in hand-managed registers (nothing moves across it).
+#define SCAML_MFMA_WAIT "s_nop 15\n\ts_nop 2"
+#define MFMA_DRAIN() asm volatile(SCAML_MFMA_WAIT ::: "memory")
+
 // The wave's index inside its workgroup as a SCALAR: tid >> 6 is the same in all 64 lanes, but the compiler cannot know, and every
 // block-row / strip index derived from it is then vector arithmetic -- on a SIMD that its waves' VALU instructions already contend
 // for (profiles/r03_probe_valu_overlap.txt).  Through readfirstlane that arithmetic moves to the scalar unit.
@@ -19,6 +26,12 @@ typedef double d4_t __attribute__((ext_vector_type(4)));
 #endif
 
 namespace scaml {
+
+__device__ __forceinline__ void mfma_settle(d4_t& v) { asm volatile(SCAML_MFMA_WAIT : "+v"(v)); }
+__device__ __forceinline__ d4_t mfma_settled(d4_t v) {
+  mfma_settle(v);
+  return v;
+}
 
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
   int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
@@ -66,8 +79,20 @@ __device__ __forceinline__ void exp2_table_init(double* tab, int tid) {
   if (tid < 64) tab[tid] = exp2((double)tid * (1.0 / 64.0));
 }
 
-__device__ __forceinline__ double exp_neg(double x, const double* tab) {
-  x = __builtin_fmax(x, -746.0);   // (a NaN becomes -746 -> 0, as the select did)
+// Bare v_max / v_min (they drop a NaN operand): the builtins add a canonicalising v_max in front.
+__device__ __forceinline__ double vmax_f64(double a, double b) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
+  return r;
+}
+__device__ __forceinline__ double vmin_f64(double a, double b) {
+  double r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
+  return r;
+}
+
+// (the body: x in [-746, 0] is the caller's business)
+__device__ __forceinline__ double exp_neg_unclamped(double x, const double* tab) {
   // n = rint(x * 64 / ln 2) by the 1.5 * 2^52 trick (|n| < 2^31 here): the integer sits in the low word of the sum
   const double sh = __builtin_fma(x, 92.332482616893656877, 0x1.8p52);
   const int n = __double2loint(sh);
@@ -80,6 +105,25 @@ __device__ __forceinline__ double exp_neg(double x, const double* tab) {
   p = __builtin_fma(p, r, 0.5);
   p = __builtin_fma(p * r, r, r);     // r + r^2 (1/2 + ...)
   return __builtin_ldexp(__builtin_fma(t, p, t), n >> 6);
+}
+__device__ __forceinline__ double exp_neg(double x, const double* tab) {
+  return exp_neg_unclamped(__builtin_fmax(x, -746.0), tab);   // (a NaN becomes -746 -> 0, as the select did)
+}
+// CLAMP = false: the caller keeps x >= -746 itself
+template <bool CLAMP>
+__device__ __forceinline__ double exp_neg_t(double x, const double* tab) {
+  return exp_neg_unclamped(CLAMP ? vmax_f64(x, -746.0) : x, tab);
+}
+
+// sqrt(dd), dd = d2 clamped to [1e-30, 1e5], straight from the f32 seed y ~ 1/sqrt(dd) without a correction step (<= 1.5 ulp):
+// g = dd y, e = 1 - g y, r = g (1 + e/2 + 3 e^2/8).  The upper clamp: a Matern k(1e5) ~ 1e-302, and -sqrt(5) r stays inside
+// the range exp_neg_t<false> handles.
+__device__ __forceinline__ double sqrt_clamped_seeded(double d2) {
+  const double dd = vmin_f64(vmax_f64(d2, 1e-30), 1e5);
+  const double y = (double)__builtin_amdgcn_rsqf((float)dd);
+  const double g = dd * y;
+  const double e = __builtin_fma(-g, y, 1.0);
+  return __builtin_fma(g * e, __builtin_fma(e, 0.375, 0.5), g);
 }
 
 // k(d2) for squared scaled distance d2 >= 0 (without the outputscale).  The clamps are v_max/v_min (which
@@ -103,45 +147,13 @@ __device__ __forceinline__ double kernel_from_sqdist(double d2, const double* ex
 // The fused fit's variant: d2 comes off the matrix core (expanded form, may be slightly negative, never NaN --
 // non-finite inputs are caught when the points are staged), the outputscale is folded into the polynomial
 // (c0 = os, c1 = sqrt(5) os, c2 = 5/3 os), and r = d2 * rsqrt(d2) without the correction step (<= 1.5 ulp).
-// d2 is clamped to [1e-30, 1e5]: k(1e5) ~ 1e-302 os, and -sqrt(5) r stays inside the range exp_neg handles
-// without its own clamp.  Bare v_max / v_min: the builtins add a canonicalising v_max in front.
-__device__ __forceinline__ double vmax_f64(double a, double b) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
-  return r;
-}
-__device__ __forceinline__ double vmin_f64(double a, double b) {
-  double r;
-  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
-  return r;
-}
-template <bool CLAMP>
-__device__ __forceinline__ double exp_neg_t(double x, const double* tab) {
-  if (CLAMP) x = vmax_f64(x, -746.0);
-  // n = rint(x * 64 / ln 2) by the 1.5 * 2^52 trick (|n| < 2^31 here): the integer sits in the low word of the sum
-  const double sh = __builtin_fma(x, 92.332482616893656877, 0x1.8p52);
-  const int n = __double2loint(sh);
-  const double nf = sh - 0x1.8p52;
-  double r = __builtin_fma(nf, -0x1.62e42fee00000p-7, x);
-  r = __builtin_fma(nf, -0x1.a39ef35793c76p-39, r);
-  const double t = tab[n & 63];
-  double p = __builtin_fma(r, 8.3333333333333332e-03, 4.1666666666666664e-02);
-  p = __builtin_fma(p, r, 1.6666666666666666e-01);
-  p = __builtin_fma(p, r, 0.5);
-  p = __builtin_fma(p * r, r, r);
-  return __builtin_ldexp(__builtin_fma(t, p, t), n >> 6);
-}
+// d2 is clamped to [1e-30, 1e5] (sqrt_clamped_seeded), so exp_neg needs no clamp of its own.
 template <int KIND>
 __device__ __forceinline__ double kernel_from_sqdist_scaled(double d2, double c0, double c1, double c2, const double* exp_tab) {
   if (KIND == 0) {  // RBF: os exp(-d2/2)
     return c0 * exp_neg_t<true>(-0.5 * d2, exp_tab);
   } else {
-    const double dd = vmin_f64(vmax_f64(d2, 1e-30), 1e5);
-    // r = sqrt(dd) straight from the f32 seed y ~ 1/sqrt(dd): g = dd y, e = 1 - g y, r = g (1 + e/2 + 3 e^2/8)
-    const double y = (double)__builtin_amdgcn_rsqf((float)dd);
-    const double g = dd * y;
-    const double e = __builtin_fma(-g, y, 1.0);
-    const double r = __builtin_fma(g * e, __builtin_fma(e, 0.375, 0.5), g);
+    const double r = sqrt_clamped_seeded(d2);
     const double poly = __builtin_fma(__builtin_fma(r, c2, c1), r, c0);
     return poly * exp_neg_t<false>(-2.2360679774997896964 * r, exp_tab);
   }
@@ -157,11 +169,7 @@ __device__ __forceinline__ void kernel_and_slope_scaled(double d2, double os, co
     dk = -0.5 * k;
   } else {
     const double s5 = 2.2360679774997896964;
-    const double dd = vmin_f64(vmax_f64(d2, 1e-30), 1e5);
-    const double y = (double)__builtin_amdgcn_rsqf((float)dd);
-    const double g = dd * y;
-    const double e = __builtin_fma(-g, y, 1.0);
-    const double r = __builtin_fma(g * e, __builtin_fma(e, 0.375, 0.5), g);
+    const double r = sqrt_clamped_seeded(d2);
     const double ex = os * exp_neg_t<false>(-s5 * r, exp_tab);
     const double lin = __builtin_fma(s5, r, 1.0);
     k = __builtin_fma((5.0 / 3.0) * r, r, lin) * ex;

@@ -739,27 +739,6 @@ size_t target_fit_lds_bytes(int n, int T, int D, bool mfma) {
 bool target_fit_use_mfma(int n, int T, int D) {
   return g_dev.target_fit_path.load(kRelaxed) == 0 && n <= 112 && target_fit_lds_bytes(n, T, D, true) <= kLdsLimit;
 }
-// one (kind, p1, p2) triple of a constraint / prior block
-int prior_from_host(const double* t, scaml::TargetPrior& pr) {
-  const int kind = (int)t[0];
-  const double p1 = t[1], p2 = t[2];
-  if (kind < 0 || kind > 2) return SCAML_E_BADARG;
-  if (kind == 1 && !(p1 > 0.0 && p2 > 0.0)) return SCAML_E_BADARG;
-  if (kind == 2 && !(p2 > 0.0)) return SCAML_E_BADARG;
-  pr.kind = kind; pr.pad_ = 0; pr.p1 = p1; pr.p2 = p2;
-  pr.c0 = kind == 1 ? p1 * log(p2) - lgamma(p1) : (kind == 2 ? -log(p2) - 0.9189385332046727 : 0.0);
-  return SCAML_OK;
-}
-int target_spec_from_host(const double* spec, scaml::TargetSpec& sp) {
-  sp.ls_lo = spec[0]; sp.ls_hi = spec[1]; sp.os_lo = spec[2]; sp.os_hi = spec[3]; sp.nz_lo = spec[4]; sp.nz_hi = spec[5];
-  if (!(sp.ls_hi > sp.ls_lo) || !(sp.os_hi > sp.os_lo) || !(sp.nz_hi > sp.nz_lo)) return SCAML_E_BADARG;
-  scaml::TargetPrior* pr[4] = {&sp.ls_prior, &sp.os_prior, &sp.nz_prior, &sp.w_prior};
-  for (int q = 0; q < 4; ++q) {
-    if (prior_from_host(spec + 6 + 3 * q, *pr[q]) != SCAML_OK) return SCAML_E_BADARG;
-  }
-  sp.w_lower = spec[18];
-  return SCAML_OK;
-}
 int target_fit_launch(scaml::TargetFitParams& p, void* stream) {
   if (p.B < 0 || p.n < 1 || p.T < 1 || p.D < 1) return SCAML_E_BADARG;
   if (!p.means_t || !p.covs_p || !p.X || !p.y || !p.z || !p.value || !p.info) return SCAML_E_BADARG;
@@ -796,8 +775,7 @@ int scaml_target_mll_f64(const double* means_t, const double* covs_packed, const
   if (!spec_host || !grad) return SCAML_E_BADARG;
   scaml::TargetFitParams p{};
   p.means_t = means_t; p.covs_p = covs_packed; p.X = X; p.y = y; p.m_all = m_all; p.s_all = s_all;
-  const int rc = target_spec_from_host(spec_host, p.spec);
-  if (rc != SCAML_OK) return rc;
+  if (!scaml::target_spec_from_host(spec_host, p.spec)) return SCAML_E_BADARG;
   p.z = const_cast<double*>(z); p.value = value; p.grad = grad; p.info = info; p.jitter = jitter_used;
   p.B = B; p.n = n; p.T = T; p.D = D; p.kind = kind; p.mode = 0; p.history = 1; p.max_ls = 0;
   return target_fit_launch(p, stream);
@@ -812,8 +790,7 @@ int scaml_target_fit_f64(const double* means_t, const double* covs_packed, const
   if (workspace_doubles < scaml_target_fit_workspace_doubles(B, T, D, history)) return SCAML_E_BADARG;
   scaml::TargetFitParams p{};
   p.means_t = means_t; p.covs_p = covs_packed; p.X = X; p.y = y; p.m_all = m_all; p.s_all = s_all;
-  const int rc = target_spec_from_host(spec_host, p.spec);
-  if (rc != SCAML_OK) return rc;
+  if (!scaml::target_spec_from_host(spec_host, p.spec)) return SCAML_E_BADARG;
   p.z = z; p.value = value; p.grad = nullptr; p.info = info; p.jitter = jitter_used; p.workspace = workspace; p.stats = stats;
   p.B = B; p.n = n; p.T = T; p.D = D; p.kind = kind; p.mode = 1; p.max_iter = max_iter; p.history = history; p.max_ls = 20;
   p.gtol = gtol; p.ftol = ftol;
@@ -861,12 +838,8 @@ int scaml_stack_fit_f64(const double* X, const double* y, const int32_t* n_point
   if (!X || !y || !spec_host || !z || !value || !stats || !workspace) return SCAML_E_BADARG;
   if (!valid_kind(kind) || (flags & ~SCAML_STACK_FIT_CONTINUE)) return SCAML_E_BADARG;
   if (history < 1 || history > scaml::STACK_FIT_HMAX) return SCAML_E_BADARG;
-  scaml::StackFitSpec sp{spec_host[0], spec_host[1], spec_host[2], spec_host[3], spec_host[4], spec_host[5], {}, {}, {}};
-  if (!(sp.ls_hi > sp.ls_lo) || !(sp.os_hi > sp.os_lo) || !(sp.nz_hi > sp.nz_lo)) return SCAML_E_BADARG;
-  scaml::TargetPrior* pr[3] = {&sp.ls_prior, &sp.os_prior, &sp.nz_prior};
-  for (int q = 0; q < 3; ++q) {
-    if (prior_from_host(spec_host + 6 + 3 * q, *pr[q]) != SCAML_OK) return SCAML_E_BADARG;
-  }
+  scaml::HyperSpec sp{};
+  if (!scaml::hyper_spec_from_host(spec_host, sp)) return SCAML_E_BADARG;
   // the shapes the fit and gradient paths take
   const bool blocked = N > scaml_fit_max_n();
   if (N > scaml_fit_blocked_max_n() || (blocked && (N & 15))) return SCAML_E_TOOLARGE;

@@ -34,6 +34,14 @@ def _check(t: torch.Tensor, name: str, shape=None, dtype=torch.float64) -> torch
     return t.contiguous()
 
 
+def _opt(t: Optional[torch.Tensor], name: str, shape=None, dtype=torch.float64) -> Optional[torch.Tensor]:
+    return None if t is None else _check(t, name, shape, dtype)
+
+
+def _empty(dev, *shape, dtype=torch.float64) -> torch.Tensor:
+    return torch.empty(shape, dtype=dtype, device=dev)
+
+
 def _stream_handle() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -71,10 +79,8 @@ def gp_fit_fused(
     X = _check(X, "X")
     y = _check(y, "y", (T, N))
     theta = _check(theta, "theta", (T, D + 2))
-    if n_points is not None:
-        n_points = _check(n_points, "n_points", (T,), torch.int32)
-    if jitter is not None:
-        jitter = _check(jitter, "jitter", (T,))
+    n_points = _opt(n_points, "n_points", (T,), torch.int32)
+    jitter = _opt(jitter, "jitter", (T,))
     if N > _lib.lib.scaml_fit_max_n():
         if out is not None:
             raise ValueError("out= is not supported beyond scaml_fit_max_n()")
@@ -93,14 +99,14 @@ def gp_fit_fused(
             if (L is None) == store_L or (alpha is None) == want_alpha or quad.shape != (T,) or (store_L and L.shape != (T, N, N)):
                 raise ValueError("out= does not match this call's shapes/flags")
         else:
-            L = torch.empty((T, N, N), dtype=torch.float64, device=dev) if store_L else None
-            alpha = torch.empty((T, N), dtype=torch.float64, device=dev) if want_alpha else None
-            quad = torch.empty((T,), dtype=torch.float64, device=dev)
-            logdet = torch.empty((T,), dtype=torch.float64, device=dev)
-            mll = torch.empty((T,), dtype=torch.float64, device=dev)
-            info = torch.empty((T,), dtype=torch.int32, device=dev)
-            jit_used = torch.empty((T,), dtype=torch.float64, device=dev)
-            linv = torch.empty((T, (N + 15) // 16, 16, 16), dtype=torch.float64, device=dev) if want_linv else None
+            L = _empty(dev, T, N, N) if store_L else None
+            alpha = _empty(dev, T, N) if want_alpha else None
+            quad = _empty(dev, T)
+            logdet = _empty(dev, T)
+            mll = _empty(dev, T)
+            info = _empty(dev, T, dtype=torch.int32)
+            jit_used = _empty(dev, T)
+            linv = _empty(dev, T, (N + 15) // 16, 16, 16) if want_linv else None
         if n_points is not None and want_alpha:
             alpha.zero_()
         flags = 0
@@ -136,11 +142,11 @@ def _gp_fit_blocked(X, y, theta, kind, n_points, jitter, zero_upper, retry) -> D
         # ragged stacks: rows past n_t are never written but READ by the strip solve -> zeros
         L = (torch.zeros if n_points is not None else torch.empty)((T, N, N), dtype=torch.float64, device=dev)
         alpha = (torch.zeros if n_points is not None else torch.empty)((T, N), dtype=torch.float64, device=dev)
-        quad, logdet, mll, jit_used = (torch.empty((T,), dtype=torch.float64, device=dev) for _ in range(4))
-        info = torch.empty((T,), dtype=torch.int32, device=dev)
-        linv = torch.empty((T, N // 16, 16, 16), dtype=torch.float64, device=dev)
+        quad, logdet, mll, jit_used = (_empty(dev, T) for _ in range(4))
+        info = _empty(dev, T, dtype=torch.int32)
+        linv = _empty(dev, T, N // 16, 16, 16)
         nbytes = int(_lib.lib.scaml_gp_fit_blocked_workspace_bytes(T, N))
-        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        ws = _empty(dev, max(nbytes, 16), dtype=torch.uint8)
         flags = _lib.FIT_STORE_L | (_lib.FIT_ZERO_UPPER if zero_upper else 0) | (0 if retry else _lib.FIT_NO_RETRY)
         rc = _lib.lib.scaml_gp_fit_blocked_f64(
             _ptr(X), _ptr(y), _ptr(theta), _ptr(n_points), _ptr(jitter), T, N, D, int(kind),
@@ -225,8 +231,7 @@ def linv_batched(L: torch.Tensor, Linv_diag: torch.Tensor, n_points: Optional[to
     T, N, _ = L.shape
     L = _check(L, "L", (T, N, N))
     Linv_diag = _check(Linv_diag, "Linv_diag", (T, (N + 15) // 16, 16, 16))
-    if n_points is not None:
-        n_points = _check(n_points, "n_points", (T,), torch.int32)
+    n_points = _opt(n_points, "n_points", (T,), torch.int32)
     out = torch.empty_like(L)
     with torch.cuda.device(L.device):
         fn = _lib.lib.scaml_linv_batched_lower_f64 if lower_only else _lib.lib.scaml_linv_batched_f64
@@ -244,8 +249,7 @@ def cho_solve(L: torch.Tensor, Linv_diag: torch.Tensor, B: torch.Tensor, n_point
     L = _check(L, "L", (T, N, N))
     Linv_diag = _check(Linv_diag, "Linv_diag", (T, (N + 15) // 16, 16, 16))
     B = _check(B, "B", (T, N, R))
-    if n_points is not None:
-        n_points = _check(n_points, "n_points", (T,), torch.int32)
+    n_points = _opt(n_points, "n_points", (T,), torch.int32)
     out = torch.empty_like(B)
     with torch.cuda.device(L.device):
         fn = _lib.lib.scaml_solve_lt_batched_f64 if backward_only else _lib.lib.scaml_cho_solve_batched_f64
@@ -267,7 +271,7 @@ def kernel_matrix(X1: torch.Tensor, theta: torch.Tensor, kind: int, X2: Optional
         shared = 1 if X2.dim() == 2 else 0
         N2 = X2.shape[-2]
         X2 = _check(X2, "X2", (N2, D) if shared else (T, N2, D))
-    K = torch.empty((T, N1, N2), dtype=torch.float64, device=X1.device)
+    K = _empty(X1.device, T, N1, N2)
     with torch.cuda.device(X1.device):
         rc = _lib.lib.scaml_kernel_matrix_f64(_ptr(X1), _ptr(X2), _ptr(theta), T, N1, N2, D, int(kind), shared,
                                               1 if add_noise else 0, _ptr(K), _stream_handle())
@@ -284,21 +288,18 @@ def potrf_batched(A: torch.Tensor, y: Optional[torch.Tensor] = None, n_points: O
         raise ValueError("A must be (T, N, N)")
     T, N, _ = A.shape
     A = _check(A, "A")
-    if y is not None:
-        y = _check(y, "y", (T, N))
-    if n_points is not None:
-        n_points = _check(n_points, "n_points", (T,), torch.int32)
-    if jitter is not None:
-        jitter = _check(jitter, "jitter", (T,))
+    y = _opt(y, "y", (T, N))
+    n_points = _opt(n_points, "n_points", (T,), torch.int32)
+    jitter = _opt(jitter, "jitter", (T,))
     dev = A.device
     with torch.cuda.device(dev):
-        L = torch.zeros((T, N, N), dtype=torch.float64, device=dev) if n_points is not None else torch.empty((T, N, N), dtype=torch.float64, device=dev)
+        L = torch.zeros((T, N, N), dtype=torch.float64, device=dev) if n_points is not None else _empty(dev, T, N, N)
         alpha = torch.zeros((T, N), dtype=torch.float64, device=dev) if y is not None else None
-        quad = torch.empty((T,), dtype=torch.float64, device=dev) if y is not None else None
-        logdet = torch.empty((T,), dtype=torch.float64, device=dev)
-        info = torch.empty((T,), dtype=torch.int32, device=dev)
-        jit_used = torch.empty((T,), dtype=torch.float64, device=dev)
-        linv = torch.empty((T, (N + 15) // 16, 16, 16), dtype=torch.float64, device=dev) if want_linv else None
+        quad = _empty(dev, T) if y is not None else None
+        logdet = _empty(dev, T)
+        info = _empty(dev, T, dtype=torch.int32)
+        jit_used = _empty(dev, T)
+        linv = _empty(dev, T, (N + 15) // 16, 16, 16) if want_linv else None
         flags = _lib.FIT_STORE_L | (_lib.FIT_ZERO_UPPER if zero_upper else 0) | (0 if retry else _lib.FIT_NO_RETRY)
         rc = _lib.lib.scaml_potrf_batched_f64(_ptr(A), _ptr(y), _ptr(n_points), _ptr(jitter), T, N, _ptr(L), _ptr(alpha),
                                               _ptr(quad), _ptr(logdet), _ptr(info), _ptr(jit_used), _ptr(linv), flags,
@@ -359,20 +360,17 @@ def source_posteriors(
         L = _check(L, "L", (T, N, N))
         Linv_diag = _check(Linv_diag, "Linv_diag", (T, (N + 15) // 16, 16, 16))
     alpha = _check(alpha, "alpha", (T, N))
-    if y_mean is not None:
-        y_mean = _check(y_mean, "y_mean", (T,))
-    if y_std is not None:
-        y_std = _check(y_std, "y_std", (T,))
-    if n_points is not None:
-        n_points = _check(n_points, "n_points", (T,), torch.int32)
+    y_mean = _opt(y_mean, "y_mean", (T,))
+    y_std = _opt(y_std, "y_std", (T,))
+    n_points = _opt(n_points, "n_points", (T,), torch.int32)
     if not 0 <= cov_first <= M:
         raise ValueError("cov_first must be within [0, M]")
     dev = X.device
     with torch.cuda.device(dev):
-        mu = torch.empty((T, M), dtype=torch.float64, device=dev)
-        var = torch.empty((T, M), dtype=torch.float64, device=dev) if want_var else None
+        mu = _empty(dev, T, M)
+        var = _empty(dev, T, M) if want_var else None
         fused_cov = (Linv is not None and not mean_only and not keep_V and 0 < cov_first <= min(96, N, M))
-        V = torch.empty((T, N, M), dtype=torch.float64, device=dev) if ((cov_first > 0 and not fused_cov) or keep_V) else None
+        V = _empty(dev, T, N, M) if ((cov_first > 0 and not fused_cov) or keep_V) else None
         cov = None
         if fused_cov:
             # the covariance block comes out of the posterior pass itself: V of the leading cov_first points first
@@ -382,15 +380,15 @@ def source_posteriors(
                 VA = _check(VA, "VA", (T, N, cov_first))
             else:
                 Xa = Xq[:, :cov_first].contiguous() if Xq.dim() == 3 else Xq[:cov_first].contiguous()
-                VA = torch.empty((T, N, cov_first), dtype=torch.float64, device=dev)
-                mu_a = torch.empty((T, cov_first), dtype=torch.float64, device=dev)
+                VA = _empty(dev, T, N, cov_first)
+                mu_a = _empty(dev, T, cov_first)
                 rc = _lib.lib.scaml_posterior_linv_f64(
                     _ptr(Xa), _ptr(X), _ptr(theta), _ptr(Linv), _ptr(alpha), _ptr(y_mean), _ptr(y_std), _ptr(n_points),
                     T, N, cov_first, D, int(kind), _ptr(mu_a), None, _ptr(VA), flags, _stream_handle())
                 _lib.check_rc(rc, "scaml_posterior_linv_f64")
-            cov = torch.empty((T, cov_first, M), dtype=torch.float64, device=dev)
+            cov = _empty(dev, T, cov_first, M)
             if var is None:
-                var = torch.empty((T, M), dtype=torch.float64, device=dev)
+                var = _empty(dev, T, M)
             rc = _lib.lib.scaml_posterior_linv_cov_f64(
                 _ptr(Xq), _ptr(X), _ptr(theta), _ptr(Linv), _ptr(alpha), _ptr(y_mean), _ptr(y_std), _ptr(n_points), _ptr(VA),
                 T, N, M, cov_first, D, int(kind), _ptr(mu), _ptr(var), _ptr(cov), flags, _stream_handle())
@@ -408,7 +406,7 @@ def source_posteriors(
                 _ptr(n_points), T, N, M, D, int(kind), _ptr(mu), _ptr(var), _ptr(V), flags, _stream_handle())
             _lib.check_rc(rc, "scaml_posterior_batched_f64")
         if cov_first > 0:
-            cov = torch.empty((T, cov_first, M), dtype=torch.float64, device=dev)
+            cov = _empty(dev, T, cov_first, M)
             rc = _lib.lib.scaml_posterior_cov_f64(_ptr(Xq), _ptr(theta), _ptr(V), _ptr(y_std), T, N, M, cov_first, D,
                                                   int(kind), _ptr(cov), flags & _lib.POST_XQ_PER_TASK, _stream_handle())
             _lib.check_rc(rc, "scaml_posterior_cov_f64")
@@ -449,8 +447,8 @@ def weighted_prior_reduce(mu: Optional[torch.Tensor], cov: Optional[torch.Tensor
     if active is not None:
         active = active.to(torch.uint8).contiguous()
     dev = weights.device
-    mu_s = torch.empty((M,), dtype=torch.float64, device=dev) if mu is not None else None
-    cov_s = torch.empty((Ma, M), dtype=torch.float64, device=dev) if cov is not None else None
+    mu_s = _empty(dev, M) if mu is not None else None
+    cov_s = _empty(dev, Ma, M) if cov is not None else None
     with torch.cuda.device(dev):
         rc = _lib.lib.scaml_weighted_prior_reduce_f64(_ptr(mu), _ptr(cov), _ptr(weights), _ptr(active), T, M, Ma, _ptr(mu_s),
                                                       _ptr(cov_s), _stream_handle())
@@ -490,16 +488,15 @@ def target_posterior_full(cov_s: torch.Tensor, mean_s: torch.Tensor, var_s: torc
     theta = _check(theta, "theta", (D + 2,))
     train_targets = _check(train_targets, "train_targets", (n,))
     dev = Xall.device
-    f64 = dict(dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        Knn, resid = torch.empty((1, n, n), **f64), torch.empty((1, n), **f64)
-        Knq, mean_q, var_q = torch.empty((1, n, M), **f64), torch.empty((M,), **f64), torch.empty((M,), **f64)
+        Knn, resid = _empty(dev, 1, n, n), _empty(dev, 1, n)
+        Knq, mean_q, var_q = _empty(dev, 1, n, M), _empty(dev, M), _empty(dev, M)
         rc = _lib.lib.scaml_target_assemble_f64(_ptr(cov_s), _ptr(mean_s), _ptr(var_s), _ptr(Xall), _ptr(theta), _ptr(train_targets),
                                                 float(m_all), float(s_all), n, M, D, int(kind), _ptr(Knn), _ptr(resid), _ptr(Knq),
                                                 _ptr(mean_q), _ptr(var_q), _stream_handle())
         _lib.check_rc(rc, "scaml_target_assemble_f64")
         f = factor if factor is not None else potrf_batched(Knn, resid, want_linv=True)
-        mu, var = torch.empty((M,), **f64), torch.empty((M,), **f64)
+        mu, var = _empty(dev, M), _empty(dev, M)
         Z = None
         if M > 0:
             Z = cho_solve(f["L"], f["Linv_diag"], Knq)
@@ -528,17 +525,14 @@ def source_posteriors_grad(Xq: torch.Tensor, Xa: Optional[torch.Tensor], X: torc
     if Ma:
         VA = _check(VA, "VA", (T, N, Ma))
         Xa = _check(Xa, "Xa", (Ma, D))
-    if y_mean is not None:
-        y_mean = _check(y_mean, "y_mean", (T,))
-    if y_std is not None:
-        y_std = _check(y_std, "y_std", (T,))
-    if n_points is not None:
-        n_points = _check(n_points, "n_points", (T,), torch.int32)
+    y_mean = _opt(y_mean, "y_mean", (T,))
+    y_std = _opt(y_std, "y_std", (T,))
+    n_points = _opt(n_points, "n_points", (T,), torch.int32)
     dev = X.device
     with torch.cuda.device(dev):
-        mu = torch.empty((T, Mq, 16), dtype=torch.float64, device=dev)
-        var = torch.empty((T, Mq, 16), dtype=torch.float64, device=dev)
-        cov = torch.empty((T, Ma, Mq * 16), dtype=torch.float64, device=dev) if Ma else None
+        mu = _empty(dev, T, Mq, 16)
+        var = _empty(dev, T, Mq, 16)
+        cov = _empty(dev, T, Ma, Mq * 16) if Ma else None
         rc = _lib.lib.scaml_posterior_linv_grad_f64(_ptr(Xq), _ptr(Xa) if Ma else None, _ptr(X), _ptr(theta), _ptr(Linv), _ptr(alpha), _ptr(y_mean),
                                                     _ptr(y_std), _ptr(n_points), _ptr(VA) if Ma else None, T, N, Mq, Ma, D, int(kind), _ptr(mu),
                                                     _ptr(var), _ptr(cov), 0, _stream_handle())
@@ -564,8 +558,8 @@ def target_posterior_grad(cov_g: Optional[torch.Tensor], mu_g: torch.Tensor, var
         Z = _check(Z, "Z", (n, Mq))
     dev = Xq.device
     with torch.cuda.device(dev):
-        dmu = torch.empty((Mq, D), dtype=torch.float64, device=dev)
-        dvar = torch.empty((Mq, D), dtype=torch.float64, device=dev)
+        dmu = _empty(dev, Mq, D)
+        dvar = _empty(dev, Mq, D)
         rc = _lib.lib.scaml_target_posterior_grad_f64(_ptr(cov_g) if n else None, _ptr(mu_g), _ptr(var_g), _ptr(Xt) if n else None, _ptr(Xq),
                                                       _ptr(theta), _ptr(alpha) if n else None, _ptr(Z) if n else None, float(s_all), _ptr(info), n, Mq, D,
                                                       int(kind), _ptr(dmu), _ptr(dvar), _stream_handle())
@@ -598,10 +592,9 @@ def target_fantasy_block(cov_s: torch.Tensor, mean_s: torch.Tensor, var_s: torch
     theta = _check(theta, "theta", (D + 2,))
     targets = _check(targets, "targets", (F, n))
     dev = Xall.device
-    f64 = dict(dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        Knn, resid = torch.empty((1, n, n), **f64), torch.empty((1, n), **f64)
-        Knq, mean_q, var_q = torch.empty((1, n, M), **f64), torch.empty((M,), **f64), torch.empty((M,), **f64)
+        Knn, resid = _empty(dev, 1, n, n), _empty(dev, 1, n)
+        Knq, mean_q, var_q = _empty(dev, 1, n, M), _empty(dev, M), _empty(dev, M)
         rc = _lib.lib.scaml_target_assemble_f64(_ptr(cov_s), _ptr(mean_s), _ptr(var_s), _ptr(Xall), _ptr(theta), _ptr(targets[0]),
                                                 float(m_all), float(s_all), n, M, D, int(kind), _ptr(Knn), _ptr(resid), _ptr(Knq),
                                                 _ptr(mean_q), _ptr(var_q), _stream_handle())
@@ -615,7 +608,7 @@ def target_fantasy_block(cov_s: torch.Tensor, mean_s: torch.Tensor, var_s: torch
         Z = cho_solve(f["L"], f["Linv_diag"], Knq)[0] if M > 0 else None
         var = None
         if var_noise_add is not None:
-            mu0, var = torch.empty((M,), **f64), torch.empty((M,), **f64)
+            mu0, var = _empty(dev, M), _empty(dev, M)
             if M > 0:
                 rc = _lib.lib.scaml_target_finish_f64(_ptr(Knq), _ptr(Z), _ptr(f["alpha"]), _ptr(mean_q), _ptr(var_q), float(m_all), float(s_all),
                                                       float(var_noise_add), _ptr(f["info"]), n, M, _ptr(mu0), _ptr(var), _stream_handle())
@@ -650,8 +643,8 @@ def target_fantasy_acqf(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor,
                  Xt=_check(grad_inputs["Xt"], "Xt", (n, D)), Xq=_check(Xq, "Xq", (M, D)),
                  theta=_check(grad_inputs["theta"], "theta", (D + 2,)))
     with torch.cuda.device(dev):
-        value = torch.empty((M,), dtype=torch.float64, device=dev)
-        grad = torch.empty((M, D), dtype=torch.float64, device=dev) if g is not None else None
+        value = _empty(dev, M)
+        grad = _empty(dev, M, D) if g is not None else None
         rc = _lib.lib.scaml_target_fantasy_acqf_f64(
             _ptr(Knq), _ptr(Z), _ptr(alpha), _ptr(mean_q), _ptr(var_q), float(m_all), float(s_all), float(noise_add), _ptr(info),
             int(acqf), float(acqf_param), *([_ptr(g[k]) for k in ("cov_g", "mu_g", "var_g", "Xt", "Xq", "theta")] if g else [None] * 6),
@@ -665,8 +658,7 @@ def mll_backward_workspace(T: int, N: int, D: int, device) -> Dict[str, torch.Te
     the per-tile partial sums.  An optimiser loop allocates them once (scaml_mll_backward_workspace_doubles)."""
     nb = (N + 15) // 16
     nt = nb * (nb + 1) // 2
-    return dict(work=torch.empty((T * N * N,), dtype=torch.float64, device=device),
-                partials=torch.empty((T, nt, D + 2), dtype=torch.float64, device=device), shape=(T, N, D))
+    return dict(work=_empty(device, T * N * N), partials=_empty(device, T, nt, D + 2), shape=(T, N, D))
 
 
 def mll_backward(
@@ -689,8 +681,7 @@ def mll_backward(
     L = _check(L, "L", (T, N, N))
     Linv_diag = _check(Linv_diag, "Linv_diag", (T, (N + 15) // 16, 16, 16))
     alpha = _check(alpha, "alpha", (T, N))
-    if n_points is not None:
-        n_points = _check(n_points, "n_points", (T,), torch.int32)
+    n_points = _opt(n_points, "n_points", (T,), torch.int32)
     dev = X.device
     if workspace is None:
         workspace = mll_backward_workspace(T, N, D, dev)
@@ -786,6 +777,29 @@ def fused_mll(X: torch.Tensor, y: torch.Tensor, theta: torch.Tensor, kind: int,
 
 
 
+def _spec_host(spec, kernel: str, weights=None):
+    """The host block of doubles the optimiser kernels read (include/scaml_gp.h (8), (9)): the Interval bounds and (kind, p1, p2) of
+    the lengthscale / outputscale / noise priors -- 15 doubles; ``weights`` = (prior, lower bound) appends the target's four."""
+    import ctypes
+
+    from . import hyper
+
+    def prior(pr):
+        if pr is None:
+            return [0.0, 0.0, 0.0]
+        if isinstance(pr, hyper.GammaPrior):
+            return [1.0, pr.concentration, pr.rate]
+        if isinstance(pr, hyper.LogNormalPrior):
+            return [2.0, pr.loc, pr.scale]
+        raise TypeError(f"prior {type(pr).__name__} is not supported by the {kernel} kernel")
+
+    vals = [spec.ls_constraint.lower, spec.ls_constraint.upper, spec.os_constraint.lower, spec.os_constraint.upper,
+            spec.noise_constraint.lower, spec.noise_constraint.upper, *prior(spec.ls_prior), *prior(spec.os_prior), *prior(spec.noise_prior)]
+    if weights is not None:
+        vals += [*prior(weights[0]), weights[1]]
+    return (ctypes.c_double * len(vals))(*[float(v) for v in vals])
+
+
 # ---- (8) target GP: objective + gradient / whole refit in one launch -------------------------------------------------------
 class TargetFitProblem:
     """Device-resident inputs of ``scaml_target_mll_f64`` / ``scaml_target_fit_f64`` for ONE ScaMLGP training set: the source
@@ -795,10 +809,6 @@ class TargetFitProblem:
 
     def __init__(self, source_means: torch.Tensor, source_covs: torch.Tensor, train_X: torch.Tensor, train_targets: torch.Tensor,
                  m_all: float, s_all: float, spec, weights_prior, weights_lower_bound: float, kind: int):
-        import ctypes
-
-        from . import hyper
-
         n, T = source_means.shape
         D = train_X.shape[-1]
         self.n, self.T, self.D, self.kind = int(n), int(T), int(D), int(kind)
@@ -810,20 +820,7 @@ class TargetFitProblem:
         self.X = _check(train_X, "train_X", (n, D))
         self.y = _check(train_targets, "train_targets", (n,))
         self.m_all, self.s_all = float(m_all), float(s_all)
-
-        def prior(pr):
-            if pr is None:
-                return [0.0, 0.0, 0.0]
-            if isinstance(pr, hyper.GammaPrior):
-                return [1.0, pr.concentration, pr.rate]
-            if isinstance(pr, hyper.LogNormalPrior):
-                return [2.0, pr.loc, pr.scale]
-            raise TypeError(f"prior {type(pr).__name__} is not supported by the target-fit kernel")
-
-        vals = [spec.ls_constraint.lower, spec.ls_constraint.upper, spec.os_constraint.lower, spec.os_constraint.upper,
-                spec.noise_constraint.lower, spec.noise_constraint.upper, *prior(spec.ls_prior), *prior(spec.os_prior),
-                *prior(spec.noise_prior), *prior(weights_prior), float(weights_lower_bound)]
-        self.spec_host = (ctypes.c_double * 19)(*[float(v) for v in vals])
+        self.spec_host = _spec_host(spec, "target-fit", (weights_prior, weights_lower_bound))
 
     @staticmethod
     def supported(n: int, T: int, D: int) -> bool:
@@ -839,10 +836,10 @@ def target_mll(prob: TargetFitProblem, z: torch.Tensor) -> Dict[str, torch.Tenso
     B = z.shape[0]
     dev = prob.device
     with torch.cuda.device(dev):
-        value = torch.empty((B,), dtype=torch.float64, device=dev)
-        grad = torch.empty((B, prob.P), dtype=torch.float64, device=dev)
-        info = torch.empty((B,), dtype=torch.int32, device=dev)
-        jit = torch.empty((B,), dtype=torch.float64, device=dev)
+        value = _empty(dev, B)
+        grad = _empty(dev, B, prob.P)
+        info = _empty(dev, B, dtype=torch.int32)
+        jit = _empty(dev, B)
         rc = _lib.lib.scaml_target_mll_f64(_ptr(prob.means_t), _ptr(prob.covs_p), _ptr(prob.X), _ptr(prob.y), prob.m_all, prob.s_all,
                                            prob.spec_host, _ptr(z), B, prob.n, prob.T, prob.D, prob.kind, _ptr(value), _ptr(grad),
                                            _ptr(info), _ptr(jit), _stream_handle())
@@ -859,12 +856,12 @@ def target_fit(prob: TargetFitProblem, z0: torch.Tensor, max_iter: int = 200, hi
     B = z.shape[0]
     dev = prob.device
     with torch.cuda.device(dev):
-        value = torch.empty((B,), dtype=torch.float64, device=dev)
-        info = torch.empty((B,), dtype=torch.int32, device=dev)
-        jit = torch.empty((B,), dtype=torch.float64, device=dev)
+        value = _empty(dev, B)
+        info = _empty(dev, B, dtype=torch.int32)
+        jit = _empty(dev, B)
         stats = torch.zeros((B, 4), dtype=torch.int32, device=dev)
         nws = int(_lib.lib.scaml_target_fit_workspace_doubles(B, prob.T, prob.D, history))
-        ws = torch.empty((max(nws, 1),), dtype=torch.float64, device=dev)
+        ws = _empty(dev, max(nws, 1))
         rc = _lib.lib.scaml_target_fit_f64(_ptr(prob.means_t), _ptr(prob.covs_p), _ptr(prob.X), _ptr(prob.y), prob.m_all, prob.s_all,
                                            prob.spec_host, _ptr(z), B, prob.n, prob.T, prob.D, prob.kind, int(max_iter), int(history),
                                            float(gtol), float(ftol), _ptr(value), _ptr(info), _ptr(jit), _ptr(stats), _ptr(ws), nws,
@@ -880,26 +877,18 @@ def target_fit(prob: TargetFitProblem, z0: torch.Tensor, max_iter: int = 200, hi
 # whole batch, so the smallest value past the knee is the default.
 STACK_FIT_EVALS_PER_CALL = 4
 _STACK_FIT_MAX_LS = 20          # trials per line search inside scaml_stack_fit_f64
+_STACK_FIT_SCALARS = 16         # STACK_FIT_SCALARS (csrc/gp_stack_fit_params.h)
+
+
+def stack_fit_state_doubles(P: int, history: int) -> int:
+    """Doubles of one problem's optimiser state at the head of the workspace: ``stack_fit_state_doubles`` of csrc/gp_stack_fit_params.h
+    (x, g, d, xt, the curvature pairs, rho, the scalars; tests/test_stack_fit_emul.py compares the two)."""
+    return (4 + 2 * history) * P + history + _STACK_FIT_SCALARS
 
 
 def stack_spec_host(spec):
     """The 15 host doubles ``scaml_stack_fit_f64`` reads: Interval bounds and (kind, p1, p2) of the three hyper-priors."""
-    import ctypes
-
-    from . import hyper
-
-    def prior(pr):
-        if pr is None:
-            return [0.0, 0.0, 0.0]
-        if isinstance(pr, hyper.GammaPrior):
-            return [1.0, pr.concentration, pr.rate]
-        if isinstance(pr, hyper.LogNormalPrior):
-            return [2.0, pr.loc, pr.scale]
-        raise TypeError(f"prior {type(pr).__name__} is not supported by the stack-fit kernel")
-
-    vals = [spec.ls_constraint.lower, spec.ls_constraint.upper, spec.os_constraint.lower, spec.os_constraint.upper,
-            spec.noise_constraint.lower, spec.noise_constraint.upper, *prior(spec.ls_prior), *prior(spec.os_prior), *prior(spec.noise_prior)]
-    return (ctypes.c_double * 15)(*[float(v) for v in vals])
+    return _spec_host(spec, "stack-fit")
 
 
 def stack_fit(X: torch.Tensor, y: torch.Tensor, n_points: Optional[torch.Tensor], spec, z0: torch.Tensor, kind: int, *,
@@ -918,8 +907,7 @@ def stack_fit(X: torch.Tensor, y: torch.Tensor, n_points: Optional[torch.Tensor]
     X = _check(X, "X")
     y = _check(y, "y", (B, N))
     z = _check(z0, "z0", (B, P)).clone()
-    if n_points is not None:
-        n_points = _check(n_points, "n_points", (B,), torch.int32)
+    n_points = _opt(n_points, "n_points", (B,), torch.int32)
     per_call = int(evals_per_call or STACK_FIT_EVALS_PER_CALL)
     if per_call < 1:
         raise ValueError("evals_per_call must be positive")
@@ -928,10 +916,10 @@ def stack_fit(X: torch.Tensor, y: torch.Tensor, n_points: Optional[torch.Tensor]
     budget = 1 + int(max_iter) * _STACK_FIT_MAX_LS
     n_eval = n_calls = 0
     with torch.cuda.device(dev):
-        value = torch.empty((B,), dtype=torch.float64, device=dev)
+        value = _empty(dev, B)
         stats = torch.zeros((B, 4), dtype=torch.int32, device=dev)
         nbytes = int(_lib.lib.scaml_stack_fit_workspace_bytes(B, N, D, int(history)))
-        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        ws = _empty(dev, max(nbytes, 16), dtype=torch.uint8)
         host = stats.cpu()
         while B > 0:
             k = min(per_call, budget - n_eval)
@@ -944,7 +932,7 @@ def stack_fit(X: torch.Tensor, y: torch.Tensor, n_points: Optional[torch.Tensor]
             host = stats.cpu()
             if not bool((host[:, 2] == 0).any()) or n_eval >= budget:
                 break
-        stride = (4 + 2 * int(history)) * P + int(history) + 16   # the per-problem state opens the workspace (include/scaml_gp.h)
+        stride = stack_fit_state_doubles(P, int(history))   # the per-problem state opens the workspace (include/scaml_gp.h)
         grad = ws[: B * stride * 8].view(torch.float64).reshape(B, stride)[:, P:2 * P].clone()
     return dict(z=z, value=value, grad=grad, stats=host, n_eval=n_eval, n_calls=n_calls)
 

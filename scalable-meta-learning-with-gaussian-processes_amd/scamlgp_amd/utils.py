@@ -109,34 +109,16 @@ def _fit_stack(stack: SourceGPStack, num_restarts: int, max_iter: int = 200, use
         return _fit_stack_device(stack, num_restarts, max_iter, evals_per_call)
     if driver != "host":
         raise ValueError(f"driver must be 'host' or 'device', got {driver!r}")
-    T, D = stack.T, stack.D
     reps = 1 + num_restarts
-    starts = [stack.raw.clone()]
-    for _ in range(num_restarts):
-        starts.append(stack.spec.to_raw(stack.spec.sample_prior((T,), D, device=stack.device)))
-    x0 = torch.cat(starts, 0)  # problem b = rep * T + task
+    x0 = _stack_starts(stack, num_restarts)
     fun = lambda r: stack.objective(r, reps)   # noqa: E731
     if use_graph and stack.device.type == "cuda":
         gfun = _GraphedBatchObjective(fun, x0)
         if gfun.ok:
             fun = gfun
     res = hyper.batched_lbfgs(fun, x0, max_iter=max_iter)
-    f = torch.where(res.failed | ~torch.isfinite(res.f), torch.full_like(res.f, float("inf")), res.f).reshape(reps, T)
-    best = f.argmin(0)
-    if bool(torch.isinf(f.min(0).values).any()):
-        bad = torch.nonzero(torch.isinf(f.min(0).values)).flatten().tolist()
-        raise ModelFittingError(
-            "Hyperparameter optimization failed for all attempts. Usually this indicates a problem with model's "
-            f"input data or hyperparameter priors definitions. (tasks {[stack.task_ids[i] for i in bad][:8]})")
-    n_failed = int(torch.isinf(f).sum())
-    if n_failed:
-        logger.warning("%d of %d hyper-parameter optimisation attempts failed and were skipped.", n_failed, f.numel())
-    stack.raw = res.x.reshape(reps, T, D + 2)[best, torch.arange(T, device=stack.device)].contiguous()
-    stack.refresh()
-    obj = -f.min(0).values
-    # (a sharded stack also reports the objective summed over every rank's tasks: the fit's one collective)
-    total = sdist.fused_allreduce([obj.sum().reshape(1)], stack.shard)[0]
-    stack.last_fit_info = dict(n_iter=res.n_iter, n_eval=res.n_eval, objective=obj, objective_sum=total.squeeze(0))
+    f = torch.where(res.failed | ~torch.isfinite(res.f), torch.full_like(res.f, float("inf")), res.f)
+    _keep_best(stack, res.x, f, reps, dict(n_iter=res.n_iter, n_eval=res.n_eval))
 
 
 class _GraphedObjective:

@@ -8,21 +8,6 @@
 
 #include "gp_stack_fit.hip"
 
-namespace {
-void fill_prior(const double* t, scaml::TargetPrior& pr) {
-  const int kind = (int)t[0];
-  pr.kind = kind; pr.pad_ = 0; pr.p1 = t[1]; pr.p2 = t[2];
-  pr.c0 = kind == 1 ? t[1] * log(t[2]) - lgamma(t[1]) : (kind == 2 ? -log(t[2]) - 0.9189385332046727 : 0.0);
-}
-scaml::StackFitSpec make_spec(const double* s) {
-  scaml::StackFitSpec sp{s[0], s[1], s[2], s[3], s[4], s[5], {}, {}, {}};
-  fill_prior(s + 6, sp.ls_prior);
-  fill_prior(s + 9, sp.os_prior);
-  fill_prior(s + 12, sp.nz_prior);
-  return sp;
-}
-}  // namespace
-
 extern "C" {
 
 long long emul_stack_fit_state_doubles(int P, int H) { return (long long)scaml::stack_fit_state_doubles(P, H); }
@@ -30,7 +15,11 @@ long long emul_stack_fit_state_doubles(int P, int H) { return (long long)scaml::
 // sf_objective for B problems: partials (B, tiles, D+2), theta / raw (B, D+2), n (B) -> f (B), g (B, D+2)
 void emul_stack_objective(const double* spec15, const double* mll, const int32_t* info, const double* partials, int tiles,
                           const double* theta, const double* raw, const int32_t* n, int B, int D, double* f, double* g) {
-  const scaml::StackFitSpec sp = make_spec(spec15);
+  scaml::HyperSpec sp{};
+  if (!scaml::hyper_spec_from_host(spec15, sp)) {   // a bad fixture fails loudly
+    for (int b = 0; b < B; ++b) f[b] = NAN;
+    return;
+  }
   const int P = D + 2;
   for (int b = 0; b < B; ++b) {
     double gl[scaml::SF_NV];

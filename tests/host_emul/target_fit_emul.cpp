@@ -15,17 +15,7 @@ extern "C" int emul_target_fit(const double* means_t, const double* covs_p, cons
   TargetFitParams p;
   memset(&p, 0, sizeof(p));
   p.means_t = means_t; p.covs_p = covs_p; p.X = X; p.y = y; p.m_all = m_all; p.s_all = s_all;
-  TargetSpec& sp = p.spec;
-  sp.ls_lo = spec[0]; sp.ls_hi = spec[1]; sp.os_lo = spec[2]; sp.os_hi = spec[3]; sp.nz_lo = spec[4]; sp.nz_hi = spec[5];
-  TargetPrior* pr[4] = {&sp.ls_prior, &sp.os_prior, &sp.nz_prior, &sp.w_prior};
-  for (int q = 0; q < 4; ++q) {
-    pr[q]->kind = (int)spec[6 + 3 * q];
-    pr[q]->p1 = spec[7 + 3 * q];
-    pr[q]->p2 = spec[8 + 3 * q];
-    pr[q]->c0 = pr[q]->kind == 1 ? pr[q]->p1 * log(pr[q]->p2) - lgamma(pr[q]->p1)
-                                 : (pr[q]->kind == 2 ? -log(pr[q]->p2) - 0.5 * log(2.0 * M_PI) : 0.0);
-  }
-  sp.w_lower = spec[18];
+  if (!target_spec_from_host(spec, p.spec)) return -2;
   const int P = D + 2 + T;
   std::vector<double> ws((size_t)B * (6 + 2 * history) * P + 1);
   p.z = z; p.value = value; p.grad = grad; p.info = info; p.jitter = jitter; p.workspace = ws.data(); p.stats = stats;

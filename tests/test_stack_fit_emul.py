@@ -223,3 +223,13 @@ def test_whole_loop_reaches_the_batched_lbfgs_optimum_on_golden_stacks(emul, fix
     assert np.isfinite(f_ref).all()
     for t in range(T):
         assert f_dev[t] <= f_ref[t] + 1e-3 * max(1.0, abs(f_ref[t])), (t, f_dev[t], f_ref[t], res["stats"].tolist())
+
+
+def test_python_state_stride_matches_header(emul):
+    """``ops.stack_fit`` reads the gradient out of the per-problem state at the head of the workspace: the stride it uses is the
+    header's ``stack_fit_state_doubles`` for every P = D + 2 and history the kernel takes."""
+    from scamlgp_amd import ops
+
+    for P in range(3, 65):
+        for history in range(1, 17):
+            assert ops.stack_fit_state_doubles(P, history) == emul.emul_stack_fit_state_doubles(P, history)
