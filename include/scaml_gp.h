@@ -339,6 +339,34 @@ int scaml_target_fit_f64(const double* means_t, const double* covs_packed, const
                          long long workspace_doubles, void* stream);
 
 /*
+ * (8b) The objective and the refit of (8) over a BATCH of training sets: S problems x B start points in ONE launch of S * B
+ * workgroups (workgroup r works on row r of z: start r % B of problem r / B).  The use: S Bayesian-optimisation studies against
+ * one fitted source stack (the repeated runs behind a regret curve, scamlgp/benchmarking/local_runner.py:174-181, which the reference
+ * fans out over a process pool) refitted in lock-step -- one study's refit occupies B of the chip's 256 CUs for its whole latency.
+ *   z (S, B, P), P = D + 2 + T, as in (8); value (S, B), grad (S, B, P), info (S, B), jitter_used (S, B), stats (S, B, 4).
+ *   means_t (S, T, n_max), covs_packed (S, T, n_max (n_max + 1) / 2), X (S, n_max, D), y (S, n_max): problem s in the leading
+ *       n_s columns / n_s (n_s + 1) / 2 packed entries / n_s rows of its slice (the packed index a (a + 1) / 2 + b does not depend
+ *       on n); what lies beyond is never read.
+ *   n_points (S) int32, 1 <= n_s <= n_max: the problems may differ in size (a study with a pending or failed evaluation is a
+ *       point behind).  A count outside the range gives value NaN, info -1 (stats status 4) for that problem's rows; nothing is read.
+ *   m_all (S), s_all (S) > 0: the standardisers, DEVICE arrays here (by value in (8)).
+ *   spec_host: HOST pointer to 19 doubles as in (8), shared by all problems; T, D, kind, the optimiser's options likewise.
+ * Every row runs the instruction sequence the single-problem kernel runs on that problem (the matrix-core factorisation where ITS
+ * n_s <= 112, the column-by-column elimination beyond), so the results equal those of (8) called per problem bit for bit.
+ * workspace: scaml_target_fit_batched_workspace_doubles(S, B, T, D, history) doubles.
+ * Limits as in (8): n_max <= scaml_target_fit_max_n(T, D), D <= scaml_target_fit_max_d(); SCAML_E_TOOLARGE otherwise.
+ * S == 0 or B == 0: nothing is enqueued.
+ */
+long long scaml_target_fit_batched_workspace_doubles(int S, int B, int T, int D, int history);
+int scaml_target_mll_batched_f64(const double* means_t, const double* covs_packed, const double* X, const double* y, const int32_t* n_points,
+                                 const double* m_all, const double* s_all, const double* spec_host, const double* z, int S, int B, int n_max,
+                                 int T, int D, int kind, double* value, double* grad, int32_t* info, double* jitter_used, void* stream);
+int scaml_target_fit_batched_f64(const double* means_t, const double* covs_packed, const double* X, const double* y, const int32_t* n_points,
+                                 const double* m_all, const double* s_all, const double* spec_host, double* z, int S, int B, int n_max, int T,
+                                 int D, int kind, int max_iter, int history, double gtol, double ftol, double* value, int32_t* info,
+                                 double* jitter_used, int32_t* stats, double* workspace, long long workspace_doubles, void* stream);
+
+/*
  * (9) Training the source GPs on the device: the hyper-parameter fit of a whole stack, B = tasks x starts problems side by side
  * (scamlgp/model.py:176-188 -> scamlgp/utils.py:139-212: L-BFGS on -(mll + sum log p(theta) / n) over the raw parameters of the
  * sigmoid Interval constraints, from the warm start and from every prior-sampled restart).

@@ -56,6 +56,11 @@ namespace scaml {
 struct TfCtx {
   int tid, nthr, lane, wave, nwave;
   int n, T, D, P, E, kind;
+  // a problem of a BATCH (tf_main_batched; unset otherwise): its slice of the (S, ...) arrays and its standardiser in place of the
+  // argument block's, and the row strides of means_t / covs_p (those of the batch's n_max) -- see TF_D
+  const double *means_t, *covs_p, *y;
+  double m_all, s_all;
+  int ldn, ldE;
   // LDS
   double *Ap, *Tp, *Xs, *col, *piv, *rs, *alpha, *vv, *w, *w2, *theta, *dth, *invl, *part, *red, *sc;
   // matrix-core path (n <= 112): 16 x 16 tiles at pitch 17, lower block triangle, tile (i, j) at (i (i + 1) / 2 + j) * TF_TS
@@ -64,6 +69,10 @@ struct TfCtx {
   int solo;   // optimiser bookkeeping by ONE wave (P <= 64: a lane per variable): reductions stay in the wave, barriers are no-ops
 };
 constexpr int TF_TP = 17, TF_TS = 16 * TF_TP;
+// Where the training set comes from.  The evaluation and the optimiser are templates over BATCH: false -- the single-problem kernel,
+// which reads the argument block exactly as it always did (its instruction stream must not move: DESIGN.md 4h); true -- the workgroup's
+// context carries the problem.
+#define TF_D(field) (BATCH ? c.field : p.field)
 
 TF_DEV int tf_idxL(int a, int b) { return a * (a + 1) / 2 + b; }
 TF_DEV int tf_rowT(int j, int n) { return j * n - j * (j - 1) / 2 - j; }   // row j of the upper-packed block: (j, k), k >= j, at tf_rowT(j) + k
@@ -159,10 +168,11 @@ TF_DEV void tf_kernel(int kind, double d2, double& kk, double& dk) {
 // Three barriers per BLOCK column instead of one per column.  Returns 0 or the 1-based index of the failing pivot.
 TF_DEV int tf_tile(int i, int j) { return (i * (i + 1) / 2 + j) * TF_TS; }
 
+template <bool BATCH>
 TF_DEV int tf_factor_mfma(const TfCtx& c, const TargetFitParams& p, double os, double noise, double jit, double& quad, double& logdet) {
-  const int n = c.n, T = c.T, D = c.D, E = c.E, nb = c.nb;
+  const int n = c.n, T = c.T, D = c.D, ldE = BATCH ? c.ldE : c.E, ldn = BATCH ? c.ldn : n, nb = c.nb;
   const int lane = c.lane, lc = lane & 15, lq = lane >> 4;
-  const double inv_s = 1.0 / p.s_all;
+  const double inv_s = 1.0 / TF_D(s_all);
   // ---- build: lower block triangle of K (+ noise + jitter), identity padding past n; residual r into vv ----
   const int ntile = nb * (nb + 1) / 2;
   for (int e = c.tid; e < ntile * 256; e += c.nthr) {
@@ -175,12 +185,12 @@ TF_DEV int tf_factor_mfma(const TfCtx& c, const TargetFitParams& p, double os, d
       val = 0.0;
       if (b <= a) {
         double acc = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-        const double* cp = p.covs_p + tf_idxL(a, b);
+        const double* cp = TF_D(covs_p) + tf_idxL(a, b);
         int i = 0;
         for (; i + 16 <= T; i += 16) {   // sixteen task rows in flight: the pass is a chain of L2 round trips, not of bytes
           double x[16];
 #pragma unroll
-          for (int j = 0; j < 16; ++j) x[j] = cp[(size_t)(i + j) * E];
+          for (int j = 0; j < 16; ++j) x[j] = cp[(size_t)(i + j) * ldE];
 #pragma unroll
           for (int j = 0; j < 16; j += 4) {
             acc += c.w2[i + j] * x[j];
@@ -190,13 +200,13 @@ TF_DEV int tf_factor_mfma(const TfCtx& c, const TargetFitParams& p, double os, d
           }
         }
         for (; i + 4 <= T; i += 4) {
-          const double x0 = cp[(size_t)i * E], x1 = cp[(size_t)(i + 1) * E], x2 = cp[(size_t)(i + 2) * E], x3 = cp[(size_t)(i + 3) * E];
+          const double x0 = cp[(size_t)i * ldE], x1 = cp[(size_t)(i + 1) * ldE], x2 = cp[(size_t)(i + 2) * ldE], x3 = cp[(size_t)(i + 3) * ldE];
           acc += c.w2[i] * x0;
           acc1 += c.w2[i + 1] * x1;
           acc2 += c.w2[i + 2] * x2;
           acc3 += c.w2[i + 3] * x3;
         }
-        for (; i < T; ++i) acc += c.w2[i] * cp[(size_t)i * E];
+        for (; i < T; ++i) acc += c.w2[i] * cp[(size_t)i * ldE];
         acc = (acc + acc1) + (acc2 + acc3);
         double k = os;
         if (a != b) {
@@ -222,13 +232,13 @@ TF_DEV int tf_factor_mfma(const TfCtx& c, const TargetFitParams& p, double os, d
       double m = 0.0, m1 = 0.0;
       int i = 0;
       for (; i + 4 <= T; i += 4) {
-        const double x0 = p.means_t[(size_t)i * n + b], x1 = p.means_t[(size_t)(i + 1) * n + b], x2 = p.means_t[(size_t)(i + 2) * n + b],
-                     x3 = p.means_t[(size_t)(i + 3) * n + b];
+        const double x0 = TF_D(means_t)[(size_t)i * ldn + b], x1 = TF_D(means_t)[(size_t)(i + 1) * ldn + b], x2 = TF_D(means_t)[(size_t)(i + 2) * ldn + b],
+                     x3 = TF_D(means_t)[(size_t)(i + 3) * ldn + b];
         m += c.w[i] * x0 + c.w[i + 2] * x2;
         m1 += c.w[i + 1] * x1 + c.w[i + 3] * x3;
       }
-      for (; i < T; ++i) m += c.w[i] * p.means_t[(size_t)i * n + b];
-      rv = p.y[b] - (m + m1 - p.m_all) * inv_s;
+      for (; i < T; ++i) m += c.w[i] * TF_D(means_t)[(size_t)i * ldn + b];
+      rv = TF_D(y)[b] - (m + m1 - TF_D(m_all)) * inv_s;
     }
     c.vv[b] = rv;
   }
@@ -398,10 +408,11 @@ TF_DEV int tf_factor_mfma(const TfCtx& c, const TargetFitParams& p, double os, d
 // One evaluation at z (P doubles, global): returns mll (every thread) and, if gz != nullptr, d mll / d z.
 // info_out / jit_out: status of the factorisation (thread 0 writes them if given).  A matrix that is not positive definite
 // even with the largest jitter gives NaN.
+template <bool BATCH>
 TF_DEV double tf_eval(const TfCtx& c, const TargetFitParams& p, const double* z, double* gz, int32_t* info_out, double* jit_out) {
-  const int n = c.n, T = c.T, D = c.D, E = c.E;
+  const int n = c.n, T = c.T, D = c.D, E = c.E, ldE = BATCH ? c.ldE : E, ldn = BATCH ? c.ldn : n;
   const TargetSpec& sp = p.spec;
-  const double inv_s = 1.0 / p.s_all, inv_s2 = inv_s * inv_s;
+  const double inv_s = 1.0 / TF_D(s_all), inv_s2 = inv_s * inv_s;
   // ---- parameters ----
   // (the Interval and the group ladders stay spelled out in this kernel: routed through hyper_var / interval_* of gp_hyper_spec.h
   //  the register allocation of the whole evaluation shifts -- 6 more instructions, two more SGPR spills)
@@ -428,7 +439,7 @@ TF_DEV double tf_eval(const TfCtx& c, const TargetFitParams& p, const double* z,
     jit = attempt == 0 ? 0.0 : (attempt == 1 ? 1e-8 : (attempt == 2 ? 1e-7 : 1e-6));
 #ifndef SCAML_HOST_EMUL
     if (c.mfma) {
-      fail = tf_factor_mfma(c, p, os, noise, jit, quad_m, logdet_m);
+      fail = tf_factor_mfma<BATCH>(c, p, os, noise, jit, quad_m, logdet_m);
       if (!fail) break;
       TF_SYNC();
       continue;
@@ -440,18 +451,18 @@ TF_DEV double tf_eval(const TfCtx& c, const TargetFitParams& p, const double* z,
       tf_decode(e, a, b);
       // (eight loads in flight per trip: one exposed memory round trip per task was 37 us of a 365-us evaluation)
       double acc = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-      const double* cp = p.covs_p + e;
+      const double* cp = TF_D(covs_p) + e;
       int i = 0;
       for (; i + 8 <= T; i += 8) {
         double x[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = cp[(size_t)(i + j) * E];
+        for (int j = 0; j < 8; ++j) x[j] = cp[(size_t)(i + j) * ldE];
         acc += c.w2[i] * x[0] + c.w2[i + 4] * x[4];
         acc1 += c.w2[i + 1] * x[1] + c.w2[i + 5] * x[5];
         acc2 += c.w2[i + 2] * x[2] + c.w2[i + 6] * x[6];
         acc3 += c.w2[i + 3] * x[3] + c.w2[i + 7] * x[7];
       }
-      for (; i < T; ++i) acc += c.w2[i] * cp[(size_t)i * E];
+      for (; i < T; ++i) acc += c.w2[i] * cp[(size_t)i * ldE];
       acc = (acc + acc1) + (acc2 + acc3);
       double k = os;
       if (a != b) {
@@ -473,14 +484,14 @@ TF_DEV double tf_eval(const TfCtx& c, const TargetFitParams& p, const double* z,
       double m = 0.0, m1 = 0.0;
       int i = 0;
       for (; i + 4 <= T; i += 4) {
-        const double x0 = p.means_t[(size_t)i * n + b], x1 = p.means_t[(size_t)(i + 1) * n + b], x2 = p.means_t[(size_t)(i + 2) * n + b],
-                     x3 = p.means_t[(size_t)(i + 3) * n + b];
+        const double x0 = TF_D(means_t)[(size_t)i * ldn + b], x1 = TF_D(means_t)[(size_t)(i + 1) * ldn + b], x2 = TF_D(means_t)[(size_t)(i + 2) * ldn + b],
+                     x3 = TF_D(means_t)[(size_t)(i + 3) * ldn + b];
         m += c.w[i] * x0 + c.w[i + 2] * x2;
         m1 += c.w[i + 1] * x1 + c.w[i + 3] * x3;
       }
-      for (; i < T; ++i) m += c.w[i] * p.means_t[(size_t)i * n + b];
+      for (; i < T; ++i) m += c.w[i] * TF_D(means_t)[(size_t)i * ldn + b];
       m += m1;
-      c.Ap[tf_idxL(n, b)] = p.y[b] - (m - p.m_all) * inv_s;
+      c.Ap[tf_idxL(n, b)] = TF_D(y)[b] - (m - TF_D(m_all)) * inv_s;
     }
     if (c.tid == 0) c.Ap[tf_idxL(n, n)] = 0.0;
     TF_SYNC();
@@ -634,8 +645,8 @@ TF_DEV double tf_eval(const TfCtx& c, const TargetFitParams& p, const double* z,
   // ---- d / d w_i: one wave per task (two tasks per trip: eight coalesced loads in flight) ----
   for (int i0 = 2 * c.wave; i0 < T; i0 += 2 * c.nwave) {
     const int i1 = i0 + 1 < T ? i0 + 1 : i0;
-    const double* cp0 = p.covs_p + (size_t)i0 * E;
-    const double* cp1 = p.covs_p + (size_t)i1 * E;
+    const double* cp0 = TF_D(covs_p) + (size_t)i0 * ldE;
+    const double* cp1 = TF_D(covs_p) + (size_t)i1 * ldE;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
     int e = c.lane;
     for (; e + 3 * TF_LANES < E; e += 4 * TF_LANES) {
@@ -653,8 +664,8 @@ TF_DEV double tf_eval(const TfCtx& c, const TargetFitParams& p, const double* z,
     double am = 0.0, bm = 0.0;
     for (int a = c.lane; a < n; a += TF_LANES) {
       const double al = c.alpha[a];
-      am += al * p.means_t[(size_t)i0 * n + a];
-      bm += al * p.means_t[(size_t)i1 * n + a];
+      am += al * TF_D(means_t)[(size_t)i0 * ldn + a];
+      bm += al * TF_D(means_t)[(size_t)i1 * ldn + a];
     }
     const double w0 = c.w[i0], w1 = c.w[i1];
     const double t0 = tf_wave_sum(((a0 + a1) + (a2 + a3)) * (2.0 * w0 * inv_s2) + am * inv_s);
@@ -742,6 +753,7 @@ TF_DEV bool tf_finite(double x) { return x - x == 0.0; }
 //   INIT       first evaluation at the start point              -> direction, first trial point
 //   TRIAL      evaluation at a line-search trial point          -> accept (curvature pair, stopping rules, new direction) or halve the step
 //   FINAL      value (and factorisation status) at the point kept
+template <bool BATCH>
 TF_DEV void tf_run(const TfCtx& c, const TargetFitParams& p, int prob) {
   enum { EVAL_ONLY = 0, INIT = 1, TRIAL = 2, FINAL = 3 };
   const int P = c.P, D = c.D, H = p.history;
@@ -777,7 +789,7 @@ TF_DEV void tf_run(const TfCtx& c, const TargetFitParams& p, int prob) {
   int n_eval = 0, it = 0, status = 0, hist = 0, head = 0, ls = 0;   // status 0 max_iter, 1 converged (gradient), 2 converged (decrease), 3 line search failed, 4 bad start
   for (;;) {
     const bool report = state != TRIAL;
-    const double val = tf_eval(c, p, zc, gout, report ? info_out : nullptr, report ? jit_out : nullptr);
+    const double val = tf_eval<BATCH>(c, p, zc, gout, report ? info_out : nullptr, report ? jit_out : nullptr);
     ++n_eval;
     if (state == EVAL_ONLY || state == FINAL) {
       if (c.tid == 0) {
@@ -977,7 +989,57 @@ TF_DEV double* tf_carve(TfCtx& c, double* lds, int n, int T, int D, int nwave, i
 TF_DEV void tf_main(TfCtx& c, const TargetFitParams& p, int prob) {
   for (int i = c.tid; i < c.n * c.D; i += c.nthr) c.Xs[i] = p.X[i];
   TF_SYNC();
-  tf_run(c, p, prob);
+  tf_run<false>(c, p, prob);
+}
+
+// ---- a batch of problems: S training sets x B start points, one workgroup per (problem, start) ---------------------------------
+// Row `row` of z belongs to problem s = row / B.  The packed index a (a + 1) / 2 + b does not depend on n, so a problem of
+// n_s <= n_max points reads the leading n_s (n_s + 1) / 2 entries of its rows of covs_packed and the leading n_s of its rows of
+// means_t -- same elements, same order, same arithmetic as the single-problem kernel on the tight layout; only the row strides
+// differ.  Everything else (spec, optimiser options, the (S * B)-row outputs and workspace) is read from bp.base as it stands.
+// may_mfma: the matrix-core factorisation is available (device build, not switched off); each problem takes it by ITS n, by the
+// rule the single-problem launcher applies (target_fit_mfma_shape), so a batch mixes both factorisations if its sizes straddle 112.
+// lds: target_fit_batched_lds_doubles(...) doubles.  c.tid .. c.nwave set by the caller.
+TF_DEV void tf_main_batched(TfCtx& c, const TargetFitBatchParams& bp, double* lds, int row, int may_mfma) {
+  const TargetFitParams& p = bp.base;
+  const int s = row / p.B, n_max = p.n, T = p.T, D = p.D, P = D + 2 + T;
+  const int n = bp.n_points[s];
+  if (n < 1 || n > n_max) {   // (a corrupt count must not index LDS: the row answers NaN / info -1 and nothing runs)
+    if (c.tid == 0) {
+#ifndef SCAML_HOST_EMUL
+      p.value[row] = __builtin_nan("");
+#else
+      p.value[row] = NAN;
+#endif
+      p.info[row] = -1;
+      if (p.jitter) p.jitter[row] = 0.0;
+      if (p.mode != 0 && p.stats) {
+        p.stats[4 * row + 0] = 0;
+        p.stats[4 * row + 1] = 0;
+        p.stats[4 * row + 2] = 4;
+        p.stats[4 * row + 3] = 0;
+      }
+    }
+    if (p.mode == 0) {
+      for (int i = c.tid; i < P; i += c.nthr) p.grad[(size_t)row * P + i] = 0.0;
+    }
+    return;
+  }
+  const int e_max = n_max * (n_max + 1) / 2;
+  c.means_t = p.means_t + (size_t)s * T * n_max;
+  c.covs_p = p.covs_p + (size_t)s * T * e_max;
+  c.y = p.y + (size_t)s * n_max;
+  c.m_all = bp.m_all[s];
+  c.s_all = bp.s_all[s];
+  c.ldn = n_max;
+  c.ldE = e_max;
+  c.n = n; c.T = T; c.D = D; c.P = P; c.E = n * (n + 1) / 2; c.kind = p.kind;
+  c.solo = 0;
+  tf_carve(c, lds, n, T, D, c.nwave, may_mfma && target_fit_mfma_shape(n, T, D, c.nwave) ? 1 : 0);
+  const double* Xp = p.X + (size_t)s * n_max * D;
+  for (int i = c.tid; i < n * D; i += c.nthr) c.Xs[i] = Xp[i];
+  TF_SYNC();
+  tf_run<true>(c, p, row);
 }
 
 #ifndef SCAML_HOST_EMUL
@@ -996,6 +1058,18 @@ extern "C" __global__ __launch_bounds__(TF_MAX_THREADS) void scaml_target_fit_ke
   c.solo = 0;
   tf_carve(c, tf_lds, p.n, p.T, p.D, c.nwave, p.use_mfma);
   tf_main(c, p, blockIdx.x);
+}
+
+// S x B workgroups in one launch: workgroup blockIdx.x is row blockIdx.x of z, start blockIdx.x % B of problem blockIdx.x / B.
+extern "C" __global__ __launch_bounds__(TF_MAX_THREADS) void scaml_target_fit_batched_kernel(TargetFitBatchParams bp) {
+  extern __shared__ double tf_lds[];
+  TfCtx c;
+  c.tid = threadIdx.x;
+  c.nthr = blockDim.x;
+  c.lane = threadIdx.x & 63;
+  c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  c.nwave = blockDim.x >> 6;
+  tf_main_batched(c, bp, tf_lds, blockIdx.x, bp.base.use_mfma);
 }
 #endif
 

@@ -65,7 +65,7 @@ struct Module {
   FitVariant fit[5] = {{2, 1, {}}, {4, 3, {}}, {8, 3, {}}, {16, 7, {}}, {8, 7, {}}};   // [4]: wide variant for 64 < N <= 128
   hipFunction_t post[2] = {}, post_cov[2] = {}, post_linv[2] = {}, post_linv_cov[2] = {}, post_linv_grad[2] = {};
   hipFunction_t wsum = nullptr, linv = nullptr, chosolve = nullptr, kmat[2] = {}, mllgrad[2] = {};
-  hipFunction_t tgt_assemble[2] = {}, tgt_finish = nullptr, tgt_fit = nullptr, tgt_grad[2] = {};
+  hipFunction_t tgt_assemble[2] = {}, tgt_finish = nullptr, tgt_fit = nullptr, tgt_fit_batched = nullptr, tgt_grad[2] = {};
   hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {};   // value only; value + gradient per kind
   hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {}, stack_step = nullptr;
   hipFunction_t blk_solve[2][2] = {}, blk_syrk[2] = {};   // solve: [kind][D <= 8]
@@ -102,6 +102,7 @@ struct Module {
         {&tgt_fantasy_grad[0], "scaml_target_fantasy_acqf_grad_rbf_kernel", 0, {}},
         {&tgt_fantasy_grad[1], "scaml_target_fantasy_acqf_grad_matern_kernel", 0, {}},
         {&tgt_fit, "scaml_target_fit_kernel", kLdsLimit, {}},
+        {&tgt_fit_batched, "scaml_target_fit_batched_kernel", kLdsLimit, {}},
         {coop, "_ZN5scaml18gp_fit_coop_kernelILi%dEEEvNS_13CoopFitParamsE", kLdsLimit, {K}},
         {&stack_step, "scaml_stack_fit_step_kernel", 0, {}},
         {&blk_round, "scaml_blocked_round_kernel", 0, {}},
@@ -735,9 +736,10 @@ constexpr int kTargetFitThreads = 512;
 size_t target_fit_lds_bytes(int n, int T, int D, bool mfma) {
   return scaml::target_fit_lds_doubles(n, T, D, mfma, kTargetFitThreads / 64) * sizeof(double);
 }
+static_assert(scaml::TARGET_FIT_LDS_LIMIT == kLdsLimit, "the matrix-core rule and the launcher count the same LDS");
 // the matrix-core factorisation takes n <= 112 (two block triangles of 16 x 17 tiles in LDS)
 bool target_fit_use_mfma(int n, int T, int D) {
-  return g_dev.target_fit_path.load(kRelaxed) == 0 && n <= 112 && target_fit_lds_bytes(n, T, D, true) <= kLdsLimit;
+  return g_dev.target_fit_path.load(kRelaxed) == 0 && scaml::target_fit_mfma_shape(n, T, D, kTargetFitThreads / 64);
 }
 int target_fit_launch(scaml::TargetFitParams& p, void* stream) {
   if (p.B < 0 || p.n < 1 || p.T < 1 || p.D < 1) return SCAML_E_BADARG;
@@ -795,6 +797,66 @@ int scaml_target_fit_f64(const double* means_t, const double* covs_packed, const
   p.B = B; p.n = n; p.T = T; p.D = D; p.kind = kind; p.mode = 1; p.max_iter = max_iter; p.history = history; p.max_ls = 20;
   p.gtol = gtol; p.ftol = ftol;
   return target_fit_launch(p, stream);
+}
+
+// ---- (8b) the same objective and refit over S problems x B start points in one launch ---------------------------------------
+namespace {
+// `p.base` filled by the caller except use_mfma; S, the per-problem arrays and the limits are checked here
+int target_fit_batched_launch(scaml::TargetFitBatchParams& bp, void* stream) {
+  scaml::TargetFitParams& p = bp.base;
+  if (bp.S < 0 || p.B < 0 || p.n < 1 || p.T < 1 || p.D < 1) return SCAML_E_BADARG;
+  if (!p.means_t || !p.covs_p || !p.X || !p.y || !p.z || !p.value || !p.info) return SCAML_E_BADARG;
+  if (!bp.n_points || !bp.m_all || !bp.s_all) return SCAML_E_BADARG;
+  if (!valid_kind(p.kind)) return SCAML_E_BADARG;
+  if (p.D > scaml::TARGET_FIT_DMAX) return SCAML_E_TOOLARGE;
+  if (p.n > scaml_target_fit_max_n(p.T, p.D)) return SCAML_E_TOOLARGE;
+  if ((long long)bp.S * p.B > 0x7fffffffLL) return SCAML_E_TOOLARGE;
+  p.use_mfma = g_dev.target_fit_path.load(kRelaxed) == 0 ? 1 : 0;
+  const size_t lds = scaml::target_fit_batched_lds_doubles(p.n, p.T, p.D, p.use_mfma != 0, kTargetFitThreads / 64) * sizeof(double);
+  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (bp.S == 0 || p.B == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  return launch(m->tgt_fit_batched, dim3((unsigned)(bp.S * p.B)), kTargetFitThreads, lds, stream, "target_fit_batched", bp);
+}
+}  // namespace
+
+long long scaml_target_fit_batched_workspace_doubles(int S, int B, int T, int D, int history) {
+  if (S < 0 || B < 0 || T < 1 || D < 1 || history < 1) return 0;
+  return (long long)S * B * (6 + 2 * (long long)history) * (D + 2 + T);
+}
+
+int scaml_target_mll_batched_f64(const double* means_t, const double* covs_packed, const double* X, const double* y, const int32_t* n_points,
+                                 const double* m_all, const double* s_all, const double* spec_host, const double* z, int S, int B, int n_max,
+                                 int T, int D, int kind, double* value, double* grad, int32_t* info, double* jitter_used, void* stream) {
+  if (!spec_host || !grad) return SCAML_E_BADARG;
+  scaml::TargetFitBatchParams bp{};
+  scaml::TargetFitParams& p = bp.base;
+  p.means_t = means_t; p.covs_p = covs_packed; p.X = X; p.y = y;
+  bp.n_points = n_points; bp.m_all = m_all; bp.s_all = s_all; bp.S = S;
+  if (!scaml::target_spec_from_host(spec_host, p.spec)) return SCAML_E_BADARG;
+  p.z = const_cast<double*>(z); p.value = value; p.grad = grad; p.info = info; p.jitter = jitter_used;
+  p.B = B; p.n = n_max; p.T = T; p.D = D; p.kind = kind; p.mode = 0; p.history = 1; p.max_ls = 0;
+  return target_fit_batched_launch(bp, stream);
+}
+
+int scaml_target_fit_batched_f64(const double* means_t, const double* covs_packed, const double* X, const double* y, const int32_t* n_points,
+                                 const double* m_all, const double* s_all, const double* spec_host, double* z, int S, int B, int n_max, int T,
+                                 int D, int kind, int max_iter, int history, double gtol, double ftol, double* value, int32_t* info,
+                                 double* jitter_used, int32_t* stats, double* workspace, long long workspace_doubles, void* stream) {
+  if (!spec_host || !workspace) return SCAML_E_BADARG;
+  if (S < 0 || B < 0) return SCAML_E_BADARG;
+  if (max_iter < 0 || history < 1 || history > scaml::TARGET_FIT_HMAX) return SCAML_E_BADARG;
+  if (workspace_doubles < scaml_target_fit_batched_workspace_doubles(S, B, T, D, history)) return SCAML_E_BADARG;
+  scaml::TargetFitBatchParams bp{};
+  scaml::TargetFitParams& p = bp.base;
+  p.means_t = means_t; p.covs_p = covs_packed; p.X = X; p.y = y;
+  bp.n_points = n_points; bp.m_all = m_all; bp.s_all = s_all; bp.S = S;
+  if (!scaml::target_spec_from_host(spec_host, p.spec)) return SCAML_E_BADARG;
+  p.z = z; p.value = value; p.grad = nullptr; p.info = info; p.jitter = jitter_used; p.workspace = workspace; p.stats = stats;
+  p.B = B; p.n = n_max; p.T = T; p.D = D; p.kind = kind; p.mode = 1; p.max_iter = max_iter; p.history = history; p.max_ls = 20;
+  p.gtol = gtol; p.ftol = ftol;
+  return target_fit_batched_launch(bp, stream);
 }
 
 // ---- (9) source stack: the whole hyper-parameter fit as rounds of { fit, MLL gradient, optimiser step } (csrc/gp_stack_fit.hip) ----

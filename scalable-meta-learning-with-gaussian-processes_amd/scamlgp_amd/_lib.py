@@ -100,6 +100,10 @@ SIGNATURES = {
     "scaml_target_fit_workspace_doubles": (_ll, [_i, _i, _i, _i]),
     "scaml_target_mll_f64": (_i, [_dp] * 4 + [_f, _f, _host_spec, _dp] + [_i] * 5 + [_dp] * 4 + [c_void_p]),
     "scaml_target_fit_f64": (_i, [_dp] * 4 + [_f, _f, _host_spec, _dp] + [_i] * 7 + [_f, _f] + [_dp] * 5 + [_ll, c_void_p]),
+    "scaml_target_fit_batched_workspace_doubles": (_ll, [_i, _i, _i, _i, _i]),
+    # problem block: means_t, covs_packed, X, y, n_points, m_all, s_all (device), spec (host), z; S, B, n_max, T, D, kind
+    "scaml_target_mll_batched_f64": (_i, [_dp] * 7 + [_host_spec, _dp] + [_i] * 6 + [_dp] * 4 + [c_void_p]),
+    "scaml_target_fit_batched_f64": (_i, [_dp] * 7 + [_host_spec, _dp] + [_i] * 8 + [_f, _f] + [_dp] * 5 + [_ll, c_void_p]),
     "scaml_stack_fit_max_d": (_i, []),
     "scaml_stack_fit_workspace_bytes": (_ll, [_i, _i, _i, _i]),
     "scaml_stack_fit_f64": (_i, [_dp, _dp, _dp, _host_spec, _dp] + [_i] * 5 + [_u, _i, _i, _f, _f, _dp, _dp, _dp, _ll, c_void_p]),

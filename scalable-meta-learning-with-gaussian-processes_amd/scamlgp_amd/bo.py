@@ -20,6 +20,7 @@ from __future__ import annotations
 
 from typing import Callable, Dict, Hashable, Optional, Sequence, Tuple, Union
 
+import copy
 import math
 
 import numpy as np
@@ -28,7 +29,7 @@ import torch
 
 from . import hyper
 from .model import ScaMLGP, SourceGP
-from .utils import ExpectedImprovement, UpperConfidenceBound, optimize_marginal_likelihood
+from .utils import ExpectedImprovement, UpperConfidenceBound, fit_targets_batched, optimize_marginal_likelihood
 
 
 class OptimizerNotReady(RuntimeError):
@@ -160,6 +161,13 @@ class ScaMLGPBOLoop:
         """Record evaluations and refit once: x (D,) with y a float, or x (q, D) with y (q,).  A y of None or NaN keeps the point in
         ``X`` / ``Y`` (as NaN) and out of the model's training set.  A reported point leaves ``pending`` (its first equal row, if any);
         reporting a point that was never suggested is allowed."""
+        self.record(x, y)
+        optimize_marginal_likelihood(self.model, self.num_restarts_log_likelihood)
+
+    def record(self, x: torch.Tensor, y: Union[float, None, Sequence[Optional[float]], torch.Tensor]) -> None:
+        """``report`` without the refit: the evaluations go into ``X`` / ``Y`` / ``pending`` and the model is rebuilt on them with the
+        previous model's modules (the warm start); its weights and hyper-parameters are still to be fitted (``ScaMLGPBOStudies`` fits
+        the models of all its studies together)."""
         xs = torch.as_tensor(x, dtype=torch.float64).reshape(-1, self.dim)
         if y is None or np.ndim(y) == 0:
             ys = [y]
@@ -188,7 +196,6 @@ class ScaMLGPBOLoop:
             likelihood=self.model.likelihood,
             covar_module=self.model.covar_module,
         )
-        optimize_marginal_likelihood(self.model, self.num_restarts_log_likelihood)
 
     def acquisition_function(self) -> Callable[[torch.Tensor], torch.Tensor]:
         model = self.model
@@ -219,3 +226,79 @@ class ScaMLGPBOLoop:
             x = self.suggest()
             self.report(x, objective(x))
         return self.X, self.Y
+
+
+class ScaMLGPBOStudies:
+    """S independent Bayesian-optimisation studies against ONE fitted source stack, stepped in lock-step on one GPU -- the repeated
+    runs behind a regret curve (scamlgp/benchmarking/local_runner.py:174-181 fans them out over a process pool, one study per core).
+
+    ``studies[s]`` is a ``ScaMLGPBOLoop`` (its ``model``, ``X``, ``Y``, ``pending``, ``model.last_fit_info``: a study's record goes
+    through ``results`` exactly as a single loop's does), built with ``seed=seeds[s]`` and the loop kwargs; given ``gp_likelihood`` /
+    ``gp_kernel`` modules are copied per study (they hold the fitted state).  What is batched is the refit: ``report`` rebuilds every
+    study's model and then runs the L-BFGS optimisations of ALL studies -- warm start plus restarts each -- in one launch
+    (``utils.fit_targets_batched`` -> ``scaml_target_fit_batched_f64``), where one study's refit keeps 1 + restarts of the chip's 256 CUs
+    busy for its whole latency.  Per study the starts, the optimiser and the best-of-restarts choice are the single loop's; study s
+    draws its restart samples from ``fit_gens[s]`` (a ``torch.Generator`` seeded with ``seeds[s]``), its acquisition samples from
+    ``studies[s].gen``.  A study whose shape the kernel does not take (n beyond its LDS, D > 16) is refitted as ``ScaMLGPBOLoop`` does
+    it, on its own.  ``suggest`` runs the studies one after the other with the existing launches.  Studies may get out of step: a
+    study with a pending or a failed (None / NaN) evaluation trains on fewer points than its neighbours."""
+
+    def __init__(self, source_gps: Dict[Hashable, SourceGP], dim: int, num_studies: int, seeds: Optional[Sequence[int]] = None, **loop_kwargs):
+        S = int(num_studies)
+        if S < 1:
+            raise ValueError("num_studies must be a positive integer")
+        seeds = list(range(S)) if seeds is None else [int(v) for v in seeds]
+        if len(seeds) != S:
+            raise ValueError(f"got {len(seeds)} seeds for {S} studies")
+        if "seed" in loop_kwargs:
+            raise TypeError("pass seeds=[...] (one per study), not seed=")
+        self.dim, self.num_studies, self.seeds = dim, S, seeds
+        self.studies = []
+        for s in range(S):
+            kw = dict(loop_kwargs)
+            for name in ("gp_likelihood", "gp_kernel"):
+                if kw.get(name) is not None:
+                    kw[name] = copy.deepcopy(kw[name])
+            self.studies.append(ScaMLGPBOLoop(source_gps, dim, seed=seeds[s], **kw))
+        if self.studies[0].model._shard is not None:
+            raise NotImplementedError("lock-step studies are not implemented for a task-sharded source stack (shard=True)")
+        self.fit_gens = [torch.Generator().manual_seed(v) for v in seeds]
+
+    def __len__(self) -> int:
+        return self.num_studies
+
+    def __getitem__(self, s: int) -> ScaMLGPBOLoop:
+        return self.studies[s]
+
+    def suggest(self) -> torch.Tensor:
+        """(S, D): every study's next point (``ScaMLGPBOLoop.suggest``; OptimizerNotReady if a study has its full count pending)."""
+        return torch.stack([st.suggest() for st in self.studies])
+
+    def report(self, X: torch.Tensor, y) -> None:
+        """One evaluation per study: X (S, D), y (S,) -- a tensor, or a sequence whose entries may be None / NaN (no objective value:
+        the point stays out of that study's fit) -- then ONE refit of all studies.  ``X[s]`` need not be the point ``suggest`` returned
+        for study s; the pending bookkeeping is ``ScaMLGPBOLoop.report``'s.  To leave a study's evaluation pending, report the others
+        through ``report_some``."""
+        xs = torch.as_tensor(X, dtype=torch.float64).reshape(-1, self.dim)
+        ys = y.detach().cpu().reshape(-1).tolist() if isinstance(y, torch.Tensor) else list(y)
+        if xs.shape[0] != self.num_studies or len(ys) != self.num_studies:
+            raise ValueError(f"report() takes one point and one objective value per study ({self.num_studies}), got {xs.shape[0]} and {len(ys)}")
+        self.report_some({s: (xs[s], ys[s]) for s in range(self.num_studies)})
+
+    def report_some(self, evaluations: Dict[int, Tuple[torch.Tensor, object]]) -> None:
+        """Evaluations of SOME studies, {study index: (x (D,) or (q, D), y float / None or (q,))}, then one refit of those studies;
+        the others keep their models (and their pending points)."""
+        idx = sorted(evaluations)
+        for s in idx:
+            self.studies[s].record(*evaluations[s])
+        nrll = self.studies[0].num_restarts_log_likelihood
+        fit_targets_batched([self.studies[s].model for s in idx], nrll, rng=[self.fit_gens[s] for s in idx])
+
+    def run(self, objectives: Union[Callable[[torch.Tensor], Sequence[float]], Sequence[Callable[[torch.Tensor], float]]], n_steps: int):
+        """``n_steps`` rounds of suggest -> evaluate -> report.  ``objectives``: one callable mapping the (S, D) points to S values, or
+        S callables, one per study.  Returns ([X_s], [Y_s])."""
+        for _ in range(n_steps):
+            X = self.suggest()
+            ys = objectives(X) if callable(objectives) else [f(x) for f, x in zip(objectives, X)]
+            self.report(X, ys)
+        return [st.X for st in self.studies], [st.Y for st in self.studies]

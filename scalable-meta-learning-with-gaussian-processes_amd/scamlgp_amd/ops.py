@@ -871,6 +871,94 @@ def target_fit(prob: TargetFitProblem, z0: torch.Tensor, max_iter: int = 200, hi
     return dict(z=z, value=value, info=info, jitter=jit, stats=stats)
 
 
+# ---- (8b) the same over a batch of training sets: S problems x B start points in one launch -----------------------------------
+class TargetFitBatch:
+    """S ``TargetFitProblem``s (anything with their attributes) in the layouts of ``scaml_target_mll_batched_f64`` /
+    ``scaml_target_fit_batched_f64``: means (S, T, n_max), packed covariances (S, T, n_max (n_max + 1) / 2), inputs (S, n_max, D),
+    targets (S, n_max), the counts n_s (S,) int32 and the standardisers m_all, s_all (S,) as device arrays.  The problems share T, D,
+    the kernel family, the device and the constraint / prior block; they may differ in n (ragged: the packed index does not depend on
+    n, so problem s fills the leading part of its slices and the rest -- zeros here -- is never read)."""
+
+    def __init__(self, problems):
+        problems = list(problems)
+        if not problems:
+            raise ValueError("TargetFitBatch needs at least one problem")
+        p0 = problems[0]
+        self.S, self.T, self.D, self.kind, self.P, self.device = len(problems), p0.T, p0.D, p0.kind, p0.P, p0.device
+        self.spec_host = p0.spec_host
+        for p in problems[1:]:
+            if (p.T, p.D, p.kind, p.device) != (self.T, self.D, self.kind, self.device) or list(p.spec_host) != list(p0.spec_host):
+                raise ValueError("the problems of a TargetFitBatch must share T, D, the kernel family, the device and the constraint / prior block")
+        self.sizes = [int(p.n) for p in problems]
+        self.n_max = n_max = max(self.sizes)
+        dev, S, T, D = self.device, self.S, self.T, self.D
+        self.means_t = torch.zeros(S, T, n_max, dtype=torch.float64, device=dev)
+        self.covs_p = torch.zeros(S, T, n_max * (n_max + 1) // 2, dtype=torch.float64, device=dev)
+        self.X = torch.zeros(S, n_max, D, dtype=torch.float64, device=dev)
+        self.y = torch.zeros(S, n_max, dtype=torch.float64, device=dev)
+        for s, p in enumerate(problems):
+            n = self.sizes[s]
+            self.means_t[s, :, :n].copy_(p.means_t)
+            self.covs_p[s, :, :n * (n + 1) // 2].copy_(p.covs_p)
+            self.X[s, :n].copy_(p.X)
+            self.y[s, :n].copy_(p.y)
+        self.n_points = torch.tensor(self.sizes, dtype=torch.int32).to(dev)
+        self.m_all = torch.tensor([float(p.m_all) for p in problems], dtype=torch.float64).to(dev)
+        self.s_all = torch.tensor([float(p.s_all) for p in problems], dtype=torch.float64).to(dev)
+
+    @staticmethod
+    def supported(n_max: int, T: int, D: int) -> bool:
+        return TargetFitProblem.supported(n_max, T, D)
+
+    def _problem_args(self):
+        return (_ptr(self.means_t), _ptr(self.covs_p), _ptr(self.X), _ptr(self.y), _ptr(self.n_points), _ptr(self.m_all), _ptr(self.s_all),
+                self.spec_host)
+
+
+def target_mll_batched(batch: TargetFitBatch, z: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """``target_mll`` for every (problem, start): z (S, B, P) -> dict(value (S, B), grad (S, B, P), info (S, B), jitter (S, B)), ONE
+    launch of scaml_target_mll_batched_f64 (S * B workgroups).  Row (s, b) is what ``target_mll`` gives for problem s at z[s, b]."""
+    if z.dim() != 3:
+        raise ValueError(f"z must have shape (S, B, P) (got {tuple(z.shape)})")
+    B = z.shape[1]
+    z = _check(z, "z", (batch.S, B, batch.P))
+    dev, S = batch.device, batch.S
+    with torch.cuda.device(dev):
+        value = _empty(dev, S, B)
+        grad = _empty(dev, S, B, batch.P)
+        info = _empty(dev, S, B, dtype=torch.int32)
+        jit = _empty(dev, S, B)
+        rc = _lib.lib.scaml_target_mll_batched_f64(*batch._problem_args(), _ptr(z), S, B, batch.n_max, batch.T, batch.D, batch.kind,
+                                                   _ptr(value), _ptr(grad), _ptr(info), _ptr(jit), _stream_handle())
+    _lib.check_rc(rc, "scaml_target_mll_batched_f64")
+    return dict(value=value, grad=grad, info=info, jitter=jit)
+
+
+def target_fit_batched(batch: TargetFitBatch, z0: torch.Tensor, max_iter: int = 200, history: int = 10, gtol: float = 1e-5,
+                       ftol: float = 2.2e-9) -> Dict[str, torch.Tensor]:
+    """``target_fit`` for every (problem, start): all S * B L-BFGS optimisations in ONE launch of scaml_target_fit_batched_f64.
+    z0 (S, B, P) -> dict(z (S, B, P), value (S, B), info, jitter, stats (S, B, 4)); row (s, b) is what ``target_fit`` gives for
+    problem s from z0[s, b]."""
+    if z0.dim() != 3:
+        raise ValueError(f"z0 must have shape (S, B, P) (got {tuple(z0.shape)})")
+    B = z0.shape[1]
+    z = _check(z0, "z0", (batch.S, B, batch.P)).clone()
+    dev, S = batch.device, batch.S
+    with torch.cuda.device(dev):
+        value = _empty(dev, S, B)
+        info = _empty(dev, S, B, dtype=torch.int32)
+        jit = _empty(dev, S, B)
+        stats = torch.zeros((S, B, 4), dtype=torch.int32, device=dev)
+        nws = int(_lib.lib.scaml_target_fit_batched_workspace_doubles(S, B, batch.T, batch.D, history))
+        ws = _empty(dev, max(nws, 1))
+        rc = _lib.lib.scaml_target_fit_batched_f64(*batch._problem_args(), _ptr(z), S, B, batch.n_max, batch.T, batch.D, batch.kind,
+                                                   int(max_iter), int(history), float(gtol), float(ftol), _ptr(value), _ptr(info), _ptr(jit),
+                                                   _ptr(stats), _ptr(ws), nws, _stream_handle())
+        ws.record_stream(torch.cuda.current_stream(dev))
+    _lib.check_rc(rc, "scaml_target_fit_batched_f64")
+    return dict(z=z, value=value, info=info, jitter=jit, stats=stats)
+
+
 # ---- (9) source stack: the whole hyper-parameter fit enqueued on the device ---------------------------------------------------
 # rounds enqueued between two reads of the status.  Measured (tools/dev_stackfit_time.py, profiles/stack_fit_timings.txt): the cost per
 # evaluation is flat from 4 on (the rounds are GPU-bound), and every round past the last problem's stop is a wasted evaluation of the

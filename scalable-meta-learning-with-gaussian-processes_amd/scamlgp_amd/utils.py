@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import logging
 import math
-from typing import Dict, Union
+from typing import Dict, Optional, Sequence, Union
 
 import numpy as np
 import scipy.optimize
@@ -199,6 +199,41 @@ def _fit_target_scipy(model: ScaMLGP, starts: torch.Tensor, maxiter: int, use_gr
     return torch.stack(zs), torch.tensor(fs, dtype=torch.float64)
 
 
+def _target_starts(model: ScaMLGP, num_restarts: int) -> torch.Tensor:
+    """(1 + num_restarts, P): the warm start, then prior samples of the hyper-parameters and weights (global torch RNG, one restart
+    after the other: scamlgp/utils.py:184-199)."""
+    D2, T = model.raw_theta.numel(), model.T
+    starts = [torch.cat([model.raw_theta, model.raw_weights])]
+    for _ in range(num_restarts):
+        th = model.spec.sample_prior((), D2 - 2, device=model.device)
+        w = model.weights_prior.sample((T,), device=model.device).clamp_min(model.weights_lower_bound)
+        starts.append(torch.cat([model.spec.to_raw(th), w]))
+    return torch.stack(starts)
+
+
+def _kernel_fit_objective(model: ScaMLGP, res: dict) -> torch.Tensor:
+    """f (B,) = -mll at the end points of a device refit (``ops.target_fit``, or one problem's rows of ``ops.target_fit_batched``), inf
+    for a run that failed; records the run in ``model.last_fit_info``."""
+    f = -res["value"]
+    f = torch.where(torch.isfinite(f) & (res["stats"][:, 2] != 4), f, torch.full_like(f, float("inf")))
+    model.last_fit_info = dict(stats=res["stats"], objective=res["value"])
+    return f
+
+
+def _best_start(z: torch.Tensor, f, best: torch.Tensor) -> None:
+    """The best end point into ``best`` = [state || ok]; f (B,) on the device or already on the host."""
+    n_failed = int(torch.isinf(f).sum())     # (the one host synchronisation of the refit, unless f is a host tensor)
+    if n_failed and n_failed < f.numel():
+        logger.warning("Error occurred while optimizing the model hyperparameters; %d restart(s) will be skipped.", n_failed)
+    if n_failed < f.numel():
+        best[:-1] = z[int(f.argmin())]
+        best[-1] = 1.0
+
+
+_FIT_FAILED = ("Hyperparameter optimization failed for all attempts. Usually this indicates a problem with "
+               "model's input data or hyperparameter priors definitions.")
+
+
 def _fit_target(model: ScaMLGP, num_restarts: int, maxiter: int = 200, use_graph: bool = True, use_kernel: bool = True) -> None:
     """Target GP: weights + kernel hyper-parameters (scamlgp/optimizer.py:176-185 -> scamlgp/utils.py:139-212).  The warm start
     and the ``num_restarts`` prior-sampled starts are ONE batch; ``scaml_target_fit_f64`` runs all their L-BFGS optimisations
@@ -211,35 +246,82 @@ def _fit_target(model: ScaMLGP, num_restarts: int, maxiter: int = 200, use_graph
     D2, T = model.raw_theta.numel(), model.T
     best = torch.zeros(D2 + T + 1, dtype=torch.float64, device=model.device)   # [state || ok]
     if shard is None or shard.rank == 0:
-        starts = [torch.cat([model.raw_theta, model.raw_weights])]
-        for _ in range(num_restarts):
-            th = model.spec.sample_prior((), D2 - 2, device=model.device)
-            w = model.weights_prior.sample((T,), device=model.device).clamp_min(model.weights_lower_bound)
-            starts.append(torch.cat([model.spec.to_raw(th), w]))
-        z0 = torch.stack(starts)
+        z0 = _target_starts(model, num_restarts)
         prob = model.target_problem() if (use_kernel and model.device.type == "cuda") else None
         if prob is not None:
             res = ops.target_fit(prob, z0, max_iter=maxiter)
-            z, f = res["z"], -res["value"]
-            f = torch.where(torch.isfinite(f) & (res["stats"][:, 2] != 4), f, torch.full_like(f, float("inf")))
-            model.last_fit_info = dict(stats=res["stats"], objective=res["value"])
+            z, f = res["z"], _kernel_fit_objective(model, res)
         else:
             z, f = _fit_target_scipy(model, z0, maxiter, use_graph)
             z, f = z.to(model.device), f.to(model.device)
-        n_failed = int(torch.isinf(f).sum())     # (the one host synchronisation of the refit)
-        if n_failed and n_failed < f.numel():
-            logger.warning("Error occurred while optimizing the model hyperparameters; %d restart(s) will be skipped.", n_failed)
-        if n_failed < f.numel():
-            best[:-1] = z[int(f.argmin())]
-            best[-1] = 1.0
+        _best_start(z, f, best)
     if shard is not None and shard.world > 1:
         import torch.distributed as dist
 
         dist.broadcast(best, src=dist.get_global_rank(shard.group, 0) if shard.group is not None else 0, group=shard.group)
     if float(best[-1]) != 1.0:
-        raise ModelFittingError("Hyperparameter optimization failed for all attempts. Usually this indicates a problem with "
-                                "model's input data or hyperparameter priors definitions.")
+        raise ModelFittingError(_FIT_FAILED)
     model.load_state_dict({"raw_theta": best[:D2].clone(), "raw_weights": best[D2:-1].clone()})
+
+
+def fit_targets_batched(models: Sequence[ScaMLGP], num_restarts: int, maxiter: int = 200, rng: Optional[Sequence[torch.Generator]] = None,
+                        **fit_options) -> None:
+    """``optimize_marginal_likelihood(model, num_restarts)`` for several ScaMLGP models on ONE source stack, with every model the
+    library's target-fit kernel takes refitted in ONE launch (``scaml_target_fit_batched_f64``: models x (1 + num_restarts) workgroups
+    instead of 1 + num_restarts per launch, one launch after the other).  Per model the starts, the device optimisation and the
+    best-of-restarts choice are those of the single call, so the fitted state is the same.  ``rng[i]``: the generator model i's
+    restart samples are drawn from (its state stands in for the global RNG's while they are drawn, and moves on); None: the global RNG,
+    model after model.  A model the kernel does not take (n beyond its LDS, D > 16) is refitted by the single call, on its own."""
+    models = list(models)
+    for m in models:
+        if not isinstance(m, ScaMLGP):
+            raise TypeError(f"cannot fit a {type(m).__name__}")
+        if m.num_fantasies is not None:
+            raise NotImplementedError("a fantasy model is not refitted: it keeps its parent's hyper-parameters")
+        if m._shard is not None:
+            raise NotImplementedError("the batched refit is not implemented for a task-sharded source stack (shard=True)")
+    batch, starts = [], []
+    for i, m in enumerate(models):
+        if m.n == 0:
+            continue
+        with _rng_of(rng[i] if rng is not None else None):
+            prob = m.target_problem() if m.device.type == "cuda" else None
+            if prob is None:
+                optimize_marginal_likelihood(m, num_restarts, maxiter=maxiter, **fit_options)
+                continue
+            starts.append(_target_starts(m, num_restarts))
+        batch.append((m, prob))
+    if not batch:
+        return
+    res = ops.target_fit_batched(ops.TargetFitBatch([p for _, p in batch]), torch.stack(starts), max_iter=maxiter)
+    fs = [_kernel_fit_objective(m, {k: v[s] for k, v in res.items()}) for s, (m, _) in enumerate(batch)]
+    f_host = torch.stack(fs).cpu()   # (the one host synchronisation of all the refits)
+    for s, (m, _) in enumerate(batch):
+        D2 = m.raw_theta.numel()
+        best = torch.zeros(D2 + m.T + 1, dtype=torch.float64, device=m.device)
+        _best_start(res["z"][s], f_host[s], best)
+        if float(f_host[s].min()) == float("inf"):
+            raise ModelFittingError(_FIT_FAILED)
+        m.load_state_dict({"raw_theta": best[:D2].clone(), "raw_weights": best[D2:-1].clone()})
+
+
+class _rng_of:
+    """While active, the global CPU RNG continues ``gen``'s stream (torch.distributions draws from the global RNG only); on exit
+    ``gen`` holds the advanced state and the global RNG is back where it was.  ``gen`` None: nothing happens."""
+
+    def __init__(self, gen: Optional[torch.Generator]):
+        self.gen = gen
+
+    def __enter__(self):
+        if self.gen is not None:
+            self.saved = torch.get_rng_state()
+            torch.set_rng_state(self.gen.get_state())
+
+    def __exit__(self, *exc):
+        if self.gen is not None:
+            self.gen.set_state(torch.get_rng_state())
+            torch.set_rng_state(self.saved)
+        return False
 
 
 def optimize_marginal_likelihood(model: Union[SourceGPStack, ScaMLGP, Dict, SourceGP], num_restarts: int = 0, **fit_options):

@@ -1,0 +1,113 @@
+"""One BO step of S studies against one source stack at configs[4] shapes (T = 32 Hartmann-6 sources of N = 512 points, D = 6, the
+target set growing to n = 80, 2 restarts of the refit): ``ScaMLGPBOStudies`` (all refits in one launch of
+scaml_target_fit_batched_f64) against S ``ScaMLGPBOLoop``s stepped one after the other -- what a caller had before --, in ONE process,
+the two sides alternating step by step, for S in {1, 8, 32, 64}.
+
+Per side and step the time is split into suggest (the acquisition optimisation of every study), model construction (ScaMLGP rebuilt on
+the new point: the source posteriors at the training inputs) and refit.  Host clock around work that ends in a device synchronise;
+medians over the timed steps (the first step of a size is a warm-up and is not counted).
+
+  python tools/dev_studies_time.py [--sizes 1,8,32,64] [--steps K] [--out profiles/studies_timings.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "scalable-meta-learning-with-gaussian-processes_amd"))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from scamlgp_amd import model as M, synthetic, utils  # noqa: E402
+from scamlgp_amd.bo import ScaMLGPBOLoop, ScaMLGPBOStudies  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--sizes", default="1,8,32,64")
+ap.add_argument("--steps", type=int, default=3, help="timed steps per size (n ends at 80)")
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
+
+T, N, D, N_END, RESTARTS = 32, 512, 6, 80, 2
+KW = dict(acquisition="ucb", num_restarts_log_likelihood=RESTARTS)
+dev = torch.device("cuda:0")
+lines = []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def obj(x):
+    return float(synthetic.hartmann6(np.asarray(x, dtype=np.float64).reshape(1, -1))[0])
+
+
+d = synthetic.hartmann6_task_stack(T, N, seed=0)
+stack = M.SourceGPStack(list(range(T)), [torch.from_numpy(d["X"][t]) for t in range(T)],
+                        [torch.from_numpy(d["Y"][t]).unsqueeze(-1) for t in range(T)], kind=1, device=dev)
+rng = np.random.default_rng(0)
+stack.set_theta(torch.from_numpy(np.concatenate([0.6 + 0.8 * rng.uniform(size=(T, D)), 0.5 + rng.uniform(size=(T, 1)),
+                                                 1e-3 + 5e-3 * rng.uniform(size=(T, 1))], 1)))
+stack.refresh()
+gps = {tid: M.SourceGP(stack, i) for i, tid in enumerate(stack.task_ids)}
+
+say(f"# BO step of S studies, T = {T}, N = {N}, D = {D}, n -> {N_END}, {RESTARTS} restarts (B = {1 + RESTARTS} starts per study), UCB; ms per step, median of "
+    f"{args.steps} steps")
+say("# batched = ScaMLGPBOStudies (one refit launch for all studies); sequential = S ScaMLGPBOLoops one after the other")
+say(f"# {'S':>3} {'side':>10} {'suggest':>9} {'construct':>9} {'refit':>9} {'step':>9}   speed-up (step)   speed-up (refit)")
+for S in [int(v) for v in args.sizes.split(",")]:
+    steps = args.steps + 1
+    n0 = N_END - steps          # history before the first step: the last timed refit is at n = 80
+    seeds = list(range(100, 100 + S))
+    studies = ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, **KW)
+    loops = [ScaMLGPBOLoop(gps, D, seed=seeds[s], **KW) for s in range(S)]
+    for s in range(S):
+        g = torch.Generator().manual_seed(seeds[s])
+        X0 = torch.rand(n0, D, dtype=torch.float64, generator=g)
+        y0 = [obj(x) for x in X0]
+        studies[s].record(X0, y0)
+        loops[s].record(X0, y0)
+    utils.fit_targets_batched([st.model for st in studies.studies], RESTARTS, rng=studies.fit_gens)
+    for lp in loops:
+        utils.optimize_marginal_likelihood(lp.model, RESTARTS)
+    rows = {"batched": [], "sequential": []}
+    for step in range(steps):
+        # -- batched side --
+        t_s, X = timed(studies.suggest)
+        ys = [obj(x) for x in X]
+        t_c, _ = timed(lambda: [studies[s].record(X[s], ys[s]) for s in range(S)])
+        t_r, _ = timed(lambda: utils.fit_targets_batched([st.model for st in studies.studies], RESTARTS, rng=studies.fit_gens))
+        rows["batched"].append((t_s, t_c, t_r))
+        # -- sequential side: the same work, study after study --
+        t_s, Xl = timed(lambda: [lp.suggest() for lp in loops])
+        yl = [obj(x) for x in Xl]
+        t_c = t_r = 0.0
+        for s, lp in enumerate(loops):
+            dt, _ = timed(lambda: lp.record(Xl[s], yl[s]))
+            t_c += dt
+            dt, _ = timed(lambda: utils.optimize_marginal_likelihood(lp.model, RESTARTS))
+            t_r += dt
+        rows["sequential"].append((t_s, t_c, t_r))
+    med = {k: [1e3 * statistics.median(r[i] for r in v[1:]) for i in range(3)] for k, v in rows.items()}
+    tot = {k: sum(v) for k, v in med.items()}
+    n_now = studies[0].model.n
+    ev = torch.stack([st.model.last_fit_info["stats"][:, 1] for st in studies.studies]).cpu()
+    for k in ("batched", "sequential"):
+        tail = f"   {tot['sequential'] / tot['batched']:6.2f}x            {med['sequential'][2] / med['batched'][2]:6.2f}x" if k == "batched" else ""
+        say(f"  {S:>3} {k:>10} {med[k][0]:9.1f} {med[k][1]:9.1f} {med[k][2]:9.1f} {tot[k]:9.1f}{tail}")
+    say(f"#     n = {n_now}; evaluations per start in the last batched refit: min {int(ev.min())}, median {int(ev.median())}, max {int(ev.max())}")
+if args.out:
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
