@@ -300,6 +300,43 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
                                   const double* theta, int n, int M, int F, int D, int kind, double* value, double* grad, void* stream);
 
 /*
+ * (5e), (7g) The acquisition function of MANY Bayesian-optimisation studies against one source stack, evaluated in two launches
+ * whatever their number: every study's start points of the acquisition optimiser in one pass (scamlgp_amd.bo.ScaMLGPBOStudies with
+ * suggest_mode="lockstep"), where (5d) + (6') + (7) + (5d)'s target gradient run once per study.
+ * scaml_posterior_linv_grad_grouped_f64: (5d)'s source pass with the Mq query points divided among G groups (studies).
+ *   group (Mq) int32: the group of query q; a negative entry is a padding row -- its strips of mu / var are zeros, nothing of any
+ *       group is read for it and no row of cov is written.
+ *   n_points_a (G) int32, 1 <= Ma_g <= Ma_max: the leading points (the study's training inputs) per group.
+ *   Xa (G, Ma_max, D): their coordinates, padded; VA_tab (G): DEVICE array of device pointers, VA_tab[g] = the group's V as in (5c'),
+ *       (T, N, Ma_g) with row stride Ma_g (the models cache it: no padded copy).
+ *   mu, var (T, Mq, 16) as in (5d); cov (T, Ma_max, Mq * 16): rows a < Ma_{group[q]} of strip q are written, the rest is untouched.
+ *   Limits: D <= 15, Ma_max <= 96 and <= N, N <= scaml_posterior_max_n().  Mq == 0, G == 0 or T == 0: nothing is enqueued.
+ * scaml_target_acqf_batched_f64: per query q of group g = group[q], from (5e)'s mu / var / cov (cov with n_max rows per task) and the
+ * group's slices of  w (G, T) weights (zero where pruned) and active (G, T) uint8 (a masked task is skipped),  Xt (G, n_max, D),
+ * theta (G, D + 2),  L (G, n_max, n_max) / Linv_diag (G, ceil(n_max / 16), 16, 16): the factor of Knn as (2) returns it for the
+ * group's n_g points, in the leading block of its slice,  alpha (G, n_max) = Knn^-1 resid,  n_points (G) int32,  m_all, s_all (G),
+ * info (G) int32,  acqf_param (G) (acqf 0: beta, acqf 1: best_f, as (7f)):
+ *   the weighted sums of the 16 columns over the active tasks (t ascending), Knq[a] = cov_g[a][0] / s^2 + os k_t(Xt_a, x_q),
+ *   mean_q / var_q as (7)'s assemble, z = Knn^-1 Knq against the factor, mu* / var* as (7)'s finish, their input gradients as (5d)'s
+ *   target gradient, then value (Mq) = UCB or EI and grad (Mq, D) (may be NULL) with (7f)'s clamps.  mu_out, var_out (Mq) or NULL:
+ *   the posterior itself.  Sums run in a fixed order (tasks, then training points, ascending): the result is a pure function of the
+ *   inputs.  info[g] != 0 (or n_points[g] outside 1 .. n_max) turns that group's outputs into NaN; a padding query gives zeros.
+ *   What lies past n_g in a group's slices is never read.
+ *   Limits: n_max <= 96, D <= 15; SCAML_E_TOOLARGE beyond them (bad arguments answer first).  Mq == 0 or G == 0: nothing is enqueued.
+ * Neither call synchronises; every status stays on the device (both can be stream-captured).
+ */
+int scaml_posterior_linv_grad_grouped_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                                          const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
+                                          const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T,
+                                          int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov,
+                                          void* stream);
+int scaml_target_acqf_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
+                                  const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
+                                  const double* Linv_diag, const double* alpha, const int32_t* n_points, const double* m_all,
+                                  const double* s_all, const int32_t* info, const double* acqf_param, int Mq, int G, int n_max, int T,
+                                  int D, int kind, int acqf, double* value, double* grad, double* mu_out, double* var_out, void* stream);
+
+/*
  * (8) The target GP's training objective with its analytic gradient, and the whole refit, in ONE launch.
  * Replaces what the reference runs on every report(): scamlgp/optimizer.py:176-185 rebuilds ScaMLGP and calls
  * optimize_marginal_likelihood (scamlgp/utils.py:139-212), which drives scipy L-BFGS-B through torch autograd over

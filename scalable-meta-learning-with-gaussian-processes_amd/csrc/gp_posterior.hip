@@ -145,8 +145,28 @@ __global__ __launch_bounds__(256) void gp_posterior_kernel(PosteriorParams p) {
 //   cov[a][.., 0] = s^2 (os k(x_a, x) - VA_a . V_0),  cov[a][.., 1 + d] = s^2 (os dk(x_a, x)/dx_d - VA_a . V_{1+d})
 // for the Ma leading points x_a (p.Xa: the target's training inputs) -- everything botorch's optimize_acqf differentiates through
 // model.posterior for (HOT LOOP #4; scamlgp/utils.py:215-224).  Outputs are (T, Mq, 16) / (T, Ma, Mq * 16): M = 16 Mq.
-template <int KIND, bool COV, bool GRAD>
-__global__ __launch_bounds__(512) void gp_posterior_linv_kernel(PosteriorParams p) {
+// The argument block of gp_posterior_linv_kernel: PosteriorParams, or PosteriorGroupedParams (the same block first, then the groups)
+template <bool GROUPED>
+struct PosteriorArgs {
+  using type = PosteriorParams;
+  static __device__ __forceinline__ const PosteriorParams& base(const type& a) { return a; }
+  static __device__ __forceinline__ PosteriorGroupArgs ga(const type&) { return PosteriorGroupArgs{}; }
+};
+template <>
+struct PosteriorArgs<true> {
+  using type = PosteriorGroupedParams;
+  static __device__ __forceinline__ const PosteriorParams& base(const type& a) { return a.base; }
+  static __device__ __forceinline__ const PosteriorGroupArgs& ga(const type& a) { return a.ga; }
+};
+
+// GROUPED (the lock-step acquisition of many BO studies, scaml_posterior_linv_grad_grouped_f64): the query points are divided among G
+// groups, each with its own leading points (count, V, coordinates) -- a strip in GRAD mode is ONE query point, so the group is uniform
+// per workgroup and its count, V pointer and coordinate base are scalar loads.  GROUPED = false is the pass as it always was: the
+// argument block is PosteriorParams itself and the group's values are read where the ungrouped ones were.
+template <int KIND, bool COV, bool GRAD, bool GROUPED = false>
+__global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename PosteriorArgs<GROUPED>::type pp) {
+  static_assert(!GROUPED || (COV && GRAD), "the grouped pass is the GRAD pass with its covariance block");
+  const PosteriorParams& p = PosteriorArgs<GROUPED>::base(pp);
   // eight waves share one K_*^T strip (the row blocks are dealt 8 ways: twice the waves per byte of LDS to hide the L^-1 segment loads)
   constexpr int NW = 8;
   extern __shared__ double lds[];
@@ -157,6 +177,17 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(PosteriorParams 
   const int task = (slot / strips) * 8 + xcd;
   const int strip = slot % strips;
   if (task >= p.T) return;
+  int grp = 0;
+  if (GROUPED) {
+    grp = PosteriorArgs<GROUPED>::ga(pp).group[strip];
+    if (grp < 0 || grp >= PosteriorArgs<GROUPED>::ga(pp).G) {   // a padding row: zeros, nothing of any group is read
+      if (threadIdx.x < 16) {
+        if (p.mu) p.mu[(size_t)task * M + 16 * strip + threadIdx.x] = 0.0;
+        if (p.var) p.var[(size_t)task * M + 16 * strip + threadIdx.x] = 0.0;
+      }
+      return;
+    }
+  }
   // (the wave index stays a vector value here: as a scalar -- SCAML_WAVE_INDEX, which pays in the L^-1 and gradient kernels -- this
   //  kernel measured 3 % slower at C3, 178.9 against 173.6 us)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -279,14 +310,18 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(PosteriorParams 
   // ---- phase 2: V = L^-1 K_*^T by row blocks, the variance on the fly
   // (COV: the variant with the fused covariance block -- ~90 more registers, so the plain pass keeps its own instantiation)
   constexpr int MAXAS = COV ? 6 : 1;   // at most 96 leading query points (the target's training points)
-  const int nas = (COV && p.VA) ? (p.Ma + 15) / 16 : 0;
+  // the leading points of the covariance block: their count and V (GROUPED: this strip's group's; p.Ma is then Ma_max, the row count
+  // of cov, which the host checked against the LDS strip)
+  const int Ma = GROUPED ? PosteriorArgs<GROUPED>::ga(pp).count(grp, p.Ma) : p.Ma;
+  const double* VAp = GROUPED ? PosteriorArgs<GROUPED>::ga(pp).VA_tab[grp] : p.VA;
+  const int nas = (COV && VAp) ? (Ma + 15) / 16 : 0;
   d4_t cacc[MAXAS];
 #pragma unroll
   for (int as = 0; as < MAXAS; ++as) cacc[as] = d4_t{0.0, 0.0, 0.0, 0.0};
   if (!p.mean_only) {
     double var_part = 0.0;
     const bool n_even = (N & 1) == 0;
-    const double* VAg = p.VA ? p.VA + (size_t)task * N * p.Ma : nullptr;
+    const double* VAg = VAp ? VAp + (size_t)task * N * Ma : nullptr;
     for (int it = 0;; ++it) {
       const int kb = (it & 1) ? (it + 1) * NW - 1 - wave : it * NW + wave;
       if (kb >= NB) {
@@ -322,7 +357,7 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(PosteriorParams 
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
               const int row = 16 * kb + lq + 4 * m;
-              va[m] = (row < n && ac < p.Ma) ? VAg[(size_t)row * p.Ma + ac] : 0.0;
+              va[m] = (row < n && ac < Ma) ? VAg[(size_t)row * Ma + ac] : 0.0;
             }
 #pragma unroll
             for (int m = 0; m < 4; ++m) cacc[as] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[m], vb[m], cacc[as], 0, 0, 0);
@@ -365,11 +400,12 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(PosteriorParams 
       __syncthreads();
     }
     // the Ma leading points: the head of the query list (the caller put the target's training points first), or p.Xa
-    const double* Xqg = p.Xa ? p.Xa : p.Xq + (p.xq_per_task ? (size_t)task * M * D : 0);
+    const double* Xap = GROUPED ? PosteriorArgs<GROUPED>::ga(pp).Xa + (size_t)grp * p.Ma * D : p.Xa;
+    const double* Xqg = Xap ? Xap : p.Xq + (p.xq_per_task ? (size_t)task * M * D : 0);
     for (int e = tid; e < nas * 256; e += blockDim.x) {
       const int as = e >> 8, g = (e >> 6) & 3, ln = e & 63;
       const int a = 16 * as + (ln >> 4) + 4 * g, c = ln & 15, qcc = 16 * strip + c;
-      if (a < p.Ma && qcc < M) {
+      if (a < Ma && qcc < M) {
         double d2 = 0.0;
         for (int d = 0; d < D; ++d) {
           const double df = Xqg[(size_t)a * D + d] * invl[d] - xqs[d * 16 + c];
@@ -644,3 +680,5 @@ template __global__ void scaml::gp_posterior_linv_kernel<0, true, false>(scaml::
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, false>(scaml::PosteriorParams);
 template __global__ void scaml::gp_posterior_linv_kernel<0, true, true>(scaml::PosteriorParams);
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, true>(scaml::PosteriorParams);
+template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, true>(scaml::PosteriorGroupedParams);   // (5e)
+template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, true>(scaml::PosteriorGroupedParams);

@@ -33,6 +33,27 @@ struct PosteriorParams {
   const double* Xa;
 };
 
+// The grouped GRAD pass (scaml_posterior_linv_grad_grouped_f64): query point q belongs to group[q], every group has its own leading
+// points.  In `base`: Ma = Ma_max (row count of cov and of a group's slice of Xa), VA / Xa unused.
+struct PosteriorGroupArgs {
+  const int32_t* group;         // (Mq) group of a query point; negative: a padding row
+  const int32_t* n_a;           // (G) leading points per group, 1 <= n_a[g] <= Ma_max
+  const double* const* VA_tab;  // (G) device pointers: group g's V of its leading points, (T, N, n_a[g]) with row stride n_a[g]
+  const double* Xa;             // (G, Ma_max, D) the leading points, padded
+  int G;
+  int pad_;
+#ifdef __HIPCC__
+  __device__ int count(int g, int ma_max) const {   // a group's count, kept inside the rows the host sized everything for
+    const int c = n_a[g];
+    return c < 0 ? 0 : (c > ma_max ? ma_max : c);
+  }
+#endif
+};
+struct PosteriorGroupedParams {
+  PosteriorParams base;
+  PosteriorGroupArgs ga;
+};
+
 struct PosteriorCovParams {
   const double* Xq;     // (M, D)
   const double* theta;  // (T, D+2)

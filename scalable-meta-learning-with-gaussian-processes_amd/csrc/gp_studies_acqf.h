@@ -1,0 +1,252 @@
+// gp_studies_acqf.h -- the batched target acquisition of many BO studies (include/scaml_gp.h (7g)): argument block, LDS footprint and
+// the arithmetic of one query point.  One source for the device kernel (csrc/gp_studies_acqf.hip: a workgroup per query point), the
+// host launcher and the single-threaded host build the CPU tests check against torch (any compiler but hipcc: tests/host_emul).
+//
+// Per query point q of group g (a study: its weights, target kernel, training inputs, cached factor of Knn, alpha, standardiser):
+//   S_mu[c]  = sum_t w_t   mu[t][q][c],   S_var[c] = sum_t w_t^2 var[t][q][c],   C[a][c] = sum_t w_t^2 cov[t][a][16 q + c]
+//              over the active tasks, t = 0 .. T-1 in order, for the 16 columns c of the GRAD pass and the n_g training points a
+//   Knq[a]   = C[a][0] / s^2 + os k_t(x_a, x_q),      dKnq[a][d] = C[a][1 + d] / s^2 + d/dx_d os k_t(x_a, x_q)
+//   z        = Knn^-1 Knq from the cached factor (blocked substitution with the 16 x 16 inverses of L's diagonal blocks)
+//   mu*      = m + s ((S_mu[0] - m) / s + Knq . alpha),   var* = s^2 (S_var[0] / s^2 + os - Knq . z)
+//   dmu*[d]  = S_mu[1 + d] + s sum_a alpha_a dKnq[a][d],   dvar*[d] = S_var[1 + d] - 2 s^2 sum_a z_a dKnq[a][d]
+//   UCB / EI and their chain rule with the clamps of scamlgp_amd/utils.py (csrc/gp_fantasy.hip states them for F fantasies).
+// Every sum runs in a fixed order (tasks ascending, training points ascending) by ONE thread per output: no atomics, no wave
+// reductions, so the result is a pure function of the inputs and the host build computes what the device computes.
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define SA_DEV __device__ __forceinline__
+#define SA_SYNC() __syncthreads()
+#else
+#define SA_DEV static inline
+#define SA_SYNC() ((void)0)
+#endif
+
+namespace scaml {
+
+constexpr int STUDIES_ACQF_MAX_N = 96;   // training points per study (the GRAD pass's covariance block)
+constexpr int STUDIES_ACQF_MAX_D = 15;   // (its 16 columns per query point)
+constexpr int STUDIES_ACQF_THREADS = 256;
+
+struct StudiesAcqfParams {
+  const double* mu;           // (T, Mq, 16)          GRAD-pass outputs of the source stack, all tasks
+  const double* var;          // (T, Mq, 16)
+  const double* cov;          // (T, n_max, Mq * 16)  rows a < n_g of query q's strip are read
+  const int32_t* group;       // (Mq) study of a query point; negative: padding (zeros come out)
+  const double* Xq;           // (Mq, D)
+  const double* w;            // (G, T) weights, zero where pruned
+  const uint8_t* active;      // (G, T) a masked task is skipped, not multiplied by zero
+  const double* Xt;           // (G, n_max, D) training inputs
+  const double* theta;        // (G, D + 2) target kernel: lengthscales, outputscale, noise
+  const double* L;            // (G, n_max, n_max) factor of Knn, row stride n_max, the leading n_g x n_g block
+  const double* Linv_diag;    // (G, ceil(n_max / 16), 16, 16) inverses of its diagonal blocks
+  const double* alpha;        // (G, n_max) Knn^-1 resid
+  const int32_t* n_points;    // (G) 1 <= n_g <= n_max
+  const double* m_all;        // (G)
+  const double* s_all;        // (G) > 0
+  const int32_t* info;        // (G) != 0: the study's factorisation failed, its outputs are NaN
+  const double* acqf_param;   // (G) UCB: beta; EI: best_f
+  double* value;              // (Mq)
+  double* grad;               // (Mq, D) or NULL
+  double* mu_out;             // (Mq) or NULL: the target posterior mean (original units)
+  double* var_out;            // (Mq) or NULL: its variance
+  int Mq, G, n_max, T, D, kind, acqf, pad_;
+};
+
+// LDS of one query point, in doubles: C [n_max][16] | S_mu, S_var [32] | u, v, alpha [3 np] | W [nb][256] | L [n_max][n_max | 1] | red [48]
+constexpr size_t studies_acqf_lds_doubles(int n_max) {
+  const size_t nb = (size_t)(n_max + 15) / 16, np = nb * 16;
+  return (size_t)n_max * 16 + 32 + 3 * np + nb * 256 + (size_t)n_max * (size_t)(n_max | 1) + 48;
+}
+
+// os k(d2) and os dk / d(d2) of the scaled squared distance (the formulas of kernel_and_slope_scaled, libm instead of the table)
+SA_DEV void sa_kernel_and_slope(int kind, double d2, double os, double& k, double& dk) {
+  if (kind == 0) {
+    k = os * exp(-0.5 * d2);
+    dk = -0.5 * k;
+  } else {
+    const double s5 = 2.2360679774997896964;
+    const double r = sqrt(fmax(d2, 1e-30));   // gpytorch clamps the squared distance before the root
+    const double ex = os * exp(-s5 * r);
+    const double lin = 1.0 + s5 * r;
+    k = (lin + (5.0 / 3.0) * r * r) * ex;
+    dk = (-5.0 / 6.0) * lin * ex;
+  }
+}
+
+// One query point by `nthr` cooperating threads (thread `tid`; SA_SYNC between the phases).  `lds`: studies_acqf_lds_doubles(n_max).
+SA_DEV void sa_query(const StudiesAcqfParams& p, double* lds, int q, int tid, int nthr) {
+  const int D = p.D, T = p.T, n_max = p.n_max;
+  const int g = p.group[q];
+  const double nan = NAN;
+  // (every branch up to the first barrier is uniform over the workgroup)
+  if (g < 0 || g >= p.G) {
+    if (tid == 0) {
+      p.value[q] = 0.0;
+      if (p.mu_out) p.mu_out[q] = 0.0;
+      if (p.var_out) p.var_out[q] = 0.0;
+    }
+    if (p.grad) for (int d = tid; d < D; d += nthr) p.grad[(size_t)q * D + d] = 0.0;
+    return;
+  }
+  const int n = p.n_points[g];
+  if (p.info[g] != 0 || n < 1 || n > n_max) {
+    if (tid == 0) {
+      p.value[q] = nan;
+      if (p.mu_out) p.mu_out[q] = nan;
+      if (p.var_out) p.var_out[q] = nan;
+    }
+    if (p.grad) for (int d = tid; d < D; d += nthr) p.grad[(size_t)q * D + d] = nan;
+    return;
+  }
+  const int nbm = (n_max + 15) / 16, np = nbm * 16, nb = (n + 15) / 16, ldl = n_max | 1;
+  double* C = lds;
+  double* Ssum = C + (size_t)n_max * 16;   // S_mu [16] | S_var [16]
+  double* u = Ssum + 32;
+  double* v = u + np;
+  double* al = v + np;
+  double* Wd = al + np;
+  double* Ls = Wd + (size_t)nbm * 256;
+  double* red = Ls + (size_t)n_max * ldl;
+
+  const double s = p.s_all[g], m = p.m_all[g], s2 = s * s, inv_s2 = 1.0 / s2;
+  const double* th = p.theta + (size_t)g * (D + 2);
+  const double os = th[D];
+  const double* wg = p.w + (size_t)g * T;
+  const uint8_t* ag = p.active + (size_t)g * T;
+  const size_t W16 = (size_t)p.Mq * 16, col0 = (size_t)q * 16;
+
+  // ---- phase 1: the weighted task sums (eight tasks' loads in flight), the factor, its block inverses and alpha into LDS
+  for (int e = tid; e < n * 16 + 32; e += nthr) {
+    const bool is_cov = e < n * 16;
+    const int a = e >> 4, c = e & 15;
+    const int which = (e - n * 16) >> 4;   // 0: mu, 1: var
+    const double* src = is_cov ? p.cov + (size_t)a * W16 + col0 + c : (which == 0 ? p.mu : p.var) + col0 + c;
+    const size_t tstride = is_cov ? (size_t)n_max * W16 : W16;
+    const bool lin = !is_cov && which == 0;
+    double acc = 0.0;
+    for (int t0 = 0; t0 < T; t0 += 8) {
+      double val[8], cf[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int t = t0 + k;
+        const bool ok = t < T && ag[t];
+        val[k] = ok ? src[(size_t)t * tstride] : 0.0;
+        const double wt = ok ? wg[t] : 0.0;
+        cf[k] = lin ? wt : wt * wt;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc = fma(cf[k], val[k], acc);
+    }
+    if (is_cov) C[e] = acc * inv_s2;
+    else Ssum[e - n * 16] = acc;
+  }
+  {
+    const double* Lg = p.L + (size_t)g * n_max * n_max;
+    for (int e = tid; e < n * n; e += nthr) {
+      const int i = e / n, j = e - i * n;
+      if (j <= i) Ls[(size_t)i * ldl + j] = Lg[(size_t)i * n_max + j];
+    }
+    const double* Wg = p.Linv_diag + (size_t)g * nbm * 256;
+    for (int e = tid; e < nb * 256; e += nthr) Wd[e] = Wg[e];
+    for (int a = tid; a < n; a += nthr) al[a] = p.alpha[(size_t)g * n_max + a];
+  }
+  SA_SYNC();
+  // ---- phase 1b: the target kernel's part of Knq and of its input gradient, one slope evaluation per training point
+  for (int a = tid; a < n; a += nthr) {
+    const double* xa = p.Xt + ((size_t)g * n_max + a) * D;
+    const double* xq = p.Xq + (size_t)q * D;
+    double d2 = 0.0;
+    for (int d = 0; d < D; ++d) {
+      const double df = (xq[d] - xa[d]) / th[d];
+      d2 = fma(df, df, d2);
+    }
+    double k0, dk;
+    sa_kernel_and_slope(p.kind, d2, os, k0, dk);
+    double* Ca = C + (size_t)a * 16;
+    Ca[0] += k0;
+    for (int d = 0; d < D; ++d) Ca[1 + d] += 2.0 * dk * ((xq[d] - xa[d]) / (th[d] * th[d]));
+    u[a] = Ca[0];
+  }
+  SA_SYNC();
+  // ---- phase 2: z = Knn^-1 Knq.  Forward L y = Knq by block rows: y_kb = W_kb u_kb, then u_i -= L[i, kb] y_kb below the block
+  for (int kb = 0; kb < nb; ++kb) {
+    const int r0 = 16 * kb, cnt = n - r0 < 16 ? n - r0 : 16;
+    for (int r = tid; r < cnt; r += nthr) {
+      double acc = 0.0;
+      for (int k = 0; k <= r; ++k) acc = fma(Wd[kb * 256 + r * 16 + k], u[r0 + k], acc);
+      v[r0 + r] = acc;
+    }
+    SA_SYNC();
+    for (int i = r0 + 16 + tid; i < n; i += nthr) {
+      double acc = u[i];
+      for (int k = 0; k < 16; ++k) acc = fma(-Ls[(size_t)i * ldl + r0 + k], v[r0 + k], acc);
+      u[i] = acc;
+    }
+    SA_SYNC();
+  }
+  // backward L^T z = y (y in v, z into u): z_kb = W_kb^T v_kb, then v_i -= L[kb, i]^T z_kb above the block
+  for (int kb = nb - 1; kb >= 0; --kb) {
+    const int r0 = 16 * kb, cnt = n - r0 < 16 ? n - r0 : 16;
+    for (int r = tid; r < cnt; r += nthr) {
+      double acc = 0.0;
+      for (int k = r; k < cnt; ++k) acc = fma(Wd[kb * 256 + k * 16 + r], v[r0 + k], acc);
+      u[r0 + r] = acc;
+    }
+    SA_SYNC();
+    for (int i = tid; i < r0; i += nthr) {
+      double acc = v[i];
+      for (int k = 0; k < cnt; ++k) acc = fma(-Ls[(size_t)(r0 + k) * ldl + i], u[r0 + k], acc);
+      v[i] = acc;
+    }
+    SA_SYNC();
+  }
+  // ---- phase 3: the contractions over the training points, one thread per output, a = 0 .. n-1 in order
+  //   red[0] = Knq . alpha, red[1] = Knq . z, red[2 + d] = sum_a alpha_a dKnq[a][d], red[18 + d] = sum_a z_a dKnq[a][d]
+  for (int o = tid; o < 2 + 2 * D; o += nthr) {
+    const bool with_alpha = o == 0 || (o >= 2 && o < 2 + D);
+    const int col = o < 2 ? 0 : (o < 2 + D ? 1 + (o - 2) : 1 + (o - 2 - D));
+    const double* lhs = with_alpha ? al : u;
+    double acc = 0.0;
+    for (int a = 0; a < n; ++a) acc = fma(lhs[a], C[(size_t)a * 16 + col], acc);
+    red[o < 2 ? o : (o < 2 + D ? 2 + (o - 2) : 18 + (o - 2 - D))] = acc;
+  }
+  SA_SYNC();
+  // ---- phase 4: the posterior, the acquisition value and its chain rule (every writing thread restates the scalars)
+  for (int o = tid; o < (D > 1 ? D : 1); o += nthr) {
+    const double mean_q = (Ssum[0] - m) / s, var_q = Ssum[16] * inv_s2 + os;
+    const double mu = fma(s, mean_q + red[0], m);
+    const double vr = s2 * (var_q - red[1]);
+    const double par = p.acqf_param[g];
+    double A, Amu, Av;
+    if (p.acqf == 0) {   // UCB: -mu + sqrt(beta max(v, 0)); d/dv = beta / (2 sqrt(beta v)), zero where v is clamped
+      const double sd = sqrt(par * (vr > 0.0 ? vr : 0.0));
+      A = sd - mu;
+      Amu = -1.0;
+      Av = vr > 0.0 ? 0.5 * par / (sd > 1e-300 ? sd : 1e-300) : 0.0;
+    } else {             // EI (minimisation): d/dmu = -Phi(u), d/dv = phi(u) / (2 sigma), zero on the 1e-9 floor
+      const double sigma = sqrt(vr > 1e-9 ? vr : 1e-9);
+      const double uu = -(mu - par) / sigma;
+      const double pdf = exp(-0.5 * uu * uu) * 0.39894228040143267794;   // 1 / sqrt(2 pi)
+      const double cdf = 0.5 * (1.0 + erf(uu * 0.70710678118654752440));
+      A = sigma * (pdf + uu * cdf);
+      Amu = -cdf;
+      Av = vr > 1e-9 ? 0.5 * pdf / sigma : 0.0;
+    }
+    if (o == 0) {
+      p.value[q] = A;
+      if (p.mu_out) p.mu_out[q] = mu;
+      if (p.var_out) p.var_out[q] = vr;
+    }
+    if (p.grad && o < D) {
+      const double dmu = fma(s, red[2 + o], Ssum[1 + o]);
+      const double dvar = fma(-2.0 * s2, red[18 + o], Ssum[17 + o]);
+      p.grad[(size_t)q * D + o] = fma(Av, dvar, Amu * dmu);
+    }
+  }
+}
+
+}  // namespace scaml

@@ -22,6 +22,7 @@
 #include "gp_target_params.h"
 #include "gp_fantasy_params.h"
 #include "gp_stack_fit_params.h"
+#include "gp_studies_acqf.h"   // (argument block and LDS footprint; its arithmetic is not called here)
 #include <math.h>
 
 extern "C" const unsigned char scaml_hsaco_blob[];   // generated: lib/hsaco_blob.c
@@ -67,6 +68,7 @@ struct Module {
   hipFunction_t wsum = nullptr, linv = nullptr, chosolve = nullptr, kmat[2] = {}, mllgrad[2] = {};
   hipFunction_t tgt_assemble[2] = {}, tgt_finish = nullptr, tgt_fit = nullptr, tgt_fit_batched = nullptr, tgt_grad[2] = {};
   hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {};   // value only; value + gradient per kind
+  hipFunction_t post_linv_grouped[2] = {}, tgt_acqf_batched = nullptr;   // lock-step studies: grouped GRAD pass, batched acquisition
   hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {}, stack_step = nullptr;
   hipFunction_t blk_solve[2][2] = {}, blk_syrk[2] = {};   // solve: [kind][D <= 8]
   hipFunction_t mllgrad_fused[4][2][2] = {};   // [size class NBT = 2, 4, 8, 16][kind][LDS-DMA staging]
@@ -85,9 +87,11 @@ struct Module {
     std::vector<KernelRow> rows = {
         {post, "_ZN5scaml19gp_posterior_kernelILi%dEEEvNS_15PosteriorParamsE", kLdsLimit, {K}},
         {post_cov, "_ZN5scaml23gp_posterior_cov_kernelILi%dEEEvNS_18PosteriorCovParamsE", 0, {K}},
-        {post_linv, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb0ELb0EEEvNS_15PosteriorParamsE", kLdsLimit, {K}},
-        {post_linv_cov, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0EEEvNS_15PosteriorParamsE", kLdsLimit, {K}},
-        {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1EEEvNS_15PosteriorParamsE", kLdsLimit, {K}},
+        {post_linv, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_cov, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {&tgt_acqf_batched, "scaml_target_acqf_batched_kernel", kLdsLimit, {}},
         {&wsum, "scaml_weighted_task_sum_kernel", 0, {}},
         {&linv, "_ZN5scaml14gp_linv_kernelENS_10LinvParamsE", kLdsLimit, {}},
         {&chosolve, "_ZN5scaml19gp_cho_solve_kernelENS_14ChoSolveParamsE", kLdsLimit, {}},
@@ -119,7 +123,7 @@ struct Module {
       for (int i = 0; i < r.ax[0].n; ++i) {
         for (int j = 0; j < r.ax[1].n; ++j) {
           for (int k = 0; k < r.ax[2].n; ++k, ++slot) {
-            char name[128];
+            char name[160];
             snprintf(name, sizeof(name), r.pattern, r.ax[0].v[i], r.ax[1].v[j], r.ax[2].v[k]);
             e = hipModuleGetFunction(slot, mod, name);
             if (e == hipSuccess && r.lds_cap) e = hipFuncSetAttribute((const void*)*slot, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds_cap);
@@ -728,6 +732,50 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
                              value, grad, n, M, F, grad ? D : 0, acqf, 0};
   // one wave per query point
   return launch(grad ? m->tgt_fantasy_grad[kind] : m->tgt_fantasy, dim3((unsigned)M), 64, 0, stream, "target_fantasy_acqf", p);
+}
+
+// ---- (5e) the GRAD pass with the query points divided among groups; (7g) the batched target acquisition behind it ---------------
+int scaml_posterior_linv_grad_grouped_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                                          const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
+                                          const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T,
+                                          int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov,
+                                          void* stream) {
+  if (T < 0 || N < 1 || Mq < 0 || G < 0 || Ma_max < 1 || D < 1) return SCAML_E_BADARG;
+  if (!Xq || !group || !Xa || !n_points_a || !VA_tab || !X || !theta || !Linv || !alpha || !mu || !var || !cov) return SCAML_E_BADARG;
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (D > 15 || Ma_max > 96 || Ma_max > N || N > scaml_posterior_max_n() || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
+  const size_t lds = scaml::posterior_linv_lds_doubles(N, D) * sizeof(double);
+  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (T == 0 || Mq == 0 || G == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  scaml::PosteriorGroupedParams p{};
+  p.base = scaml::PosteriorParams{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N, 16 * Mq, D, 0, 0, 0,
+                                  nullptr, cov, Ma_max, 0, nullptr};
+  p.ga = scaml::PosteriorGroupArgs{group, n_points_a, VA_tab, Xa, G, 0};
+  const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * (unsigned)Mq;   // XCD-aware (task, strip) map inside the kernel
+  return launch(m->post_linv_grouped[kind], dim3(blocks), 512, lds, stream, "gp_posterior_linv_grouped", p);
+}
+
+int scaml_target_acqf_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
+                                  const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
+                                  const double* Linv_diag, const double* alpha, const int32_t* n_points, const double* m_all,
+                                  const double* s_all, const int32_t* info, const double* acqf_param, int Mq, int G, int n_max, int T,
+                                  int D, int kind, int acqf, double* value, double* grad, double* mu_out, double* var_out, void* stream) {
+  if (Mq < 0 || G < 0 || n_max < 1 || T < 1 || D < 1) return SCAML_E_BADARG;
+  if (!mu || !var || !cov || !group || !Xq || !w || !active || !Xt || !theta || !L || !Linv_diag || !alpha || !n_points || !m_all || !s_all ||
+      !info || !acqf_param || !value)
+    return SCAML_E_BADARG;
+  if (!valid_kind(kind) || (acqf != 0 && acqf != 1)) return SCAML_E_BADARG;
+  if (n_max > scaml::STUDIES_ACQF_MAX_N || D > scaml::STUDIES_ACQF_MAX_D || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
+  const size_t lds = scaml::studies_acqf_lds_doubles(n_max) * sizeof(double);
+  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (Mq == 0 || G == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  scaml::StudiesAcqfParams p{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param,
+                             value, grad, mu_out, var_out, Mq, G, n_max, T, D, kind, acqf, 0};
+  return launch(m->tgt_acqf_batched, dim3((unsigned)Mq), scaml::STUDIES_ACQF_THREADS, lds, stream, "target_acqf_batched", p);   // a workgroup per query point
 }
 
 // ---- (8) target GP: objective + gradient, and the whole L-BFGS refit, in one launch (csrc/gp_target_fit.hip) -------------

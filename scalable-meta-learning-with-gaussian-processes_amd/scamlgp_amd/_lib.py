@@ -95,6 +95,10 @@ SIGNATURES = {
     "scaml_posterior_linv_grad_f64": (_i, [_dp] * 10 + [_i] * 6 + [_dp, _dp, _dp, _u, c_void_p]),
     "scaml_target_posterior_grad_f64": (_i, [_dp] * 8 + [_f, _dp, _i, _i, _i, _i, _dp, _dp, c_void_p]),
     "scaml_target_fantasy_acqf_f64": (_i, [_dp] * 5 + [_f, _f, _f, _dp, _i, _f] + [_dp] * 6 + [_i] * 5 + [_dp, _dp, c_void_p]),
+    # (5e) Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points; T, N, Mq, G, Ma_max, D, kind; mu, var, cov
+    "scaml_posterior_linv_grad_grouped_f64": (_i, [_dp] * 12 + [_i] * 7 + [_dp, _dp, _dp, c_void_p]),
+    # (7g) 17 arrays; Mq, G, n_max, T, D, kind, acqf; value, grad, mu_out, var_out
+    "scaml_target_acqf_batched_f64": (_i, [_dp] * 17 + [_i] * 7 + [_dp] * 4 + [c_void_p]),
     "scaml_target_fit_max_n": (_i, [_i, _i]),
     "scaml_target_fit_max_d": (_i, []),
     "scaml_target_fit_workspace_doubles": (_ll, [_i, _i, _i, _i]),

@@ -22,6 +22,7 @@ from typing import Callable, Dict, Hashable, Optional, Sequence, Tuple, Union
 
 import copy
 import math
+import time
 
 import numpy as np
 import scipy.optimize
@@ -68,18 +69,11 @@ class GraphedAcquisition:
         return tuple(o.clone() for o in self.out) if isinstance(self.out, tuple) else self.out.clone()
 
 
-def optimize_acqf(af: Callable[[torch.Tensor], torch.Tensor], dim: int, raw_samples: int = 1024, num_restarts: int = 10,
-                  max_iter: int = 50, generator: Optional[torch.Generator] = None, fd_step: float = 1e-4,
-                  eta: float = 2.0, graph_device: Optional[torch.device] = None, analytic_grad: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Maximise ``af`` over [0, 1]^dim; returns (x_best (dim,), af(x_best)).  botorch's ``optimize_acqf`` recipe:
-    ``raw_samples`` random candidates -> ``num_restarts`` initial conditions (the best candidate plus a Boltzmann sample
-    of the rest, ``initialize_q_batch``) -> ONE box-constrained L-BFGS-B run over all starts jointly (the summed
-    acquisition value, which is separable over the starts: botorch's ``gen_candidates_scipy`` does the same) -> the
-    best end point.  Gradients: analytic when the acquisition function offers ``value_and_grad`` and its model the posterior
-    input-gradient kernels (``ScaMLGP.posterior_with_grad``: an evaluation then scores just the R starts); otherwise every
-    objective evaluation is one batched posterior call over the starts and their central-difference stencils (one-sided at the
-    box faces, 2 dim + 1 points per start).  With ``graph_device`` (the model's GPU) the evaluation is captured into a HIP graph
-    once and replayed per L-BFGS-B step (``GraphedAcquisition``)."""
+def acqf_initial_conditions(af: Callable[[torch.Tensor], torch.Tensor], dim: int, raw_samples: int, num_restarts: int,
+                            generator: Optional[torch.Generator], eta: float = 2.0):
+    """Stage 1 of ``optimize_acqf``: ``raw_samples`` uniform candidates scored in one pass, then ``num_restarts`` initial conditions (the
+    best candidate plus a Boltzmann sample of the rest, botorch's ``initialize_q_batch``).  Everything drawn comes from ``generator``.
+    Returns (cand (raw_samples, dim), vals (raw_samples,), best0, x0 (R, dim))."""
     cand = torch.rand(raw_samples, dim, dtype=torch.float64, generator=generator)
     vals = af(cand).detach().cpu()
     R = min(num_restarts, raw_samples)
@@ -92,8 +86,14 @@ def optimize_acqf(af: Callable[[torch.Tensor], torch.Tensor], dim: int, raw_samp
         if float(pr.sum()) > 0:
             k = min(R - 1, int((pr > 0).sum()))
             picks += torch.multinomial(pr, k, replacement=False, generator=generator).tolist()
-    x0 = cand[picks]
-    R = x0.shape[0]
+    return cand, vals, best0, cand[picks]
+
+
+def acqf_local_optimization(af: Callable[[torch.Tensor], torch.Tensor], x0: torch.Tensor, max_iter: int = 50, fd_step: float = 1e-4,
+                            graph_device: Optional[torch.device] = None, analytic_grad: bool = True) -> torch.Tensor:
+    """Stage 2 of ``optimize_acqf``: ONE box-constrained scipy L-BFGS-B run over the R starts jointly (the summed acquisition value);
+    returns the end points (R, dim) inside [0, 1]^dim."""
+    R, dim = x0.shape
     eye = torch.eye(dim, dtype=torch.float64)
     analytic = analytic_grad and hasattr(af, "value_and_grad") and getattr(getattr(af, "model", None), "supports_posterior_grad", lambda: False)()
     if analytic:
@@ -124,12 +124,36 @@ def optimize_acqf(af: Callable[[torch.Tensor], torch.Tensor], dim: int, raw_samp
 
     res = scipy.optimize.minimize(fun if analytic else fun_fd, x0.reshape(-1).numpy(), jac=True, method="L-BFGS-B", bounds=[(0.0, 1.0)] * (R * dim),
                                   options=dict(maxiter=max_iter))
-    xs = torch.from_numpy(np.clip(res.x, 0.0, 1.0)).reshape(R, dim)
-    fin = torch.nan_to_num(af(xs).detach().cpu(), nan=-float("inf"))
+    return torch.from_numpy(np.clip(res.x, 0.0, 1.0)).reshape(R, dim)
+
+
+def acqf_final_choice(cand: torch.Tensor, vals: torch.Tensor, best0: int, xs: torch.Tensor, fin: torch.Tensor):
+    """Stage 3 of ``optimize_acqf``: the best end point (``fin`` = the acquisition values at ``xs``, re-scored), unless the best raw
+    candidate is better.  Returns (x (dim,), value)."""
+    fin = torch.nan_to_num(fin.detach().cpu(), nan=-float("inf"))
     j = int(fin.argmax())
     if float(fin[j]) >= float(vals[best0]):
         return xs[j], fin[j]
     return cand[best0], vals[best0]
+
+
+def optimize_acqf(af: Callable[[torch.Tensor], torch.Tensor], dim: int, raw_samples: int = 1024, num_restarts: int = 10,
+                  max_iter: int = 50, generator: Optional[torch.Generator] = None, fd_step: float = 1e-4,
+                  eta: float = 2.0, graph_device: Optional[torch.device] = None, analytic_grad: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Maximise ``af`` over [0, 1]^dim; returns (x_best (dim,), af(x_best)).  botorch's ``optimize_acqf`` recipe:
+    ``raw_samples`` random candidates -> ``num_restarts`` initial conditions (the best candidate plus a Boltzmann sample
+    of the rest, ``initialize_q_batch``) -> ONE box-constrained L-BFGS-B run over all starts jointly (the summed
+    acquisition value, which is separable over the starts: botorch's ``gen_candidates_scipy`` does the same) -> the
+    best end point.  Gradients: analytic when the acquisition function offers ``value_and_grad`` and its model the posterior
+    input-gradient kernels (``ScaMLGP.posterior_with_grad``: an evaluation then scores just the R starts); otherwise every
+    objective evaluation is one batched posterior call over the starts and their central-difference stencils (one-sided at the
+    box faces, 2 dim + 1 points per start).  With ``graph_device`` (the model's GPU) the evaluation is captured into a HIP graph
+    once and replayed per L-BFGS-B step (``GraphedAcquisition``).  The three stages are functions of their own
+    (``acqf_initial_conditions``, ``acqf_local_optimization``, ``acqf_final_choice``): ``ScaMLGPBOStudies`` runs the middle one for
+    all its studies at once."""
+    cand, vals, best0, x0 = acqf_initial_conditions(af, dim, raw_samples, num_restarts, generator, eta)
+    xs = acqf_local_optimization(af, x0, max_iter, fd_step, graph_device, analytic_grad)
+    return acqf_final_choice(cand, vals, best0, xs, af(xs))
 
 
 class ScaMLGPBOLoop:
@@ -240,10 +264,24 @@ class ScaMLGPBOStudies:
     busy for its whole latency.  Per study the starts, the optimiser and the best-of-restarts choice are the single loop's; study s
     draws its restart samples from ``fit_gens[s]`` (a ``torch.Generator`` seeded with ``seeds[s]``), its acquisition samples from
     ``studies[s].gen``.  A study whose shape the kernel does not take (n beyond its LDS, D > 16) is refitted as ``ScaMLGPBOLoop`` does
-    it, on its own.  ``suggest`` runs the studies one after the other with the existing launches.  Studies may get out of step: a
-    study with a pending or a failed (None / NaN) evaluation trains on fewer points than its neighbours."""
+    it, on its own.  Studies may get out of step: a study with a pending or a failed (None / NaN) evaluation trains on fewer points than
+    its neighbours.
 
-    def __init__(self, source_gps: Dict[Hashable, SourceGP], dim: int, num_studies: int, seeds: Optional[Sequence[int]] = None, **loop_kwargs):
+    ``suggest_mode="sequential"`` (default): ``suggest`` runs the studies one after the other with the existing launches.
+    ``suggest_mode="lockstep"``: per study the initial conditions of ``optimize_acqf`` as before (its own ``gen``, its own scoring pass:
+    the same draws), then ONE box-constrained ``hyper.batched_lbfgs`` over the starts of all studies -- every objective evaluation is one
+    grouped source pass and one batched acquisition launch for all of them (``utils.StudiesAcquisition``), captured into one HIP graph per
+    ``suggest`` with ``use_graph`` --, one batched re-scoring of the end points, and per study the final choice of ``optimize_acqf``.  Each
+    start is a problem of its own there (own history, step and stopping flag; ``optimize_acqf`` sums over a study's starts), so a
+    start's path does not depend on the other studies.  A study the batched path does not take -- no training data yet, n > 96, D > 15,
+    pending evaluations (a fantasy model) -- takes its own ``ScaMLGPBOLoop.suggest()`` in the same call."""
+
+    def __init__(self, source_gps: Dict[Hashable, SourceGP], dim: int, num_studies: int, seeds: Optional[Sequence[int]] = None,
+                 suggest_mode: str = "sequential", **loop_kwargs):
+        if suggest_mode not in ("sequential", "lockstep"):
+            raise ValueError(f"suggest_mode must be 'sequential' or 'lockstep', got {suggest_mode!r}")
+        self.suggest_mode = suggest_mode
+        self.last_suggest_info: dict = {}
         S = int(num_studies)
         if S < 1:
             raise ValueError("num_studies must be a positive integer")
@@ -272,7 +310,64 @@ class ScaMLGPBOStudies:
 
     def suggest(self) -> torch.Tensor:
         """(S, D): every study's next point (``ScaMLGPBOLoop.suggest``; OptimizerNotReady if a study has its full count pending)."""
-        return torch.stack([st.suggest() for st in self.studies])
+        if self.suggest_mode == "sequential":
+            return torch.stack([st.suggest() for st in self.studies])
+        # as the sequential loop leaves it: the studies in front of one that is not ready have suggested (and recorded) their points
+        blocked = [s for s, st in enumerate(self.studies)
+                   if st.max_pending_evaluations is not None and st.pending.shape[0] >= st.max_pending_evaluations]
+        if blocked:
+            self._suggest_lockstep(self.studies[:blocked[0]])
+            self.studies[blocked[0]].suggest()   # raises OptimizerNotReady
+        return torch.stack(self._suggest_lockstep(self.studies))
+
+    @staticmethod
+    def _batched_study(st: ScaMLGPBOLoop) -> bool:
+        """Does the batched acquisition take this study's step?  (An ordinary model with training data within the GRAD pass's limits;
+        pending evaluations make it a fantasy model.)"""
+        return (not (st.max_pending_evaluations is not None and st.pending.shape[0] > 0)) and st.model.supports_posterior_grad()
+
+    def _suggest_lockstep(self, studies: Sequence[ScaMLGPBOLoop]):
+        out = [None] * len(studies)
+        batch = []   # (position, study, af, cand, vals, best0, x0)
+        for i, st in enumerate(studies):
+            if not self._batched_study(st):
+                out[i] = st.suggest()
+                continue
+            st.model.eval()
+            af = st.acquisition_function()
+            batch.append((i, st, af) + acqf_initial_conditions(af, self.dim, st.raw_samples, st.num_restarts, st.gen))
+        self.last_suggest_info = dict(batched=[b[0] for b in batch], n_eval=0, n_iter=0)
+        if not batch:
+            return out
+        from .utils import StudiesAcquisition
+
+        sa = StudiesAcquisition([b[2] for b in batch])
+        counts = [b[6].shape[0] for b in batch]
+        group = sa.group_of(counts)
+        X0 = torch.cat([b[6] for b in batch], 0)
+        B = X0.shape[0]
+        vg = lambda X: sa.value_and_grad(X, group)   # noqa: E731
+        if studies[0].use_graph:   # one capture per suggest() serves all studies: a single stream, two library launches
+            vg = GraphedAcquisition(vg, B, self.dim, sa.device)
+
+        t_eval = [0.0]
+
+        def fun(x: torch.Tensor):
+            t0 = time.perf_counter()
+            v, g = vg(x)
+            o = torch.cat([v.reshape(B, 1), g.reshape(B, self.dim)], 1).cpu()   # one device -> host copy per evaluation
+            t_eval[0] += time.perf_counter() - t0   # (the copy has waited for the evaluation)
+            return -o[:, 0], -o[:, 1:]
+
+        res = hyper.batched_lbfgs(fun, X0, max_iter=studies[0].af_max_iter, bounds=(0.0, 1.0))
+        fin = sa.value(res.x, group).cpu()   # the end points of all studies re-scored in one evaluation
+        self.last_suggest_info.update(n_eval=res.n_eval, n_iter=res.n_iter, eval_seconds=t_eval[0])
+        for (i, st, af, cand, vals, best0, x0), xs, fs in zip(batch, res.x.split(counts), fin.split(counts)):
+            x, _ = acqf_final_choice(cand, vals, best0, xs, fs)
+            if st.max_pending_evaluations is not None:
+                st.pending = torch.cat([st.pending, x.reshape(1, -1)], 0)
+            out[i] = x
+        return out
 
     def report(self, X: torch.Tensor, y) -> None:
         """One evaluation per study: X (S, D), y (S,) -- a tensor, or a sequence whose entries may be None / NaN (no objective value:

@@ -305,13 +305,17 @@ class LBFGSResult:
 
 def batched_lbfgs(fun: Callable[[torch.Tensor], Tuple[torch.Tensor, torch.Tensor]], x0: torch.Tensor,
                   max_iter: int = 200, history: int = 10, gtol: float = 1e-5, ftol: float = 2.2e-9,
-                  c1: float = 1e-4, max_ls: int = 20) -> LBFGSResult:
+                  c1: float = 1e-4, max_ls: int = 20, bounds=None, callback=None) -> LBFGSResult:
     """Minimise B independent functions of P variables at once.  ``fun(x)`` -> (f (B,), g (B, P))
     evaluates all of them in one call (for the GP stack: one fused launch).  Two-loop L-BFGS with a
     per-problem backtracking (Armijo) line search; problems whose trial value is not finite shrink
     their step; stopping rules follow scipy's L-BFGS-B (projected-gradient ``gtol``, relative
     decrease ``ftol``), which botorch's fit_gpytorch_mll drives in the reference
-    (scamlgp/utils.py:175).  No bounds: the raw parameters are unconstrained."""
+    (scamlgp/utils.py:175).  ``bounds=None``: the raw parameters are unconstrained.  ``bounds=(lo, hi)`` (scalars or (P,)): the
+    box-constrained variant below (``_batched_lbfgs_box``).  ``callback(it, x, f, done)`` (optional, either variant) sees the accepted
+    points after every iteration (it = 0: the start)."""
+    if bounds is not None:
+        return _batched_lbfgs_box(fun, x0, bounds, max_iter, history, gtol, ftol, c1, max_ls, callback)
     x = x0.clone()
     B, P = x.shape
     f, g = fun(x)
@@ -324,6 +328,8 @@ def batched_lbfgs(fun: Callable[[torch.Tensor], Tuple[torch.Tensor, torch.Tensor
     rho = torch.zeros(B, history, dtype=x.dtype, device=x.device)
     valid = torch.zeros(B, history, dtype=torch.bool, device=x.device)
     done = failed.clone()
+    if callback is not None:
+        callback(0, x, f, done)
     it = 0
     for it in range(1, max_iter + 1):
         # two-loop recursion (newest pair at index 0)
@@ -374,6 +380,112 @@ def batched_lbfgs(fun: Callable[[torch.Tensor], Tuple[torch.Tensor, torch.Tensor
         rel = (f - f_new) / torch.maximum(torch.maximum(f.abs(), f_new.abs()), torch.ones_like(f))
         x, f_prev, f, g = x_new, f, f_new, g_new
         done = done | stalled | (g.abs().amax(-1) <= gtol) | ((rel <= ftol) & ~stalled & (it > 1))
+        if callback is not None:
+            callback(it, x, f, done)
         if bool(done.all()):
             break
     return LBFGSResult(x=x, f=f, n_iter=it, n_eval=n_eval, converged=done & ~failed, failed=failed)
+
+
+def _rowdot(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Row-wise dot product of (B, P) tensors, coordinate after coordinate: element-wise operations only, so that a row's value
+    does not depend on how many rows there are (a library reduction may pick its summation order by shape)."""
+    acc = a[:, 0] * b[:, 0]
+    for j in range(1, a.shape[1]):
+        acc = acc + a[:, j] * b[:, j]
+    return acc
+
+
+def projected_gradient(x: torch.Tensor, g: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
+    """scipy L-BFGS-B's stopping quantity: P(x - g) - x with P the projection onto the box (zero where a bound holds x against -g)."""
+    return torch.minimum(torch.maximum(x - g, lo), hi) - x
+
+
+def _batched_lbfgs_box(fun, x0, bounds, max_iter, history, gtol, ftol, c1, max_ls, callback) -> LBFGSResult:
+    """``batched_lbfgs`` on the box lo <= x <= hi: B independent problems, each with its own history, step and stopping flag (a
+    problem's trajectory does not depend on what else is in the batch: every per-problem quantity is computed row by row).
+    Projected quasi-Newton: the two-loop direction, zeroed on the coordinates that sit at a bound with the gradient pointing outward;
+    trial points projected onto the box (the Armijo test uses g . (trial - x)); a curvature pair is kept only when s . y > 0; the
+    stopping rule is scipy L-BFGS-B's, max |P(x - g) - x| <= gtol, next to the relative decrease ``ftol``.  ``converged`` flags the
+    problems that stopped on the projected-gradient rule.  ``callback(it, x, f, done)`` (optional) sees the accepted points after
+    every iteration (it = 0: the projected start).  The state lives where x0 lives (the host, for the acquisition optimiser: B x P is
+    tiny); each ``fun`` call is one batched evaluation."""
+    lo = torch.as_tensor(bounds[0], dtype=x0.dtype, device=x0.device).expand(x0.shape[-1]).clone()
+    hi = torch.as_tensor(bounds[1], dtype=x0.dtype, device=x0.device).expand(x0.shape[-1]).clone()
+    if bool((lo > hi).any()):
+        raise ValueError("bounds: lo > hi")
+    x = torch.minimum(torch.maximum(x0, lo), hi)
+    B, P = x.shape
+    f, g = fun(x)
+    n_eval = 1
+    failed = ~torch.isfinite(f) | ~torch.isfinite(g).all(-1)
+    f = torch.where(failed, torch.full_like(f, float("inf")), f)
+    g = torch.where(failed.unsqueeze(-1), torch.zeros_like(g), g)
+    S = torch.zeros(B, history, P, dtype=x.dtype, device=x.device)
+    Y = torch.zeros_like(S)
+    rho = torch.zeros(B, history, dtype=x.dtype, device=x.device)
+    valid = torch.zeros(B, history, dtype=torch.bool, device=x.device)
+    pg_small = projected_gradient(x, g, lo, hi).abs().amax(-1) <= gtol
+    done = failed | pg_small
+    if callback is not None:
+        callback(0, x, f, done)
+    it = 0
+    for it in range(1, max_iter + 1):
+        if bool(done.all()):
+            it -= 1
+            break
+        # coordinates held by a bound: at it, and -g points out of the box
+        held = ((x <= lo) & (g > 0)) | ((x >= hi) & (g < 0))
+        q = torch.where(held, torch.zeros_like(g), g)
+        gfree = q
+        alphas = []
+        for i in range(history):
+            a = torch.where(valid[:, i], rho[:, i] * _rowdot(S[:, i], q), torch.zeros_like(f))
+            q = q - a.unsqueeze(-1) * Y[:, i]
+            alphas.append(a)
+        ys = _rowdot(S[:, 0], Y[:, 0])
+        yy = _rowdot(Y[:, 0], Y[:, 0])
+        gamma = torch.where(valid[:, 0] & (yy > 0), ys / yy.clamp_min(1e-300), torch.ones_like(f))
+        r = gamma.unsqueeze(-1) * q
+        for i in reversed(range(history)):
+            b = torch.where(valid[:, i], rho[:, i] * _rowdot(Y[:, i], r), torch.zeros_like(f))
+            r = r + (alphas[i] - b).unsqueeze(-1) * S[:, i]
+        d = torch.where(held, torch.zeros_like(r), -r)
+        gd = _rowdot(g, d)
+        bad_dir = ~(gd < 0)   # not a descent direction (or no pair yet): projected steepest descent, scaled like scipy's first step
+        d = torch.where(bad_dir.unsqueeze(-1), -gfree, d)
+        gnorm = torch.sqrt(_rowdot(gfree, gfree))
+        t = torch.where(valid[:, 0] & ~bad_dir, torch.ones_like(f), (1.0 / gnorm.clamp_min(1e-12)).clamp_max(1.0))
+        accepted = done.clone()
+        x_new, f_new, g_new = x.clone(), f.clone(), g.clone()
+        for _ in range(max_ls):
+            trial = torch.minimum(torch.maximum(x + t.unsqueeze(-1) * d, lo), hi)
+            ft, gt = fun(torch.where(accepted.unsqueeze(-1), x, trial))
+            n_eval += 1
+            slope = _rowdot(g, trial - x)
+            ok = torch.isfinite(ft) & torch.isfinite(gt).all(-1) & (slope < 0) & (ft <= f + c1 * slope) & ~accepted
+            x_new = torch.where(ok.unsqueeze(-1), trial, x_new)
+            f_new = torch.where(ok, ft, f_new)
+            g_new = torch.where(ok.unsqueeze(-1), gt, g_new)
+            accepted = accepted | ok
+            if bool(accepted.all()):
+                break
+            t = torch.where(accepted, t, 0.5 * t)
+        stalled = ~accepted   # line search failed: the problem stops where it is
+        s_vec = x_new - x
+        y_vec = g_new - g
+        sy = _rowdot(s_vec, y_vec)
+        upd = (sy > 0) & (sy > 1e-10 * torch.sqrt(_rowdot(y_vec, y_vec)) * torch.sqrt(_rowdot(s_vec, s_vec))) & ~done & ~stalled
+        S = torch.where(upd[:, None, None], torch.cat([s_vec.unsqueeze(1), S[:, :-1]], 1), S)
+        Y = torch.where(upd[:, None, None], torch.cat([y_vec.unsqueeze(1), Y[:, :-1]], 1), Y)
+        rho = torch.where(upd[:, None], torch.cat([(1.0 / sy.clamp_min(1e-300)).unsqueeze(1), rho[:, :-1]], 1), rho)
+        valid = torch.where(upd[:, None], torch.cat([torch.ones_like(upd).unsqueeze(1), valid[:, :-1]], 1), valid)
+        rel = (f - f_new) / torch.maximum(torch.maximum(f.abs(), f_new.abs()), torch.ones_like(f))
+        moved = ~done & ~stalled
+        x, f, g = x_new, f_new, g_new
+        pg_now = projected_gradient(x, g, lo, hi).abs().amax(-1) <= gtol
+        pg_small = torch.where(moved, pg_now, pg_small)
+        done = done | stalled | pg_now | ((rel <= ftol) & moved & (it > 1))
+        if callback is not None:
+            callback(it, x, f, done)
+    return LBFGSResult(x=x, f=f, n_iter=it, n_eval=n_eval, converged=pg_small & ~failed, failed=failed)

@@ -653,6 +653,85 @@ def target_fantasy_acqf(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor,
     return value, grad
 
 
+def source_posteriors_grad_grouped(Xq: torch.Tensor, group: torch.Tensor, Xa: torch.Tensor, n_points_a: torch.Tensor, VA_tab: torch.Tensor,
+                                   X: torch.Tensor, theta: torch.Tensor, kind: int, Linv: torch.Tensor, alpha: torch.Tensor,
+                                   y_mean: Optional[torch.Tensor] = None, y_std: Optional[torch.Tensor] = None,
+                                   n_points: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """``source_posteriors_grad`` with the query points Xq (Mq, D) divided among G groups, one launch of
+    scaml_posterior_linv_grad_grouped_f64: ``group`` (Mq,) int32 (negative: a padding row, zeros), ``Xa`` (G, Ma_max, D) the groups'
+    leading points, ``n_points_a`` (G,) int32 their counts, ``VA_tab`` (G,) int64: the ADDRESSES of the groups' V (T, N, Ma_g) tensors
+    (``ScaMLGP._train_VA``; the caller keeps them alive).  Returns dict(mu, var (T, Mq, 16), cov (T, Ma_max, Mq * 16): rows
+    a < Ma_{group[q]} of strip q are written, the rest is uninitialised)."""
+    T, N, D = X.shape
+    Mq = Xq.shape[0]
+    G, Ma_max = int(Xa.shape[0]), int(Xa.shape[1])
+    X = _check(X, "X")
+    Xq = _check(Xq, "Xq", (Mq, D))
+    group = _check(group, "group", (Mq,), torch.int32)
+    Xa = _check(Xa, "Xa", (G, Ma_max, D))
+    n_points_a = _check(n_points_a, "n_points_a", (G,), torch.int32)
+    VA_tab = _check(VA_tab, "VA_tab", (G,), torch.int64)
+    theta = _check(theta, "theta", (T, D + 2))
+    Linv = _check(Linv, "Linv", (T, N, N))
+    alpha = _check(alpha, "alpha", (T, N))
+    y_mean = _opt(y_mean, "y_mean", (T,))
+    y_std = _opt(y_std, "y_std", (T,))
+    n_points = _opt(n_points, "n_points", (T,), torch.int32)
+    dev = X.device
+    with torch.cuda.device(dev):
+        mu = _empty(dev, T, Mq, 16)
+        var = _empty(dev, T, Mq, 16)
+        cov = _empty(dev, T, Ma_max, Mq * 16)
+        rc = _lib.lib.scaml_posterior_linv_grad_grouped_f64(_ptr(Xq), _ptr(group), _ptr(Xa), _ptr(n_points_a), _ptr(VA_tab), _ptr(X), _ptr(theta),
+                                                            _ptr(Linv), _ptr(alpha), _ptr(y_mean), _ptr(y_std), _ptr(n_points), T, N, Mq, G, Ma_max, D,
+                                                            int(kind), _ptr(mu), _ptr(var), _ptr(cov), _stream_handle())
+    _lib.check_rc(rc, "scaml_posterior_linv_grad_grouped_f64")
+    return dict(mu=mu, var=var, cov=cov)
+
+
+def target_acqf_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor, group: torch.Tensor, Xq: torch.Tensor, w: torch.Tensor,
+                        active: torch.Tensor, Xt: torch.Tensor, theta: torch.Tensor, L: torch.Tensor, Linv_diag: torch.Tensor,
+                        alpha: torch.Tensor, n_points: torch.Tensor, m_all: torch.Tensor, s_all: torch.Tensor, info: torch.Tensor,
+                        acqf_param: torch.Tensor, acqf: int, kind: int, want_grad: bool = True, want_posterior: bool = False):
+    """The acquisition value (and input gradient) of every query point of G studies from the grouped GRAD pass's outputs
+    (``source_posteriors_grad_grouped``: mu, var (T, Mq, 16), cov (T, n_max, Mq * 16)) and the studies' padded arrays: w (G, T),
+    active (G, T) uint8, Xt (G, n_max, D), theta (G, D + 2), L (G, n_max, n_max), Linv_diag (G, ceil(n_max / 16), 16, 16),
+    alpha (G, n_max), n_points, info (G,) int32, m_all, s_all, acqf_param (G,).  One launch of scaml_target_acqf_batched_f64.
+    Returns dict(value (Mq,), grad (Mq, D) or None, mu, var (Mq,) or None)."""
+    Mq, D = Xq.shape
+    G, n_max = int(Xt.shape[0]), int(Xt.shape[1])
+    T = int(w.shape[1])
+    mu = _check(mu, "mu", (T, Mq, 16))
+    var = _check(var, "var", (T, Mq, 16))
+    cov = _check(cov, "cov", (T, n_max, Mq * 16))
+    group = _check(group, "group", (Mq,), torch.int32)
+    Xq = _check(Xq, "Xq")
+    w = _check(w, "w", (G, T))
+    active = _check(active, "active", (G, T), torch.uint8)
+    Xt = _check(Xt, "Xt", (G, n_max, D))
+    theta = _check(theta, "theta", (G, D + 2))
+    L = _check(L, "L", (G, n_max, n_max))
+    Linv_diag = _check(Linv_diag, "Linv_diag", (G, (n_max + 15) // 16, 16, 16))
+    alpha = _check(alpha, "alpha", (G, n_max))
+    n_points = _check(n_points, "n_points", (G,), torch.int32)
+    m_all = _check(m_all, "m_all", (G,))
+    s_all = _check(s_all, "s_all", (G,))
+    info = _check(info, "info", (G,), torch.int32)
+    acqf_param = _check(acqf_param, "acqf_param", (G,))
+    dev = Xq.device
+    with torch.cuda.device(dev):
+        value = _empty(dev, Mq)
+        grad = _empty(dev, Mq, D) if want_grad else None
+        mu_o = _empty(dev, Mq) if want_posterior else None
+        var_o = _empty(dev, Mq) if want_posterior else None
+        rc = _lib.lib.scaml_target_acqf_batched_f64(_ptr(mu), _ptr(var), _ptr(cov), _ptr(group), _ptr(Xq), _ptr(w), _ptr(active), _ptr(Xt),
+                                                    _ptr(theta), _ptr(L), _ptr(Linv_diag), _ptr(alpha), _ptr(n_points), _ptr(m_all), _ptr(s_all),
+                                                    _ptr(info), _ptr(acqf_param), Mq, G, n_max, T, D, int(kind), int(acqf), _ptr(value), _ptr(grad),
+                                                    _ptr(mu_o), _ptr(var_o), _stream_handle())
+    _lib.check_rc(rc, "scaml_target_acqf_batched_f64")
+    return dict(value=value, grad=grad, mu=mu_o, var=var_o)
+
+
 def mll_backward_workspace(T: int, N: int, D: int, device) -> Dict[str, torch.Tensor]:
     """Reusable buffers of ``mll_backward`` for a (T, N, D) stack: the explicit inverse factors (T N^2 doubles) and
     the per-tile partial sums.  An optimiser loop allocates them once (scaml_mll_backward_workspace_doubles)."""

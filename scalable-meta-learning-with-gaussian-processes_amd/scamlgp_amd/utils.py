@@ -417,3 +417,90 @@ class ExpectedImprovement:
         cdf = 0.5 * (1.0 + torch.erf(u / math.sqrt(2.0)))
         dsig = torch.where(var > 1e-9, 0.5 / sigma, torch.zeros_like(sigma)).unsqueeze(-1) * dvar
         return sigma * (pdf + u * cdf), -cdf.unsqueeze(-1) * dmu + pdf.unsqueeze(-1) * dsig
+
+
+class StudiesAcquisition:
+    """The acquisition functions of S ScaMLGP models on ONE source stack, evaluated together: ``value_and_grad(X, group)`` is two
+    library launches whatever S is -- the grouped GRAD source pass (``ops.source_posteriors_grad_grouped``: a query point's covariance
+    block is taken against ITS study's training inputs) and the batched target acquisition (``ops.target_acqf_batched``: weighted
+    task sums, Knq, the solve against the study's cached factor of Knn, posterior, gradient, UCB / EI) -- where each model's own
+    ``af.value_and_grad`` is about fifteen.  Nothing is read back and every status stays on the device, so an evaluation can be
+    captured into a HIP graph (``bo.GraphedAcquisition``).
+
+    ``afs``: one ``UpperConfidenceBound`` or ``ExpectedImprovement`` per study, all of the same class, on models that share the source
+    stack and the kernel family, ``supports_posterior_grad()`` and are no fantasy models.  Built once per parameter state: the per-study
+    arrays (pruned weights and mask, theta, training inputs, standardiser, the factor ``_target_factor()`` -- computed through the
+    model's own posterior path where it is absent --, alpha, beta or best_f) are packed from the models' caches here, padded to the
+    largest n.  The models' ``_train_VA()`` tensors are passed by address (10 MB each at configs[4]: no padded copy); this object
+    keeps them alive."""
+
+    def __init__(self, afs: Sequence[Union[UpperConfidenceBound, ExpectedImprovement]]):
+        afs = list(afs)
+        if not afs:
+            raise ValueError("StudiesAcquisition needs at least one acquisition function")
+        kinds = {type(a) for a in afs}
+        if len(kinds) != 1 or not kinds <= {UpperConfidenceBound, ExpectedImprovement}:
+            raise TypeError("the acquisition functions must all be UpperConfidenceBound or all ExpectedImprovement")
+        self.acqf = ops.ACQF_UCB if isinstance(afs[0], UpperConfidenceBound) else ops.ACQF_EI
+        models = [a.model for a in afs]
+        m0 = models[0]
+        for m in models:
+            if m._stack is not m0._stack or m.kind != m0.kind or m.T != m0.T:
+                raise ValueError("the studies' models must share one source stack and one kernel family")
+            if m._shard is not None:
+                raise NotImplementedError("the batched acquisition is not implemented for a task-sharded source stack (shard=True)")
+            if m.num_fantasies is not None or not m.supports_posterior_grad():
+                raise NotImplementedError("the batched acquisition takes ordinary models with 1 <= n <= 96 training points and D <= 15")
+        self.models, self.kind, self.device = models, m0.kind, m0.device
+        st = m0._stack
+        G, D, dev = len(models), st.D, m0.device
+        ns = [m.n for m in models]
+        n_max, nbm = max(ns), (max(ns) + 15) // 16
+        self.G, self.D, self.n_max = G, D, n_max
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        self.w, self.active = z(G, st.T), torch.zeros(G, st.T, dtype=torch.uint8, device=dev)
+        self.Xt, self.theta = z(G, n_max, D), z(G, D + 2)
+        self.L, self.Linv_diag, self.alpha = z(G, n_max, n_max), z(G, nbm, 16, 16), z(G, n_max)
+        self.info = torch.zeros(G, dtype=torch.int32, device=dev)
+        self._VA = []
+        for g, (af, m) in enumerate(zip(afs, models)):
+            n = m.n
+            f = m._target_factor()
+            if f is None:   # (present after the study's scoring pass; otherwise the model's own path computes and caches it)
+                m.posterior_with_grad(m.train_X[:1])
+                f = m._target_factor()
+            w_full, act = m._active_tasks()
+            self.w[g], self.active[g] = w_full, act.to(torch.uint8)
+            self.Xt[g, :n], self.theta[g] = m.train_X, m.theta
+            self.L[g, :n, :n], self.Linv_diag[g, :(n + 15) // 16], self.alpha[g, :n] = f["L"][0], f["Linv_diag"][0], f["alpha"][0]
+            self.info[g] = f["info"][0]
+            self._VA.append(m._train_VA().contiguous())
+        host = lambda vals, dt: torch.tensor(vals, dtype=dt).to(dev)   # noqa: E731
+        self.n_points = host(ns, torch.int32)
+        self.m_all = host([m._m_all_f for m in models], torch.float64)
+        self.s_all = host([m._s_all_f for m in models], torch.float64)
+        self.acqf_param = host([float(a.beta if self.acqf == ops.ACQF_UCB else a.best_f) for a in afs], torch.float64)
+        self.VA_tab = host([v.data_ptr() for v in self._VA], torch.int64)
+
+    def group_of(self, counts: Sequence[int]) -> torch.Tensor:
+        """(sum counts,) int32 on the device: study s's index ``counts[s]`` times -- the ``group`` of a batch that lists the studies'
+        points one study after the other."""
+        return torch.repeat_interleave(torch.arange(self.G, dtype=torch.int32), torch.as_tensor(list(counts))).to(self.device)
+
+    def evaluate(self, X: torch.Tensor, group: torch.Tensor, want_grad: bool = True, want_posterior: bool = False) -> Dict[str, torch.Tensor]:
+        """dict(value (Mq,), grad (Mq, D) or None, mu, var (Mq,) or None) at X (Mq, D), point q scored by study ``group[q]`` (int32, on the
+        device; a negative entry is a padding row and gives zeros)."""
+        Xq = torch.as_tensor(X, dtype=torch.float64).reshape(-1, self.D).to(self.device).contiguous()
+        st, f = self.models[0]._stack, self.models[0]._stack.fit
+        g = ops.source_posteriors_grad_grouped(Xq, group, self.Xt, self.n_points, self.VA_tab, st.X, st.theta, st.kind, f["Linv"], f["alpha"],
+                                               st.y_mean, st.y_std, st.n_points)
+        return ops.target_acqf_batched(g["mu"], g["var"], g["cov"], group, Xq, self.w, self.active, self.Xt, self.theta, self.L, self.Linv_diag,
+                                       self.alpha, self.n_points, self.m_all, self.s_all, self.info, self.acqf_param, self.acqf, self.kind,
+                                       want_grad=want_grad, want_posterior=want_posterior)
+
+    def value_and_grad(self, X: torch.Tensor, group: torch.Tensor):
+        out = self.evaluate(X, group)
+        return out["value"], out["grad"]
+
+    def value(self, X: torch.Tensor, group: torch.Tensor) -> torch.Tensor:
+        return self.evaluate(X, group, want_grad=False)["value"]

@@ -29,6 +29,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--sizes", default="1,8,32,64")
 ap.add_argument("--steps", type=int, default=3, help="timed steps per size (n ends at 80)")
 ap.add_argument("--out", default=None)
+ap.add_argument("--suggest", action="store_true", help="time suggest(): suggest_mode='lockstep' against the default, interleaved in one process")
 args = ap.parse_args()
 
 T, N, D, N_END, RESTARTS = 32, 512, 6, 80, 2
@@ -63,6 +64,55 @@ stack.set_theta(torch.from_numpy(np.concatenate([0.6 + 0.8 * rng.uniform(size=(T
 stack.refresh()
 gps = {tid: M.SourceGP(stack, i) for i, tid in enumerate(stack.task_ids)}
 
+
+def suggest_table():
+    """Lock-step against study-by-study suggest(): two ScaMLGPBOStudies on the same data (both are told the sequential side's points),
+    timed alternately step by step; n = 78 .. 80 over the three timed steps."""
+    say(f"# suggest() of S studies, T = {T}, N = {N}, D = {D}, UCB, 10 starts per study, af_max_iter 50; ms, median of {args.steps} steps (n = "
+        f"{N_END - args.steps + 1} .. {N_END}); spread = min .. max of the sequential suggest over those steps")
+    say(f"# {'S':>3} {'side':>10} {'suggest':>9} {'evals':>6} {'ms/eval':>8} {'step':>9}   seq/lock (suggest)   seq spread")
+    for S in [int(v) for v in args.sizes.split(",")]:
+        steps = args.steps + 1
+        n0 = N_END - steps
+        seeds = list(range(100, 100 + S))
+        sides = {"lockstep": ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, suggest_mode="lockstep", **KW),
+                 "sequential": ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, **KW)}
+        for side in sides.values():
+            for s in range(S):
+                g = torch.Generator().manual_seed(seeds[s])
+                X0 = torch.rand(n0, D, dtype=torch.float64, generator=g)
+                side[s].record(X0, [obj(x) for x in X0])
+            utils.fit_targets_batched([st.model for st in side.studies], RESTARTS, rng=side.fit_gens)
+        rows = {k: [] for k in sides}
+        for step in range(steps):
+            t_l, _ = timed(sides["lockstep"].suggest)
+            info = dict(sides["lockstep"].last_suggest_info)
+            t_s, X = timed(sides["sequential"].suggest)
+            ys = [obj(x) for x in X]
+            t_rep = {}
+            for k, side in sides.items():
+                t_rep[k], _ = timed(lambda: side.report(X, ys))
+            rows["lockstep"].append((t_l, t_rep["lockstep"], info["n_eval"], info["eval_seconds"]))
+            rows["sequential"].append((t_s, t_rep["sequential"], 0, 0.0))
+        med = {k: [1e3 * statistics.median(r[i] for r in v[1:]) for i in range(2)] for k, v in rows.items()}
+        ne = statistics.median(r[2] for r in rows["lockstep"][1:])
+        per_eval = statistics.median(1e3 * r[3] / max(r[2], 1) for r in rows["lockstep"][1:])   # the objective calls alone: copy in, replay, copy out
+        seq = [1e3 * r[0] for r in rows["sequential"][1:]]
+        for k in ("lockstep", "sequential"):
+            if k == "lockstep":
+                tail = f"   {med['sequential'][0] / med[k][0]:8.2f}x          {min(seq):.1f} .. {max(seq):.1f}"
+                say(f"  {S:>3} {k:>10} {med[k][0]:9.1f} {ne:6.0f} {per_eval:8.2f} {sum(med[k]):9.1f}{tail}")
+            else:
+                say(f"  {S:>3} {k:>10} {med[k][0]:9.1f} {'-':>6} {'-':>8} {sum(med[k]):9.1f}")
+        say(f"#     n = {sides['lockstep'][0].model.n}; gap {med['sequential'][0] - med['lockstep'][0]:.1f} ms against a sequential spread of {max(seq) - min(seq):.1f} ms")
+
+
+if args.suggest:
+    suggest_table()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 say(f"# BO step of S studies, T = {T}, N = {N}, D = {D}, n -> {N_END}, {RESTARTS} restarts (B = {1 + RESTARTS} starts per study), UCB; ms per step, median of "
     f"{args.steps} steps")
 say("# batched = ScaMLGPBOStudies (one refit launch for all studies); sequential = S ScaMLGPBOLoops one after the other")
