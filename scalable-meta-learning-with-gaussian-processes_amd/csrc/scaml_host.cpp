@@ -789,12 +789,19 @@ static_assert(scaml::TARGET_FIT_LDS_LIMIT == kLdsLimit, "the matrix-core rule an
 bool target_fit_use_mfma(int n, int T, int D) {
   return g_dev.target_fit_path.load(kRelaxed) == 0 && scaml::target_fit_mfma_shape(n, T, D, kTargetFitThreads / 64);
 }
-int target_fit_launch(scaml::TargetFitParams& p, void* stream) {
+// Argument checks of both launchers.  The order that can be observed is kept by both: every SCAML_E_BADARG check (the entry point's,
+// the filler's, the launcher's own, these) comes before every SCAML_E_TOOLARGE check (D here, then the launcher's sizes), and an empty
+// launch is SCAML_OK only after all of them.
+int target_fit_check(const scaml::TargetFitParams& p) {
   if (p.B < 0 || p.n < 1 || p.T < 1 || p.D < 1) return SCAML_E_BADARG;
   if (!p.means_t || !p.covs_p || !p.X || !p.y || !p.z || !p.value || !p.info) return SCAML_E_BADARG;
   if (!valid_kind(p.kind)) return SCAML_E_BADARG;
-  if (!(p.s_all > 0.0)) return SCAML_E_BADARG;
   if (p.D > scaml::TARGET_FIT_DMAX) return SCAML_E_TOOLARGE;
+  return SCAML_OK;
+}
+int target_fit_launch(scaml::TargetFitParams& p, void* stream) {
+  if (!(p.s_all > 0.0)) return SCAML_E_BADARG;
+  if (const int rc = target_fit_check(p)) return rc;
   p.use_mfma = target_fit_use_mfma(p.n, p.T, p.D) ? 1 : 0;
   const size_t lds = target_fit_lds_bytes(p.n, p.T, p.D, p.use_mfma != 0);
   if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
@@ -802,6 +809,33 @@ int target_fit_launch(scaml::TargetFitParams& p, void* stream) {
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
   return launch(m->tgt_fit, dim3((unsigned)p.B), kTargetFitThreads, lds, stream, "target_fit", p);
+}
+// Fillers of the kernel arguments both pairs of entry points share (the single problem's m_all / s_all, the batch's arrays and S are
+// the caller's): evaluation mode, value + gradient at z ...
+int target_fill_mll(scaml::TargetFitParams& p, const double* means_t, const double* covs_packed, const double* X, const double* y,
+                    const double* spec_host, const double* z, int B, int n, int T, int D, int kind, double* value, double* grad,
+                    int32_t* info, double* jitter_used) {
+  if (!spec_host || !grad) return SCAML_E_BADARG;
+  if (!scaml::target_spec_from_host(spec_host, p.spec)) return SCAML_E_BADARG;
+  p.means_t = means_t; p.covs_p = covs_packed; p.X = X; p.y = y;
+  p.z = const_cast<double*>(z); p.value = value; p.grad = grad; p.info = info; p.jitter = jitter_used;
+  p.B = B; p.n = n; p.T = T; p.D = D; p.kind = kind; p.mode = 0; p.history = 1; p.max_ls = 0;
+  return SCAML_OK;
+}
+// ... and optimiser mode, L-BFGS from z (`workspace_needed`: the entry point's own scaml_target_fit*_workspace_doubles)
+int target_fill_fit(scaml::TargetFitParams& p, const double* means_t, const double* covs_packed, const double* X, const double* y,
+                    const double* spec_host, double* z, int B, int n, int T, int D, int kind, int max_iter, int history, double gtol,
+                    double ftol, double* value, int32_t* info, double* jitter_used, int32_t* stats, double* workspace,
+                    long long workspace_doubles, long long workspace_needed) {
+  if (!spec_host || !workspace) return SCAML_E_BADARG;
+  if (max_iter < 0 || history < 1 || history > scaml::TARGET_FIT_HMAX) return SCAML_E_BADARG;
+  if (workspace_doubles < workspace_needed) return SCAML_E_BADARG;
+  if (!scaml::target_spec_from_host(spec_host, p.spec)) return SCAML_E_BADARG;
+  p.means_t = means_t; p.covs_p = covs_packed; p.X = X; p.y = y;
+  p.z = z; p.value = value; p.grad = nullptr; p.info = info; p.jitter = jitter_used; p.workspace = workspace; p.stats = stats;
+  p.B = B; p.n = n; p.T = T; p.D = D; p.kind = kind; p.mode = 1; p.max_iter = max_iter; p.history = history; p.max_ls = 20;
+  p.gtol = gtol; p.ftol = ftol;
+  return SCAML_OK;
 }
 }  // namespace
 
@@ -822,41 +856,31 @@ long long scaml_target_fit_workspace_doubles(int B, int T, int D, int history) {
 int scaml_target_mll_f64(const double* means_t, const double* covs_packed, const double* X, const double* y, double m_all, double s_all,
                          const double* spec_host, const double* z, int B, int n, int T, int D, int kind, double* value, double* grad,
                          int32_t* info, double* jitter_used, void* stream) {
-  if (!spec_host || !grad) return SCAML_E_BADARG;
   scaml::TargetFitParams p{};
-  p.means_t = means_t; p.covs_p = covs_packed; p.X = X; p.y = y; p.m_all = m_all; p.s_all = s_all;
-  if (!scaml::target_spec_from_host(spec_host, p.spec)) return SCAML_E_BADARG;
-  p.z = const_cast<double*>(z); p.value = value; p.grad = grad; p.info = info; p.jitter = jitter_used;
-  p.B = B; p.n = n; p.T = T; p.D = D; p.kind = kind; p.mode = 0; p.history = 1; p.max_ls = 0;
-  return target_fit_launch(p, stream);
+  p.m_all = m_all; p.s_all = s_all;
+  const int rc = target_fill_mll(p, means_t, covs_packed, X, y, spec_host, z, B, n, T, D, kind, value, grad, info, jitter_used);
+  return rc ? rc : target_fit_launch(p, stream);
 }
 
 int scaml_target_fit_f64(const double* means_t, const double* covs_packed, const double* X, const double* y, double m_all, double s_all,
                          const double* spec_host, double* z, int B, int n, int T, int D, int kind, int max_iter, int history, double gtol,
                          double ftol, double* value, int32_t* info, double* jitter_used, int32_t* stats, double* workspace,
                          long long workspace_doubles, void* stream) {
-  if (!spec_host || !workspace) return SCAML_E_BADARG;
-  if (max_iter < 0 || history < 1 || history > scaml::TARGET_FIT_HMAX) return SCAML_E_BADARG;
-  if (workspace_doubles < scaml_target_fit_workspace_doubles(B, T, D, history)) return SCAML_E_BADARG;
   scaml::TargetFitParams p{};
-  p.means_t = means_t; p.covs_p = covs_packed; p.X = X; p.y = y; p.m_all = m_all; p.s_all = s_all;
-  if (!scaml::target_spec_from_host(spec_host, p.spec)) return SCAML_E_BADARG;
-  p.z = z; p.value = value; p.grad = nullptr; p.info = info; p.jitter = jitter_used; p.workspace = workspace; p.stats = stats;
-  p.B = B; p.n = n; p.T = T; p.D = D; p.kind = kind; p.mode = 1; p.max_iter = max_iter; p.history = history; p.max_ls = 20;
-  p.gtol = gtol; p.ftol = ftol;
-  return target_fit_launch(p, stream);
+  p.m_all = m_all; p.s_all = s_all;
+  const int rc = target_fill_fit(p, means_t, covs_packed, X, y, spec_host, z, B, n, T, D, kind, max_iter, history, gtol, ftol, value, info,
+                                 jitter_used, stats, workspace, workspace_doubles, scaml_target_fit_workspace_doubles(B, T, D, history));
+  return rc ? rc : target_fit_launch(p, stream);
 }
 
 // ---- (8b) the same objective and refit over S problems x B start points in one launch ---------------------------------------
 namespace {
-// `p.base` filled by the caller except use_mfma; S, the per-problem arrays and the limits are checked here
+// `p.base` filled by the caller except use_mfma; S, the per-problem arrays and the limits are checked here.  There is no host value
+// of s_all to check; n_max against scaml_target_fit_max_n comes before the LDS size (which is a loop over 1 .. n_max).
 int target_fit_batched_launch(scaml::TargetFitBatchParams& bp, void* stream) {
   scaml::TargetFitParams& p = bp.base;
-  if (bp.S < 0 || p.B < 0 || p.n < 1 || p.T < 1 || p.D < 1) return SCAML_E_BADARG;
-  if (!p.means_t || !p.covs_p || !p.X || !p.y || !p.z || !p.value || !p.info) return SCAML_E_BADARG;
-  if (!bp.n_points || !bp.m_all || !bp.s_all) return SCAML_E_BADARG;
-  if (!valid_kind(p.kind)) return SCAML_E_BADARG;
-  if (p.D > scaml::TARGET_FIT_DMAX) return SCAML_E_TOOLARGE;
+  if (bp.S < 0 || !bp.n_points || !bp.m_all || !bp.s_all) return SCAML_E_BADARG;
+  if (const int rc = target_fit_check(p)) return rc;
   if (p.n > scaml_target_fit_max_n(p.T, p.D)) return SCAML_E_TOOLARGE;
   if ((long long)bp.S * p.B > 0x7fffffffLL) return SCAML_E_TOOLARGE;
   p.use_mfma = g_dev.target_fit_path.load(kRelaxed) == 0 ? 1 : 0;
@@ -877,34 +901,21 @@ long long scaml_target_fit_batched_workspace_doubles(int S, int B, int T, int D,
 int scaml_target_mll_batched_f64(const double* means_t, const double* covs_packed, const double* X, const double* y, const int32_t* n_points,
                                  const double* m_all, const double* s_all, const double* spec_host, const double* z, int S, int B, int n_max,
                                  int T, int D, int kind, double* value, double* grad, int32_t* info, double* jitter_used, void* stream) {
-  if (!spec_host || !grad) return SCAML_E_BADARG;
   scaml::TargetFitBatchParams bp{};
-  scaml::TargetFitParams& p = bp.base;
-  p.means_t = means_t; p.covs_p = covs_packed; p.X = X; p.y = y;
   bp.n_points = n_points; bp.m_all = m_all; bp.s_all = s_all; bp.S = S;
-  if (!scaml::target_spec_from_host(spec_host, p.spec)) return SCAML_E_BADARG;
-  p.z = const_cast<double*>(z); p.value = value; p.grad = grad; p.info = info; p.jitter = jitter_used;
-  p.B = B; p.n = n_max; p.T = T; p.D = D; p.kind = kind; p.mode = 0; p.history = 1; p.max_ls = 0;
-  return target_fit_batched_launch(bp, stream);
+  const int rc = target_fill_mll(bp.base, means_t, covs_packed, X, y, spec_host, z, B, n_max, T, D, kind, value, grad, info, jitter_used);
+  return rc ? rc : target_fit_batched_launch(bp, stream);
 }
 
 int scaml_target_fit_batched_f64(const double* means_t, const double* covs_packed, const double* X, const double* y, const int32_t* n_points,
                                  const double* m_all, const double* s_all, const double* spec_host, double* z, int S, int B, int n_max, int T,
                                  int D, int kind, int max_iter, int history, double gtol, double ftol, double* value, int32_t* info,
                                  double* jitter_used, int32_t* stats, double* workspace, long long workspace_doubles, void* stream) {
-  if (!spec_host || !workspace) return SCAML_E_BADARG;
-  if (S < 0 || B < 0) return SCAML_E_BADARG;
-  if (max_iter < 0 || history < 1 || history > scaml::TARGET_FIT_HMAX) return SCAML_E_BADARG;
-  if (workspace_doubles < scaml_target_fit_batched_workspace_doubles(S, B, T, D, history)) return SCAML_E_BADARG;
   scaml::TargetFitBatchParams bp{};
-  scaml::TargetFitParams& p = bp.base;
-  p.means_t = means_t; p.covs_p = covs_packed; p.X = X; p.y = y;
   bp.n_points = n_points; bp.m_all = m_all; bp.s_all = s_all; bp.S = S;
-  if (!scaml::target_spec_from_host(spec_host, p.spec)) return SCAML_E_BADARG;
-  p.z = z; p.value = value; p.grad = nullptr; p.info = info; p.jitter = jitter_used; p.workspace = workspace; p.stats = stats;
-  p.B = B; p.n = n_max; p.T = T; p.D = D; p.kind = kind; p.mode = 1; p.max_iter = max_iter; p.history = history; p.max_ls = 20;
-  p.gtol = gtol; p.ftol = ftol;
-  return target_fit_batched_launch(bp, stream);
+  const int rc = target_fill_fit(bp.base, means_t, covs_packed, X, y, spec_host, z, B, n_max, T, D, kind, max_iter, history, gtol, ftol, value, info,
+                                 jitter_used, stats, workspace, workspace_doubles, scaml_target_fit_batched_workspace_doubles(S, B, T, D, history));
+  return rc ? rc : target_fit_batched_launch(bp, stream);
 }
 
 // ---- (9) source stack: the whole hyper-parameter fit as rounds of { fit, MLL gradient, optimiser step } (csrc/gp_stack_fit.hip) ----

@@ -30,7 +30,7 @@ import torch
 
 from . import hyper
 from .model import ScaMLGP, SourceGP
-from .utils import ExpectedImprovement, UpperConfidenceBound, fit_targets_batched, optimize_marginal_likelihood
+from .utils import ExpectedImprovement, UpperConfidenceBound, capture_graph, fit_targets_batched, optimize_marginal_likelihood
 
 
 class OptimizerNotReady(RuntimeError):
@@ -51,15 +51,8 @@ class GraphedAcquisition:
     def __init__(self, af: Callable[[torch.Tensor], torch.Tensor], batch: int, dim: int, device: torch.device):
         self.af, self.batch = af, batch
         self.x = torch.zeros(batch, dim, dtype=torch.float64, device=device)
-        side = torch.cuda.Stream(device=device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):          # warm-up off the default stream (allocator state, lazy module load)
-            for _ in range(2):
-                af(self.x)
-        torch.cuda.current_stream(device).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out = af(self.x)   # a tensor, or a tuple of tensors (value, gradient)
+        # a tensor, or a tuple of tensors (value, gradient); a capture that fails raises (the callers have no eager twin to fall back on)
+        self.graph, self.out = capture_graph(lambda: af(self.x), device, warmup=2)
 
     def __call__(self, X: torch.Tensor):
         if X.shape[0] != self.batch:

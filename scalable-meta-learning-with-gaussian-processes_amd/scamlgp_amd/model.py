@@ -471,6 +471,24 @@ class TargetPosterior:
         return (mean + (L @ eps.unsqueeze(-1)).squeeze(-1)).unsqueeze(-1)
 
 
+class _StateCache:
+    """Values computed from parameter tensors, kept per name until one of those tensors is replaced or modified in place.  An entry
+    holds (tensor, version) pairs: the held references keep the objects alive, so identity cannot be faked by a recycled address."""
+
+    def __init__(self) -> None:
+        self._entries: dict = {}
+
+    def get(self, name: str, tensors):
+        """The value ``put`` under ``name`` if ``tensors`` are the very tensors it was computed from, unmodified since; else None."""
+        held, value = self._entries.get(name, ((), None))
+        same = len(held) == len(tensors) and all(h is t and v == t._version for (h, v), t in zip(held, tensors))
+        return value if same else None
+
+    def put(self, name: str, tensors, value):
+        self._entries[name] = (tuple((t, t._version) for t in tensors), value)
+        return value
+
+
 class ScaMLGP:
     """Scalable meta-learning GP (scamlgp/model.py:218-384): target prior
     N(sum_i w_i mu_i, sum_i w_i^2 Sigma_i + k_t) over the posteriors of the source stack.
@@ -516,6 +534,8 @@ class ScaMLGP:
         self.outcome_transform = _OutcomeTransform(self.m_all, self.s_all) if self.has_transform else None
         self.train_inputs = (self.train_X,)
         self.train_targets = ((self.train_Y - self.m_all) / self.s_all).squeeze(-1)
+        self._cache = _StateCache()                       # per parameter state: theta, pruned weights, training prior, Knn's factor
+        self._stds_all = self._VA = self._tprob = None    # fixed for the model's lifetime, computed on first use
         # cached source posteriors at the target inputs, all tasks, no pruning (scamlgp/model.py:279-289)
         if self.n > 0:
             # (V of the training points: computed once here, reused by every later posterior / gradient call of this model)
@@ -606,23 +626,14 @@ class ScaMLGP:
         cov, lik = self.covar_module, self.likelihood
         return (cov.base_kernel.raw_lengthscale, cov.raw_outputscale, lik.raw_noise)
 
-    @staticmethod
-    def _same_tensors(held, now) -> bool:
-        """True if `now` are the very tensors `held` was computed from, unmodified since ((tensor, version) pairs: the held
-        references keep the objects alive, so identity cannot be faked by a recycled address)."""
-        return held is not None and len(held) == len(now) and all(h is t and v == t._version for (h, v), t in zip(held, now))
-
     @property
     def theta(self) -> torch.Tensor:
         """Constrained target hyper-parameters [lengthscales, outputscale, noise].  Cached per parameter state: an acquisition
         pass asks for them (and for the pruned weights below) on every call, each time a dozen element-wise launches for the
         same numbers -- a quarter of a scoring pass at configs[4] was such glue."""
         now = self._param_tensors()
-        c = getattr(self, "_theta_cache", None)
-        if c is None or not self._same_tensors(c[0], now):
-            c = (tuple((t, t._version) for t in now), self.spec.to_theta(self.raw_theta))
-            self._theta_cache = c
-        return c[1]
+        theta = self._cache.get("theta", now)
+        return theta if theta is not None else self._cache.put("theta", now, self.spec.to_theta(self.raw_theta))
 
     def train(self):
         self.training = True
@@ -640,18 +651,17 @@ class ScaMLGP:
 
     # -- model ------------------------------------------------------------------------------
     def _std_source_stds(self) -> torch.Tensor:
-        if getattr(self, "_stds_all", None) is None:
+        if self._stds_all is None:
             self._stds_all = sdist.gather_task_axis(self._stack.y_std[self._idx], self._shard)
         return self._stds_all
 
     def _active_tasks(self):
         """Pruned weights as vectors over this rank's stack: w_full (T_stack,), active mask (bool)
         (scamlgp/model.py:365-372; the mask is decided on ALL T weights, each rank then takes its slice)."""
-        w = self.weights
-        c = getattr(self, "_active_cache", None)
-        if c is not None and self._same_tensors(c[0], (w,)):
-            return c[1], c[2]      # (same weights as last time: see `theta`)
-        held = ((w, w._version),)
+        w = key = self.weights
+        c = self._cache.get("active", (key,))
+        if c is not None:
+            return c      # (same weights as last time: see `theta`)
         mask = significant_weights_mask(w, self._std_source_stds(), self._weight_pruning_threshold)
         if self._shard is not None:
             w, mask = w[self._shard.local], mask[self._shard.local]
@@ -660,8 +670,7 @@ class ScaMLGP:
         idx = self._idx_dev
         w_full = torch.zeros(self._stack.T, dtype=torch.float64, device=self.device).scatter(0, idx, w)
         active = torch.zeros(self._stack.T, dtype=torch.bool, device=self.device).scatter(0, idx, mask)
-        self._active_cache = (held, w_full, active)
-        return w_full, active
+        return self._cache.put("active", (key,), (w_full, active))
 
     def _source_prior(self, x: torch.Tensor, cov_first: int, train_first: bool = False):
         """sum_i w_i mu_i(x) (M,), sum_i w_i^2 Sigma_i (cov_first, M), sum_i w_i^2 var_i (M,) over the significant tasks
@@ -722,7 +731,7 @@ class ScaMLGP:
     def target_problem(self) -> Optional[ops.TargetFitProblem]:
         """The training set in the layouts of the library's target-fit kernel (built once; None if the kernel does not take
         this shape -- more target points than its LDS holds, D > 16 -- and the torch objective ``mll`` is all there is)."""
-        if getattr(self, "_tprob", None) is None:
+        if self._tprob is None:
             if self.num_fantasies is not None:
                 raise NotImplementedError("a fantasy model is not fitted: it keeps its parent's hyper-parameters")
             if self.n < 1 or not ops.TargetFitProblem.supported(self.n, self.T, self._stack.D):
@@ -767,7 +776,7 @@ class ScaMLGP:
 
     def _train_VA(self) -> torch.Tensor:
         """V = L^-1 K(X_t, train_X) of every source task (T, N, n): fixed for the model's lifetime (sources and training inputs are)."""
-        if getattr(self, "_VA", None) is None:
+        if self._VA is None:
             st, f = self._stack, self._stack.fit
             self._VA = ops.source_posteriors(self.train_X, st.X, st.theta, st.kind, f["L"], f["Linv_diag"], f["alpha"], st.y_mean, st.y_std,
                                              n_points=st.n_points, want_var=False, keep_V=True, Linv=f["Linv"])["V"]
@@ -776,23 +785,17 @@ class ScaMLGP:
     def _train_prior(self):
         """The weighted source sums at the training inputs (mu_s (n,), Sigma_s (n, n), var_s (n,)): per weight state."""
         w = self.weights
-        c = getattr(self, "_train_prior_cache", None)
-        if c is None or not self._same_tensors(c[0], (w,)):
-            c = (((w, w._version),), self._source_prior(self.train_X, self.n))
-            self._train_prior_cache = c
-        return c[1]
+        c = self._cache.get("train_prior", (w,))
+        return c if c is not None else self._cache.put("train_prior", (w,), self._source_prior(self.train_X, self.n))
 
     def _target_factor(self):
         """The jittered Cholesky of the target GP's training block Knn (+ alpha) at the current weights / hyper-parameters, or None
         if it has not been computed for this parameter state yet: it does not depend on the query points, and an acquisition
         optimisation scores hundreds of query batches against one parameter state."""
-        c = getattr(self, "_factor_cache", None)
-        now = (self.weights,) + self._param_tensors()
-        return c[1] if c is not None and self._same_tensors(c[0], now) else None
+        return self._cache.get("factor", (self.weights,) + self._param_tensors())
 
     def _keep_target_factor(self, factor) -> None:
-        now = (self.weights,) + self._param_tensors()
-        self._factor_cache = (tuple((t, t._version) for t in now), factor)
+        self._cache.put("factor", (self.weights,) + self._param_tensors(), factor)
 
     def posterior_with_grad(self, X: torch.Tensor):
         """Target posterior mean / variance at X (Mq, D) in original units AND their gradients w.r.t. X: (mu (Mq,), var (Mq,),
@@ -885,17 +888,21 @@ class ScaMLGP:
         mu = self.m_all + self.s_all * (blk["mean_q"] + blk["alpha"].transpose(0, 1) @ blk["Knq"])   # (F, M)
         mu = torch.where(blk["info"][0] > 0, torch.full_like(mu, float("nan")), mu)
         var = blk["var"].unsqueeze(0).expand(F, M)
+        return TargetPosterior(mu, var, lambda: self._full_cov(Xq, observation_noise).unsqueeze(0).expand(F, M, M))
 
-        def full_cov() -> torch.Tensor:
-            _, cj, _, th = self._joint(Xq, full=True)
+    def _full_cov(self, Xq: torch.Tensor, observation_noise: bool) -> torch.Tensor:
+        """The joint (M, M) posterior covariance at Xq in original units: the Schur complement of the training block in the joint
+        prior over cat(train_X, Xq) (a second source launch with the full query block)."""
+        n = self.n
+        _, cj, _, th = self._joint(Xq, full=True)
+        S = cj[n:, n:]
+        if n > 0:
             Lc2 = psd_safe_cholesky(cj[:n, :n] + th[-1] * torch.eye(n, dtype=torch.float64, device=self.device))
             V2 = torch.linalg.solve_triangular(Lc2, cj[:n, n:], upper=False)
-            S = cj[n:, n:] - V2.transpose(0, 1) @ V2
-            if observation_noise:
-                S = S + th[-1] * torch.eye(M, dtype=torch.float64, device=self.device)
-            return (self.s_all ** 2 * S).unsqueeze(0).expand(F, M, M)
-
-        return TargetPosterior(mu, var, full_cov)
+            S = S - V2.transpose(0, 1) @ V2
+        if observation_noise:
+            S = S + th[-1] * torch.eye(S.shape[0], dtype=torch.float64, device=self.device)
+        return self.s_all ** 2 * S
 
     def posterior(self, X: torch.Tensor, observation_noise: bool = False) -> TargetPosterior:
         """Target posterior at X (M, D) in original units (A10).  The source prior is evaluated ONCE at
@@ -935,17 +942,7 @@ class ScaMLGP:
                 var = var + theta[-1]
             mu_o, var_o = self.m_all + self.s_all * mu, self.s_all ** 2 * var
 
-        def full_cov() -> torch.Tensor:
-            _, cj, _, th = self._joint(Xq, full=True)
-            S = cj[n:, n:]
-            if n > 0:
-                Lc2 = psd_safe_cholesky(cj[:n, :n] + th[-1] * torch.eye(n, dtype=torch.float64, device=self.device))
-                V2 = torch.linalg.solve_triangular(Lc2, cj[:n, n:], upper=False)
-                S = S - V2.transpose(0, 1) @ V2
-            if observation_noise:
-                S = S + th[-1] * torch.eye(S.shape[0], dtype=torch.float64, device=self.device)
-            return self.s_all ** 2 * S
-
+        full_cov = lambda: self._full_cov(Xq, observation_noise)   # noqa: E731
         if batch is not None:
             # botorch's batch_shape x q x d convention (scamlgp/model.py:359-384 keeps the batch dimensions): mean / variance
             # (*batch, q, 1), covariance (*batch, q, q) -- one joint per batch element, NOT one joint over all points.  q = 1 (what

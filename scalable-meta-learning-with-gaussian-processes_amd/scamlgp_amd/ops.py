@@ -905,25 +905,51 @@ class TargetFitProblem:
     def supported(n: int, T: int, D: int) -> bool:
         return D <= _lib.lib.scaml_target_fit_max_d() and 1 <= n <= _lib.lib.scaml_target_fit_max_n(T, D)
 
+    _symbol = "scaml_target_%s"   # (+ "_f64" / "_workspace_doubles"; "%s": mll or fit)
+
+    def _problem_args(self):
+        return (_ptr(self.means_t), _ptr(self.covs_p), _ptr(self.X), _ptr(self.y), self.m_all, self.s_all, self.spec_host)
+
+    def _dims(self):
+        """(leading shape of the results in front of B, the n the entry point takes)."""
+        return (), self.n
+
+
+def _target_launch(prob, z: torch.Tensor, fit=None) -> Dict[str, torch.Tensor]:
+    """The one call path of the four wrappers below.  ``prob``: a TargetFitProblem with z (B, P), or a TargetFitBatch with z (S, B, P).
+    ``fit`` None: value and gradient at z; ``fit`` = (max_iter, history, gtol, ftol): the L-BFGS runs from z, which is overwritten."""
+    lead, n = prob._dims()
+    B = z.shape[-2]
+    dev = prob.device
+    name = prob._symbol % ("mll" if fit is None else "fit")
+    with torch.cuda.device(dev):
+        value = _empty(dev, *lead, B)
+        info = _empty(dev, *lead, B, dtype=torch.int32)
+        jit = _empty(dev, *lead, B)
+        head = (*prob._problem_args(), _ptr(z), *lead, B, n, prob.T, prob.D, prob.kind)
+        if fit is None:
+            grad = _empty(dev, *lead, B, prob.P)
+            rc = getattr(_lib.lib, name + "_f64")(*head, _ptr(value), _ptr(grad), _ptr(info), _ptr(jit), _stream_handle())
+            out = dict(value=value, grad=grad, info=info, jitter=jit)
+        else:
+            max_iter, history, gtol, ftol = fit
+            stats = torch.zeros((*lead, B, 4), dtype=torch.int32, device=dev)
+            nws = int(getattr(_lib.lib, name + "_workspace_doubles")(*lead, B, prob.T, prob.D, history))
+            ws = _empty(dev, max(nws, 1))
+            rc = getattr(_lib.lib, name + "_f64")(*head, int(max_iter), int(history), float(gtol), float(ftol), _ptr(value), _ptr(info),
+                                                  _ptr(jit), _ptr(stats), _ptr(ws), nws, _stream_handle())
+            ws.record_stream(torch.cuda.current_stream(dev))
+            out = dict(z=z, value=value, info=info, jitter=jit, stats=stats)
+    _lib.check_rc(rc, name + "_f64")
+    return out
+
 
 def target_mll(prob: TargetFitProblem, z: torch.Tensor) -> Dict[str, torch.Tensor]:
     """mll(z_b) and d mll / d z_b for the rows of z (B, D + 2 + T) = [raw lengthscales, raw outputscale, raw noise, weights]:
     the ScaMLGP training objective of scamlgp/model.py:360-363 + utils.py:171-177 (priors included, divided by n) with its
     analytic gradient, ONE launch of scaml_target_mll_f64.  Returns dict(value (B,), grad (B, P), info (B,), jitter (B,));
     a matrix that is not positive definite even with jitter 1e-6 gives value NaN, info > 0 and a zero gradient."""
-    z = _check(z, "z", (z.shape[0], prob.P))
-    B = z.shape[0]
-    dev = prob.device
-    with torch.cuda.device(dev):
-        value = _empty(dev, B)
-        grad = _empty(dev, B, prob.P)
-        info = _empty(dev, B, dtype=torch.int32)
-        jit = _empty(dev, B)
-        rc = _lib.lib.scaml_target_mll_f64(_ptr(prob.means_t), _ptr(prob.covs_p), _ptr(prob.X), _ptr(prob.y), prob.m_all, prob.s_all,
-                                           prob.spec_host, _ptr(z), B, prob.n, prob.T, prob.D, prob.kind, _ptr(value), _ptr(grad),
-                                           _ptr(info), _ptr(jit), _stream_handle())
-    _lib.check_rc(rc, "scaml_target_mll_f64")
-    return dict(value=value, grad=grad, info=info, jitter=jit)
+    return _target_launch(prob, _check(z, "z", (z.shape[0], prob.P)))
 
 
 def target_fit(prob: TargetFitProblem, z0: torch.Tensor, max_iter: int = 200, history: int = 10, gtol: float = 1e-5,
@@ -931,23 +957,7 @@ def target_fit(prob: TargetFitProblem, z0: torch.Tensor, max_iter: int = 200, hi
     """Maximise mll from every row of z0 (B, P) on the device: ONE launch of scaml_target_fit_f64 runs all B L-BFGS
     optimisations (warm start + restarts of scamlgp/utils.py:184-199) to convergence -- no host round trip per evaluation.
     Returns dict(z (B, P) optima, value (B,) mll there, info, jitter, stats (B, 4) = [iterations, evaluations, status, 0])."""
-    z = _check(z0, "z0", (z0.shape[0], prob.P)).clone()
-    B = z.shape[0]
-    dev = prob.device
-    with torch.cuda.device(dev):
-        value = _empty(dev, B)
-        info = _empty(dev, B, dtype=torch.int32)
-        jit = _empty(dev, B)
-        stats = torch.zeros((B, 4), dtype=torch.int32, device=dev)
-        nws = int(_lib.lib.scaml_target_fit_workspace_doubles(B, prob.T, prob.D, history))
-        ws = _empty(dev, max(nws, 1))
-        rc = _lib.lib.scaml_target_fit_f64(_ptr(prob.means_t), _ptr(prob.covs_p), _ptr(prob.X), _ptr(prob.y), prob.m_all, prob.s_all,
-                                           prob.spec_host, _ptr(z), B, prob.n, prob.T, prob.D, prob.kind, int(max_iter), int(history),
-                                           float(gtol), float(ftol), _ptr(value), _ptr(info), _ptr(jit), _ptr(stats), _ptr(ws), nws,
-                                           _stream_handle())
-        ws.record_stream(torch.cuda.current_stream(dev))
-    _lib.check_rc(rc, "scaml_target_fit_f64")
-    return dict(z=z, value=value, info=info, jitter=jit, stats=stats)
+    return _target_launch(prob, _check(z0, "z0", (z0.shape[0], prob.P)).clone(), (max_iter, history, gtol, ftol))
 
 
 # ---- (8b) the same over a batch of training sets: S problems x B start points in one launch -----------------------------------
@@ -989,9 +999,14 @@ class TargetFitBatch:
     def supported(n_max: int, T: int, D: int) -> bool:
         return TargetFitProblem.supported(n_max, T, D)
 
+    _symbol = "scaml_target_%s_batched"
+
     def _problem_args(self):
         return (_ptr(self.means_t), _ptr(self.covs_p), _ptr(self.X), _ptr(self.y), _ptr(self.n_points), _ptr(self.m_all), _ptr(self.s_all),
                 self.spec_host)
+
+    def _dims(self):
+        return (self.S,), self.n_max
 
 
 def target_mll_batched(batch: TargetFitBatch, z: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -999,18 +1014,7 @@ def target_mll_batched(batch: TargetFitBatch, z: torch.Tensor) -> Dict[str, torc
     launch of scaml_target_mll_batched_f64 (S * B workgroups).  Row (s, b) is what ``target_mll`` gives for problem s at z[s, b]."""
     if z.dim() != 3:
         raise ValueError(f"z must have shape (S, B, P) (got {tuple(z.shape)})")
-    B = z.shape[1]
-    z = _check(z, "z", (batch.S, B, batch.P))
-    dev, S = batch.device, batch.S
-    with torch.cuda.device(dev):
-        value = _empty(dev, S, B)
-        grad = _empty(dev, S, B, batch.P)
-        info = _empty(dev, S, B, dtype=torch.int32)
-        jit = _empty(dev, S, B)
-        rc = _lib.lib.scaml_target_mll_batched_f64(*batch._problem_args(), _ptr(z), S, B, batch.n_max, batch.T, batch.D, batch.kind,
-                                                   _ptr(value), _ptr(grad), _ptr(info), _ptr(jit), _stream_handle())
-    _lib.check_rc(rc, "scaml_target_mll_batched_f64")
-    return dict(value=value, grad=grad, info=info, jitter=jit)
+    return _target_launch(batch, _check(z, "z", (batch.S, z.shape[1], batch.P)))
 
 
 def target_fit_batched(batch: TargetFitBatch, z0: torch.Tensor, max_iter: int = 200, history: int = 10, gtol: float = 1e-5,
@@ -1020,22 +1024,7 @@ def target_fit_batched(batch: TargetFitBatch, z0: torch.Tensor, max_iter: int = 
     problem s from z0[s, b]."""
     if z0.dim() != 3:
         raise ValueError(f"z0 must have shape (S, B, P) (got {tuple(z0.shape)})")
-    B = z0.shape[1]
-    z = _check(z0, "z0", (batch.S, B, batch.P)).clone()
-    dev, S = batch.device, batch.S
-    with torch.cuda.device(dev):
-        value = _empty(dev, S, B)
-        info = _empty(dev, S, B, dtype=torch.int32)
-        jit = _empty(dev, S, B)
-        stats = torch.zeros((S, B, 4), dtype=torch.int32, device=dev)
-        nws = int(_lib.lib.scaml_target_fit_batched_workspace_doubles(S, B, batch.T, batch.D, history))
-        ws = _empty(dev, max(nws, 1))
-        rc = _lib.lib.scaml_target_fit_batched_f64(*batch._problem_args(), _ptr(z), S, B, batch.n_max, batch.T, batch.D, batch.kind,
-                                                   int(max_iter), int(history), float(gtol), float(ftol), _ptr(value), _ptr(info), _ptr(jit),
-                                                   _ptr(stats), _ptr(ws), nws, _stream_handle())
-        ws.record_stream(torch.cuda.current_stream(dev))
-    _lib.check_rc(rc, "scaml_target_fit_batched_f64")
-    return dict(z=z, value=value, info=info, jitter=jit, stats=stats)
+    return _target_launch(batch, _check(z0, "z0", (batch.S, z0.shape[1], batch.P)).clone(), (max_iter, history, gtol, ftol))
 
 
 # ---- (9) source stack: the whole hyper-parameter fit enqueued on the device ---------------------------------------------------

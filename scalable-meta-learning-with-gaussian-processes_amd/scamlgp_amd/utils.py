@@ -28,6 +28,22 @@ class ModelFittingError(RuntimeError):
     """All optimisation attempts failed (mirrors botorch.exceptions.ModelFittingError)."""
 
 
+def capture_graph(fn, device, warmup: int):
+    """Capture one call of ``fn()`` into a HIP graph: ``warmup`` eager calls on a side stream first (allocator state, lazy module
+    load, workspaces: all outside the graph's pool), then the captured call.  Returns (graph, outputs); ``graph.replay()`` recomputes
+    ``outputs`` -- a tensor or a tuple of tensors -- in place from the static buffers ``fn`` reads."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        for _ in range(warmup):
+            fn()
+    torch.cuda.current_stream(device).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        outputs = fn()
+    return graph, outputs
+
+
 class _GraphedBatchObjective:
     """``fun(x) -> (f (B,), g (B, P))`` of the batched L-BFGS (one fused fit + one gradient launch + constraint transform, priors
     and their autograd backward: ~40 launches around ~0.1 ms of GPU work for a small stack) captured once into a HIP graph on a
@@ -38,15 +54,8 @@ class _GraphedBatchObjective:
         dev = x0.device
         try:
             self.x = x0.detach().clone()
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(3):   # (also allocates the factor buffers and the gradient workspace outside the graph's pool)
-                    fun(self.x)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.f, self.g = fun(self.x)
+            # (the warm-up also allocates the factor buffers and the gradient workspace outside the graph's pool)
+            self.graph, (self.f, self.g) = capture_graph(lambda: fun(self.x), dev, warmup=3)
             self.ok = True
         except Exception as e:
             logger.warning("stack objective: HIP graph capture failed (%s); evaluating eagerly", e)
@@ -138,15 +147,7 @@ class _GraphedObjective:
                 (g,) = torch.autograd.grad(val, self.z)
                 return torch.cat([val.detach().reshape(1), g])
 
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(3):
-                    body()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.out = body()
+            self.graph, self.out = capture_graph(body, dev, warmup=3)
             self.ok = True
         except Exception as e:  # capture unsupported for some op on this build: eager evaluation is always available
             logger.warning("target objective: HIP graph capture failed (%s); evaluating eagerly", e)
@@ -221,7 +222,7 @@ def _kernel_fit_objective(model: ScaMLGP, res: dict) -> torch.Tensor:
 
 
 def _best_start(z: torch.Tensor, f, best: torch.Tensor) -> None:
-    """The best end point into ``best`` = [state || ok]; f (B,) on the device or already on the host."""
+    """The best end point into ``best`` = [state || ok] (ok stays 0 if every start failed); f (B,) on the device or already on the host."""
     n_failed = int(torch.isinf(f).sum())     # (the one host synchronisation of the refit, unless f is a host tensor)
     if n_failed and n_failed < f.numel():
         logger.warning("Error occurred while optimizing the model hyperparameters; %d restart(s) will be skipped.", n_failed)
@@ -230,8 +231,13 @@ def _best_start(z: torch.Tensor, f, best: torch.Tensor) -> None:
         best[-1] = 1.0
 
 
-_FIT_FAILED = ("Hyperparameter optimization failed for all attempts. Usually this indicates a problem with "
-               "model's input data or hyperparameter priors definitions.")
+def _load_best(model: ScaMLGP, best: torch.Tensor, ok: bool) -> None:
+    """The end of a refit: ``best`` = [state || ok] becomes the model's state, or ModelFittingError if no start succeeded."""
+    if not ok:
+        raise ModelFittingError("Hyperparameter optimization failed for all attempts. Usually this indicates a problem with "
+                                "model's input data or hyperparameter priors definitions.")
+    D2 = model.raw_theta.numel()
+    model.load_state_dict({"raw_theta": best[:D2].clone(), "raw_weights": best[D2:-1].clone()})
 
 
 def _fit_target(model: ScaMLGP, num_restarts: int, maxiter: int = 200, use_graph: bool = True, use_kernel: bool = True) -> None:
@@ -259,9 +265,7 @@ def _fit_target(model: ScaMLGP, num_restarts: int, maxiter: int = 200, use_graph
         import torch.distributed as dist
 
         dist.broadcast(best, src=dist.get_global_rank(shard.group, 0) if shard.group is not None else 0, group=shard.group)
-    if float(best[-1]) != 1.0:
-        raise ModelFittingError(_FIT_FAILED)
-    model.load_state_dict({"raw_theta": best[:D2].clone(), "raw_weights": best[D2:-1].clone()})
+    _load_best(model, best, float(best[-1]) == 1.0)
 
 
 def fit_targets_batched(models: Sequence[ScaMLGP], num_restarts: int, maxiter: int = 200, rng: Optional[Sequence[torch.Generator]] = None,
@@ -297,12 +301,9 @@ def fit_targets_batched(models: Sequence[ScaMLGP], num_restarts: int, maxiter: i
     fs = [_kernel_fit_objective(m, {k: v[s] for k, v in res.items()}) for s, (m, _) in enumerate(batch)]
     f_host = torch.stack(fs).cpu()   # (the one host synchronisation of all the refits)
     for s, (m, _) in enumerate(batch):
-        D2 = m.raw_theta.numel()
-        best = torch.zeros(D2 + m.T + 1, dtype=torch.float64, device=m.device)
+        best = torch.zeros(m.raw_theta.numel() + m.T + 1, dtype=torch.float64, device=m.device)
         _best_start(res["z"][s], f_host[s], best)
-        if float(f_host[s].min()) == float("inf"):
-            raise ModelFittingError(_FIT_FAILED)
-        m.load_state_dict({"raw_theta": best[:D2].clone(), "raw_weights": best[D2:-1].clone()})
+        _load_best(m, best, float(f_host[s].min()) != float("inf"))   # (decided on the host copy: no further synchronisation)
 
 
 class _rng_of:

@@ -5,7 +5,6 @@ whole loop -- emulated step around the oracle's marginal likelihood -- against `
 parallel execution (wave reductions, the launches in between) is what tests/test_stack_fit_gpu.py covers on the MI355X."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,9 +14,8 @@ torch.set_num_threads(1)
 
 from oracle import gp_oracle as O
 from scamlgp_amd import hyper as H
+from tests._host_emul import DP as dp, IP as ip, ROOT, build, ptr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "scalable-meta-learning-with-gaussian-processes_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 SPEC = H.source_gp_spec()
@@ -25,17 +23,12 @@ SPEC = H.source_gp_spec()
 SPEC15 = np.array([1e-4, 1e2, 1e-4, 1e2, 1e-8, 1e-2, 1, 3.0, 6.0, 1, 2.0, 0.15, 2, -8.0, 2.0], dtype=np.float64)
 _LOG_2PI = float(np.log(2.0 * np.pi))
 
-dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
-_d = lambda a: a.ctypes.data_as(dp)   # noqa: E731
-_i = lambda a: a.ctypes.data_as(ip)   # noqa: E731
+_d = _i = ptr   # (float64 arrays -> dp, int32 arrays -> ip)
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul") / "stack_fit_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-I", CSRC,
-                    os.path.join(ROOT, "tests", "host_emul", "stack_fit_emul.cpp"), "-o", so], check=True)
-    lib = ctypes.CDLL(so)
+    lib = build(tmp_path_factory, "stack_fit_emul")
     lib.emul_stack_fit_state_doubles.restype, lib.emul_stack_fit_state_doubles.argtypes = ctypes.c_longlong, [ctypes.c_int] * 2
     lib.emul_stack_objective.restype = None
     lib.emul_stack_objective.argtypes = [dp, dp, ip, dp, ctypes.c_int, dp, dp, ip, ctypes.c_int, ctypes.c_int, dp, dp]

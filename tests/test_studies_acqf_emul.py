@@ -9,8 +9,6 @@ tests/test_target_fit_emul.py against autograd (value rtol 1e-9; gradient rtol 1
 tests/test_studies_acqf_gpu.py covers."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,9 +16,8 @@ import torch
 
 torch.set_num_threads(1)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "scalable-meta-learning-with-gaussian-processes_amd", "csrc")
-DP, IP, BP = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8)
+from tests._host_emul import BP, DP, IP, build, ptr as _p
+
 NS, T = (1, 17, 96), 3
 COUNTS = (2, 3, 2)      # queries per group; then one padding row
 LOW_VAR_Q = 3           # a query of group 1 whose source variance is pushed far below zero
@@ -28,17 +25,10 @@ LOW_VAR_Q = 3           # a query of group 1 whose source variance is pushed far
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul") / "studies_acqf_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-I", CSRC,
-                    os.path.join(ROOT, "tests", "host_emul", "studies_acqf_emul.cpp"), "-o", so], check=True)
-    lib = ctypes.CDLL(so)
+    lib = build(tmp_path_factory, "studies_acqf_emul")
     lib.emul_studies_acqf.restype = ctypes.c_int
     lib.emul_studies_acqf.argtypes = [DP, DP, DP, IP, DP, DP, BP, DP, DP, DP, DP, DP, IP, DP, DP, IP, DP] + [ctypes.c_int] * 7 + [DP] * 4
     return lib
-
-
-def _p(a):
-    return a.ctypes.data_as({np.dtype(np.int32): IP, np.dtype(np.uint8): BP}.get(a.dtype, DP))
 
 
 def _kernel(x1, x2, theta, kind):

@@ -5,8 +5,6 @@ through the oracle's target_train_mll, with the tolerances tests/test_target_fit
 single-problem emulation of the same source, problem by problem.  What the slices past n_s hold must not matter: they are filled with
 NaN.  The parallel execution is what tests/test_target_fit_batched_gpu.py covers."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,19 +12,13 @@ import torch
 
 torch.set_num_threads(1)
 
+from tests._host_emul import DP, IP, build, ptr as _p
 from tests._target_problem import TARGET_SPEC, make_target_problem, oracle_mll_and_grad, pack_lower, raw_start
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "scalable-meta-learning-with-gaussian-processes_amd", "csrc")
-DP, IP = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul") / "target_fit_batched_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-I", CSRC,
-                    os.path.join(ROOT, "tests", "host_emul", "target_fit_batched_emul.cpp"), "-o", so], check=True)
-    lib = ctypes.CDLL(so)
+    lib = build(tmp_path_factory, "target_fit_batched_emul")
     lib.emul_target_fit_batched.restype = ctypes.c_int
     lib.emul_target_fit_batched.argtypes = [DP, DP, DP, DP, IP, DP, DP, DP, DP] + [ctypes.c_int] * 9 + [ctypes.c_double, ctypes.c_double,
                                                                                                     DP, DP, IP, DP, IP]
@@ -36,10 +28,6 @@ def emul(tmp_path_factory):
     for f in (lib.emul_target_fit_batched_lds_doubles, lib.emul_target_fit_problem_lds_doubles):
         f.restype, f.argtypes = ctypes.c_longlong, [ctypes.c_int] * 5
     return lib
-
-
-def _p(a):
-    return a.ctypes.data_as(IP if a.dtype == np.int32 else DP)
 
 
 def pack_batch(probs, fill=float("nan")):

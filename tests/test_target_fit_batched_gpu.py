@@ -69,6 +69,30 @@ def test_one_study_reproduces_the_single_entry_point(device):
     assert torch.equal(fa["z"][0], fb["z"]) and torch.equal(fa["value"][0], fb["value"]) and torch.equal(fa["stats"][0], fb["stats"])
 
 
+def test_result_layouts_are_the_documented_ones_and_the_starts_are_left_alone(device):
+    """What the docstrings of the four ``ops.target_*`` wrappers promise: keys, shapes and dtypes of the results, fresh tensors, and
+    z0 unchanged by a refit (the wrappers optimise a copy)."""
+    (S, B), T, D = (2, 2), 4, 3
+    _, tps, z = _batch(device, (5, 12), T, D, 1, B=B)
+    P = D + 2 + T
+    batch, z_before = ops.TargetFitBatch(tps), z.clone()
+    f64, i32 = torch.float64, torch.int32
+    for lead, mll, fit in (((), ops.target_mll(tps[1], z[1]), ops.target_fit(tps[1], z[1])),
+                           ((S,), ops.target_mll_batched(batch, z), ops.target_fit_batched(batch, z))):
+        want_mll = dict(value=((*lead, B), f64), grad=((*lead, B, P), f64), info=((*lead, B), i32), jitter=((*lead, B), f64))
+        want_fit = dict(z=((*lead, B, P), f64), value=((*lead, B), f64), info=((*lead, B), i32), jitter=((*lead, B), f64),
+                        stats=((*lead, B, 4), i32))
+        for out, want in ((mll, want_mll), (fit, want_fit)):
+            assert list(out) == list(want)
+            for k, (shape, dtype) in want.items():
+                assert tuple(out[k].shape) == shape and out[k].dtype == dtype and out[k].device == z.device, k
+                assert out[k].is_contiguous(), k
+        assert bool((fit["stats"][..., 0] >= 1).all()) and bool((fit["stats"][..., 3] == 0).all())
+        z_in = z[1] if lead == () else z
+        assert not torch.equal(fit["z"], z_in) and fit["z"].data_ptr() != z_in.data_ptr()   # the optimiser moved, on its own copy
+    assert torch.equal(z, z_before)
+
+
 def test_an_indefinite_problem_fails_alone(device, fit_path):
     """Problem 1 is indefinite by construction, as tests/test_target_fit_gpu.py builds it: duplicated target points, a source term of
     -6e-8 on the diagonal under 1e-8 noise -- and a NaN weight in one of its starts, which no jitter saves.  That row answers

@@ -4,8 +4,6 @@ gradient against torch autograd through the oracle's target_train_mll (scamlgp/m
 and the in-kernel L-BFGS against scipy L-BFGS-B on the oracle objective.  The parallel execution of the kernel (barriers, wave
 reductions) is what tests/test_target_fit_gpu.py covers on the MI355X."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,19 +12,13 @@ import torch
 
 torch.set_num_threads(1)   # (many small oracle ops: threads only get in each other's way)
 
+from tests._host_emul import DP as dp, IP as ip, build
 from tests._target_problem import TARGET_SPEC, make_target_problem, oracle_mll_and_grad, pack_lower, raw_start
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "scalable-meta-learning-with-gaussian-processes_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emul") / "target_fit_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-I", CSRC,
-                    os.path.join(ROOT, "tests", "host_emul", "target_fit_emul.cpp"), "-o", so], check=True)
-    lib = ctypes.CDLL(so)
-    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
+    lib = build(tmp_path_factory, "target_fit_emul")
     lib.emul_target_fit.restype = ctypes.c_int
     lib.emul_target_fit.argtypes = [dp, dp, dp, dp, ctypes.c_double, ctypes.c_double, dp, dp] + [ctypes.c_int] * 8 + [
         ctypes.c_double, ctypes.c_double, dp, dp, ip, dp, ip]
@@ -45,7 +37,6 @@ def test_carve_ends_at_the_footprint_the_launcher_requests(emul):
 
 
 def _call(lib, prob, z, mode, max_iter=200, history=10):
-    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
     B, P = z.shape
     arr = lambda t: np.ascontiguousarray(t.numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float64)   # noqa: E731
     mt = arr(prob["source_means"].transpose(0, 1).contiguous())
