@@ -65,7 +65,8 @@ int scaml_fit_max_d(int N);         /* largest D for that N (LDS budget)        
  * whose factorisation hits a non-positive pivot is retried IN-KERNEL with 1e-8, 1e-7, 1e-6
  * added to its diagonal (only that task); jitter_used[t] reports the value that succeeded,
  * info[t] > 0 that all attempts failed.  `jitter_in` (T) may be NULL; if given it is added to
- * every attempt (caller-controlled extra jitter).
+ * every attempt (caller-controlled extra jitter) and is NOT part of jitter_used[t], which reports
+ * the ladder's value only (0 for a task that succeeds at the first attempt with jitter_in alone).
  * Linv_diag (T, ceil(N/16), 16, 16), optional: the inverses of the 16x16 diagonal blocks of L
  * (identity-padded past n_t); scaml_posterior_batched_f64 needs them.
  * Outputs L, alpha, quad, logdet, mll, jitter_used, Linv_diag may individually be NULL (not
