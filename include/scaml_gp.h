@@ -435,6 +435,52 @@ int scaml_stack_fit_f64(const double* X, const double* y, const int32_t* n_point
                         int D, int kind, int n_evals, unsigned flags, int max_iter, int history, double gtol, double ftol,
                         double* value, int32_t* stats, void* workspace, long long workspace_bytes, void* stream);
 
+/*
+ * (7h) The acquisition OPTIMISER of many studies' start points on the device: a box-constrained L-BFGS per start around the two
+ * evaluation launches of (5e) / (7g) (scamlgp_amd.bo.ScaMLGPBOStudies with suggest_mode="device"; botorch's optimize_acqf runs scipy
+ * L-BFGS-B on the host around every evaluation).  One call enqueues n_evals rounds of { grouped GRAD source pass (5e), batched target
+ * acquisition (7g), optimiser step } on `stream` and returns; no graph, nothing is synchronised.  The step kernel
+ * (csrc/gp_acqf_opt.hip, one wave per start, one lane per coordinate) runs the per-start state machine of a projected L-BFGS that
+ * MAXIMISES the acquisition value: the start projected onto the box, coordinates at a bound with the gradient pointing outward held,
+ * two-loop direction (`history` <= 16 pairs, kept when s . y > 0), projected trial points, Armijo test on g . (trial - x) with halving
+ * (c1, max_ls trials), scipy L-BFGS-B's stopping rules max |P(x - g) - x| <= gtol, relative decrease <= ftol, max_iter iterations.
+ * Starts do not wait for each other, and a start that has stopped is no longer evaluated: each launch writes the next trial points
+ * and a LIVE group table (the start's study while it runs, -1 afterwards) that the evaluation kernels are handed in place of `group`.
+ *   x0 (B, D): the start points; group (B) int32: the study of start b, negative = a padding row (status 6, never evaluated).
+ *   VA_tab, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s: the source stack as (5e) takes it (theta / alpha / n_points of the
+ *       SOURCE GPs; y_mean, y_std, n_points_s may be NULL);  w, active, Xt, theta_t, L, Linv_diag, alpha_t, n_points_t, m_all, s_all,
+ *       info, acqf_param: the studies as (7g) takes them -- Xt / n_points_t are also (5e)'s leading points Xa / n_points_a, n_max its
+ *       Ma_max.  info[g] != 0: the study's starts fail at their first evaluation (status 4).
+ *   kind_s: the kernel family of the source stack, kind_t: of the studies' target kernels; acqf 0: UCB, 1: EI, as (7g).
+ *   lo, hi (D): the box (device arrays), lo <= hi.
+ *   flags: SCAML_ACQF_OPT_CONTINUE resumes from the state the previous call left in `workspace` (same arguments otherwise); without it
+ *       a reset launch first makes the projected x0 the first trial.  The caller reads stats and calls again while any start is still
+ *       running (at most 1 + max_iter max_ls evaluations per start).  Chunking does not change what a start does with the
+ *       evaluations it is given.
+ *   x (B, D), f (B): the accepted point of each start and the acquisition value THERE (the evaluation made when it was accepted: no
+ *       re-scoring pass is needed); -inf for a failed start, 0 for a padding row.
+ *   stats (B, 4) int32: [iterations, evaluations, status, pairs held], status 0 still running, 1 converged on the projected gradient,
+ *       2 stopped on ftol, 3 line search failed, 4 acquisition not finite at the start point, 5 max_iter, 6 padding row.
+ *   workspace: scaml_studies_acqf_opt_workspace_bytes(B, G, n_max, T, D, history) bytes (0 for shapes the call does not take),
+ *       16-byte aligned; it starts with the per-start state, (4 + 2 history) D + history + 16 doubles each: accepted point, gradient of
+ *       -acquisition there, direction, trial point, the pairs (S, Y, rho), scalars; then Xq, the live group table, mu / var / cov of
+ *       (5e) and value / grad of (7g).
+ * Limits: those of (5e) / (7g) -- n_max <= 96 and <= N, N <= scaml_posterior_max_n(), D <= scaml_studies_acqf_opt_max_d() = 15;
+ * SCAML_E_TOOLARGE beyond them (bad arguments answer first).  B == 0 or G == 0: nothing is enqueued.  Everything is checked once,
+ * before the first launch; SCAML_E_LAUNCH from a later round leaves the rounds before it enqueued -- start the optimisation again.
+ */
+#define SCAML_ACQF_OPT_CONTINUE 1u
+int scaml_studies_acqf_opt_max_d(void);
+long long scaml_studies_acqf_opt_workspace_bytes(int B, int G, int n_max, int T, int D, int history);
+int scaml_studies_acqf_opt_f64(const double* x0, const int32_t* group, const double* const* VA_tab, const double* X, const double* theta_s,
+                               const double* Linv, const double* alpha_s, const double* y_mean, const double* y_std,
+                               const int32_t* n_points_s, const double* w, const uint8_t* active, const double* Xt, const double* theta_t,
+                               const double* L, const double* Linv_diag, const double* alpha_t, const int32_t* n_points_t,
+                               const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int B, int G,
+                               int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi, int max_iter,
+                               int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace,
+                               double* x, double* f, int32_t* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@
 #include "gp_fantasy_params.h"
 #include "gp_stack_fit_params.h"
 #include "gp_studies_acqf.h"   // (argument block and LDS footprint; its arithmetic is not called here)
+#include "gp_acqf_opt.h"       // (argument block and state stride; likewise)
 #include <math.h>
 
 extern "C" const unsigned char scaml_hsaco_blob[];   // generated: lib/hsaco_blob.c
@@ -69,7 +70,7 @@ struct Module {
   hipFunction_t tgt_assemble[2] = {}, tgt_finish = nullptr, tgt_fit = nullptr, tgt_fit_batched = nullptr, tgt_grad[2] = {};
   hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {};   // value only; value + gradient per kind
   hipFunction_t post_linv_grouped[2] = {}, tgt_acqf_batched = nullptr;   // lock-step studies: grouped GRAD pass, batched acquisition
-  hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {}, stack_step = nullptr;
+  hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {}, stack_step = nullptr, acqf_opt_step = nullptr;
   hipFunction_t blk_solve[2][2] = {}, blk_syrk[2] = {};   // solve: [kind][D <= 8]
   hipFunction_t mllgrad_fused[4][2][2] = {};   // [size class NBT = 2, 4, 8, 16][kind][LDS-DMA staging]
   hipFunction_t mllgrad_split[2][2][2] = {};   // LDS-DMA staging, [N <= 128 | N <= 256 class][kind][2 | 4 workgroups per task]
@@ -109,6 +110,7 @@ struct Module {
         {&tgt_fit_batched, "scaml_target_fit_batched_kernel", kLdsLimit, {}},
         {coop, "_ZN5scaml18gp_fit_coop_kernelILi%dEEEvNS_13CoopFitParamsE", kLdsLimit, {K}},
         {&stack_step, "scaml_stack_fit_step_kernel", 0, {}},
+        {&acqf_opt_step, "scaml_acqf_opt_step_kernel", 0, {}},
         {&blk_round, "scaml_blocked_round_kernel", 0, {}},
         {&blk_finish, "scaml_blocked_finish_kernel", 0, {}},
         {&blk_solve[0][0], "_ZN5scaml23gp_blocked_solve_kernelILi%dELb%dEEEvNS_16BlockedFitParamsE", kLdsLimit, {K, B}},
@@ -735,6 +737,32 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
 }
 
 // ---- (5e) the GRAD pass with the query points divided among groups; (7g) the batched target acquisition behind it ---------------
+// The two launches on checked arguments (non-empty shapes within the kernels' limits): the entry points below check and call them,
+// and (7h) checks once and calls them per round.
+namespace {
+int grouped_grad_launch(Module& m, const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                        const double* const* VA_tab, const double* X, const double* theta, const double* Linv, const double* alpha,
+                        const double* y_mean, const double* y_std, const int32_t* n_points, int T, int N, int Mq, int G, int Ma_max, int D,
+                        int kind, double* mu, double* var, double* cov, void* stream) {
+  const size_t lds = scaml::posterior_linv_lds_doubles(N, D) * sizeof(double);
+  scaml::PosteriorGroupedParams p{};
+  p.base = scaml::PosteriorParams{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N, 16 * Mq, D, 0, 0, 0,
+                                  nullptr, cov, Ma_max, 0, nullptr};
+  p.ga = scaml::PosteriorGroupArgs{group, n_points_a, VA_tab, Xa, G, 0};
+  const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * (unsigned)Mq;   // XCD-aware (task, strip) map inside the kernel
+  return launch(m.post_linv_grouped[kind], dim3(blocks), 512, lds, stream, "gp_posterior_linv_grouped", p);
+}
+int acqf_batched_launch(Module& m, const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
+                        const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
+                        const double* Linv_diag, const double* alpha, const int32_t* n_points, const double* m_all, const double* s_all,
+                        const int32_t* info, const double* acqf_param, int Mq, int G, int n_max, int T, int D, int kind, int acqf,
+                        double* value, double* grad, double* mu_out, double* var_out, void* stream) {
+  const size_t lds = scaml::studies_acqf_lds_doubles(n_max) * sizeof(double);
+  scaml::StudiesAcqfParams p{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param,
+                             value, grad, mu_out, var_out, Mq, G, n_max, T, D, kind, acqf, 0};
+  return launch(m.tgt_acqf_batched, dim3((unsigned)Mq), scaml::STUDIES_ACQF_THREADS, lds, stream, "target_acqf_batched", p);   // a workgroup per query point
+}
+}  // namespace
 int scaml_posterior_linv_grad_grouped_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
                                           const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
                                           const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T,
@@ -749,12 +777,8 @@ int scaml_posterior_linv_grad_grouped_f64(const double* Xq, const int32_t* group
   if (T == 0 || Mq == 0 || G == 0) return SCAML_OK;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
-  scaml::PosteriorGroupedParams p{};
-  p.base = scaml::PosteriorParams{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N, 16 * Mq, D, 0, 0, 0,
-                                  nullptr, cov, Ma_max, 0, nullptr};
-  p.ga = scaml::PosteriorGroupArgs{group, n_points_a, VA_tab, Xa, G, 0};
-  const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * (unsigned)Mq;   // XCD-aware (task, strip) map inside the kernel
-  return launch(m->post_linv_grouped[kind], dim3(blocks), 512, lds, stream, "gp_posterior_linv_grouped", p);
+  return grouped_grad_launch(*m, Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
+                             mu, var, cov, stream);
 }
 
 int scaml_target_acqf_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
@@ -773,9 +797,8 @@ int scaml_target_acqf_batched_f64(const double* mu, const double* var, const dou
   if (Mq == 0 || G == 0) return SCAML_OK;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
-  scaml::StudiesAcqfParams p{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param,
-                             value, grad, mu_out, var_out, Mq, G, n_max, T, D, kind, acqf, 0};
-  return launch(m->tgt_acqf_batched, dim3((unsigned)Mq), scaml::STUDIES_ACQF_THREADS, lds, stream, "target_acqf_batched", p);   // a workgroup per query point
+  return acqf_batched_launch(*m, mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param, Mq,
+                             G, n_max, T, D, kind, acqf, value, grad, mu_out, var_out, stream);
 }
 
 // ---- (8) target GP: objective + gradient, and the whole L-BFGS refit, in one launch (csrc/gp_target_fit.hip) -------------
@@ -1002,6 +1025,88 @@ int scaml_stack_fit_f64(const double* X, const double* y, const int32_t* n_point
     if (rc != SCAML_OK) return rc;
     if ((rc = scaml_mll_backward_f64(X, theta, L, linv, alpha, n_points, B, N, D, kind, gwork, partials, stream)) != SCAML_OK) return rc;
     if ((rc = launch(m->stack_step, dim3((unsigned)B), 64, 0, stream, "stack_fit_step", p)) != SCAML_OK) return rc;
+  }
+  return SCAML_OK;
+}
+
+// ---- (7h) the acquisition optimiser of many studies' start points as rounds of { (5e), (7g), optimiser step } (csrc/gp_acqf_opt.hip) ----
+namespace {
+struct AcqfOptLayout {
+  size_t state, Xq, group_live, mu, var, cov, value, grad, total;
+};
+AcqfOptLayout acqf_opt_layout(int B, int n_max, int T, int D, int history) {
+  const size_t b = (size_t)B, t = (size_t)T, d = (size_t)D;
+  AcqfOptLayout l{};
+  size_t o = 0;
+  auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  l.state = take(b * scaml::acqf_opt_state_doubles(D, history) * 8);   // (first: the caller may read the state, include/scaml_gp.h)
+  l.Xq = take(b * d * 8);
+  l.group_live = take(b * 4);
+  l.mu = take(t * b * 16 * 8);
+  l.var = take(t * b * 16 * 8);
+  l.cov = take(t * (size_t)n_max * b * 16 * 8);
+  l.value = take(b * 8);
+  l.grad = take(b * d * 8);
+  l.total = o;
+  return l;
+}
+}  // namespace
+
+int scaml_studies_acqf_opt_max_d(void) { return scaml::ACQF_OPT_MAX_D; }
+
+long long scaml_studies_acqf_opt_workspace_bytes(int B, int G, int n_max, int T, int D, int history) {
+  if (B < 0 || G < 0 || n_max < 1 || n_max > scaml::STUDIES_ACQF_MAX_N || T < 1 || D < 1 || D > scaml::ACQF_OPT_MAX_D || history < 1 ||
+      history > scaml::ACQF_OPT_HMAX || B > (1 << 26))
+    return 0;
+  return (long long)acqf_opt_layout(B, n_max, T, D, history).total;
+}
+
+int scaml_studies_acqf_opt_f64(const double* x0, const int32_t* group, const double* const* VA_tab, const double* X, const double* theta_s,
+                               const double* Linv, const double* alpha_s, const double* y_mean, const double* y_std,
+                               const int32_t* n_points_s, const double* w, const uint8_t* active, const double* Xt, const double* theta_t,
+                               const double* L, const double* Linv_diag, const double* alpha_t, const int32_t* n_points_t,
+                               const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int B, int G,
+                               int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi, int max_iter,
+                               int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace,
+                               double* x, double* f, int32_t* stats, void* stream) {
+  if (B < 0 || G < 0 || n_max < 1 || T < 1 || N < 1 || D < 1 || n_evals < 0 || max_iter < 0 || max_ls < 1) return SCAML_E_BADARG;
+  if (!x0 || !group || !VA_tab || !X || !theta_s || !Linv || !alpha_s || !w || !active || !Xt || !theta_t || !L || !Linv_diag || !alpha_t ||
+      !n_points_t || !m_all || !s_all || !info || !acqf_param || !lo || !hi || !workspace || !x || !f || !stats)
+    return SCAML_E_BADARG;
+  if (!valid_kind(kind_s) || !valid_kind(kind_t) || (acqf != 0 && acqf != 1) || (flags & ~SCAML_ACQF_OPT_CONTINUE)) return SCAML_E_BADARG;
+  if (history < 1 || history > scaml::ACQF_OPT_HMAX || ((uintptr_t)workspace & 15)) return SCAML_E_BADARG;
+  if (!(gtol >= 0.0) || !(c1 > 0.0) || ftol != ftol) return SCAML_E_BADARG;
+  // the shapes (5e) and (7g) take
+  if (n_max > scaml::STUDIES_ACQF_MAX_N || D > scaml::ACQF_OPT_MAX_D || n_max > N || N > scaml_posterior_max_n() || B > (1 << 26))
+    return SCAML_E_TOOLARGE;
+  if (scaml::posterior_linv_lds_doubles(N, D) * sizeof(double) > kLdsLimit || scaml::studies_acqf_lds_doubles(n_max) * sizeof(double) > kLdsLimit)
+    return SCAML_E_TOOLARGE;
+  if (B == 0 || G == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  const AcqfOptLayout lay = acqf_opt_layout(B, n_max, T, D, history);
+  char* ws = (char*)workspace;
+  double *Xq = (double*)(ws + lay.Xq), *mu = (double*)(ws + lay.mu), *var = (double*)(ws + lay.var), *cov = (double*)(ws + lay.cov);
+  double *value = (double*)(ws + lay.value), *grad = (double*)(ws + lay.grad);
+  int32_t* live = (int32_t*)(ws + lay.group_live);
+  scaml::AcqfOptParams p{value, grad, group, x0, lo, hi, (double*)(ws + lay.state), Xq, live, x, f, stats, B, G, D, 1, max_iter, history,
+                         max_ls, 0, gtol, ftol, c1};
+  int rc = SCAML_OK;
+  if (!(flags & SCAML_ACQF_OPT_CONTINUE)) {
+    p.mode = 0;
+    if ((rc = launch(m->acqf_opt_step, dim3((unsigned)B), 64, 0, stream, "acqf_opt_step", p)) != SCAML_OK) return rc;
+    p.mode = 1;
+  }
+  for (int r = 0; r < n_evals; ++r) {
+    // the evaluation kernels are handed group_live where they were handed group: a stopped start (and a padding row) returns at once.
+    // (Arguments and sizes were checked above, once; only a failing launch can end the call here, with the rounds before it enqueued.)
+    if ((rc = grouped_grad_launch(*m, Xq, live, Xt, n_points_t, VA_tab, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, T, N, B, G, n_max,
+                                  D, kind_s, mu, var, cov, stream)) != SCAML_OK)
+      return rc;
+    if ((rc = acqf_batched_launch(*m, mu, var, cov, live, Xq, w, active, Xt, theta_t, L, Linv_diag, alpha_t, n_points_t, m_all, s_all, info,
+                                  acqf_param, B, G, n_max, T, D, kind_t, acqf, value, grad, nullptr, nullptr, stream)) != SCAML_OK)
+      return rc;
+    if ((rc = launch(m->acqf_opt_step, dim3((unsigned)B), 64, 0, stream, "acqf_opt_step", p)) != SCAML_OK) return rc;
   }
   return SCAML_OK;
 }

@@ -29,6 +29,7 @@ FIT_NO_RETRY = 4
 POST_XQ_PER_TASK = 1
 POST_MEAN_ONLY = 2
 STACK_FIT_CONTINUE = 1
+ACQF_OPT_CONTINUE = 1
 
 E_BADARG = -1
 E_TOOLARGE = -2
@@ -111,6 +112,11 @@ SIGNATURES = {
     "scaml_stack_fit_max_d": (_i, []),
     "scaml_stack_fit_workspace_bytes": (_ll, [_i, _i, _i, _i]),
     "scaml_stack_fit_f64": (_i, [_dp, _dp, _dp, _host_spec, _dp] + [_i] * 5 + [_u, _i, _i, _f, _f, _dp, _dp, _dp, _ll, c_void_p]),
+    "scaml_studies_acqf_opt_max_d": (_i, []),
+    "scaml_studies_acqf_opt_workspace_bytes": (_ll, [_i] * 6),
+    # (7h) x0, group; 8 source-stack arrays (5e); 12 study arrays (7g); B, G, n_max, T, N, D, kind_s, kind_t, acqf; lo, hi; max_iter, history, max_ls;
+    # gtol, ftol, c1; n_evals, flags; workspace, x, f, stats
+    "scaml_studies_acqf_opt_f64": (_i, [_dp] * 22 + [_i] * 9 + [_dp, _dp] + [_i] * 3 + [_f] * 3 + [_i, _u] + [_dp] * 4 + [c_void_p]),
     "scaml_debug_target_fit_path": (_i, [_i]),
     "scaml_debug_blocked_fit_path": (_i, [_i]),
     "scaml_debug_coop_far": (_i, [_i]),

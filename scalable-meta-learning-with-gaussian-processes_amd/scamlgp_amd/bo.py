@@ -267,12 +267,18 @@ class ScaMLGPBOStudies:
     ``suggest`` with ``use_graph`` --, one batched re-scoring of the end points, and per study the final choice of ``optimize_acqf``.  Each
     start is a problem of its own there (own history, step and stopping flag; ``optimize_acqf`` sums over a study's starts), so a
     start's path does not depend on the other studies.  A study the batched path does not take -- no training data yet, n > 96, D > 15,
-    pending evaluations (a fantasy model) -- takes its own ``ScaMLGPBOLoop.suggest()`` in the same call."""
+    pending evaluations (a fantasy model) -- takes its own ``ScaMLGPBOLoop.suggest()`` in the same call.
+    ``suggest_mode="device"``: ``"lockstep"`` with the optimiser itself on the device (``StudiesAcquisition.optimize`` ->
+    ``scaml_studies_acqf_opt_f64``): the same initial conditions, the same per-start box-constrained L-BFGS, but its step is a kernel
+    between the two evaluation launches, so no start waits for another, a start that has stopped is no longer evaluated and the host
+    reads one status block per chunk of rounds.  The end points come back with their acquisition values (no re-scoring pass); the final
+    choice and the fall-back of the studies the batch does not take are ``"lockstep"``'s.  ``last_suggest_info``: ``batched``,
+    ``n_eval`` (rounds enqueued), ``n_calls``, ``evals_per_start`` and ``status`` per start.  ``num_studies=1`` is a legitimate use."""
 
     def __init__(self, source_gps: Dict[Hashable, SourceGP], dim: int, num_studies: int, seeds: Optional[Sequence[int]] = None,
                  suggest_mode: str = "sequential", **loop_kwargs):
-        if suggest_mode not in ("sequential", "lockstep"):
-            raise ValueError(f"suggest_mode must be 'sequential' or 'lockstep', got {suggest_mode!r}")
+        if suggest_mode not in ("sequential", "lockstep", "device"):
+            raise ValueError(f"suggest_mode must be 'sequential', 'lockstep' or 'device', got {suggest_mode!r}")
         self.suggest_mode = suggest_mode
         self.last_suggest_info: dict = {}
         S = int(num_studies)
@@ -339,6 +345,11 @@ class ScaMLGPBOStudies:
         group = sa.group_of(counts)
         X0 = torch.cat([b[6] for b in batch], 0)
         B = X0.shape[0]
+        if self.suggest_mode == "device":   # the optimiser on the device: end points and THEIR values in one status read per chunk
+            res = sa.optimize(X0, group, studies[0].af_max_iter, bounds=(0.0, 1.0))
+            self.last_suggest_info.update(n_eval=res["n_eval"], n_calls=res["n_calls"], n_iter=int(res["stats"][:, 0].max()),
+                                          evals_per_start=res["stats"][:, 1].tolist(), status=res["stats"][:, 2].tolist())
+            return self._final_choices(batch, out, res["x"].cpu().split(counts), res["f"].cpu().split(counts))
         vg = lambda X: sa.value_and_grad(X, group)   # noqa: E731
         if studies[0].use_graph:   # one capture per suggest() serves all studies: a single stream, two library launches
             vg = GraphedAcquisition(vg, B, self.dim, sa.device)
@@ -355,7 +366,11 @@ class ScaMLGPBOStudies:
         res = hyper.batched_lbfgs(fun, X0, max_iter=studies[0].af_max_iter, bounds=(0.0, 1.0))
         fin = sa.value(res.x, group).cpu()   # the end points of all studies re-scored in one evaluation
         self.last_suggest_info.update(n_eval=res.n_eval, n_iter=res.n_iter, eval_seconds=t_eval[0])
-        for (i, st, af, cand, vals, best0, x0), xs, fs in zip(batch, res.x.split(counts), fin.split(counts)):
+        return self._final_choices(batch, out, res.x.split(counts), fin.split(counts))
+
+    @staticmethod
+    def _final_choices(batch, out, xs_per_study, fin_per_study):
+        for (i, st, af, cand, vals, best0, x0), xs, fs in zip(batch, xs_per_study, fin_per_study):
             x, _ = acqf_final_choice(cand, vals, best0, xs, fs)
             if st.max_pending_evaluations is not None:
                 st.pending = torch.cat([st.pending, x.reshape(1, -1)], 0)

@@ -1093,6 +1093,93 @@ def stack_fit(X: torch.Tensor, y: torch.Tensor, n_points: Optional[torch.Tensor]
     return dict(z=z, value=value, grad=grad, stats=host, n_eval=n_eval, n_calls=n_calls)
 
 
+# ---- (7h) the acquisition optimiser of many studies' start points enqueued on the device --------------------------------------
+# rounds enqueued between two reads of the status.  Measured (tools/dev_studies_time.py --suggest --sweep 1,2,4,8,16,
+# profiles/studies_suggest_device_timings.txt): the suggest time is flat within 10 % from 1 to 16 at S = 1, 8 and 32 -- a status
+# read costs little next to a round, a round after the last stop evaluates no start -- and 8 is the fastest column or within 0.2 ms of it.
+ACQF_OPT_EVALS_PER_CALL = 8
+ACQF_OPT_MAX_LS = 20            # trials per line search (hyper.batched_lbfgs's max_ls)
+_ACQF_OPT_SCALARS = 16          # ACQF_OPT_SCALARS (csrc/gp_acqf_opt.h)
+ACQF_OPT_STATUS = ("running", "converged", "ftol", "stalled", "failed", "max_iter", "padding")
+
+
+def studies_acqf_opt_state_doubles(D: int, history: int) -> int:
+    """Doubles of one start's optimiser state at the head of the workspace: ``acqf_opt_state_doubles`` of csrc/gp_acqf_opt.h (x, g, d,
+    xt, the curvature pairs, rho, the scalars; tests/test_acqf_opt_emul.py compares the two)."""
+    return (4 + 2 * history) * D + history + _ACQF_OPT_SCALARS
+
+
+class StudiesAcqfOpt:
+    """One optimisation of ``scaml_studies_acqf_opt_f64``: the checked arguments, the workspace and the outputs, so that the rounds can
+    be enqueued in chunks (``enqueue``; the first call resets, the later ones continue).  ``arrays``: the 22 device arrays of the C
+    signature from ``x0`` to ``acqf_param``, in its order (None for the optional y_mean / y_std / n_points_s)."""
+
+    def __init__(self, arrays, B: int, G: int, n_max: int, T: int, N: int, D: int, kind_s: int, kind_t: int, acqf: int, lo: torch.Tensor, hi: torch.Tensor,
+                 max_iter: int, history: int = 10, max_ls: int = ACQF_OPT_MAX_LS, gtol: float = 1e-5, ftol: float = 2.2e-9, c1: float = 1e-4):
+        dev = arrays[0].device
+        i32, u8, i64, f64, nbm = torch.int32, torch.uint8, torch.int64, torch.float64, (n_max + 15) // 16
+        spec = [("x0", (B, D), f64), ("group", (B,), i32), ("VA_tab", (G,), i64), ("X", (T, N, D), f64), ("theta_s", (T, D + 2), f64),
+                ("Linv", (T, N, N), f64), ("alpha_s", (T, N), f64), ("y_mean", (T,), f64), ("y_std", (T,), f64), ("n_points_s", (T,), i32),
+                ("w", (G, T), f64), ("active", (G, T), u8), ("Xt", (G, n_max, D), f64), ("theta_t", (G, D + 2), f64),
+                ("L", (G, n_max, n_max), f64), ("Linv_diag", (G, nbm, 16, 16), f64), ("alpha_t", (G, n_max), f64), ("n_points_t", (G,), i32),
+                ("m_all", (G,), f64), ("s_all", (G,), f64), ("info", (G,), i32), ("acqf_param", (G,), f64)]
+        if len(arrays) != len(spec):
+            raise ValueError(f"expected {len(spec)} arrays, got {len(arrays)}")
+        arrays = [_opt(a, name, shape, dt) for a, (name, shape, dt) in zip(arrays, spec)]
+        self._keep = arrays
+        self._ptrs = [_ptr(a) for a in arrays]
+        self._shape = (B, G, n_max, T, N, D, int(kind_s), int(kind_t), int(acqf))
+        self._opts = (int(max_iter), int(history), int(max_ls), float(gtol), float(ftol), float(c1))
+        self.lo, self.hi = _check(lo, "lo", (D,)), _check(hi, "hi", (D,))
+        self.device, self.n_calls, self.n_eval = dev, 0, 0
+        self.budget = 1 + int(max_iter) * int(max_ls)
+        with torch.cuda.device(dev):
+            self.x, self.f = _empty(dev, B, D), _empty(dev, B)
+            self.stats = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+            self.nbytes = int(_lib.lib.scaml_studies_acqf_opt_workspace_bytes(B, G, n_max, T, D, int(history)))
+            if self.nbytes == 0 and B > 0:
+                raise ValueError("scaml_studies_acqf_opt_f64: problem size exceeds kernel limits")
+            self.ws = _empty(dev, max(self.nbytes, 16), dtype=torch.uint8)
+
+    def enqueue(self, n_evals: int) -> None:
+        with torch.cuda.device(self.device):
+            rc = _lib.lib.scaml_studies_acqf_opt_f64(*self._ptrs, *self._shape, _ptr(self.lo), _ptr(self.hi), *self._opts, int(n_evals),
+                                                     _lib.ACQF_OPT_CONTINUE if self.n_calls else 0, _ptr(self.ws), _ptr(self.x), _ptr(self.f),
+                                                     _ptr(self.stats), _stream_handle())
+        _lib.check_rc(rc, "scaml_studies_acqf_opt_f64")
+        self.n_calls += 1
+        self.n_eval += int(n_evals)
+
+    def run(self, evals_per_call: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Every call enqueues ``evals_per_call`` rounds of grouped source pass + batched acquisition + optimiser step for all B starts,
+        then the status column is read -- the only synchronisation -- and the optimisation continues while a start is still running (at
+        most ``1 + max_iter * max_ls`` evaluations: then every start has stopped).  Returns dict(x (B, D), f (B,) the acquisition value
+        there, stats (B, 4) int32 [iterations, evaluations, status, pairs] on the host, n_eval rounds enqueued, n_calls, state)."""
+        per_call = int(evals_per_call or ACQF_OPT_EVALS_PER_CALL)
+        if per_call < 1:
+            raise ValueError("evals_per_call must be positive")
+        host = self.stats.cpu()
+        while self._shape[0] > 0 and self._shape[1] > 0:
+            self.enqueue(min(per_call, self.budget - self.n_eval))
+            host = self.stats.cpu()
+            if not bool((host[:, 2] == 0).any()) or self.n_eval >= self.budget:
+                break
+        return dict(x=self.x, f=self.f, stats=host, n_eval=self.n_eval, n_calls=self.n_calls, state=self.state())
+
+    def state(self) -> torch.Tensor:
+        """(B, studies_acqf_opt_state_doubles(D, history)): the per-start state that opens the workspace (a view)."""
+        B, D, history = self._shape[0], self._shape[5], self._opts[1]
+        stride = studies_acqf_opt_state_doubles(D, history)
+        return self.ws[: B * stride * 8].view(torch.float64).reshape(B, stride)
+
+
+def studies_acqf_opt(arrays, B: int, G: int, n_max: int, T: int, N: int, D: int, kind_s: int, kind_t: int, acqf: int, lo: torch.Tensor, hi: torch.Tensor,
+                     max_iter: int, evals_per_call: Optional[int] = None, **options) -> Dict[str, torch.Tensor]:
+    """Maximise the studies' acquisition functions from every start with ``scaml_studies_acqf_opt_f64`` (``StudiesAcqfOpt(...).run``):
+    ``arrays`` are the 22 device arrays of the C signature from ``x0`` to ``acqf_param``, ``kind_s`` / ``kind_t`` the kernel families of the source stack and of the target kernels; ``options``: history, max_ls, gtol, ftol, c1."""
+    return StudiesAcqfOpt(arrays, B, G, n_max, T, N, D, kind_s, kind_t, acqf, lo, hi, max_iter, **options).run(evals_per_call)
+
+
 def raise_if_not_psd(info: torch.Tensor) -> None:
     """Host-side check of the per-task status (one device->host sync)."""
     if bool((info < 0).any()):

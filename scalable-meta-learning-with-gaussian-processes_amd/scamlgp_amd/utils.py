@@ -505,3 +505,33 @@ class StudiesAcquisition:
 
     def value(self, X: torch.Tensor, group: torch.Tensor) -> torch.Tensor:
         return self.evaluate(X, group, want_grad=False)["value"]
+
+    def optimizer(self, X0: torch.Tensor, group: torch.Tensor, max_iter: int, bounds=(0.0, 1.0), **options) -> "ops.StudiesAcqfOpt":
+        """The device-side optimisation of ``optimize`` before its first round: an ``ops.StudiesAcqfOpt`` on this object's arrays (packed
+        once, at construction) whose rounds the caller enqueues itself (``enqueue`` / ``run``).  ``options``: history, max_ls, gtol, ftol,
+        c1 of ``hyper.batched_lbfgs``."""
+        D, dev = self.D, self.device
+        X0 = torch.as_tensor(X0, dtype=torch.float64).reshape(-1, D).to(dev).contiguous()
+        B = X0.shape[0]
+        if tuple(group.shape) != (B,) or group.dtype != torch.int32:
+            raise ValueError("group must be (B,) int32")
+        lo = torch.as_tensor(bounds[0], dtype=torch.float64).expand(D).contiguous()
+        hi = torch.as_tensor(bounds[1], dtype=torch.float64).expand(D).contiguous()
+        if bool((lo > hi).any()):
+            raise ValueError("bounds: lo > hi")
+        st, f = self.models[0]._stack, self.models[0]._stack.fit
+        arrays = [X0, group.to(dev), self.VA_tab, st.X, st.theta, f["Linv"], f["alpha"], st.y_mean, st.y_std, st.n_points, self.w, self.active,
+                  self.Xt, self.theta, self.L, self.Linv_diag, self.alpha, self.n_points, self.m_all, self.s_all, self.info, self.acqf_param]
+        T, N = st.X.shape[0], st.X.shape[1]
+        return ops.StudiesAcqfOpt(arrays, B, self.G, self.n_max, T, N, D, st.kind, self.kind, self.acqf, lo.to(dev), hi.to(dev), max_iter, **options)
+
+    def optimize(self, X0: torch.Tensor, group: torch.Tensor, max_iter: int, bounds=(0.0, 1.0), evals_per_call: Optional[int] = None,
+                 **options) -> Dict[str, torch.Tensor]:
+        """Maximise every study's acquisition function from its starts ON THE DEVICE (``scaml_studies_acqf_opt_f64``):
+        ``hyper.batched_lbfgs(bounds=...)`` per start, the optimiser step a kernel between the two evaluation launches.  X0 (B, D) start
+        points, ``group`` (B,) int32 on the device (negative: a padding row), ``bounds`` scalars or (D,).  The loop enqueues
+        ``evals_per_call`` (default ``ops.ACQF_OPT_EVALS_PER_CALL``) rounds per call while any start is running (at most
+        1 + max_iter * max_ls evaluations) and reads ``stats`` once per call -- the only synchronisation.
+        Returns dict(x (B, D), f (B,) the acquisition value at x -- the evaluation made there, no re-scoring --, stats (B, 4) int32 on
+        the host [iterations, evaluations, status, pairs], n_eval rounds enqueued, n_calls, state)."""
+        return self.optimizer(X0, group, max_iter, bounds, **options).run(evals_per_call)

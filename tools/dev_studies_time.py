@@ -8,6 +8,7 @@ the new point: the source posteriors at the training inputs) and refit.  Host cl
 medians over the timed steps (the first step of a size is a warm-up and is not counted).
 
   python tools/dev_studies_time.py [--sizes 1,8,32,64] [--steps K] [--out profiles/studies_timings.txt]
+  python tools/dev_studies_time.py --suggest [--sweep 1,2,4,8,16] [--evals-per-call K]    suggest() alone, in its three modes
 """
 import argparse
 import os
@@ -22,14 +23,16 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from scamlgp_amd import model as M, synthetic, utils  # noqa: E402
+from scamlgp_amd import model as M, ops, synthetic, utils  # noqa: E402
 from scamlgp_amd.bo import ScaMLGPBOLoop, ScaMLGPBOStudies  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--sizes", default="1,8,32,64")
 ap.add_argument("--steps", type=int, default=3, help="timed steps per size (n ends at 80)")
 ap.add_argument("--out", default=None)
-ap.add_argument("--suggest", action="store_true", help="time suggest(): suggest_mode='lockstep' against the default, interleaved in one process")
+ap.add_argument("--suggest", action="store_true", help="time suggest(): suggest_mode='device', 'lockstep' and the default, interleaved in one process")
+ap.add_argument("--sweep", default=None, help="with a list such as 1,2,4,8,16: the device mode's suggest() against ops.ACQF_OPT_EVALS_PER_CALL")
+ap.add_argument("--evals-per-call", type=int, default=None, help="ops.ACQF_OPT_EVALS_PER_CALL for --suggest")
 args = ap.parse_args()
 
 T, N, D, N_END, RESTARTS = 32, 512, 6, 80, 2
@@ -66,17 +69,21 @@ gps = {tid: M.SourceGP(stack, i) for i, tid in enumerate(stack.task_ids)}
 
 
 def suggest_table():
-    """Lock-step against study-by-study suggest(): two ScaMLGPBOStudies on the same data (both are told the sequential side's points),
-    timed alternately step by step; n = 78 .. 80 over the three timed steps."""
+    """suggest() in the three modes: three ScaMLGPBOStudies on the same data (all are told the sequential side's points), timed
+    alternately step by step; n = 78 .. 80 over the three timed steps.  "rounds": batched evaluations (lock-step) or
+    rounds enqueued (device); "ev/start": the evaluations a start consumed, mean over the starts; "ms/eval": lock-step only, the
+    objective calls alone per evaluation (copy in, graph replay, copy out: the figure of DESIGN 4j); "sug/round": device only, the WHOLE
+    suggest (stage 1 and packing included) divided by the rounds enqueued."""
     say(f"# suggest() of S studies, T = {T}, N = {N}, D = {D}, UCB, 10 starts per study, af_max_iter 50; ms, median of {args.steps} steps (n = "
-        f"{N_END - args.steps + 1} .. {N_END}); spread = min .. max of the sequential suggest over those steps")
-    say(f"# {'S':>3} {'side':>10} {'suggest':>9} {'evals':>6} {'ms/eval':>8} {'step':>9}   seq/lock (suggest)   seq spread")
+        f"{N_END - args.steps + 1} .. {N_END}); spread = min .. max of that side's suggest over those steps; device: "
+        f"{ops.ACQF_OPT_EVALS_PER_CALL} rounds per call")
+    say(f"# {'S':>3} {'side':>10} {'suggest':>9} {'rounds':>6} {'ev/start':>8} {'ms/eval':>8} {'sug/round':>9} {'step':>9}   {'spread':>16}   lock-step / device   sequential / device")
     for S in [int(v) for v in args.sizes.split(",")]:
         steps = args.steps + 1
         n0 = N_END - steps
         seeds = list(range(100, 100 + S))
-        sides = {"lockstep": ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, suggest_mode="lockstep", **KW),
-                 "sequential": ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, **KW)}
+        modes = ("device", "lockstep", "sequential")
+        sides = {k: ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, suggest_mode=k, **KW) for k in modes}
         for side in sides.values():
             for s in range(S):
                 g = torch.Generator().manual_seed(seeds[s])
@@ -85,32 +92,75 @@ def suggest_table():
             utils.fit_targets_batched([st.model for st in side.studies], RESTARTS, rng=side.fit_gens)
         rows = {k: [] for k in sides}
         for step in range(steps):
-            t_l, _ = timed(sides["lockstep"].suggest)
-            info = dict(sides["lockstep"].last_suggest_info)
-            t_s, X = timed(sides["sequential"].suggest)
-            ys = [obj(x) for x in X]
+            t, info, X = {}, {}, None
+            for k in modes:
+                t[k], X = timed(sides[k].suggest)
+                info[k] = dict(sides[k].last_suggest_info)
+            ys = [obj(x) for x in X]   # (the sequential side's points)
             t_rep = {}
             for k, side in sides.items():
                 t_rep[k], _ = timed(lambda: side.report(X, ys))
-            rows["lockstep"].append((t_l, t_rep["lockstep"], info["n_eval"], info["eval_seconds"]))
-            rows["sequential"].append((t_s, t_rep["sequential"], 0, 0.0))
+            ev = info["device"]["evals_per_start"]
+            rows["device"].append((t["device"], t_rep["device"], info["device"]["n_eval"], sum(ev) / max(len(ev), 1), 0.0))
+            rows["lockstep"].append((t["lockstep"], t_rep["lockstep"], info["lockstep"]["n_eval"], float(info["lockstep"]["n_eval"]),
+                                     info["lockstep"]["eval_seconds"]))
+            rows["sequential"].append((t["sequential"], t_rep["sequential"], 0, 0.0, 0.0))
         med = {k: [1e3 * statistics.median(r[i] for r in v[1:]) for i in range(2)] for k, v in rows.items()}
-        ne = statistics.median(r[2] for r in rows["lockstep"][1:])
-        per_eval = statistics.median(1e3 * r[3] / max(r[2], 1) for r in rows["lockstep"][1:])   # the objective calls alone: copy in, replay, copy out
-        seq = [1e3 * r[0] for r in rows["sequential"][1:]]
-        for k in ("lockstep", "sequential"):
-            if k == "lockstep":
-                tail = f"   {med['sequential'][0] / med[k][0]:8.2f}x          {min(seq):.1f} .. {max(seq):.1f}"
-                say(f"  {S:>3} {k:>10} {med[k][0]:9.1f} {ne:6.0f} {per_eval:8.2f} {sum(med[k]):9.1f}{tail}")
-            else:
-                say(f"  {S:>3} {k:>10} {med[k][0]:9.1f} {'-':>6} {'-':>8} {sum(med[k]):9.1f}")
-        say(f"#     n = {sides['lockstep'][0].model.n}; gap {med['sequential'][0] - med['lockstep'][0]:.1f} ms against a sequential spread of {max(seq) - min(seq):.1f} ms")
+        ms = {k: [1e3 * r[0] for r in v[1:]] for k, v in rows.items()}
+        for k in modes:
+            ne = statistics.median(r[2] for r in rows[k][1:])
+            per = statistics.median(r[3] for r in rows[k][1:])
+            per_eval = statistics.median(1e3 * r[4] / max(r[2], 1) for r in rows[k][1:])   # the objective calls alone
+            per_round = statistics.median(1e3 * r[0] / max(r[2], 1) for r in rows[k][1:])  # the whole suggest per round enqueued
+            cols = {"device": f"{ne:6.0f} {per:8.1f} {'-':>8} {per_round:9.2f}", "lockstep": f"{ne:6.0f} {per:8.1f} {per_eval:8.2f} {'-':>9}",
+                    "sequential": f"{'-':>6} {'-':>8} {'-':>8} {'-':>9}"}[k]
+            tail = f"   {med['lockstep'][0] / med[k][0]:8.2f}x            {med['sequential'][0] / med[k][0]:8.2f}x" if k == "device" else ""
+            say(f"  {S:>3} {k:>10} {med[k][0]:9.1f} {cols} {sum(med[k]):9.1f}   {min(ms[k]):7.1f} .. {max(ms[k]):5.1f}{tail}")
+        lk = ms["lockstep"]
+        say(f"#     n = {sides['device'][0].model.n}; lock-step - device = {med['lockstep'][0] - med['device'][0]:.1f} ms against a lock-step spread of "
+            f"{max(lk) - min(lk):.1f} ms; sequential - device = {med['sequential'][0] - med['device'][0]:.1f} ms")
 
 
+def sweep_table():
+    """ops.ACQF_OPT_EVALS_PER_CALL: the device mode's suggest() at 1 / 2 / 4 / 8 / 16 rounds per call, the values alternating call by
+    call on one set of studies (n = 80; each call draws new starts from the studies' generators), median of --steps calls."""
+    chunks = [int(v) for v in args.sweep.split(",")]
+    default_chunk = ops.ACQF_OPT_EVALS_PER_CALL
+    say(f"# device suggest() against rounds per call, T = {T}, N = {N}, D = {D}, n = {N_END}; ms (rounds enqueued), median of {args.steps} calls")
+    say(f"# {'S':>3} " + " ".join(f"{'k = ' + str(k):>16}" for k in chunks))
+    for S in [int(v) for v in args.sizes.split(",")]:
+        seeds = list(range(100, 100 + S))
+        side = ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, suggest_mode="device", **KW)
+        for s in range(S):
+            g = torch.Generator().manual_seed(seeds[s])
+            X0 = torch.rand(N_END, D, dtype=torch.float64, generator=g)
+            side[s].record(X0, [obj(x) for x in X0])
+        utils.fit_targets_batched([st.model for st in side.studies], RESTARTS, rng=side.fit_gens)
+        side.suggest()   # warm-up
+        got = {k: [] for k in chunks}
+        for _ in range(args.steps):
+            for k in chunks:
+                ops.ACQF_OPT_EVALS_PER_CALL = k
+                t, _ = timed(side.suggest)
+                got[k].append((1e3 * t, side.last_suggest_info["n_eval"]))
+        say(f"  {S:>3} " + " ".join(f"{statistics.median(v[0] for v in got[k]):9.1f} ({statistics.median(v[1] for v in got[k]):4.0f})" for k in chunks))
+    ops.ACQF_OPT_EVALS_PER_CALL = default_chunk
+
+
+if args.sweep:
+    sweep_table()
+    if args.out:
+        with open(args.out, "a" if args.suggest else "w") as f:
+            f.write("\n".join(lines) + "\n")
+    lines.clear()
+    if not args.suggest:
+        sys.exit(0)
 if args.suggest:
+    default_chunk = ops.ACQF_OPT_EVALS_PER_CALL
+    ops.ACQF_OPT_EVALS_PER_CALL = args.evals_per_call or default_chunk
     suggest_table()
     if args.out:
-        with open(args.out, "w") as f:
+        with open(args.out, "a" if args.sweep else "w") as f:
             f.write("\n".join(lines) + "\n")
     sys.exit(0)
 say(f"# BO step of S studies, T = {T}, N = {N}, D = {D}, n -> {N_END}, {RESTARTS} restarts (B = {1 + RESTARTS} starts per study), UCB; ms per step, median of "
