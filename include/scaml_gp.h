@@ -139,6 +139,8 @@ int scaml_potrf_batched_f64(const double* A, const double* y, const int32_t* n_p
  *   NULL.  N <= scaml_posterior_max_n().
  *   flags: SCAML_POST_XQ_PER_TASK — Xq is (T, M, D), one query set per task;
  *          SCAML_POST_MEAN_ONLY   — only mu = m + s K_* alpha (no solve; L, Linv_diag, var, V unused/NULL).
+ * Non-finite query points: a query point with a NaN or infinite coordinate gives NaN in its own mu, var and column of V (and,
+ * in (5b), in its row / column of cov); the other query points are not affected.
  */
 #define SCAML_POST_XQ_PER_TASK 1u
 #define SCAML_POST_MEAN_ONLY 2u
@@ -165,6 +167,10 @@ int scaml_posterior_cov_f64(const double* Xq, const double* theta, const double*
  * the BO loop wants: the source GPs of scamlgp/model.py:128, :281 are fixed while every acquisition step
  * scores thousands of candidates.  scaml_posterior_linv_f64 has the semantics of
  * scaml_posterior_batched_f64 (same mu, var, V; SCAML_POST_XQ_PER_TASK allowed, SCAML_POST_MEAN_ONLY not).
+ * Non-finite query points, every pass over Linv ((5c), (5c'), (5d), (5e)): a query point with a NaN or infinite coordinate gives NaN
+ * in its own mu, var and column of cov -- in (5d) / (5e) in all 16 columns of its strip --, and the other query points are not
+ * affected.  The NaN is put back where those results are written; the point's column of V (scaml_posterior_linv_f64) is
+ * unspecified (finite): use mu / var to detect such a point.
  */
 int scaml_linv_batched_f64(const double* L, const double* Linv_diag, const int32_t* n_points, int T, int N, double* Linv,
                            void* stream);

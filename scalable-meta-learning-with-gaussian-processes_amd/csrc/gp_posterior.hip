@@ -370,12 +370,16 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
     __syncthreads();
   }
   if (tid < 16 && qc < M) {
+    // a query point with a NaN / inf coordinate: phase 1 clamps d2 with bare v_max, which drops a NaN operand -- the strip would hold
+    // the posterior of a point at distance zero from everything.  |xq|^2 - |xq|^2 (0, or NaN for such a point) puts the NaN back where
+    // the results are written, as `d2 - d2` does in kernel_from_sqdist (GRAD: all 16 columns are the one point)
+    const double bad = nq[tid] - nq[tid];
     if (GRAD && tid > 0) {
-      if (p.mu) p.mu[(size_t)task * M + qc] = ys * red[tid];
-      if (p.var) p.var[(size_t)task * M + qc] = -2.0 * ys * ys * red[16 + tid];
+      if (p.mu) p.mu[(size_t)task * M + qc] = ys * red[tid] + bad;
+      if (p.var) p.var[(size_t)task * M + qc] = -2.0 * ys * ys * red[16 + tid] + bad;
     } else {
-      if (p.mu) p.mu[(size_t)task * M + qc] = __builtin_fma(ys, red[tid], ym);
-      if (p.var) p.var[(size_t)task * M + qc] = ys * ys * (os - red[16 + tid]);
+      if (p.mu) p.mu[(size_t)task * M + qc] = __builtin_fma(ys, red[tid], ym) + bad;
+      if (p.var) p.var[(size_t)task * M + qc] = ys * ys * (os - red[16 + tid]) + bad;
     }
   }
   if (nas && !p.mean_only) {
@@ -422,7 +426,7 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
         } else {
           kv = os * kernel_from_sqdist<KIND>(d2, exptab);
         }
-        p.cov[((size_t)task * p.Ma + a) * M + qcc] = ys * ys * (kv - cb[e]);
+        p.cov[((size_t)task * p.Ma + a) * M + qcc] = ys * ys * (kv - cb[e]) + (nq[c] - nq[c]);   // (NaN for a non-finite query, as above)
       }
     }
   }

@@ -79,7 +79,7 @@ def test_two_block_fit_jitter_ladder(device):
     assert (one["info"].cpu() > 0).tolist() == [False, True, True]
 
 
-@pytest.mark.parametrize("N,R", [(16, 1), (100, 5), (256, 40), (512, 17)])
+@pytest.mark.parametrize("N,R", [(16, 1), (100, 5), (129, 3), (256, 40), (512, 17)])
 def test_cho_solve_matches_torch(N, R, device):
     g = torch.Generator().manual_seed(N + R)
     T = 3
