@@ -33,12 +33,16 @@
 //       U2  all remaining tiles get the rank-16 update of panel k (4 MFMAs per tile, operands from
 //           the LDS panel) -- the bulk, during which the other waves' F(k+1) results arrive
 //       then column k+1 goes to HBM (128-byte row segments; the mirrored upper tile as zeros).
+// Which tile a slot holds is fixed for the whole kernel: every update wave works its schedule out once per attempt
+// (csrc/gf_schedule.hpp: operand offsets per slot and the slot range per column, in the lanes of one VGPR) and the phases
+// above fetch it with v_readlane instead of walking the triangle's columns again for every tile.
 // alpha comes from a blocked back-substitution over the L tiles still held in registers.  A
 // failed pivot restarts the task in-kernel with the next jitter (1e-8, 1e-7, 1e-6), as
 // linear_operator's psd_safe_cholesky does on the host.
 #include "scaml_common.hpp"
 #include "../../include/scaml_gp.h"
 #include "gp_fit_params.h"
+#include "gf_schedule.hpp"
 
 #ifdef SCAML_STAMPS
 // Diagnostic build only (python __graft_entry__.py --stamps): update wave 0 and the panel wave of
@@ -84,6 +88,12 @@ namespace scaml {
 // (lane -> row (lane >> 4) + 4g, column lane & 15) and the per-row reads are all bank-conflict free.
 constexpr int PP = 17;
 static_assert(PP == FIT_PP, "gp_fit_params.h sizes the LDS with this pitch");
+static_assert(PP == GF_SCHED_PITCH, "gf_schedule.hpp packs byte offsets at this pitch");
+
+// 32-bit LDS addresses: a tile's operand rows are (per-lane base) + (byte offset out of the wave's schedule)
+typedef __attribute__((address_space(3))) double lds_f64_t;
+__device__ __forceinline__ unsigned lds_addr(const double* p) { return (unsigned)(size_t)(const lds_f64_t*)p; }
+__device__ __forceinline__ lds_f64_t* lds_ptr(unsigned a) { return (lds_f64_t*)a; }
 
 __device__ __forceinline__ int opaque_s(int v) {
   asm volatile("" : "+s"(v));  // keeps per-slot address arithmetic from being hoisted out of the panel loop
@@ -397,7 +407,8 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   const bool is_panel = wave == WU;
   const int lc = lane & 15;   // tile column owned by this lane
   const int lq = lane >> 4;   // tile row group: rows lq + 4 * reg
-  const int N = p.N, D = p.D;
+  // (wave-uniform: the jitter retries read `p` through a pointer, and without this every size derived from D sat in a VGPR there)
+  const int N = __builtin_amdgcn_readfirstlane(p.N), D = __builtin_amdgcn_readfirstlane(p.D);
   const int LD = b.ldl(N);   // leading dimension of the stored factor (N, or the full size when this is a diagonal block of a blocked fit)
   int n = p.n_points ? p.n_points[task] : N;
   n = n < 0 ? 0 : (n > N ? N : n);
@@ -417,7 +428,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   // owns tiles t = s * WU + wave (slot s), so its tiles of column j are the contiguous slots
   // [slo(j), slo(j+1)) and everything right of column j is the suffix starting at slo(j+1).
   auto off = [](int j) { return j * NB - j * (j - 1) / 2; };
-  auto slo = [&](int j) { const int o = off(j) - wave; return o <= 0 ? 0 : (o + WU - 1) / WU; };
+  // (slo(j) = ceil((off(j) - wave) / WU), clamped at 0: the update waves read it out of their schedule, csrc/gf_schedule.hpp)
 
   STAMP_DECL;
   int fail = 0;
@@ -595,15 +606,15 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
     fail = 0;
     // park tile t (index in column-major order over the triangle) as a register image at dst[256] if
     // this wave owns it
-    auto park_tile = [&](int t, double* dst) {
-      if (t % WU == wave) {
-        const int s = t / WU;
-        double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;
+    auto park_slot = [&](int s, double* dst) {
+      double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;
 #define SCAML_BODY(r0, r1, r2, r3, r4, r5, r6, r7) TILE_GET(r0, r1, r2, r3, r4, r5, r6, r7, e0, e1, e2, e3);
-        SCAML_DISPATCH(s)
+      SCAML_DISPATCH(s)
 #undef SCAML_BODY
-        dst[lane] = e0; dst[64 + lane] = e1; dst[128 + lane] = e2; dst[192 + lane] = e3;
-      }
+      dst[lane] = e0; dst[64 + lane] = e1; dst[128 + lane] = e2; dst[192 + lane] = e3;
+    };
+    auto park_tile = [&](int t, double* dst) {
+      if (t % WU == wave) park_slot(t / WU, dst);
     };
     if (!is_panel) {
       park_tile(off(0), DG);
@@ -782,19 +793,31 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
       // (the second wave of a SIMD loses the issue arbitration to its older mate in every phase and is the iteration's
       //  long pole: a static raise for that half -- 107.7 -> 107.0 us in interleaved A/B, priority 2 the same)
       if (WU == 7 && wave >= 4) __builtin_amdgcn_s_setprio(SCAML_YOUNG_PRIO);
-      auto store_column = [&](int c) {
+      // This wave's tile schedule (csrc/gf_schedule.hpp), one word per lane, worked out once per attempt in the shadow of
+      // the panel wave's first diagonal block: which tile a slot holds never changes, so the phases below fetch a
+      // slot's operand offsets and a column's slot range with one v_readlane instead of walking the columns again.
+      // (from a copy of the lane number that the compiler cannot trace back: nothing of this is computed ahead of the
+      //  branch that separates the update waves from the panel wave, where it would cost the panel wave a register)
+      int ul = lane;
+      asm volatile("" : "+v"(ul));
+      unsigned sched = gf_sched_word(NB, WU, wave, ul);
+      auto sched_at = [&](int l) { return (unsigned)__builtin_amdgcn_readlane((int)sched, l); };
+      auto slo_at = [&](int j) { return (int)sched_at(GF_SCHED_COL_LANE + j); };
+      // per-lane part of an operand row's LDS address, (lc * PP + lq) * 8
+      const unsigned lane_opnd = (unsigned)((ul & 15) * PP + (ul >> 4)) * 8u;
+      auto store_column = [&](int c, int sa, int sb) {
         if (Lg && c >= PSTORE) {
-          const int sa = slo(c), sb = slo(c + 1), offc = off(c);
           for (int s = sa; s < sb; ++s) {
-            const int ti = c + (s * WU + wave - offc);
+            const int ti = (int)(sched_at(GF_SCHED_IDX_LANE + s) >> 8);
             if (ti != c) store_tile(c, ti);   // (the diagonal tile: store_diag)
           }
         }
       };
       // L_cc left its owner's registers long ago: it comes from the panel wave's LDS copy LT[c & 1], which
       // step c+2 overwrites once cntS[c] is complete -- so this runs before the wave's arrival there
-      auto store_diag = [&](int c) {
-        if (Lg && off(c) % WU == wave) {
+      // (own: the diagonal tile is the first of its column, so it sits in the wave's first slot of the column or nowhere)
+      auto store_diag = [&](int c, bool own) {
+        if (Lg && own) {
           const double* lt = LT + (c & 1) * 16 * PP + lq * PP + lc;
           double* tb = Lg + ((size_t)(16 * c) * LD + 16 * c);
           const int col = 16 * c + lc;
@@ -811,6 +834,12 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
         const int c = k + 1;                          // the column finalised in this iteration
         const double* buf = PT + ((k + 3) % 3) * PANEL;     // column k, final (operand reads)
         double* cbuf = PT + (c % 3) * PANEL;          // receives column c
+        asm volatile("" : "+v"(sched));   // (the schedule is fetched slot by slot where it is used, not hoisted into SGPRs for the whole loop)
+        const int sa = slo_at(c), sb = slo_at(c + 1);   // this wave's slots of column c; everything right of it: sb on
+        const unsigned colb = (unsigned)c * GF_SCHED_BLOCK_BYTES;   // byte offset of block row c in a column buffer
+        const unsigned obase = lds_addr(buf) + lane_opnd;           // operand rows of column k: + block offset
+        // the parked diagonal tile D_{k+2} as a schedule word (block column = block row = k + 2)
+        const unsigned parked = (unsigned)(k + 2) * (GF_SCHED_BLOCK_BYTES * 0x10001u);
         if (k >= 0) {
           // (every wait below gives up when the panel wave has reported a failed pivot: the waves it is
           //  waiting for may have left already)
@@ -819,22 +848,23 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
           STAMP_K(k, 1);
           STAMP(3);
           // U1: column k+1 and the diagonal tile D_{k+2} first
-          const int sa = slo(c), sb = slo(c + 1), offc = off(c);
-          const double* pj = buf + (16 * c + lc) * PP + lq;         // L_{k+1,k} rows: the A operand
+          const lds_f64_t* pj = lds_ptr(obase + colb);              // L_{k+1,k} rows: the A operand
+          int sr = -1;                                              // slot of R_{k+2} = tile (k+2, k+1), if it is here
           for (int s = sa; s < sb; ++s) {
-            const int ti = c + (s * WU + wave - offc);
-            if (ti == c) continue;   // D_{k+1} left during U1(k-1)
-            const double* pi = buf + (16 * ti + lc) * PP + lq;      // L_{ti,k} rows: the B operand
+            const unsigned rowb = sched_at(s) >> 16;
+            if (rowb == colb) continue;   // D_{k+1} left during U1(k-1)
+            if (rowb == colb + GF_SCHED_BLOCK_BYTES) sr = s;
+            const lds_f64_t* pi = lds_ptr(obase + rowb);            // L_{ti,k} rows: the B operand
 #define SCAML_BODY(r0, r1, r2, r3, r4, r5, r6, r7) \
             TILE_MFMA4_SUB(r0, r1, r2, r3, r4, r5, r6, r7, pj[0], pj[4], pj[8], pj[12], pi[0], pi[4], pi[8], pi[12]);
             SCAML_DISPATCH(s)
 #undef SCAML_BODY
           }
-          const int td = off(k + 2);     // tile (k+2, k+2)
-          const bool own_d = k + 2 < NB && td % WU == wave;
+          // tile (k+2, k+2) is the first of column k+2: in slot sb or not here
+          const bool own_d = k + 2 < NB && sched_at(sb) == parked;
           if (own_d) {
-            const int s = td / WU;
-            const double* pd = buf + (16 * (k + 2) + lc) * PP + lq;
+            const int s = sb;
+            const lds_f64_t* pd = lds_ptr(obase + colb + GF_SCHED_BLOCK_BYTES);
 #define SCAML_BODY(r0, r1, r2, r3, r4, r5, r6, r7) \
             TILE_MFMA4_SUB(r0, r1, r2, r3, r4, r5, r6, r7, pd[0], pd[4], pd[8], pd[12], pd[0], pd[4], pd[8], pd[12]);
             SCAML_DISPATCH(s)
@@ -842,8 +872,8 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
           }
           MFMA_DRAIN();
           STAMP_K(k, 2);
-          if (k + 2 < NB) park_tile(offc + 1, CR + (k & 1) * 256);   // R_{k+2} = tile (k+2, k+1), raw
-          if (own_d) park_tile(td, DG + (k & 1) * 256);
+          if (sr >= 0) park_slot(sr, CR + (k & 1) * 256);   // R_{k+2} = tile (k+2, k+1), raw
+          if (own_d) park_slot(sb, DG + (k & 1) * 256);
           sync_arrive(cntS + k, lane);
           STAMP_K(k, 3);
           STAMP_AT(k);
@@ -851,26 +881,22 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
         }
         if (k >= 0) {
           // U2: the bulk of the trailing update with panel k: every slot from slo(k+2) on, entered through
-          // one switch and then falling through slot after slot (the parked D_{k+2} is skipped).
+          // one switch and then falling through slot after slot (the parked D_{k+2} is skipped; only the last slot
+          // can be empty).  A slot is: fetch its schedule word, one test, two adds onto the lane's base, reads, MFMAs.
           // Round 2: U2(k) runs BEFORE F(k+1) -- the time a wave used to spend in front of flagW[k+1] waiting for the
           // panel wave (1.4-2.9 k cycles per iteration) is bulk work now; cntT[k+1] arrives later, but nobody needs it
           // before his own U2(k) is through (109.2 -> 108.0 us in interleaved A/B; round 1 had F first).
-          const int s0 = slo(k + 2);
-          int uj = k + 2, ur = s0 * WU + wave - off(k + 2);
 #define SCAML_U2_(S, r0, r1, r2, r3, r4, r5, r6, r7)                                               \
           case S:                                                                                  \
             if (S < SLOTS) {                                                                       \
-              while (uj < NB && ur >= NB - uj) { ur -= NB - uj; ++uj; }                            \
-              if (uj < NB) {                                                                       \
-                if (ur != 0 || uj != k + 2) {                                                      \
-                  const double* pj = buf + (16 * uj + lc) * PP + lq;                               \
-                  const double* pi = buf + (16 * (uj + ur) + lc) * PP + lq;                        \
-                  TILE_MFMA4_SUB(r0, r1, r2, r3, r4, r5, r6, r7, pj[0], pj[4], pj[8], pj[12], pi[0], pi[4], pi[8], pi[12]); \
-                }                                                                                  \
-                ur += WU;                                                                          \
+              const unsigned pk = sched_at(S);                                                     \
+              if (pk != parked && (S + 1 < SLOTS || pk != GF_SCHED_NONE)) {                        \
+                const lds_f64_t* pj = lds_ptr(obase + (pk & 0xffffu));                             \
+                const lds_f64_t* pi = lds_ptr(obase + (pk >> 16));                                 \
+                TILE_MFMA4_SUB(r0, r1, r2, r3, r4, r5, r6, r7, pj[0], pj[4], pj[8], pj[12], pi[0], pi[4], pi[8], pi[12]); \
               }                                                                                    \
             }
-          switch (s0) { SCAML_TILE_LIST(SCAML_U2_) default: break; }
+          switch (sb) { SCAML_TILE_LIST(SCAML_U2_) default: break; }
 #undef SCAML_U2_
           MFMA_DRAIN();
           sync_arrive(cntU + k, lane);
@@ -885,7 +911,10 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
           STAMP(5);
           if (fw == 2) break;
           const double* Wc = WAll + c * 16 * PP;
-          const int sa = slo(c), sb = slo(c + 1), offc = off(c);
+          const int sa = slo_at(c), sb = slo_at(c + 1), offc = off(c);
+          // (what the closed form told the compiler: without it the tiles' result registers are merged where the physical-tile
+          //  cases meet, with copies right behind the MFMAs -- the hazard audit of the build refuses that code)
+          __builtin_assume(sa >= 0 && sb >= sa && sb - sa <= MAXC && sb <= SLOTS);
           // everyone must be done reading column c-3 (operands of U2(c-3), its HBM stores) before its buffer -- one of three -- is reused
           if (sa < sb && c >= 3 && !sync_wait_ge_or_fail(cntU + c - 3, WU, flagp)) goto update_done;
           STAMP_K(k, 6);
@@ -932,11 +961,11 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
             }
           }
           STAMP_K(k, 9);
-          store_diag(c);
+          store_diag(c, sa < sb && sched_at(sa) >> 16 == colb);
           STAMP_K(k, 10);
           STAMP(6);
         }
-        store_column(c);
+        store_column(c, sa, sb);
         STAMP_K(k, 12);
         STAMP(8);
       }
