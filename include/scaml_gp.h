@@ -255,6 +255,9 @@ int scaml_posterior_linv_cov_f64(const double* Xq, const double* X, const double
  *                               (psd_safe_cholesky would raise NotPSDError) turns every output into NaN on the device
  * Inputs: cov_s (n, n + M), mean_s (n + M), var_s (n + M) from (6') at cat(train_X, Xq); Xall (n + M, D) = cat(train_X, Xq);
  * theta (D + 2) of the TARGET kernel; train_targets (n) standardised with (m_all, s_all).  n >= 1.
+ * Non-finite query points: a query point with a NaN or infinite coordinate gives NaN in exactly its column of Knq from the assemble
+ * (mean_q / var_q carry whatever the source sums hold: NaN from (5) / (5c)), hence in its column of Z and in its mu and var from the
+ * finish; the other query points are not affected.  (tests/_target_bounds.py states the accuracy every stage is held to.)
  */
 int scaml_target_assemble_f64(const double* cov_s, const double* mean_s, const double* var_s, const double* Xall,
                               const double* theta, const double* train_targets, double m_all, double s_all, int n, int M, int D,
@@ -278,6 +281,9 @@ int scaml_target_finish_f64(const double* Knq, const double* Z, const double* al
  * (cov_g (n, Mq * 16), mu_g / var_g (Mq * 16): (6') applied to cov / mu / var above), the target inputs Xt (n, D), the target
  * kernel theta (D + 2), and alpha (n), Z (n, Mq) = Knn^-1 Knq of the value path ((7): the POTRF's alpha, the Cholesky solve's result).
  * info (1) int32 or NULL: a failed target factorisation turns the outputs into NaN.
+ * Non-finite query points (scaml_target_posterior_grad_f64): a query point with a NaN or infinite coordinate gives NaN in EVERY entry
+ * of its dmu and dvar, whatever mu_g / var_g / cov_g hold for it (the kernel clamps drop a NaN: without this only the entry of that
+ * coordinate would show it); the other query points are not affected.  D > 15: SCAML_E_TOOLARGE, nothing is written.
  */
 int scaml_posterior_linv_grad_f64(const double* Xq, const double* Xa, const double* X, const double* theta, const double* Linv,
                                   const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points,
@@ -328,7 +334,8 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
  *   target gradient, then value (Mq) = UCB or EI and grad (Mq, D) (may be NULL) with (7f)'s clamps.  mu_out, var_out (Mq) or NULL:
  *   the posterior itself.  Sums run in a fixed order (tasks, then training points, ascending): the result is a pure function of the
  *   inputs.  info[g] != 0 (or n_points[g] outside 1 .. n_max) turns that group's outputs into NaN; a padding query gives zeros.
- *   What lies past n_g in a group's slices is never read.
+ *   What lies past n_g in a group's slices is never read.  A query point with a NaN or infinite coordinate gives NaN in its value, every
+ *   entry of its grad, mu_out and var_out, as in (5d) / (7); the other query points are not affected.
  *   Limits: n_max <= 96, D <= 15; SCAML_E_TOOLARGE beyond them (bad arguments answer first).  Mq == 0 or G == 0: nothing is enqueued.
  * Neither call synchronises; every status stays on the device (both can be stream-captured).
  */

@@ -605,6 +605,15 @@ __global__ __launch_bounds__(64) void scaml_target_grad_kernel(const double* __r
   double gm[DM], gv[DM];
 #pragma unroll
   for (int d = 0; d < DM; ++d) gm[d] = gv[d] = 0.0;
+  // a query point with a NaN / inf coordinate: the clamps of kernel_and_slope_scaled are bare v_max / v_min, which drop a NaN operand --
+  // only that coordinate's df[d] would carry it, the other D - 1 entries would be those of a point at distance ~0 (Matern) or far away
+  // (RBF).  sum_d (x_d - x_d) is 0, or NaN for such a point: every entry of its dmu / dvar is NaN where the results are stored (a
+  // select: finite inputs stay bit for bit what they were)
+  double bad = 0.0;
+  for (int d = 0; d < D; ++d) {
+    const double x = Xq[(size_t)q * D + d];
+    bad += x - x;
+  }
   for (int a = lane; a < n; a += 64) {
     double df[DM];
     double d2 = 0.0;
@@ -636,8 +645,8 @@ __global__ __launch_bounds__(64) void scaml_target_grad_kernel(const double* __r
     if (d < D) {
       const double sm = scaml::wave_sum_to_lane15(gm[d]), sv = scaml::wave_sum_to_lane15(gv[d]);
       if (lane == 63) {
-        dmu[(size_t)q * D + d] = mu_g[col0 + d] + s_all * sm;
-        dvar[(size_t)q * D + d] = var_g[col0 + d] - 2.0 * s_all * s_all * sv;
+        dmu[(size_t)q * D + d] = bad == 0.0 ? mu_g[col0 + d] + s_all * sm : bad;
+        dvar[(size_t)q * D + d] = bad == 0.0 ? var_g[col0 + d] - 2.0 * s_all * s_all * sv : bad;
       }
     }
   }

@@ -236,15 +236,23 @@ SA_DEV void sa_query(const StudiesAcqfParams& p, double* lds, int q, int tid, in
       Amu = -cdf;
       Av = vr > 1e-9 ? 0.5 * pdf / sigma : 0.0;
     }
+    // a query point with a NaN / inf coordinate: fmax in the Matern branch drops a NaN operand, so only that coordinate's slope
+    // would carry it (and nothing at all with source sums that happen to be finite).  sum_d (x_d - x_d) is 0, or NaN for such a
+    // point: every output of the query is NaN, as (5d)'s target gradient has it (a select: finite inputs are untouched)
+    double bad = 0.0;
+    for (int d = 0; d < D; ++d) {
+      const double x = p.Xq[(size_t)q * D + d];
+      bad += x - x;
+    }
     if (o == 0) {
-      p.value[q] = A;
-      if (p.mu_out) p.mu_out[q] = mu;
-      if (p.var_out) p.var_out[q] = vr;
+      p.value[q] = bad == 0.0 ? A : bad;
+      if (p.mu_out) p.mu_out[q] = bad == 0.0 ? mu : bad;
+      if (p.var_out) p.var_out[q] = bad == 0.0 ? vr : bad;
     }
     if (p.grad && o < D) {
       const double dmu = fma(s, red[2 + o], Ssum[1 + o]);
       const double dvar = fma(-2.0 * s2, red[18 + o], Ssum[17 + o]);
-      p.grad[(size_t)q * D + o] = fma(Av, dvar, Amu * dmu);
+      p.grad[(size_t)q * D + o] = bad == 0.0 ? fma(Av, dvar, Amu * dmu) : bad;
     }
   }
 }

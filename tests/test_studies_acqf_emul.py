@@ -142,8 +142,10 @@ class Problem:
         return float(val.detach()), g.squeeze(0).numpy(), float(mu.detach()), float(var.detach())
 
 
-def _run(lib, prob, acqf, info=(0, 0, 0)):
+def _run(lib, prob, acqf, info=(0, 0, 0), edit=None):
     a = prob.arrays(acqf, info)
+    if edit is not None:
+        edit(a)
     Mq, D = a["Xq"].shape
     out = dict(value=np.full(Mq, 7.0), grad=np.full((Mq, D), 7.0), mu=np.full(Mq, 7.0), var=np.full(Mq, 7.0))
     order = ("mu", "var", "cov", "group", "Xq", "w", "active", "Xt", "theta", "L", "Linv_diag", "alpha", "n_points", "m_all", "s_all", "info",
@@ -182,6 +184,25 @@ def test_a_failed_factorisation_is_nan_for_that_group_only(emul):
         for s_ in (0, 2):
             assert np.array_equal(bad[k][g == s_], good[k][g == s_]), (k, s_)   # bit for bit
         assert np.array_equal(bad[k][g < 0], good[k][g < 0])
+
+
+@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("acqf", [0, 1])
+def test_a_non_finite_query_coordinate_is_nan_in_all_its_outputs(emul, kind, acqf):
+    """include/scaml_gp.h (7g): one NaN coordinate in a query point whose source-pass columns are all finite (the Matern branch's fmax
+    drops the NaN: without the rule only that coordinate's gradient entry showed it, value / mu / var were those of a point at
+    distance ~0 from every training point) -- NaN in its value, every entry of its gradient, mu and var; the other queries bit for bit."""
+    prob = Problem(6, kind, seed=11)
+    q = LOW_VAR_Q + 1          # the last query of group 1 (n = 17)
+
+    def poison(a):
+        a["Xq"][q, 2] = float("nan")
+
+    good, bad = _run(emul, prob, acqf), _run(emul, prob, acqf, edit=poison)
+    others = np.arange(prob.Xq.shape[0]) != q
+    for k in ("value", "grad", "mu", "var"):
+        assert np.isnan(bad[k][q]).all(), (k, bad[k][q])
+        assert np.array_equal(bad[k][others], good[k][others]), k   # bit for bit
 
 
 def test_lds_footprint_holds_the_carve(emul):
