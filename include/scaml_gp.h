@@ -351,6 +351,24 @@ int scaml_target_acqf_batched_f64(const double* mu, const double* var, const dou
                                   int D, int kind, int acqf, double* value, double* grad, double* mu_out, double* var_out, void* stream);
 
 /*
+ * (5e') (5e) for studies that each own their source tasks (one source stack per study, scamlgp/benchmarking/local_runner.py:51-65:
+ * every study draws its own meta-tasks): the source arrays hold the tasks of ALL studies, Tsrc of them, and a group reads T of them.
+ *   task_base (G) int32: task slot t (0 <= t < T) of group g is source task src = task_base[g] + t.  X, theta, Linv, alpha, y_mean,
+ *       y_std and n_points -- (Tsrc, ...) arrays here -- are read at src; mu, var, cov and VA_tab[g] (T, N, Ma_g) stay indexed by the
+ *       slot, so (7g) takes the results with w / active (G, T) unchanged.
+ *   A src outside 0 .. Tsrc-1 makes (slot, query) a padding row: zeros in its strips of mu / var, no row of cov written, nothing read.
+ *   The grid is T x Mq workgroups as in (5e); a slot's workgroups stay on one XCD, and a study's query points are neighbours there.
+ *   Checks and limits: those of (5e), and task_base != NULL, Tsrc >= 1 (SCAML_E_BADARG).  Mq == 0, G == 0 or T == 0: nothing is enqueued.
+ * With task_base[g] = 0 for every g and Tsrc = T the results equal (5e)'s within the pass's own run-to-run scatter (the means are summed
+ * with LDS float atomics, and this is another kernel instance).
+ */
+int scaml_posterior_linv_grad_grouped_own_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                                              const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
+                                              const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points,
+                                              int T, int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var,
+                                              double* cov, const int32_t* task_base, int Tsrc, void* stream);
+
+/*
  * (8) The target GP's training objective with its analytic gradient, and the whole refit, in ONE launch.
  * Replaces what the reference runs on every report(): scamlgp/optimizer.py:176-185 rebuilds ScaMLGP and calls
  * optimize_marginal_likelihood (scamlgp/utils.py:139-212), which drives scipy L-BFGS-B through torch autograd over
@@ -493,6 +511,22 @@ int scaml_studies_acqf_opt_f64(const double* x0, const int32_t* group, const dou
                                int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi, int max_iter,
                                int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace,
                                double* x, double* f, int32_t* stats, void* stream);
+
+/*
+ * (7h') (7h) for studies that each own their source tasks: the same workspace (scaml_studies_acqf_opt_workspace_bytes with T = the
+ * tasks per study), the same state machine and step kernel; only the evaluation launch of every round is (5e') instead of (5e).
+ *   task_base (G) int32, Tsrc: as (5e') takes them -- X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s hold Tsrc tasks, study g
+ *       reads tasks task_base[g] .. task_base[g] + T - 1; w, active (G, T) and VA_tab[g] (T, N, n_g) are per slot.
+ * Checks and limits: those of (7h), and task_base != NULL, Tsrc >= 1 (SCAML_E_BADARG), all before the first launch.
+ */
+int scaml_studies_acqf_opt_own_f64(const double* x0, const int32_t* group, const double* const* VA_tab, const double* X, const double* theta_s,
+                                   const double* Linv, const double* alpha_s, const double* y_mean, const double* y_std,
+                                   const int32_t* n_points_s, const double* w, const uint8_t* active, const double* Xt, const double* theta_t,
+                                   const double* L, const double* Linv_diag, const double* alpha_t, const int32_t* n_points_t,
+                                   const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int B, int G,
+                                   int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi,
+                                   int max_iter, int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags,
+                                   void* workspace, double* x, double* f, int32_t* stats, const int32_t* task_base, int Tsrc, void* stream);
 
 #ifdef __cplusplus
 }

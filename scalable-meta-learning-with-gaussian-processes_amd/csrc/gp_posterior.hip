@@ -163,9 +163,13 @@ struct PosteriorArgs<true> {
 // groups, each with its own leading points (count, V, coordinates) -- a strip in GRAD mode is ONE query point, so the group is uniform
 // per workgroup and its count, V pointer and coordinate base are scalar loads.  GROUPED = false is the pass as it always was: the
 // argument block is PosteriorParams itself and the group's values are read where the ungrouped ones were.
-template <int KIND, bool COV, bool GRAD, bool GROUPED = false>
+// OWN (scaml_posterior_linv_grad_grouped_own_f64): every group owns its source tasks -- task slot `task` of group g reads source task
+// task_base[g] + task of the Tsrc tasks in the source arrays; the outputs and the group's VA stay indexed by the slot.  An instantiation
+// of its own: the grouped pass without the table keeps its instruction stream.
+template <int KIND, bool COV, bool GRAD, bool GROUPED = false, bool OWN = false>
 __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename PosteriorArgs<GROUPED>::type pp) {
   static_assert(!GROUPED || (COV && GRAD), "the grouped pass is the GRAD pass with its covariance block");
+  static_assert(!OWN || GROUPED, "per-group source tasks belong to the grouped pass");
   const PosteriorParams& p = PosteriorArgs<GROUPED>::base(pp);
   // eight waves share one K_*^T strip (the row blocks are dealt 8 ways: twice the waves per byte of LDS to hide the L^-1 segment loads)
   constexpr int NW = 8;
@@ -178,6 +182,7 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
   const int strip = slot % strips;
   if (task >= p.T) return;
   int grp = 0;
+  int src = task;   // the source task read; `task` stays the slot of the outputs and of a group's VA
   if (GROUPED) {
     grp = PosteriorArgs<GROUPED>::ga(pp).group[strip];
     if (grp < 0 || grp >= PosteriorArgs<GROUPED>::ga(pp).G) {   // a padding row: zeros, nothing of any group is read
@@ -187,12 +192,24 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
       }
       return;
     }
+    if (OWN) {
+      // slot `task` of this group is source task task_base[grp] + task (uniform per workgroup: a scalar load, as the group's count and
+      // V pointer are); a source task outside the arrays is a padding row like the one above
+      src = (int)((unsigned)PosteriorArgs<GROUPED>::ga(pp).task_base[grp] + (unsigned)task);
+      if ((unsigned)src >= (unsigned)PosteriorArgs<GROUPED>::ga(pp).Tsrc) {
+        if (threadIdx.x < 16) {
+          if (p.mu) p.mu[(size_t)task * M + 16 * strip + threadIdx.x] = 0.0;
+          if (p.var) p.var[(size_t)task * M + 16 * strip + threadIdx.x] = 0.0;
+        }
+        return;
+      }
+    }
   }
   // (the wave index stays a vector value here: as a scalar -- SCAML_WAVE_INDEX, which pays in the L^-1 and gradient kernels -- this
   //  kernel measured 3 % slower at C3, 178.9 against 173.6 us)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lc = lane & 15, lq = lane >> 4;
-  int n = p.n_points ? p.n_points[task] : N;
+  int n = p.n_points ? p.n_points[src] : N;
   n = n < 0 ? 0 : (n > N ? N : n);
   // LDS: exp table [64] | alpha [NP] | invl [D4] | xq [D4][16] | red [32] | |xq|^2 [16] | |x|^2 [NP] | K_*^T strip [NP][16];
   // D4 = D rounded up to the MFMA k-step, the extra entries are zeros.  (Round 2: the task's points are no longer staged -- they
@@ -208,18 +225,18 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
   double* Ks = nr + NP;
   // End of the carve, Ks + NP * 16: posterior_linv_lds_doubles(N, D) (gp_posterior_params.h) -- change both together.
 
-  const double* Xg = p.X + (size_t)task * N * D;
-  const double* th = p.theta + (size_t)task * (D + 2);
-  const double* Li = p.L + (size_t)task * N * N;   // L^-1 here
+  const double* Xg = p.X + (size_t)src * N * D;
+  const double* th = p.theta + (size_t)src * (D + 2);
+  const double* Li = p.L + (size_t)src * N * N;   // L^-1 here
   const double os = th[D];
-  const double ym = p.y_mean ? p.y_mean[task] : 0.0;
-  const double ys = p.y_std ? p.y_std[task] : 1.0;
+  const double ym = p.y_mean ? p.y_mean[src] : 0.0;
+  const double ys = p.y_std ? p.y_std[src] : 1.0;
   const int qc = 16 * strip + lc;   // this lane's query point
 
   exp2_table_init(exptab, tid);
   for (int d = tid; d < D4; d += blockDim.x) invl[d] = d < D ? 1.0 / th[d] : 0.0;   // strided: D may exceed the 256 threads
   if (tid < 32) red[tid] = 0.0;
-  for (int r = tid; r < NP; r += blockDim.x) alpha_s[r] = r < n ? p.alpha[(size_t)task * N + r] : 0.0;
+  for (int r = tid; r < NP; r += blockDim.x) alpha_s[r] = r < n ? p.alpha[(size_t)src * N + r] : 0.0;
   __syncthreads();
   for (int r = tid; r < NP; r += blockDim.x) {
     double nrm = 0.0;
@@ -695,3 +712,5 @@ template __global__ void scaml::gp_posterior_linv_kernel<0, true, true>(scaml::P
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, true>(scaml::PosteriorParams);
 template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, true>(scaml::PosteriorGroupedParams);   // (5e)
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, true>(scaml::PosteriorGroupedParams);
+template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, true, true>(scaml::PosteriorGroupedParams);   // (5e')
+template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, true, true>(scaml::PosteriorGroupedParams);

@@ -35,6 +35,7 @@ struct PosteriorParams {
 
 // The grouped GRAD pass (scaml_posterior_linv_grad_grouped_f64): query point q belongs to group[q], every group has its own leading
 // points.  In `base`: Ma = Ma_max (row count of cov and of a group's slice of Xa), VA / Xa unused.
+// T = the task slots of a group (rows of mu / var / cov).
 struct PosteriorGroupArgs {
   const int32_t* group;         // (Mq) group of a query point; negative: a padding row
   const int32_t* n_a;           // (G) leading points per group, 1 <= n_a[g] <= Ma_max
@@ -42,6 +43,12 @@ struct PosteriorGroupArgs {
   const double* Xa;             // (G, Ma_max, D) the leading points, padded
   int G;
   int pad_;
+  // per-group source tasks (scaml_posterior_linv_grad_grouped_own_f64, the kernel's OWN instantiation; unused otherwise -- appended, so
+  // that the block above keeps its offsets): task slot t of group g reads source task task_base[g] + t of the Tsrc tasks in the source
+  // arrays (X, theta, L, alpha, y_mean, y_std, n_points); outputs and VA_tab[g] stay indexed by the slot
+  const int32_t* task_base;     // (G)
+  int Tsrc;
+  int pad2_;
 #ifdef __HIPCC__
   __device__ int count(int g, int ma_max) const {   // a group's count, kept inside the rows the host sized everything for
     const int c = n_a[g];

@@ -70,6 +70,7 @@ struct Module {
   hipFunction_t tgt_assemble[2] = {}, tgt_finish = nullptr, tgt_fit = nullptr, tgt_fit_batched = nullptr, tgt_grad[2] = {};
   hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {};   // value only; value + gradient per kind
   hipFunction_t post_linv_grouped[2] = {}, tgt_acqf_batched = nullptr;   // lock-step studies: grouped GRAD pass, batched acquisition
+  hipFunction_t post_linv_grouped_own[2] = {};                           // the grouped pass with per-group source tasks
   hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {}, stack_step = nullptr, acqf_opt_step = nullptr;
   hipFunction_t blk_solve[2][2] = {}, blk_syrk[2] = {};   // solve: [kind][D <= 8]
   hipFunction_t mllgrad_fused[4][2][2] = {};   // [size class NBT = 2, 4, 8, 16][kind][LDS-DMA staging]
@@ -88,10 +89,11 @@ struct Module {
     std::vector<KernelRow> rows = {
         {post, "_ZN5scaml19gp_posterior_kernelILi%dEEEvNS_15PosteriorParamsE", kLdsLimit, {K}},
         {post_cov, "_ZN5scaml23gp_posterior_cov_kernelILi%dEEEvNS_18PosteriorCovParamsE", 0, {K}},
-        {post_linv, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_cov, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_cov, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
         {&tgt_acqf_batched, "scaml_target_acqf_batched_kernel", kLdsLimit, {}},
         {&wsum, "scaml_weighted_task_sum_kernel", 0, {}},
         {&linv, "_ZN5scaml14gp_linv_kernelENS_10LinvParamsE", kLdsLimit, {}},
@@ -743,14 +745,15 @@ namespace {
 int grouped_grad_launch(Module& m, const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
                         const double* const* VA_tab, const double* X, const double* theta, const double* Linv, const double* alpha,
                         const double* y_mean, const double* y_std, const int32_t* n_points, int T, int N, int Mq, int G, int Ma_max, int D,
-                        int kind, double* mu, double* var, double* cov, void* stream) {
+                        int kind, double* mu, double* var, double* cov, const int32_t* task_base, int Tsrc, void* stream) {   // (task_base NULL: (5e) as it was)
   const size_t lds = scaml::posterior_linv_lds_doubles(N, D) * sizeof(double);
   scaml::PosteriorGroupedParams p{};
   p.base = scaml::PosteriorParams{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N, 16 * Mq, D, 0, 0, 0,
                                   nullptr, cov, Ma_max, 0, nullptr};
-  p.ga = scaml::PosteriorGroupArgs{group, n_points_a, VA_tab, Xa, G, 0};
+  p.ga = scaml::PosteriorGroupArgs{group, n_points_a, VA_tab, Xa, G, 0, task_base, Tsrc, 0};   // (with the table: T = task slots per group)
   const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * (unsigned)Mq;   // XCD-aware (task, strip) map inside the kernel
-  return launch(m.post_linv_grouped[kind], dim3(blocks), 512, lds, stream, "gp_posterior_linv_grouped", p);
+  return launch(task_base ? m.post_linv_grouped_own[kind] : m.post_linv_grouped[kind], dim3(blocks), 512, lds, stream,
+                task_base ? "gp_posterior_linv_grouped_own" : "gp_posterior_linv_grouped", p);
 }
 int acqf_batched_launch(Module& m, const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
                         const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
@@ -763,13 +766,15 @@ int acqf_batched_launch(Module& m, const double* mu, const double* var, const do
   return launch(m.tgt_acqf_batched, dim3((unsigned)Mq), scaml::STUDIES_ACQF_THREADS, lds, stream, "target_acqf_batched", p);   // a workgroup per query point
 }
 }  // namespace
-int scaml_posterior_linv_grad_grouped_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
-                                          const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
-                                          const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T,
-                                          int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov,
-                                          void* stream) {
+namespace {
+// (5e) and its per-group-source-task form: `own` = the entry point that takes task_base / Tsrc
+int grouped_grad_checked(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a, const double* const* VA_tab,
+                         const double* X, const double* theta, const double* Linv, const double* alpha, const double* y_mean,
+                         const double* y_std, const int32_t* n_points, int T, int N, int Mq, int G, int Ma_max, int D, int kind, double* mu,
+                         double* var, double* cov, bool own, const int32_t* task_base, int Tsrc, void* stream) {
   if (T < 0 || N < 1 || Mq < 0 || G < 0 || Ma_max < 1 || D < 1) return SCAML_E_BADARG;
   if (!Xq || !group || !Xa || !n_points_a || !VA_tab || !X || !theta || !Linv || !alpha || !mu || !var || !cov) return SCAML_E_BADARG;
+  if (own && (!task_base || Tsrc < 1)) return SCAML_E_BADARG;
   if (!valid_kind(kind)) return SCAML_E_BADARG;
   if (D > 15 || Ma_max > 96 || Ma_max > N || N > scaml_posterior_max_n() || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
   const size_t lds = scaml::posterior_linv_lds_doubles(N, D) * sizeof(double);
@@ -778,7 +783,24 @@ int scaml_posterior_linv_grad_grouped_f64(const double* Xq, const int32_t* group
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
   return grouped_grad_launch(*m, Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
-                             mu, var, cov, stream);
+                             mu, var, cov, own ? task_base : nullptr, Tsrc, stream);
+}
+}  // namespace
+int scaml_posterior_linv_grad_grouped_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                                          const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
+                                          const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T,
+                                          int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov,
+                                          void* stream) {
+  return grouped_grad_checked(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
+                              mu, var, cov, false, nullptr, 0, stream);
+}
+int scaml_posterior_linv_grad_grouped_own_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                                              const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
+                                              const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points,
+                                              int T, int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var,
+                                              double* cov, const int32_t* task_base, int Tsrc, void* stream) {
+  return grouped_grad_checked(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
+                              mu, var, cov, true, task_base, Tsrc, stream);
 }
 
 int scaml_target_acqf_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
@@ -1061,14 +1083,17 @@ long long scaml_studies_acqf_opt_workspace_bytes(int B, int G, int n_max, int T,
   return (long long)acqf_opt_layout(B, n_max, T, D, history).total;
 }
 
-int scaml_studies_acqf_opt_f64(const double* x0, const int32_t* group, const double* const* VA_tab, const double* X, const double* theta_s,
-                               const double* Linv, const double* alpha_s, const double* y_mean, const double* y_std,
-                               const int32_t* n_points_s, const double* w, const uint8_t* active, const double* Xt, const double* theta_t,
-                               const double* L, const double* Linv_diag, const double* alpha_t, const int32_t* n_points_t,
-                               const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int B, int G,
-                               int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi, int max_iter,
-                               int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace,
-                               double* x, double* f, int32_t* stats, void* stream) {
+namespace {
+// (7h) and its per-group-source-task form (`own`): only the evaluation launch of a round is handed the table
+int studies_acqf_opt_checked(const double* x0, const int32_t* group, const double* const* VA_tab, const double* X, const double* theta_s,
+                             const double* Linv, const double* alpha_s, const double* y_mean, const double* y_std,
+                             const int32_t* n_points_s, const double* w, const uint8_t* active, const double* Xt, const double* theta_t,
+                             const double* L, const double* Linv_diag, const double* alpha_t, const int32_t* n_points_t,
+                             const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int B, int G,
+                             int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi, int max_iter,
+                             int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace,
+                             double* x, double* f, int32_t* stats, bool own, const int32_t* task_base, int Tsrc, void* stream) {
+  if (own && (!task_base || Tsrc < 1)) return SCAML_E_BADARG;
   if (B < 0 || G < 0 || n_max < 1 || T < 1 || N < 1 || D < 1 || n_evals < 0 || max_iter < 0 || max_ls < 1) return SCAML_E_BADARG;
   if (!x0 || !group || !VA_tab || !X || !theta_s || !Linv || !alpha_s || !w || !active || !Xt || !theta_t || !L || !Linv_diag || !alpha_t ||
       !n_points_t || !m_all || !s_all || !info || !acqf_param || !lo || !hi || !workspace || !x || !f || !stats)
@@ -1101,7 +1126,7 @@ int scaml_studies_acqf_opt_f64(const double* x0, const int32_t* group, const dou
     // the evaluation kernels are handed group_live where they were handed group: a stopped start (and a padding row) returns at once.
     // (Arguments and sizes were checked above, once; only a failing launch can end the call here, with the rounds before it enqueued.)
     if ((rc = grouped_grad_launch(*m, Xq, live, Xt, n_points_t, VA_tab, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, T, N, B, G, n_max,
-                                  D, kind_s, mu, var, cov, stream)) != SCAML_OK)
+                                  D, kind_s, mu, var, cov, own ? task_base : nullptr, Tsrc, stream)) != SCAML_OK)
       return rc;
     if ((rc = acqf_batched_launch(*m, mu, var, cov, live, Xq, w, active, Xt, theta_t, L, Linv_diag, alpha_t, n_points_t, m_all, s_all, info,
                                   acqf_param, B, G, n_max, T, D, kind_t, acqf, value, grad, nullptr, nullptr, stream)) != SCAML_OK)
@@ -1109,6 +1134,33 @@ int scaml_studies_acqf_opt_f64(const double* x0, const int32_t* group, const dou
     if ((rc = launch(m->acqf_opt_step, dim3((unsigned)B), 64, 0, stream, "acqf_opt_step", p)) != SCAML_OK) return rc;
   }
   return SCAML_OK;
+}
+}  // namespace
+
+int scaml_studies_acqf_opt_f64(const double* x0, const int32_t* group, const double* const* VA_tab, const double* X, const double* theta_s,
+                               const double* Linv, const double* alpha_s, const double* y_mean, const double* y_std,
+                               const int32_t* n_points_s, const double* w, const uint8_t* active, const double* Xt, const double* theta_t,
+                               const double* L, const double* Linv_diag, const double* alpha_t, const int32_t* n_points_t,
+                               const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int B, int G,
+                               int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi, int max_iter,
+                               int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace,
+                               double* x, double* f, int32_t* stats, void* stream) {
+  return studies_acqf_opt_checked(x0, group, VA_tab, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, w, active, Xt, theta_t, L, Linv_diag,
+                                  alpha_t, n_points_t, m_all, s_all, info, acqf_param, B, G, n_max, T, N, D, kind_s, kind_t, acqf, lo, hi,
+                                  max_iter, history, max_ls, gtol, ftol, c1, n_evals, flags, workspace, x, f, stats, false, nullptr, 0, stream);
+}
+
+int scaml_studies_acqf_opt_own_f64(const double* x0, const int32_t* group, const double* const* VA_tab, const double* X, const double* theta_s,
+                                   const double* Linv, const double* alpha_s, const double* y_mean, const double* y_std,
+                                   const int32_t* n_points_s, const double* w, const uint8_t* active, const double* Xt, const double* theta_t,
+                                   const double* L, const double* Linv_diag, const double* alpha_t, const int32_t* n_points_t,
+                                   const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int B, int G,
+                                   int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi,
+                                   int max_iter, int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags,
+                                   void* workspace, double* x, double* f, int32_t* stats, const int32_t* task_base, int Tsrc, void* stream) {
+  return studies_acqf_opt_checked(x0, group, VA_tab, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, w, active, Xt, theta_t, L, Linv_diag,
+                                  alpha_t, n_points_t, m_all, s_all, info, acqf_param, B, G, n_max, T, N, D, kind_s, kind_t, acqf, lo, hi,
+                                  max_iter, history, max_ls, gtol, ftol, c1, n_evals, flags, workspace, x, f, stats, true, task_base, Tsrc, stream);
 }
 
 }  // extern "C"

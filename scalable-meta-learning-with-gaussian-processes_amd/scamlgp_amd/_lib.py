@@ -98,6 +98,8 @@ SIGNATURES = {
     "scaml_target_fantasy_acqf_f64": (_i, [_dp] * 5 + [_f, _f, _f, _dp, _i, _f] + [_dp] * 6 + [_i] * 5 + [_dp, _dp, c_void_p]),
     # (5e) Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points; T, N, Mq, G, Ma_max, D, kind; mu, var, cov
     "scaml_posterior_linv_grad_grouped_f64": (_i, [_dp] * 12 + [_i] * 7 + [_dp, _dp, _dp, c_void_p]),
+    # (5e') (5e)'s arrays and shapes; mu, var, cov; task_base, Tsrc
+    "scaml_posterior_linv_grad_grouped_own_f64": (_i, [_dp] * 12 + [_i] * 7 + [_dp, _dp, _dp, _dp, _i, c_void_p]),
     # (7g) 17 arrays; Mq, G, n_max, T, D, kind, acqf; value, grad, mu_out, var_out
     "scaml_target_acqf_batched_f64": (_i, [_dp] * 17 + [_i] * 7 + [_dp] * 4 + [c_void_p]),
     "scaml_target_fit_max_n": (_i, [_i, _i]),
@@ -117,6 +119,8 @@ SIGNATURES = {
     # (7h) x0, group; 8 source-stack arrays (5e); 12 study arrays (7g); B, G, n_max, T, N, D, kind_s, kind_t, acqf; lo, hi; max_iter, history, max_ls;
     # gtol, ftol, c1; n_evals, flags; workspace, x, f, stats
     "scaml_studies_acqf_opt_f64": (_i, [_dp] * 22 + [_i] * 9 + [_dp, _dp] + [_i] * 3 + [_f] * 3 + [_i, _u] + [_dp] * 4 + [c_void_p]),
+    # (7h') (7h)'s arguments; task_base, Tsrc
+    "scaml_studies_acqf_opt_own_f64": (_i, [_dp] * 22 + [_i] * 9 + [_dp, _dp] + [_i] * 3 + [_f] * 3 + [_i, _u] + [_dp] * 4 + [_dp, _i, c_void_p]),
     "scaml_debug_target_fit_path": (_i, [_i]),
     "scaml_debug_blocked_fit_path": (_i, [_i]),
     "scaml_debug_coop_far": (_i, [_i]),

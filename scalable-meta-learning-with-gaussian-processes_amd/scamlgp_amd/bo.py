@@ -273,10 +273,16 @@ class ScaMLGPBOStudies:
     between the two evaluation launches, so no start waits for another, a start that has stopped is no longer evaluated and the host
     reads one status block per chunk of rounds.  The end points come back with their acquisition values (no re-scoring pass); the final
     choice and the fall-back of the studies the batch does not take are ``"lockstep"``'s.  ``last_suggest_info``: ``batched``,
-    ``n_eval`` (rounds enqueued), ``n_calls``, ``evals_per_start`` and ``status`` per start.  ``num_studies=1`` is a legitimate use."""
+    ``n_eval`` (rounds enqueued), ``n_calls``, ``evals_per_start`` and ``status`` per start.  ``num_studies=1`` is a legitimate use.
 
-    def __init__(self, source_gps: Dict[Hashable, SourceGP], dim: int, num_studies: int, seeds: Optional[Sequence[int]] = None,
-                 suggest_mode: str = "sequential", **loop_kwargs):
+    One source stack PER study (the reference's protocol: ``benchmark_cls(seed=study_seed)`` / ``meta_data_seed=study_seed``,
+    scamlgp/benchmarking/local_runner.py:51-65, 178-181 -- every study draws its own meta-tasks): ``source_gps`` may be a sequence of S
+    dicts, as ``model.meta_fit_scamlgp_studies`` returns them (slices of one stack fitted in one call).  All three modes work: the
+    batched refit takes its source terms per study anyway, and the grouped source pass reads study s's tasks only
+    (``utils.StudiesAcquisition``).  A single dict keeps meaning "shared"."""
+
+    def __init__(self, source_gps: Union[Dict[Hashable, SourceGP], Sequence[Dict[Hashable, SourceGP]]], dim: int, num_studies: int,
+                 seeds: Optional[Sequence[int]] = None, suggest_mode: str = "sequential", **loop_kwargs):
         if suggest_mode not in ("sequential", "lockstep", "device"):
             raise ValueError(f"suggest_mode must be 'sequential', 'lockstep' or 'device', got {suggest_mode!r}")
         self.suggest_mode = suggest_mode
@@ -290,13 +296,17 @@ class ScaMLGPBOStudies:
         if "seed" in loop_kwargs:
             raise TypeError("pass seeds=[...] (one per study), not seed=")
         self.dim, self.num_studies, self.seeds = dim, S, seeds
+        # one dict: the stack shared by all studies; a sequence of S dicts: study s's own (model.meta_fit_scamlgp_studies)
+        per_study = None if isinstance(source_gps, dict) else list(source_gps)
+        if per_study is not None and len(per_study) != S:
+            raise ValueError(f"got {len(per_study)} source stacks for {S} studies")
         self.studies = []
         for s in range(S):
             kw = dict(loop_kwargs)
             for name in ("gp_likelihood", "gp_kernel"):
                 if kw.get(name) is not None:
                     kw[name] = copy.deepcopy(kw[name])
-            self.studies.append(ScaMLGPBOLoop(source_gps, dim, seed=seeds[s], **kw))
+            self.studies.append(ScaMLGPBOLoop(source_gps if per_study is None else per_study[s], dim, seed=seeds[s], **kw))
         if self.studies[0].model._shard is not None:
             raise NotImplementedError("lock-step studies are not implemented for a task-sharded source stack (shard=True)")
         self.fit_gens = [torch.Generator().manual_seed(v) for v in seeds]

@@ -254,6 +254,67 @@ class SourceGPStack:
             out.append(self.y_mean[t] + self.y_std[t] * self.y[t, :n])
         return torch.cat(out).unsqueeze(-1)
 
+    def slice(self, lo: int, hi: int) -> "SourceGPStackSlice":
+        """The stack over tasks [lo, hi) of this one: views of its tensors and factors, no copy (``SourceGPStackSlice``)."""
+        return SourceGPStackSlice(self, lo, hi)
+
+
+class SourceGPStackSlice(SourceGPStack):
+    """Tasks [lo, hi) of a parent stack as a stack of its own: ``X``, ``y``, ``y_mean``, ``y_std``, ``n_float``, ``n_points``, ``raw`` and
+    every entry of ``fit`` are the parent's tensors ``narrow``ed along the task axis (no copy; ``raw`` and ``fit`` follow the parent when
+    it is refitted), ``N`` is the parent's padded N, ``task_ids`` / ``n_list`` / ``raw_targets()`` are the slice's own -- so a ScaMLGP on
+    it standardises over ITS tasks' observations (scamlgp/model.py:264-273) and its source pass launches hi - lo tasks.  The
+    hyper-parameters and factors belong to the parent: ``set_theta`` and ``refresh`` raise here.  ``parent`` and ``lo`` are what the
+    grouped source pass of several slices needs (``utils.StudiesAcquisition``: the parent's arrays and a task base per study)."""
+
+    def __init__(self, parent: SourceGPStack, lo: int, hi: int):
+        if isinstance(parent, SourceGPStackSlice):
+            raise TypeError("slice the parent stack (a slice of a slice would hide the arrays the factors live in)")
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= parent.T:
+            raise ValueError(f"slice [{lo}, {hi}) of a stack of {parent.T} tasks")
+        if parent.shard is not None:
+            raise NotImplementedError("slices of a task-sharded source stack (shard=True) are not implemented")
+        self.parent, self.lo, self.hi = parent, lo, hi
+        T = hi - lo
+        self.device, self.kind, self.spec, self.D, self.N = parent.device, parent.kind, parent.spec, parent.D, parent.N
+        self.task_ids = parent.task_ids[lo:hi]
+        self.n_list = parent.n_list[lo:hi]
+        self.ragged = min(self.n_list) != self.N
+        self.X, self.y = parent.X.narrow(0, lo, T), parent.y.narrow(0, lo, T)
+        self.y_mean, self.y_std = parent.y_mean.narrow(0, lo, T), parent.y_std.narrow(0, lo, T)
+        self.n_float = parent.n_float.narrow(0, lo, T)
+        self.n_points = parent.n_points.narrow(0, lo, T) if self.ragged else None
+        self._rep_cache = {}
+        self._fit_view = (None, None)   # (the parent's fit dict, its narrowed twin)
+        self.shard = None
+
+    @property
+    def raw(self) -> torch.Tensor:
+        return self.parent.raw.narrow(0, self.lo, self.hi - self.lo)
+
+    @raw.setter
+    def raw(self, value) -> None:
+        raise RuntimeError("a slice's hyper-parameters belong to its parent stack: set them on the parent")
+
+    def set_theta(self, theta: torch.Tensor) -> None:
+        raise RuntimeError("a slice's hyper-parameters belong to its parent stack: call set_theta on the parent")
+
+    def refresh(self) -> dict:
+        raise RuntimeError("a slice's factors belong to its parent stack: call refresh on the parent")
+
+    @property
+    def fit(self) -> dict:
+        pf = self.parent.fit
+        if self._fit_view[0] is not pf:
+            Tp, T = self.parent.T, self.hi - self.lo
+            view = {k: (v.narrow(0, self.lo, T) if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == Tp else v) for k, v in pf.items()}
+            self._fit_view = (pf, view)
+        return self._fit_view[1]
+
+    def slice(self, lo: int, hi: int) -> "SourceGPStackSlice":
+        return SourceGPStackSlice(self, lo, hi)   # (raises)
+
 
 class SourceGP:
     """View of one task of a SourceGPStack with the attributes the reference touches on a
@@ -353,6 +414,56 @@ def meta_fit_scamlgp(
     stack.shard = ts if ts is not None and ts.world > 1 else None
     optimize_marginal_likelihood(stack, num_restarts=num_restarts_log_likelihood, **(fit_options or {}))
     return {tid: SourceGP(stack, i) for i, tid in enumerate(stack.task_ids)}
+
+
+def meta_fit_scamlgp_studies(
+    meta_data_per_study: Sequence[Dict[Hashable, SupervisedDataset]],
+    likelihood: Optional[hyper.GaussianLikelihood] = None,
+    covar_module: Optional[hyper.ScaleKernel] = None,
+    num_restarts_log_likelihood: int = 5,
+    seed: Optional[int] = None,
+    device: Optional[torch.device] = None,
+    shard: bool = False,
+    group=None,
+    fit_options: Optional[dict] = None,
+) -> List[Dict[Hashable, SourceGP]]:
+    """``meta_fit_scamlgp`` for S studies that each bring their own meta-data (scamlgp/benchmarking/local_runner.py:51-65: every
+    study of a configuration draws its own meta-tasks): ONE stack of S * T tasks, fitted by one ``optimize_marginal_likelihood`` call
+    exactly as one large stack is (``fit_options={"driver": "device"}`` for the optimiser on the device), and S dicts of ``SourceGP``s
+    on its slices (``SourceGPStack.slice``: study s = tasks [s T, (s + 1) T)).  A ``ScaMLGP`` on such a dict sees a T-task stack;
+    ``bo.ScaMLGPBOStudies`` takes the list as its ``source_gps``.  The dicts need an equal number of tasks T and one input dimension;
+    task ids need only be unique within a study.  ``shard=True`` is refused."""
+    from .utils import optimize_marginal_likelihood
+
+    if shard:
+        raise NotImplementedError("per-study source stacks are not implemented for a task-sharded fit (shard=True)")
+    studies = list(meta_data_per_study)
+    if not studies:
+        raise ValueError("Empty meta data. Needs at least one study.")
+    if seed is not None:
+        torch.manual_seed(seed=seed)
+    for md in studies:
+        validate_meta_data(md)
+        if list(md.values())[0].X.dim() != 2:
+            raise ValueError("batched (batch_shape x n x d) meta-data is not supported by the stacked GPU path")
+    T, D = len(studies[0]), int(list(studies[0].values())[0].X.shape[-1])
+    for s, md in enumerate(studies):
+        if len(md) != T:
+            raise ValueError(f"study {s} has {len(md)} source tasks but study 0 has {T}: the studies must have an equal number of tasks")
+        d = int(list(md.values())[0].X.shape[-1])
+        if d != D:
+            raise ValueError(f"study {s} has input dimension {d} but study 0 has {D}")
+    lik, cov = _resolve_modules(likelihood, covar_module, D, hyper.get_kernel_source_gp)
+    ids = [(s, tid) for s, md in enumerate(studies) for tid in md]
+    Xs, Ys = zip(*[_canonical_order(d.X(), d.Y()) for md in studies for d in md.values()])
+    stack = SourceGPStack(ids, Xs, Ys, kind=cov.kind, spec=hyper.spec_from_modules(lik, cov), device=device)
+    optimize_marginal_likelihood(stack, num_restarts=num_restarts_log_likelihood, **(fit_options or {}))
+    out = []
+    for s, md in enumerate(studies):
+        sl = stack.slice(s * T, (s + 1) * T)
+        sl.task_ids = list(md.keys())
+        out.append({tid: SourceGP(sl, i) for i, tid in enumerate(sl.task_ids)})
+    return out
 
 
 def significant_weights_mask(weights: torch.Tensor, std_Y_vals: torch.Tensor, threshold: float) -> torch.Tensor:

@@ -656,12 +656,22 @@ def target_fantasy_acqf(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor,
 def source_posteriors_grad_grouped(Xq: torch.Tensor, group: torch.Tensor, Xa: torch.Tensor, n_points_a: torch.Tensor, VA_tab: torch.Tensor,
                                    X: torch.Tensor, theta: torch.Tensor, kind: int, Linv: torch.Tensor, alpha: torch.Tensor,
                                    y_mean: Optional[torch.Tensor] = None, y_std: Optional[torch.Tensor] = None,
-                                   n_points: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                                   n_points: Optional[torch.Tensor] = None, task_base: Optional[torch.Tensor] = None,
+                                   tasks_per_group: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """``source_posteriors_grad`` with the query points Xq (Mq, D) divided among G groups, one launch of
     scaml_posterior_linv_grad_grouped_f64: ``group`` (Mq,) int32 (negative: a padding row, zeros), ``Xa`` (G, Ma_max, D) the groups'
     leading points, ``n_points_a`` (G,) int32 their counts, ``VA_tab`` (G,) int64: the ADDRESSES of the groups' V (T, N, Ma_g) tensors
     (``ScaMLGP._train_VA``; the caller keeps them alive).  Returns dict(mu, var (T, Mq, 16), cov (T, Ma_max, Mq * 16): rows
-    a < Ma_{group[q]} of strip q are written, the rest is uninitialised)."""
+    a < Ma_{group[q]} of strip q are written, the rest is uninitialised).
+
+    ``task_base`` (G,) int32: every group owns its source tasks (scaml_posterior_linv_grad_grouped_own_f64) -- the source arrays hold
+    Tsrc = X.shape[0] tasks, task slot t of group g reads task ``task_base[g] + t``, and T = ``tasks_per_group`` slots are the leading
+    axis of the outputs and of the groups' V."""
+    if task_base is not None:
+        return _source_posteriors_grad_grouped_own(Xq, group, Xa, n_points_a, VA_tab, X, theta, kind, Linv, alpha, y_mean, y_std, n_points,
+                                                   task_base, tasks_per_group)
+    if tasks_per_group is not None:
+        raise ValueError("tasks_per_group goes with task_base")
     T, N, D = X.shape
     Mq = Xq.shape[0]
     G, Ma_max = int(Xa.shape[0]), int(Xa.shape[1])
@@ -686,6 +696,41 @@ def source_posteriors_grad_grouped(Xq: torch.Tensor, group: torch.Tensor, Xa: to
                                                             _ptr(Linv), _ptr(alpha), _ptr(y_mean), _ptr(y_std), _ptr(n_points), T, N, Mq, G, Ma_max, D,
                                                             int(kind), _ptr(mu), _ptr(var), _ptr(cov), _stream_handle())
     _lib.check_rc(rc, "scaml_posterior_linv_grad_grouped_f64")
+    return dict(mu=mu, var=var, cov=cov)
+
+
+def _source_posteriors_grad_grouped_own(Xq, group, Xa, n_points_a, VA_tab, X, theta, kind, Linv, alpha, y_mean, y_std, n_points, task_base,
+                                        tasks_per_group, cov_out=None) -> Dict[str, torch.Tensor]:
+    """``source_posteriors_grad_grouped`` with ``task_base``: the source arrays are (Tsrc, ...), the outputs (T, ...).  ``cov_out``: the
+    (T, Ma_max, Mq * 16) buffer cov is written into (tests prefill it to see which rows a launch writes)."""
+    if tasks_per_group is None:
+        raise ValueError("task_base needs tasks_per_group (the task slots of a group)")
+    Tsrc, N, D = X.shape
+    T, Mq = int(tasks_per_group), Xq.shape[0]
+    G, Ma_max = int(Xa.shape[0]), int(Xa.shape[1])
+    X = _check(X, "X")
+    Xq = _check(Xq, "Xq", (Mq, D))
+    group = _check(group, "group", (Mq,), torch.int32)
+    Xa = _check(Xa, "Xa", (G, Ma_max, D))
+    n_points_a = _check(n_points_a, "n_points_a", (G,), torch.int32)
+    VA_tab = _check(VA_tab, "VA_tab", (G,), torch.int64)
+    task_base = _check(task_base, "task_base", (G,), torch.int32)
+    theta = _check(theta, "theta", (Tsrc, D + 2))
+    Linv = _check(Linv, "Linv", (Tsrc, N, N))
+    alpha = _check(alpha, "alpha", (Tsrc, N))
+    y_mean = _opt(y_mean, "y_mean", (Tsrc,))
+    y_std = _opt(y_std, "y_std", (Tsrc,))
+    n_points = _opt(n_points, "n_points", (Tsrc,), torch.int32)
+    dev = X.device
+    with torch.cuda.device(dev):
+        mu = _empty(dev, T, Mq, 16)
+        var = _empty(dev, T, Mq, 16)
+        cov = _empty(dev, T, Ma_max, Mq * 16) if cov_out is None else _check(cov_out, "cov_out", (T, Ma_max, Mq * 16))
+        rc = _lib.lib.scaml_posterior_linv_grad_grouped_own_f64(_ptr(Xq), _ptr(group), _ptr(Xa), _ptr(n_points_a), _ptr(VA_tab), _ptr(X),
+                                                                _ptr(theta), _ptr(Linv), _ptr(alpha), _ptr(y_mean), _ptr(y_std), _ptr(n_points),
+                                                                T, N, Mq, G, Ma_max, D, int(kind), _ptr(mu), _ptr(var), _ptr(cov),
+                                                                _ptr(task_base), Tsrc, _stream_handle())
+    _lib.check_rc(rc, "scaml_posterior_linv_grad_grouped_own_f64")
     return dict(mu=mu, var=var, cov=cov)
 
 
@@ -1112,14 +1157,21 @@ def studies_acqf_opt_state_doubles(D: int, history: int) -> int:
 class StudiesAcqfOpt:
     """One optimisation of ``scaml_studies_acqf_opt_f64``: the checked arguments, the workspace and the outputs, so that the rounds can
     be enqueued in chunks (``enqueue``; the first call resets, the later ones continue).  ``arrays``: the 22 device arrays of the C
-    signature from ``x0`` to ``acqf_param``, in its order (None for the optional y_mean / y_std / n_points_s)."""
+    signature from ``x0`` to ``acqf_param``, in its order (None for the optional y_mean / y_std / n_points_s).  ``task_base`` (G,)
+    int32: every study owns its source tasks (scaml_studies_acqf_opt_own_f64) -- the eight source arrays then hold ``Tsrc`` tasks and T
+    is the tasks per study."""
 
     def __init__(self, arrays, B: int, G: int, n_max: int, T: int, N: int, D: int, kind_s: int, kind_t: int, acqf: int, lo: torch.Tensor, hi: torch.Tensor,
-                 max_iter: int, history: int = 10, max_ls: int = ACQF_OPT_MAX_LS, gtol: float = 1e-5, ftol: float = 2.2e-9, c1: float = 1e-4):
+                 max_iter: int, history: int = 10, max_ls: int = ACQF_OPT_MAX_LS, gtol: float = 1e-5, ftol: float = 2.2e-9, c1: float = 1e-4,
+                 task_base: Optional[torch.Tensor] = None, Tsrc: Optional[int] = None):
         dev = arrays[0].device
         i32, u8, i64, f64, nbm = torch.int32, torch.uint8, torch.int64, torch.float64, (n_max + 15) // 16
-        spec = [("x0", (B, D), f64), ("group", (B,), i32), ("VA_tab", (G,), i64), ("X", (T, N, D), f64), ("theta_s", (T, D + 2), f64),
-                ("Linv", (T, N, N), f64), ("alpha_s", (T, N), f64), ("y_mean", (T,), f64), ("y_std", (T,), f64), ("n_points_s", (T,), i32),
+        if (task_base is None) != (Tsrc is None):
+            raise ValueError("task_base and Tsrc go together")
+        Ts = T if task_base is None else int(Tsrc)   # tasks in the source arrays
+        self._own = None if task_base is None else (_check(task_base, "task_base", (G,), i32), Ts)
+        spec = [("x0", (B, D), f64), ("group", (B,), i32), ("VA_tab", (G,), i64), ("X", (Ts, N, D), f64), ("theta_s", (Ts, D + 2), f64),
+                ("Linv", (Ts, N, N), f64), ("alpha_s", (Ts, N), f64), ("y_mean", (Ts,), f64), ("y_std", (Ts,), f64), ("n_points_s", (Ts,), i32),
                 ("w", (G, T), f64), ("active", (G, T), u8), ("Xt", (G, n_max, D), f64), ("theta_t", (G, D + 2), f64),
                 ("L", (G, n_max, n_max), f64), ("Linv_diag", (G, nbm, 16, 16), f64), ("alpha_t", (G, n_max), f64), ("n_points_t", (G,), i32),
                 ("m_all", (G,), f64), ("s_all", (G,), f64), ("info", (G,), i32), ("acqf_param", (G,), f64)]
@@ -1142,11 +1194,12 @@ class StudiesAcqfOpt:
             self.ws = _empty(dev, max(self.nbytes, 16), dtype=torch.uint8)
 
     def enqueue(self, n_evals: int) -> None:
+        fn, own = ("scaml_studies_acqf_opt_f64", ()) if self._own is None else ("scaml_studies_acqf_opt_own_f64", (_ptr(self._own[0]), self._own[1]))
         with torch.cuda.device(self.device):
-            rc = _lib.lib.scaml_studies_acqf_opt_f64(*self._ptrs, *self._shape, _ptr(self.lo), _ptr(self.hi), *self._opts, int(n_evals),
-                                                     _lib.ACQF_OPT_CONTINUE if self.n_calls else 0, _ptr(self.ws), _ptr(self.x), _ptr(self.f),
-                                                     _ptr(self.stats), _stream_handle())
-        _lib.check_rc(rc, "scaml_studies_acqf_opt_f64")
+            rc = getattr(_lib.lib, fn)(*self._ptrs, *self._shape, _ptr(self.lo), _ptr(self.hi), *self._opts, int(n_evals),
+                                       _lib.ACQF_OPT_CONTINUE if self.n_calls else 0, _ptr(self.ws), _ptr(self.x), _ptr(self.f),
+                                       _ptr(self.stats), *own, _stream_handle())
+        _lib.check_rc(rc, fn)
         self.n_calls += 1
         self.n_eval += int(n_evals)
 

@@ -114,6 +114,8 @@ def _fit_stack(stack: SourceGPStack, num_restarts: int, max_iter: int = 200, use
     """All T tasks x (1 + num_restarts) starts as ONE batch: every L-BFGS iteration is one fused-fit
     launch + one gradient launch over (1 + R) * T problems.  ``driver="device"`` keeps the optimiser itself on the device as well
     (``scaml_stack_fit_f64``: same starts, same algorithm per problem, no host round trip per evaluation)."""
+    if getattr(stack, "parent", None) is not None:
+        raise RuntimeError("a slice's hyper-parameters belong to its parent stack: fit the parent")
     if driver == "device":
         return _fit_stack_device(stack, num_restarts, max_iter, evals_per_call)
     if driver != "host":
@@ -270,7 +272,9 @@ def _fit_target(model: ScaMLGP, num_restarts: int, maxiter: int = 200, use_graph
 
 def fit_targets_batched(models: Sequence[ScaMLGP], num_restarts: int, maxiter: int = 200, rng: Optional[Sequence[torch.Generator]] = None,
                         **fit_options) -> None:
-    """``optimize_marginal_likelihood(model, num_restarts)`` for several ScaMLGP models on ONE source stack, with every model the
+    """``optimize_marginal_likelihood(model, num_restarts)`` for several ScaMLGP models -- on one source stack, or each on its own
+    (slices of one parent, ``model.meta_fit_scamlgp_studies``: the kernel takes means and covariances per problem; the models need only
+    agree in T, D and the kernel family) --, with every model the
     library's target-fit kernel takes refitted in ONE launch (``scaml_target_fit_batched_f64``: models x (1 + num_restarts) workgroups
     instead of 1 + num_restarts per launch, one launch after the other).  Per model the starts, the device optimisation and the
     best-of-restarts choice are those of the single call, so the fitted state is the same.  ``rng[i]``: the generator model i's
@@ -421,7 +425,7 @@ class ExpectedImprovement:
 
 
 class StudiesAcquisition:
-    """The acquisition functions of S ScaMLGP models on ONE source stack, evaluated together: ``value_and_grad(X, group)`` is two
+    """The acquisition functions of S ScaMLGP models on ONE source stack (or on slices of one: see below), evaluated together: ``value_and_grad(X, group)`` is two
     library launches whatever S is -- the grouped GRAD source pass (``ops.source_posteriors_grad_grouped``: a query point's covariance
     block is taken against ITS study's training inputs) and the batched target acquisition (``ops.target_acqf_batched``: weighted
     task sums, Knq, the solve against the study's cached factor of Knn, posterior, gradient, UCB / EI) -- where each model's own
@@ -433,7 +437,12 @@ class StudiesAcquisition:
     arrays (pruned weights and mask, theta, training inputs, standardiser, the factor ``_target_factor()`` -- computed through the
     model's own posterior path where it is absent --, alpha, beta or best_f) are packed from the models' caches here, padded to the
     largest n.  The models' ``_train_VA()`` tensors are passed by address (10 MB each at configs[4]: no padded copy); this object
-    keeps them alive."""
+    keeps them alive.
+
+    Per-study source stacks: the models' stacks may instead be slices of one parent with an equal number of tasks T
+    (``model.meta_fit_scamlgp_studies``).  The source pass then reads the PARENT's arrays with ``task_base[g]`` = the first task of
+    study g (``scaml_posterior_linv_grad_grouped_own_f64``: a study's query points meet only its own T tasks, the grid stays T x Mq);
+    ``w`` / ``active`` stay (G, T) per slice.  ``task_base`` is None on the shared-stack path."""
 
     def __init__(self, afs: Sequence[Union[UpperConfidenceBound, ExpectedImprovement]]):
         afs = list(afs)
@@ -445,8 +454,14 @@ class StudiesAcquisition:
         self.acqf = ops.ACQF_UCB if isinstance(afs[0], UpperConfidenceBound) else ops.ACQF_EI
         models = [a.model for a in afs]
         m0 = models[0]
+        # the source stacks: one object shared by all studies, or slices of one parent with an equal number of tasks (per-study stacks,
+        # model.meta_fit_scamlgp_studies) -- then the pass reads the parent's arrays, study g's tasks from task_base[g]
+        st0 = m0._stack
+        parent = getattr(st0, "parent", None)
+        shared = all(m._stack is st0 for m in models)
+        own = (not shared) and parent is not None and all(getattr(m._stack, "parent", None) is parent and m._stack.T == st0.T for m in models)
         for m in models:
-            if m._stack is not m0._stack or m.kind != m0.kind or m.T != m0.T:
+            if not (shared or own) or m.kind != m0.kind or m.T != m0.T:
                 raise ValueError("the studies' models must share one source stack and one kernel family")
             if m._shard is not None:
                 raise NotImplementedError("the batched acquisition is not implemented for a task-sharded source stack (shard=True)")
@@ -454,6 +469,9 @@ class StudiesAcquisition:
                 raise NotImplementedError("the batched acquisition takes ordinary models with 1 <= n <= 96 training points and D <= 15")
         self.models, self.kind, self.device = models, m0.kind, m0.device
         st = m0._stack
+        self.source = parent if own else st0   # whose arrays the source pass reads
+        self.task_base = torch.tensor([m._stack.lo for m in models], dtype=torch.int32).to(m0.device) if own else None
+        self._own = dict(task_base=self.task_base, tasks_per_group=st0.T) if own else {}
         G, D, dev = len(models), st.D, m0.device
         ns = [m.n for m in models]
         n_max, nbm = max(ns), (max(ns) + 15) // 16
@@ -492,9 +510,9 @@ class StudiesAcquisition:
         """dict(value (Mq,), grad (Mq, D) or None, mu, var (Mq,) or None) at X (Mq, D), point q scored by study ``group[q]`` (int32, on the
         device; a negative entry is a padding row and gives zeros)."""
         Xq = torch.as_tensor(X, dtype=torch.float64).reshape(-1, self.D).to(self.device).contiguous()
-        st, f = self.models[0]._stack, self.models[0]._stack.fit
+        st, f = self.source, self.source.fit
         g = ops.source_posteriors_grad_grouped(Xq, group, self.Xt, self.n_points, self.VA_tab, st.X, st.theta, st.kind, f["Linv"], f["alpha"],
-                                               st.y_mean, st.y_std, st.n_points)
+                                               st.y_mean, st.y_std, st.n_points, **self._own)
         return ops.target_acqf_batched(g["mu"], g["var"], g["cov"], group, Xq, self.w, self.active, self.Xt, self.theta, self.L, self.Linv_diag,
                                        self.alpha, self.n_points, self.m_all, self.s_all, self.info, self.acqf_param, self.acqf, self.kind,
                                        want_grad=want_grad, want_posterior=want_posterior)
@@ -519,10 +537,12 @@ class StudiesAcquisition:
         hi = torch.as_tensor(bounds[1], dtype=torch.float64).expand(D).contiguous()
         if bool((lo > hi).any()):
             raise ValueError("bounds: lo > hi")
-        st, f = self.models[0]._stack, self.models[0]._stack.fit
+        st, f = self.source, self.source.fit
         arrays = [X0, group.to(dev), self.VA_tab, st.X, st.theta, f["Linv"], f["alpha"], st.y_mean, st.y_std, st.n_points, self.w, self.active,
                   self.Xt, self.theta, self.L, self.Linv_diag, self.alpha, self.n_points, self.m_all, self.s_all, self.info, self.acqf_param]
-        T, N = st.X.shape[0], st.X.shape[1]
+        T, N = self.w.shape[1], st.X.shape[1]
+        if self.task_base is not None:   # per-study source tasks: T slots per study of the Tsrc tasks in the parent's arrays
+            options = dict(options, task_base=self.task_base, Tsrc=st.X.shape[0])
         return ops.StudiesAcqfOpt(arrays, B, self.G, self.n_max, T, N, D, st.kind, self.kind, self.acqf, lo.to(dev), hi.to(dev), max_iter, **options)
 
     def optimize(self, X0: torch.Tensor, group: torch.Tensor, max_iter: int, bounds=(0.0, 1.0), evals_per_call: Optional[int] = None,

@@ -9,6 +9,8 @@ medians over the timed steps (the first step of a size is a warm-up and is not c
 
   python tools/dev_studies_time.py [--sizes 1,8,32,64] [--steps K] [--out profiles/studies_timings.txt]
   python tools/dev_studies_time.py --suggest [--sweep 1,2,4,8,16] [--evals-per-call K]    suggest() alone, in its three modes
+  python tools/dev_studies_time.py --own-stacks [--sizes 8,32,128] [--out profiles/studies_own_stacks_timings.txt]
+      one source stack PER study at hartmann6.py's shape (see own_stacks_table)
 """
 import argparse
 import os
@@ -23,7 +25,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from scamlgp_amd import model as M, ops, synthetic, utils  # noqa: E402
+from scamlgp_amd import hyper, model as M, ops, synthetic, utils  # noqa: E402
 from scamlgp_amd.bo import ScaMLGPBOLoop, ScaMLGPBOStudies  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -33,6 +35,7 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--suggest", action="store_true", help="time suggest(): suggest_mode='device', 'lockstep' and the default, interleaved in one process")
 ap.add_argument("--sweep", default=None, help="with a list such as 1,2,4,8,16: the device mode's suggest() against ops.ACQF_OPT_EVALS_PER_CALL")
 ap.add_argument("--evals-per-call", type=int, default=None, help="ops.ACQF_OPT_EVALS_PER_CALL for --suggest")
+ap.add_argument("--own-stacks", action="store_true", help="per-study source stacks: meta-fit, BO step and the grouped pass against what a caller had before")
 args = ap.parse_args()
 
 T, N, D, N_END, RESTARTS = 32, 512, 6, 80, 2
@@ -57,6 +60,126 @@ def timed(fn):
 def obj(x):
     return float(synthetic.hartmann6(np.asarray(x, dtype=np.float64).reshape(1, -1))[0])
 
+
+def own_stacks_table():
+    """Studies that each own their source stack, at the shape of the reference's configurations/hartmann6.py: T = 8 Hartmann-6 tasks of
+    N = 128 points per study, D = 6, Matern-5/2, n = 40 target points, 10 starts per study, S in --sizes.  All sides alternate in one
+    process; the first round of a size is a warm-up and is not counted; medians, spread = min .. max of the slower side.
+      (a) meta-fit: ``meta_fit_scamlgp_studies`` (ONE stack of S T tasks) against S calls of ``meta_fit_scamlgp``; device driver,
+          max_iter = 30, RESTARTS restarts each.
+      (b) one BO step (suggest + report): ``ScaMLGPBOStudies`` on the per-study dicts, suggest_mode="device", against S
+          ``ScaMLGPBOLoop``s on the S separately fitted stacks, stepped in turn; n = 40 at the last timed step.
+      (c) one grouped source pass over S * 10 points: per-study tasks (task_base) against the same points through the shared-stack pass
+          on study 0's stack alone -- the same T x Mq grid, so the ratio is what the lost sharing of L^-1 between studies costs."""
+    To, No, n_end, starts = 8, 128, 40, 10
+    kspec = M.KernelSpec(1)
+    fit_kw = dict(covar_module=kspec, num_restarts_log_likelihood=RESTARTS, device=dev, fit_options=dict(driver="device", max_iter=30))
+    # (the target GPs are Matern-5/2 as well: ScaMLGPBOStudies copies the module per study, every loop gets its own)
+    tkern = lambda: hyper.get_default_kernel(hyper.MaternKernel, D)   # noqa: E731
+    kw = dict(acquisition="ucb", num_restarts_log_likelihood=RESTARTS, num_restarts=starts)
+    say(f"# one source stack per study: T = {To} tasks x N = {No}, D = {D}, Matern-5/2 (source and target kernels), n -> {n_end}, {starts} starts per study, {RESTARTS} restarts of "
+        f"every fit; median of {args.steps} rounds, spread = min .. max of the slower side")
+    for S in [int(v) for v in args.sizes.split(",")]:
+        data = synthetic.hartmann6_task_stack(S * To, No, seed=S)
+        metas = [{t: M.SupervisedDataset(torch.from_numpy(data["X"][s * To + t]), torch.from_numpy(data["Y"][s * To + t]).unsqueeze(-1))
+                  for t in range(To)} for s in range(S)]
+        # (a) ------------------------------------------------------------------------------------------------------------
+        ta, tb = [], []
+        for _ in range(args.steps + 1):
+            dt, own = timed(lambda: M.meta_fit_scamlgp_studies(metas, seed=0, **fit_kw))
+            ta.append(dt)
+            dt, sep = timed(lambda: [M.meta_fit_scamlgp(md, seed=0, **fit_kw) for md in metas])
+            tb.append(dt)
+        ma, mb = statistics.median(ta[1:]), statistics.median(tb[1:])
+        say(f"  (a) S = {S:>3}  meta-fit: one stack of {S * To} tasks {1e3 * ma:10.1f} ms   S calls {1e3 * mb:10.1f} ms ({1e3 * min(tb[1:]):.1f} .. "
+            f"{1e3 * max(tb[1:]):.1f})   {mb / ma:6.2f}x")
+        # (b) ------------------------------------------------------------------------------------------------------------
+        steps = args.steps + 1
+        seeds = list(range(100, 100 + S))
+        studies = ScaMLGPBOStudies(own, D, num_studies=S, seeds=seeds, suggest_mode="device", gp_kernel=tkern(), **kw)
+        loops = [ScaMLGPBOLoop(sep[s], D, seed=seeds[s], gp_kernel=tkern(), **kw) for s in range(S)]
+        for s in range(S):
+            g = torch.Generator().manual_seed(seeds[s])
+            X0 = torch.rand(n_end - steps, D, dtype=torch.float64, generator=g)
+            y0 = [obj(x) for x in X0]
+            studies[s].record(X0, y0)
+            loops[s].record(X0, y0)
+        utils.fit_targets_batched([st.model for st in studies.studies], RESTARTS, rng=studies.fit_gens)
+        for lp in loops:
+            utils.optimize_marginal_likelihood(lp.model, RESTARTS)
+        rows = {"studies": [], "loops": []}
+        for _ in range(steps):
+            t_s, X = timed(studies.suggest)
+            ys = [obj(x) for x in X]
+            t_r, _ = timed(lambda: studies.report(X, ys))
+            rows["studies"].append((t_s, t_r))
+            t_s = t_r = 0.0
+            for lp in loops:
+                dt, x = timed(lp.suggest)
+                t_s += dt
+                y = obj(x)
+                dt, _ = timed(lambda: lp.report(x, y))
+                t_r += dt
+            rows["loops"].append((t_s, t_r))
+        med = {k: [1e3 * statistics.median(r[i] for r in v[1:]) for i in range(2)] for k, v in rows.items()}
+        tot = {k: [1e3 * sum(r) for r in v[1:]] for k, v in rows.items()}
+        info = studies.last_suggest_info
+        say(f"  (b) S = {S:>3}  BO step at n = {studies[0].model.n}: studies (device) suggest {med['studies'][0]:9.1f} + report {med['studies'][1]:9.1f} = "
+            f"{statistics.median(tot['studies']):9.1f} ms   S loops suggest {med['loops'][0]:9.1f} + report {med['loops'][1]:9.1f} = "
+            f"{statistics.median(tot['loops']):9.1f} ms ({min(tot['loops']):.1f} .. {max(tot['loops']):.1f})   "
+            f"{statistics.median(tot['loops']) / statistics.median(tot['studies']):6.2f}x   [batched {len(info['batched'])} studies, {info['n_eval']} rounds]")
+        # (c) ------------------------------------------------------------------------------------------------------------
+        models = [st.model.eval() for st in studies.studies]
+        sa_own = utils.StudiesAcquisition([utils.UpperConfidenceBound(m, 9.0) for m in models])
+        twins = []
+        for m in models:   # the same training sets, all on study 0's stack: the shared-stack pass
+            tw = M.ScaMLGP(m.train_X, m.train_Y, own[0], covar_module=tkern()).eval()   # (the studies' target kernel family)
+            tw.raw_theta, tw.weights = m.raw_theta.clone(), m.weights.clone()
+            twins.append(tw)
+        sa_sh = utils.StudiesAcquisition([utils.UpperConfidenceBound(m, 9.0) for m in twins])
+        assert sa_own.task_base is not None and sa_sh.task_base is None
+        g = torch.Generator().manual_seed(S)
+        Xq = torch.rand(S * starts, D, dtype=torch.float64, generator=g).to(dev)
+        group = sa_own.group_of([starts] * S)
+
+        def source_pass(sa):
+            st, f = sa.source, sa.source.fit
+            theta = st.theta
+            kwo = dict(task_base=sa.task_base, tasks_per_group=To) if sa.task_base is not None else {}
+            return lambda: ops.source_posteriors_grad_grouped(Xq, group, sa.Xt, sa.n_points, sa.VA_tab, st.X, theta, st.kind, f["Linv"], f["alpha"],
+                                                              st.y_mean, st.y_std, st.n_points, **kwo)
+
+        calls = {"own": source_pass(sa_own), "shared": source_pass(sa_sh)}
+        reps, inner = 10, 20
+        got = {k: [] for k in calls}
+        for r in range(reps + 1):
+            for k, fn in calls.items():
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                ev0.record()
+                for _ in range(inner):
+                    fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                if r:
+                    got[k].append(1e3 * ev0.elapsed_time(ev1) / inner)
+        mo, msh = statistics.median(got["own"]), statistics.median(got["shared"])
+        slow = "own" if mo >= msh else "shared"
+        say(f"  (c) S = {S:>3}  grouped source pass, {S * starts} points x {To} task slots (n = {sa_own.n_max}): per-study tasks {mo:9.1f} us   shared stack "
+            f"{msh:9.1f} us ({slow}: {min(got[slow]):.1f} .. {max(got[slow]):.1f})   own / shared = {mo / msh:5.2f}   [device events over {inner} calls, "
+            f"allocation of the outputs included]")
+        del studies, loops, own, sep, sa_own, sa_sh, twins, models
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if args.own_stacks:
+    if args.sizes == ap.get_default("sizes"):
+        args.sizes = "8,32,128"
+    own_stacks_table()
+    sys.exit(0)
 
 d = synthetic.hartmann6_task_stack(T, N, seed=0)
 stack = M.SourceGPStack(list(range(T)), [torch.from_numpy(d["X"][t]) for t in range(T)],
