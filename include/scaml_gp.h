@@ -453,9 +453,12 @@ int scaml_target_fit_batched_f64(const double* means_t, const double* covs_packe
  *   flags: SCAML_STACK_FIT_CONTINUE resumes from the state the previous call left in `workspace` (same arguments otherwise);
  *       without it the first round evaluates z and initialises the state.  The caller reads stats and calls again while any
  *       problem is still running.  Chunking does not change the result.
- *   workspace: scaml_stack_fit_workspace_bytes(B, N, D, history) bytes, 16-byte aligned; it starts with the per-problem state,
- *       (4 + 2 history) (D + 2) + history + 16 doubles each: accepted point, its gradient (d objective / d raw, objective =
- *       -value), direction, trial point, the pairs, scalars.
+ *   workspace: scaml_stack_fit_workspace_bytes(B, N, D, history) bytes, 16-byte aligned; it starts with the per-problem state of
+ *       the L-BFGS state machine that (9) and (7h) share (csrc/gp_lbfgs_core.h), P = D + 2 variables here:
+ *       (4 + 2 history) P + history + 16 doubles each -- accepted point x[P], gradient g[P] of the minimised function there (here
+ *       d objective / d raw, objective = -value), direction d[P], trial point xt[P], the pairs S[history][P], Y[history][P] (a ring),
+ *       rho[history], and 16 scalars: f, step, g . d ((7h): g . (xt - x)), iteration, evaluations, status, failed trials of this
+ *       line search, pairs held, ring head, phase.
  * Shapes: what (3) / (3b) and (4) take (N <= 512, a multiple of 16 beyond 256; their D limits) and D <= scaml_stack_fit_max_d();
  * SCAML_E_TOOLARGE otherwise.  B == 0 or n_evals == 0: nothing is enqueued.
  */
@@ -493,9 +496,8 @@ int scaml_stack_fit_f64(const double* X, const double* y, const int32_t* n_point
  *   stats (B, 4) int32: [iterations, evaluations, status, pairs held], status 0 still running, 1 converged on the projected gradient,
  *       2 stopped on ftol, 3 line search failed, 4 acquisition not finite at the start point, 5 max_iter, 6 padding row.
  *   workspace: scaml_studies_acqf_opt_workspace_bytes(B, G, n_max, T, D, history) bytes (0 for shapes the call does not take),
- *       16-byte aligned; it starts with the per-start state, (4 + 2 history) D + history + 16 doubles each: accepted point, gradient of
- *       -acquisition there, direction, trial point, the pairs (S, Y, rho), scalars; then Xq, the live group table, mu / var / cov of
- *       (5e) and value / grad of (7g).
+ *       16-byte aligned; it starts with the per-start state in the layout given under (9), P = D variables and the minimised function
+ *       -acquisition; then Xq, the live group table, mu / var / cov of (5e) and value / grad of (7g).
  * Limits: those of (5e) / (7g) -- n_max <= 96 and <= N, N <= scaml_posterior_max_n(), D <= scaml_studies_acqf_opt_max_d() = 15;
  * SCAML_E_TOOLARGE beyond them (bad arguments answer first).  B == 0 or G == 0: nothing is enqueued.  Everything is checked once,
  * before the first launch; SCAML_E_LAUNCH from a later round leaves the rounds before it enqueued -- start the optimisation again.

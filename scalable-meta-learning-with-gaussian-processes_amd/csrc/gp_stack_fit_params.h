@@ -4,19 +4,15 @@
 #include <stdint.h>
 
 #include "gp_hyper_spec.h"   // HyperSpec
+#include "gp_lbfgs_core.h"   // state layout and machine; taken with no contraction pragma set (csrc/gp_stack_fit.hip)
 
 namespace scaml {
 
-constexpr int STACK_FIT_HMAX = 16;   // curvature pairs kept at most
+constexpr int STACK_FIT_HMAX = LBFGS_HMAX;
 constexpr int STACK_FIT_PMAX = 64;   // one lane per variable: D + 2 <= 64
-constexpr int STACK_FIT_SCALARS = 16;
-
-// Per-problem optimiser state in the caller's workspace, in doubles (P = D + 2, H = history):
-//   x[P] accepted point (raw)   g[P] gradient there   d[P] search direction   xt[P] trial point (raw)
-//   S[H][P], Y[H][P] curvature pairs (ring: the newest in slot head - 1)   rho[H]
-//   sc[16]: f, step t, g.d, iteration, evaluations, status, failed trials of this line search, pairs held, head, phase
-constexpr size_t stack_fit_state_doubles(int P, int H) { return (size_t)(4 + 2 * H) * P + H + STACK_FIT_SCALARS; }
-enum { SF_F = 0, SF_T = 1, SF_GD = 2, SF_IT = 3, SF_NEVAL = 4, SF_STATUS = 5, SF_LS = 6, SF_HIST = 7, SF_HEAD = 8, SF_PHASE = 9 };
+constexpr int STACK_FIT_SCALARS = LBFGS_SCALARS;
+// per-problem optimiser state in the caller's workspace, in doubles (P = D + 2 raw variables): the layout of csrc/gp_lbfgs_core.h
+constexpr size_t stack_fit_state_doubles(int P, int H) { return lbfgs_state_doubles(P, H); }
 
 struct StackFitParams {
   const double* mll;         // (B)  marginal log-likelihood / n of the fit at `theta`

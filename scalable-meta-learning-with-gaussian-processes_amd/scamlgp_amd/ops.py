@@ -1072,19 +1072,51 @@ def target_fit_batched(batch: TargetFitBatch, z0: torch.Tensor, max_iter: int = 
     return _target_launch(batch, _check(z0, "z0", (batch.S, z0.shape[1], batch.P)).clone(), (max_iter, history, gtol, ftol))
 
 
+# ---- the L-BFGS state machine of (9) and (7h): csrc/gp_lbfgs_core.h ---------------------------------------------------------------
+_LBFGS_SCALARS = 16             # LBFGS_SCALARS
+# status codes of both optimisers (stats[:, 2] of stack_fit and of StudiesAcqfOpt; "padding" only in the latter)
+ACQF_OPT_STATUS = ("running", "converged", "ftol", "stalled", "failed", "max_iter", "padding")
+
+
+def _lbfgs_state_doubles(P: int, history: int) -> int:
+    """Doubles of one problem's optimiser state at the head of the workspace: ``lbfgs_state_doubles`` of csrc/gp_lbfgs_core.h (x, g, d,
+    xt, the curvature pairs, rho, the scalars; tests/test_stack_fit_emul.py and tests/test_acqf_opt_emul.py compare the two)."""
+    return (4 + 2 * history) * P + history + _LBFGS_SCALARS
+
+
+stack_fit_state_doubles = studies_acqf_opt_state_doubles = _lbfgs_state_doubles
+
+
+def _lbfgs_state(ws: torch.Tensor, B: int, P: int, history: int) -> torch.Tensor:
+    """(B, _lbfgs_state_doubles(P, history)) float64: the per-problem state that opens the workspace (include/scaml_gp.h), a view."""
+    stride = _lbfgs_state_doubles(P, history)
+    return ws[: B * stride * 8].view(torch.float64).reshape(B, stride)
+
+
+def _lbfgs_rounds(enqueue, stats: torch.Tensor, per_call: int, budget: int, live: bool, n_eval: int = 0, n_calls: int = 0) -> Dict:
+    """The chunked round loop of both optimisers: ``enqueue(k, n_calls)`` enqueues k rounds (n_calls == 0: from a reset), then the status
+    column is read -- the only synchronisation -- and the loop goes on while a problem is still running and the budget of
+    ``1 + max_iter * max_ls`` evaluations is not spent.  Returns dict(stats on the host, n_eval rounds enqueued, n_calls)."""
+    if per_call < 1:
+        raise ValueError("evals_per_call must be positive")
+    host = stats.cpu()
+    while live:
+        k = min(per_call, budget - n_eval)
+        enqueue(k, n_calls)
+        n_eval += k
+        n_calls += 1
+        host = stats.cpu()
+        if not bool((host[:, 2] == 0).any()) or n_eval >= budget:
+            break
+    return dict(stats=host, n_eval=n_eval, n_calls=n_calls)
+
+
 # ---- (9) source stack: the whole hyper-parameter fit enqueued on the device ---------------------------------------------------
 # rounds enqueued between two reads of the status.  Measured (tools/dev_stackfit_time.py, profiles/stack_fit_timings.txt): the cost per
 # evaluation is flat from 4 on (the rounds are GPU-bound), and every round past the last problem's stop is a wasted evaluation of the
 # whole batch, so the smallest value past the knee is the default.
 STACK_FIT_EVALS_PER_CALL = 4
 _STACK_FIT_MAX_LS = 20          # trials per line search inside scaml_stack_fit_f64
-_STACK_FIT_SCALARS = 16         # STACK_FIT_SCALARS (csrc/gp_stack_fit_params.h)
-
-
-def stack_fit_state_doubles(P: int, history: int) -> int:
-    """Doubles of one problem's optimiser state at the head of the workspace: ``stack_fit_state_doubles`` of csrc/gp_stack_fit_params.h
-    (x, g, d, xt, the curvature pairs, rho, the scalars; tests/test_stack_fit_emul.py compares the two)."""
-    return (4 + 2 * history) * P + history + _STACK_FIT_SCALARS
 
 
 def stack_spec_host(spec):
@@ -1110,32 +1142,23 @@ def stack_fit(X: torch.Tensor, y: torch.Tensor, n_points: Optional[torch.Tensor]
     z = _check(z0, "z0", (B, P)).clone()
     n_points = _opt(n_points, "n_points", (B,), torch.int32)
     per_call = int(evals_per_call or STACK_FIT_EVALS_PER_CALL)
-    if per_call < 1:
-        raise ValueError("evals_per_call must be positive")
     spec_host = stack_spec_host(spec)
     dev = X.device
-    budget = 1 + int(max_iter) * _STACK_FIT_MAX_LS
-    n_eval = n_calls = 0
     with torch.cuda.device(dev):
         value = _empty(dev, B)
         stats = torch.zeros((B, 4), dtype=torch.int32, device=dev)
         nbytes = int(_lib.lib.scaml_stack_fit_workspace_bytes(B, N, D, int(history)))
         ws = _empty(dev, max(nbytes, 16), dtype=torch.uint8)
-        host = stats.cpu()
-        while B > 0:
-            k = min(per_call, budget - n_eval)
+
+        def enqueue(k, n_calls):
             rc = _lib.lib.scaml_stack_fit_f64(_ptr(X), _ptr(y), _ptr(n_points), spec_host, _ptr(z), B, N, D, int(kind), k,
                                               _lib.STACK_FIT_CONTINUE if n_calls else 0, int(max_iter), int(history), float(gtol),
                                               float(ftol), _ptr(value), _ptr(stats), _ptr(ws), nbytes, _stream_handle())
             _lib.check_rc(rc, "scaml_stack_fit_f64")
-            n_eval += k
-            n_calls += 1
-            host = stats.cpu()
-            if not bool((host[:, 2] == 0).any()) or n_eval >= budget:
-                break
-        stride = stack_fit_state_doubles(P, int(history))   # the per-problem state opens the workspace (include/scaml_gp.h)
-        grad = ws[: B * stride * 8].view(torch.float64).reshape(B, stride)[:, P:2 * P].clone()
-    return dict(z=z, value=value, grad=grad, stats=host, n_eval=n_eval, n_calls=n_calls)
+
+        out = _lbfgs_rounds(enqueue, stats, per_call, 1 + int(max_iter) * _STACK_FIT_MAX_LS, B > 0)
+        grad = _lbfgs_state(ws, B, P, int(history))[:, P:2 * P].clone()
+    return dict(z=z, value=value, grad=grad, **out)
 
 
 # ---- (7h) the acquisition optimiser of many studies' start points enqueued on the device --------------------------------------
@@ -1144,14 +1167,6 @@ def stack_fit(X: torch.Tensor, y: torch.Tensor, n_points: Optional[torch.Tensor]
 # read costs little next to a round, a round after the last stop evaluates no start -- and 8 is the fastest column or within 0.2 ms of it.
 ACQF_OPT_EVALS_PER_CALL = 8
 ACQF_OPT_MAX_LS = 20            # trials per line search (hyper.batched_lbfgs's max_ls)
-_ACQF_OPT_SCALARS = 16          # ACQF_OPT_SCALARS (csrc/gp_acqf_opt.h)
-ACQF_OPT_STATUS = ("running", "converged", "ftol", "stalled", "failed", "max_iter", "padding")
-
-
-def studies_acqf_opt_state_doubles(D: int, history: int) -> int:
-    """Doubles of one start's optimiser state at the head of the workspace: ``acqf_opt_state_doubles`` of csrc/gp_acqf_opt.h (x, g, d,
-    xt, the curvature pairs, rho, the scalars; tests/test_acqf_opt_emul.py compares the two)."""
-    return (4 + 2 * history) * D + history + _ACQF_OPT_SCALARS
 
 
 class StudiesAcqfOpt:
@@ -1208,22 +1223,13 @@ class StudiesAcqfOpt:
         then the status column is read -- the only synchronisation -- and the optimisation continues while a start is still running (at
         most ``1 + max_iter * max_ls`` evaluations: then every start has stopped).  Returns dict(x (B, D), f (B,) the acquisition value
         there, stats (B, 4) int32 [iterations, evaluations, status, pairs] on the host, n_eval rounds enqueued, n_calls, state)."""
-        per_call = int(evals_per_call or ACQF_OPT_EVALS_PER_CALL)
-        if per_call < 1:
-            raise ValueError("evals_per_call must be positive")
-        host = self.stats.cpu()
-        while self._shape[0] > 0 and self._shape[1] > 0:
-            self.enqueue(min(per_call, self.budget - self.n_eval))
-            host = self.stats.cpu()
-            if not bool((host[:, 2] == 0).any()) or self.n_eval >= self.budget:
-                break
-        return dict(x=self.x, f=self.f, stats=host, n_eval=self.n_eval, n_calls=self.n_calls, state=self.state())
+        out = _lbfgs_rounds(lambda k, _: self.enqueue(k), self.stats, int(evals_per_call or ACQF_OPT_EVALS_PER_CALL), self.budget,
+                            self._shape[0] > 0 and self._shape[1] > 0, self.n_eval, self.n_calls)
+        return dict(x=self.x, f=self.f, state=self.state(), **out)
 
     def state(self) -> torch.Tensor:
         """(B, studies_acqf_opt_state_doubles(D, history)): the per-start state that opens the workspace (a view)."""
-        B, D, history = self._shape[0], self._shape[5], self._opts[1]
-        stride = studies_acqf_opt_state_doubles(D, history)
-        return self.ws[: B * stride * 8].view(torch.float64).reshape(B, stride)
+        return _lbfgs_state(self.ws, self._shape[0], self._shape[5], self._opts[1])
 
 
 def studies_acqf_opt(arrays, B: int, G: int, n_max: int, T: int, N: int, D: int, kind_s: int, kind_t: int, acqf: int, lo: torch.Tensor, hi: torch.Tensor,
