@@ -390,7 +390,7 @@ __global__ __launch_bounds__(512) void gp_fit_coop_kernel(CoopFitParams p) {
   double* tv = invl + 16;                // [32] right-hand side of the column's forward substitution
   double* rvs = tv + 32;                 // [32] L_j,0:j v
   double* red = rvs + 32;                // [16]
-  int* ctrl = (int*)(red + 16);          // [0] abandon the attempt, [1] failing pivot (local), [2] all parts of the task on one XCD
+  int* ctrl = (int*)(red + 16);          // [0] abandon the attempt, [1] failing pivot (local), [2] all parts of the task on one XCD, [3] a non-finite point
   double* Cb = red + 16 + 8;             // [4][32][CF_BP] the chunk's blocks before the multiplication by L_jj^-T
   double* Dg = Cb + 4 * CF_BS;           // L_jj
   double* Wb = Dg + CF_BS;               // L_jj^-1
@@ -412,13 +412,18 @@ __global__ __launch_bounds__(512) void gp_fit_coop_kernel(CoopFitParams p) {
 
   exp2_table_init(exptab, tid);
   if (tid < 16) invl[tid] = tid < D ? 1.0 / th[tid] : 0.0;
-  if (tid == 0) { ctrl[0] = 0; ctrl[1] = 0; }
+  if (tid == 0) { ctrl[0] = 0; ctrl[1] = 0; ctrl[3] = 0; }
   __syncthreads();
   for (int e = tid; e < N * D; e += blockDim.x) {
     const int r = e / D, d = e - r * D;
-    Xs[r * DP + d] = r < n ? Xg[e] * invl[d] : 0.0;
+    const double v = r < n ? Xg[e] * invl[d] : 0.0;
+    Xs[r * DP + d] = v;
+    // NaN / inf points or lengthscales: the clamps of the kernel function would swallow a NaN, so the diagonal is poisoned instead and
+    // the factorisation fails the way psd_safe_cholesky fails on NaN (as in csrc/gp_fit_fused.hip; every part stages all points)
+    if (!(__builtin_fabs(v) <= 1e150)) ctrl[3] = 1;
   }
   __syncthreads();
+  const double poison = ctrl[3] ? __builtin_nan("") : 0.0;
 
   // XCD census: do all P workgroups of this task share an XCD (and with it an L2)?  The host's block map puts them on one (blockIdx & 7
   // is the same), but placement is the dispatcher's business: every part publishes the XCC id it actually runs on, and only if all P agree
@@ -453,7 +458,7 @@ __global__ __launch_bounds__(512) void gp_fit_coop_kernel(CoopFitParams p) {
 
   for (int attempt = 1;; ++attempt) {
     const double ladder = attempt == 1 ? 0.0 : (attempt == 2 ? 1e-8 : (attempt == 3 ? 1e-7 : 1e-6));
-    const double diag_add = noise + base_jit + ladder;
+    const double diag_add = noise + base_jit + ladder + poison;
     bool gone = false;
     // kernel values of this wave's tile of block (i, j)
     auto kvals = [&](int j, int i) -> d4_t {
