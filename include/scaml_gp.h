@@ -369,6 +369,28 @@ int scaml_posterior_linv_grad_grouped_own_f64(const double* Xq, const int32_t* g
                                               double* cov, const int32_t* task_base, int Tsrc, void* stream);
 
 /*
+ * (5f), (5f') The grouped pass in VALUE mode: (5c')'s posteriors and covariance block for a TABLE of candidates divided among G groups
+ * -- stage 1 of the studies' acquisition optimiser (scamlgp_amd.bo.ScaMLGPBOStudies with score_mode="batched"): every study's raw
+ * candidates in one launch, no gradient columns.  The arguments are (5e)'s / (5e')'s; what differs:
+ *   Mq: the number of candidates, a multiple of 16 (SCAML_E_BADARG otherwise).  A strip is 16 DIFFERENT query points of ONE group.
+ *   group (Mq / 16) int32: the group of a strip.  A negative or out-of-range entry marks a padding strip: zeros in its 16 entries of
+ *       mu / var, no row of cov written, nothing of any group read -- as (5e) treats a padding row.
+ *   mu, var (T, Mq); cov (T, Ma_max, Mq): rows a < Ma_g of a strip are written, the rest is untouched.
+ *   The group's leading points, count and V pointer (Xa, n_points_a, VA_tab) are (5e)'s; task_base / Tsrc are (5e')'s.
+ * Limits and error codes: those of (5e) / (5e'), everything checked before the first HIP call.  Mq == 0, G == 0 or T == 0: nothing is
+ * enqueued.  A candidate with a non-finite coordinate gives NaN in its own mu, var and column of cov only.
+ */
+int scaml_posterior_linv_grouped_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                                     const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
+                                     const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T, int N,
+                                     int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov, void* stream);
+int scaml_posterior_linv_grouped_own_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                                         const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
+                                         const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T,
+                                         int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov,
+                                         const int32_t* task_base, int Tsrc, void* stream);
+
+/*
  * (8) The target GP's training objective with its analytic gradient, and the whole refit, in ONE launch.
  * Replaces what the reference runs on every report(): scamlgp/optimizer.py:176-185 rebuilds ScaMLGP and calls
  * optimize_marginal_likelihood (scamlgp/utils.py:139-212), which drives scipy L-BFGS-B through torch autograd over
@@ -529,6 +551,43 @@ int scaml_studies_acqf_opt_own_f64(const double* x0, const int32_t* group, const
                                    int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi,
                                    int max_iter, int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags,
                                    void* workspace, double* x, double* f, int32_t* stats, const int32_t* task_base, int Tsrc, void* stream);
+
+/*
+ * (7i) The acquisition VALUE of a table of candidates of many studies, behind (5f): one workgroup per strip of 16 candidates of one
+ * study; the study's L, Linv_diag and alpha are staged in LDS once per workgroup and serve all 16 columns (csrc/gp_studies_score.h).
+ *   mu, var (T, Mq), cov (T, n_max, Mq): (5f)'s outputs; group (Mq / 16) int32 per strip; Xq (Mq, D); Mq a multiple of 16.
+ *   w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param: the studies as (7g) takes them.
+ *   value (Mq); mu_out, var_out (Mq) or NULL.  No gradient.
+ * Per candidate the operations are exactly (7g)'s on column 0 of its 16-column layout, in (7g)'s order, each output by one thread and
+ * without atomics: value, mu_out and var_out are a pure function of the inputs and BIT-IDENTICAL to (7g)'s for the same per-task numbers.
+ * info[g] != 0 (or n_points[g] outside 1 .. n_max) gives NaN for the study's candidates, a padding strip zeros; an inactive task is
+ * skipped, not multiplied by zero; what lies past n_g in a study's slices is never read; a candidate with a NaN or infinite coordinate
+ * gives NaN in its own outputs only.
+ * Checks: sizes (Mq < 0 or not a multiple of 16, G < 0, n_max < 1, T < 1, D < 1), NULL required pointers, kind, acqf: SCAML_E_BADARG.
+ * Limits: n_max <= 96, D <= 15 and the LDS footprint of a strip (a constexpr of csrc/gp_studies_score.h): SCAML_E_TOOLARGE beyond them
+ * (bad arguments answer first).  Mq == 0 or G == 0: nothing is enqueued.  Does not synchronise.
+ */
+int scaml_target_score_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
+                                   const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
+                                   const double* Linv_diag, const double* alpha, const int32_t* n_points, const double* m_all,
+                                   const double* s_all, const int32_t* info, const double* acqf_param, int Mq, int G, int n_max, int T,
+                                   int D, int kind, int acqf, double* value, double* mu_out, double* var_out, void* stream);
+
+/*
+ * (7j) The training blocks of G studies in one launch, a workgroup per study: what (6') and (7)'s assemble produce for ONE study's
+ * training block, from the padded per-study source terms in the layout (8b) takes:
+ *   means_t (G, T, n_max), covs_packed (G, T, n_max (n_max + 1) / 2), X (G, n_max, D), y (G, n_max), n_points (G) int32,
+ *   m_all, s_all (G); and each study's pruned w (G, T), active (G, T) uint8 and theta (G, D + 2).
+ *   Knn (G, n_max, n_max): the leading n_g x n_g block, Knn[i][c] = sum_t w_t^2 cov_t[i][c] / s^2 + os k_t(x_i, x_c) (+ noise on the
+ *   diagonal); resid (G, n_max): y_i - (sum_t w_t mean_t[i] - m) / s.  The task sums run in (6)'s order.  The rest is untouched.
+ * One call of (2) with n_points then factors all blocks (ragged sizes, the jitter ladder and info per study).
+ * Checks: G < 0, n_max < 1, T < 1, D < 1, a NULL pointer, kind: SCAML_E_BADARG.  n_max > scaml_fit_max_n(): SCAML_E_TOOLARGE.
+ * G == 0: nothing is enqueued.
+ */
+int scaml_target_train_block_batched_f64(const double* means_t, const double* covs_packed, const double* X, const double* y,
+                                         const int32_t* n_points, const double* m_all, const double* s_all, const double* w,
+                                         const uint8_t* active, const double* theta, int G, int n_max, int T, int D, int kind, double* Knn,
+                                         double* resid, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1110,11 +1110,24 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
           const int* rl = rowlist + (wave * NB + k) * 8;
           const int cnt = rl[0];
           if (cnt == 0 || (cnt == 1 && (rl[1] >> 16))) continue;   // nothing of this block row here: do not even wait
+          // w_j collects one term per block row k = NB-1 .. j+2, from different waves: they are added in that order, whatever the
+          // waves' timing (the term of row k waits for the NB-1-k arrivals of the rows below it), so that alpha does not depend on
+          // which wave reaches the LDS first.  Row i > k is signalled before row k, by this wave (k descends) or by a wave that
+          // waits on rows below i only: no cycle.  Normally the count is already there: it is read one tile ahead (the first one
+          // in the trip that fetches alpha_k), a stale value only sends the wave into the wait it would have needed anyway.
+          const int before = NB - 1 - k;
+          int nxt = rl[cnt];
           sync_wait_ge(flagW + k, 1);
+          int have = before > 0 ? __hip_atomic_load((const lds_int_t*)(cntB + (nxt & 0xff)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
           const double* pa = dl + 16 * k + lq;
           const double a0 = pa[0], a1 = pa[4], a2 = pa[8], a3 = pa[12];
           for (int i = cnt - 1; i >= 0; --i) {
-            const int sj = rl[1 + i], s = (sj >> 8) & 0xff, j = sj & 0xff;
+            const int sj = nxt, s = (sj >> 8) & 0xff, j = sj & 0xff;
+            const int have_i = have;
+            if (i > 0) {
+              nxt = rl[i];
+              if (before > 0) have = __hip_atomic_load((const lds_int_t*)(cntB + (nxt & 0xff)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
             if (sj >> 16) continue;   // the tile next to the diagonal went into M_k
             double e0, e1, e2, e3;
 #define SCAML_BODY(r0, r1, r2, r3, r4, r5, r6, r7) TILE_GET(r0, r1, r2, r3, r4, r5, r6, r7, e0, e1, e2, e3);
@@ -1124,6 +1137,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
             part = __builtin_fma(e1, a1, part);
             part = __builtin_fma(e2, a2, part);
             part = __builtin_fma(e3, a3, part);
+            if (have_i < before) sync_wait_ge(cntB + j, before);
             __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double*)(ww + 16 * j + lc), -part);
             sync_arrive(cntB + j, lane);
           }

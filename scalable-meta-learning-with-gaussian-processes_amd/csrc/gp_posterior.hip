@@ -166,9 +166,12 @@ struct PosteriorArgs<true> {
 // OWN (scaml_posterior_linv_grad_grouped_own_f64): every group owns its source tasks -- task slot `task` of group g reads source task
 // task_base[g] + task of the Tsrc tasks in the source arrays; the outputs and the group's VA stay indexed by the slot.  An instantiation
 // of its own: the grouped pass without the table keeps its instruction stream.
+// GROUPED without GRAD (scaml_posterior_linv_grouped_f64 and its OWN twin): a strip holds 16 DIFFERENT query points of one
+// group -- the raw candidates of a study's stage 1 --, the group table has one entry per strip, and the outputs are the value layout
+// mu / var (T, Mq), cov (T, Ma_max, Mq).  Nothing else differs: the group is still uniform per workgroup.
 template <int KIND, bool COV, bool GRAD, bool GROUPED = false, bool OWN = false>
 __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename PosteriorArgs<GROUPED>::type pp) {
-  static_assert(!GROUPED || (COV && GRAD), "the grouped pass is the GRAD pass with its covariance block");
+  static_assert(!GROUPED || COV, "the grouped pass comes with its covariance block");
   static_assert(!OWN || GROUPED, "per-group source tasks belong to the grouped pass");
   const PosteriorParams& p = PosteriorArgs<GROUPED>::base(pp);
   // eight waves share one K_*^T strip (the row blocks are dealt 8 ways: twice the waves per byte of LDS to hide the L^-1 segment loads)
@@ -714,3 +717,7 @@ template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, true>(sc
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, true>(scaml::PosteriorGroupedParams);
 template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, true, true>(scaml::PosteriorGroupedParams);   // (5e')
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, true, true>(scaml::PosteriorGroupedParams);
+template __global__ void scaml::gp_posterior_linv_kernel<0, true, false, true>(scaml::PosteriorGroupedParams);   // (5f)
+template __global__ void scaml::gp_posterior_linv_kernel<1, true, false, true>(scaml::PosteriorGroupedParams);
+template __global__ void scaml::gp_posterior_linv_kernel<0, true, false, true, true>(scaml::PosteriorGroupedParams);   // (5f')
+template __global__ void scaml::gp_posterior_linv_kernel<1, true, false, true, true>(scaml::PosteriorGroupedParams);

@@ -37,7 +37,7 @@ struct PosteriorParams {
 // points.  In `base`: Ma = Ma_max (row count of cov and of a group's slice of Xa), VA / Xa unused.
 // T = the task slots of a group (rows of mu / var / cov).
 struct PosteriorGroupArgs {
-  const int32_t* group;         // (Mq) group of a query point; negative: a padding row
+  const int32_t* group;         // (Mq) group of a query point; negative: a padding row.  Value mode (5f): one entry per STRIP of 16
   const int32_t* n_a;           // (G) leading points per group, 1 <= n_a[g] <= Ma_max
   const double* const* VA_tab;  // (G) device pointers: group g's V of its leading points, (T, N, n_a[g]) with row stride n_a[g]
   const double* Xa;             // (G, Ma_max, D) the leading points, padded

@@ -13,17 +13,7 @@
 // Every sum runs in a fixed order (tasks ascending, training points ascending) by ONE thread per output: no atomics, no wave
 // reductions, so the result is a pure function of the inputs and the host build computes what the device computes.
 #pragma once
-#include <math.h>
-#include <stddef.h>
-#include <stdint.h>
-
-#ifdef __HIPCC__
-#define SA_DEV __device__ __forceinline__
-#define SA_SYNC() __syncthreads()
-#else
-#define SA_DEV static inline
-#define SA_SYNC() ((void)0)
-#endif
+#include "gp_studies_formulas.h"   // SA_DEV / SA_SYNC, sa_kernel_and_slope, sa_acquisition (shared with csrc/gp_studies_score.h)
 
 namespace scaml {
 
@@ -60,21 +50,6 @@ struct StudiesAcqfParams {
 constexpr size_t studies_acqf_lds_doubles(int n_max) {
   const size_t nb = (size_t)(n_max + 15) / 16, np = nb * 16;
   return (size_t)n_max * 16 + 32 + 3 * np + nb * 256 + (size_t)n_max * (size_t)(n_max | 1) + 48;
-}
-
-// os k(d2) and os dk / d(d2) of the scaled squared distance (the formulas of kernel_and_slope_scaled, libm instead of the table)
-SA_DEV void sa_kernel_and_slope(int kind, double d2, double os, double& k, double& dk) {
-  if (kind == 0) {
-    k = os * exp(-0.5 * d2);
-    dk = -0.5 * k;
-  } else {
-    const double s5 = 2.2360679774997896964;
-    const double r = sqrt(fmax(d2, 1e-30));   // gpytorch clamps the squared distance before the root
-    const double ex = os * exp(-s5 * r);
-    const double lin = 1.0 + s5 * r;
-    k = (lin + (5.0 / 3.0) * r * r) * ex;
-    dk = (-5.0 / 6.0) * lin * ex;
-  }
 }
 
 // One query point by `nthr` cooperating threads (thread `tid`; SA_SYNC between the phases).  `lds`: studies_acqf_lds_doubles(n_max).
@@ -222,20 +197,7 @@ SA_DEV void sa_query(const StudiesAcqfParams& p, double* lds, int q, int tid, in
     const double vr = s2 * (var_q - red[1]);
     const double par = p.acqf_param[g];
     double A, Amu, Av;
-    if (p.acqf == 0) {   // UCB: -mu + sqrt(beta max(v, 0)); d/dv = beta / (2 sqrt(beta v)), zero where v is clamped
-      const double sd = sqrt(par * (vr > 0.0 ? vr : 0.0));
-      A = sd - mu;
-      Amu = -1.0;
-      Av = vr > 0.0 ? 0.5 * par / (sd > 1e-300 ? sd : 1e-300) : 0.0;
-    } else {             // EI (minimisation): d/dmu = -Phi(u), d/dv = phi(u) / (2 sigma), zero on the 1e-9 floor
-      const double sigma = sqrt(vr > 1e-9 ? vr : 1e-9);
-      const double uu = -(mu - par) / sigma;
-      const double pdf = exp(-0.5 * uu * uu) * 0.39894228040143267794;   // 1 / sqrt(2 pi)
-      const double cdf = 0.5 * (1.0 + erf(uu * 0.70710678118654752440));
-      A = sigma * (pdf + uu * cdf);
-      Amu = -cdf;
-      Av = vr > 1e-9 ? 0.5 * pdf / sigma : 0.0;
-    }
+    sa_acquisition(p.acqf, par, mu, vr, A, Amu, Av);
     // a query point with a NaN / inf coordinate: fmax in the Matern branch drops a NaN operand, so only that coordinate's slope
     // would carry it (and nothing at all with source sums that happen to be finite).  sum_d (x_d - x_d) is 0, or NaN for such a
     // point: every output of the query is NaN, as (5d)'s target gradient has it (a select: finite inputs are untouched)

@@ -24,6 +24,7 @@
 #include "gp_stack_fit_params.h"
 #include "gp_studies_acqf.h"   // (argument block and LDS footprint; its arithmetic is not called here)
 #include "gp_acqf_opt.h"       // (argument block and state stride; likewise)
+#include "gp_studies_score.h"  // (likewise: the strip scoring kernel's LDS footprint, the train-block arguments)
 #include <math.h>
 
 extern "C" const unsigned char scaml_hsaco_blob[];   // generated: lib/hsaco_blob.c
@@ -71,6 +72,8 @@ struct Module {
   hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {};   // value only; value + gradient per kind
   hipFunction_t post_linv_grouped[2] = {}, tgt_acqf_batched = nullptr;   // lock-step studies: grouped GRAD pass, batched acquisition
   hipFunction_t post_linv_grouped_own[2] = {};                           // the grouped pass with per-group source tasks
+  hipFunction_t post_linv_grouped_val[2] = {}, post_linv_grouped_val_own[2] = {};   // the value-only grouped pass (16 candidates per strip)
+  hipFunction_t tgt_score_batched = nullptr, tgt_train_block[2] = {};     // studies' stage 1: strip scoring; the training blocks of all studies
   hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {}, stack_step = nullptr, acqf_opt_step = nullptr;
   hipFunction_t blk_solve[2][2] = {}, blk_syrk[2] = {};   // solve: [kind][D <= 8]
   hipFunction_t mllgrad_fused[4][2][2] = {};   // [size class NBT = 2, 4, 8, 16][kind][LDS-DMA staging]
@@ -94,7 +97,12 @@ struct Module {
         {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
         {post_linv_grouped, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
         {post_linv_grouped_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_val, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_val_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
         {&tgt_acqf_batched, "scaml_target_acqf_batched_kernel", kLdsLimit, {}},
+        {&tgt_score_batched, "scaml_target_score_batched_kernel", kLdsLimit, {}},
+        {&tgt_train_block[0], "scaml_target_train_block_rbf_kernel", 0, {}},
+        {&tgt_train_block[1], "scaml_target_train_block_matern_kernel", 0, {}},
         {&wsum, "scaml_weighted_task_sum_kernel", 0, {}},
         {&linv, "_ZN5scaml14gp_linv_kernelENS_10LinvParamsE", kLdsLimit, {}},
         {&chosolve, "_ZN5scaml19gp_cho_solve_kernelENS_14ChoSolveParamsE", kLdsLimit, {}},
@@ -745,15 +753,17 @@ namespace {
 int grouped_grad_launch(Module& m, const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
                         const double* const* VA_tab, const double* X, const double* theta, const double* Linv, const double* alpha,
                         const double* y_mean, const double* y_std, const int32_t* n_points, int T, int N, int Mq, int G, int Ma_max, int D,
-                        int kind, double* mu, double* var, double* cov, const int32_t* task_base, int Tsrc, void* stream) {   // (task_base NULL: (5e) as it was)
+                        int kind, double* mu, double* var, double* cov, const int32_t* task_base, int Tsrc, void* stream,
+                        bool value = false) {   // (task_base NULL: (5e) as it was; value: (5f), Mq candidates in strips of 16)
   const size_t lds = scaml::posterior_linv_lds_doubles(N, D) * sizeof(double);
   scaml::PosteriorGroupedParams p{};
-  p.base = scaml::PosteriorParams{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N, 16 * Mq, D, 0, 0, 0,
+  p.base = scaml::PosteriorParams{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N, value ? Mq : 16 * Mq, D, 0, 0, 0,
                                   nullptr, cov, Ma_max, 0, nullptr};
   p.ga = scaml::PosteriorGroupArgs{group, n_points_a, VA_tab, Xa, G, 0, task_base, Tsrc, 0};   // (with the table: T = task slots per group)
-  const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * (unsigned)Mq;   // XCD-aware (task, strip) map inside the kernel
-  return launch(task_base ? m.post_linv_grouped_own[kind] : m.post_linv_grouped[kind], dim3(blocks), 512, lds, stream,
-                task_base ? "gp_posterior_linv_grouped_own" : "gp_posterior_linv_grouped", p);
+  const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * (unsigned)(value ? Mq / 16 : Mq);   // XCD-aware (task, strip) map inside the kernel
+  hipFunction_t fn = value ? (task_base ? m.post_linv_grouped_val_own[kind] : m.post_linv_grouped_val[kind])
+                           : (task_base ? m.post_linv_grouped_own[kind] : m.post_linv_grouped[kind]);
+  return launch(fn, dim3(blocks), 512, lds, stream, task_base ? "gp_posterior_linv_grouped_own" : "gp_posterior_linv_grouped", p);
 }
 int acqf_batched_launch(Module& m, const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
                         const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
@@ -771,8 +781,9 @@ namespace {
 int grouped_grad_checked(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a, const double* const* VA_tab,
                          const double* X, const double* theta, const double* Linv, const double* alpha, const double* y_mean,
                          const double* y_std, const int32_t* n_points, int T, int N, int Mq, int G, int Ma_max, int D, int kind, double* mu,
-                         double* var, double* cov, bool own, const int32_t* task_base, int Tsrc, void* stream) {
+                         double* var, double* cov, bool own, const int32_t* task_base, int Tsrc, void* stream, bool value = false) {
   if (T < 0 || N < 1 || Mq < 0 || G < 0 || Ma_max < 1 || D < 1) return SCAML_E_BADARG;
+  if (value && (Mq & 15)) return SCAML_E_BADARG;   // (5f): whole strips of 16 candidates
   if (!Xq || !group || !Xa || !n_points_a || !VA_tab || !X || !theta || !Linv || !alpha || !mu || !var || !cov) return SCAML_E_BADARG;
   if (own && (!task_base || Tsrc < 1)) return SCAML_E_BADARG;
   if (!valid_kind(kind)) return SCAML_E_BADARG;
@@ -783,7 +794,7 @@ int grouped_grad_checked(const double* Xq, const int32_t* group, const double* X
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
   return grouped_grad_launch(*m, Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
-                             mu, var, cov, own ? task_base : nullptr, Tsrc, stream);
+                             mu, var, cov, own ? task_base : nullptr, Tsrc, stream, value);
 }
 }  // namespace
 int scaml_posterior_linv_grad_grouped_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
@@ -821,6 +832,62 @@ int scaml_target_acqf_batched_f64(const double* mu, const double* var, const dou
   if (!m) return SCAML_E_LAUNCH;
   return acqf_batched_launch(*m, mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param, Mq,
                              G, n_max, T, D, kind, acqf, value, grad, mu_out, var_out, stream);
+}
+
+// ---- (5f), (5f') the grouped pass in VALUE mode: a strip is 16 different candidates of one group, `group` has one entry per strip ----
+int scaml_posterior_linv_grouped_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                                     const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
+                                     const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T, int N,
+                                     int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov, void* stream) {
+  return grouped_grad_checked(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
+                              mu, var, cov, false, nullptr, 0, stream, true);
+}
+int scaml_posterior_linv_grouped_own_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                                         const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
+                                         const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T,
+                                         int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov,
+                                         const int32_t* task_base, int Tsrc, void* stream) {
+  return grouped_grad_checked(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
+                              mu, var, cov, true, task_base, Tsrc, stream, true);
+}
+
+// ---- (7i) the acquisition value of a table of candidates of many studies, a workgroup per strip of 16 (csrc/gp_studies_score.hip) ----
+int scaml_target_score_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
+                                   const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
+                                   const double* Linv_diag, const double* alpha, const int32_t* n_points, const double* m_all,
+                                   const double* s_all, const int32_t* info, const double* acqf_param, int Mq, int G, int n_max, int T,
+                                   int D, int kind, int acqf, double* value, double* mu_out, double* var_out, void* stream) {
+  if (Mq < 0 || (Mq & 15) || G < 0 || n_max < 1 || T < 1 || D < 1) return SCAML_E_BADARG;
+  if (!mu || !var || !cov || !group || !Xq || !w || !active || !Xt || !theta || !L || !Linv_diag || !alpha || !n_points || !m_all || !s_all ||
+      !info || !acqf_param || !value)
+    return SCAML_E_BADARG;
+  if (!valid_kind(kind) || (acqf != 0 && acqf != 1)) return SCAML_E_BADARG;
+  if (n_max > scaml::STUDIES_ACQF_MAX_N || D > scaml::STUDIES_ACQF_MAX_D || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
+  const size_t lds = scaml::studies_score_lds_doubles(n_max) * sizeof(double);
+  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (Mq == 0 || G == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  scaml::StudiesScoreParams p{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param,
+                              value, nullptr, mu_out, var_out, Mq, G, n_max, T, D, kind, acqf, 0};
+  return launch(m->tgt_score_batched, dim3((unsigned)(Mq / 16)), scaml::STUDIES_SCORE_THREADS, lds, stream, "target_score_batched", p);
+}
+static_assert(scaml::studies_score_lds_doubles(scaml::STUDIES_ACQF_MAX_N) * sizeof(double) <= kLdsLimit, "a strip at n_max = 96 fits the LDS");
+
+// ---- (7j) the training blocks Knn / resid of G studies in one launch (csrc/gp_studies_score.hip); (2) factors them together ----
+int scaml_target_train_block_batched_f64(const double* means_t, const double* covs_packed, const double* X, const double* y,
+                                         const int32_t* n_points, const double* m_all, const double* s_all, const double* w,
+                                         const uint8_t* active, const double* theta, int G, int n_max, int T, int D, int kind, double* Knn,
+                                         double* resid, void* stream) {
+  if (G < 0 || n_max < 1 || T < 1 || D < 1) return SCAML_E_BADARG;
+  if (!means_t || !covs_packed || !X || !y || !n_points || !m_all || !s_all || !w || !active || !theta || !Knn || !resid) return SCAML_E_BADARG;
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (n_max > scaml_fit_max_n()) return SCAML_E_TOOLARGE;   // what (2) factors
+  if (G == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  scaml::TrainBlockParams p{means_t, covs_packed, X, y, n_points, m_all, s_all, w, active, theta, Knn, resid, G, n_max, T, D};
+  return launch(m->tgt_train_block[kind], dim3((unsigned)G), 256, 0, stream, "target_train_block_batched", p);
 }
 
 // ---- (8) target GP: objective + gradient, and the whole L-BFGS refit, in one launch (csrc/gp_target_fit.hip) -------------

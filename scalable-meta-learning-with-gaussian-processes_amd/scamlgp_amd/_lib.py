@@ -102,6 +102,13 @@ SIGNATURES = {
     "scaml_posterior_linv_grad_grouped_own_f64": (_i, [_dp] * 12 + [_i] * 7 + [_dp, _dp, _dp, _dp, _i, c_void_p]),
     # (7g) 17 arrays; Mq, G, n_max, T, D, kind, acqf; value, grad, mu_out, var_out
     "scaml_target_acqf_batched_f64": (_i, [_dp] * 17 + [_i] * 7 + [_dp] * 4 + [c_void_p]),
+    # (5f), (5f') the value-only grouped pass: (5e)'s / (5e')'s argument lists, Mq candidates in strips of 16
+    "scaml_posterior_linv_grouped_f64": (_i, [_dp] * 12 + [_i] * 7 + [_dp, _dp, _dp, c_void_p]),
+    "scaml_posterior_linv_grouped_own_f64": (_i, [_dp] * 12 + [_i] * 7 + [_dp, _dp, _dp, _dp, _i, c_void_p]),
+    # (7i) (7g)'s 17 arrays; Mq, G, n_max, T, D, kind, acqf; value, mu_out, var_out
+    "scaml_target_score_batched_f64": (_i, [_dp] * 17 + [_i] * 7 + [_dp] * 3 + [c_void_p]),
+    # (7j) means_t, covs_packed, X, y, n_points, m_all, s_all, w, active, theta; G, n_max, T, D, kind; Knn, resid
+    "scaml_target_train_block_batched_f64": (_i, [_dp] * 10 + [_i] * 5 + [_dp, _dp, c_void_p]),
     "scaml_target_fit_max_n": (_i, [_i, _i]),
     "scaml_target_fit_max_d": (_i, []),
     "scaml_target_fit_workspace_doubles": (_ll, [_i, _i, _i, _i]),

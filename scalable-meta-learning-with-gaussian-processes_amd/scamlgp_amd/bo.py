@@ -67,9 +67,22 @@ def acqf_initial_conditions(af: Callable[[torch.Tensor], torch.Tensor], dim: int
     """Stage 1 of ``optimize_acqf``: ``raw_samples`` uniform candidates scored in one pass, then ``num_restarts`` initial conditions (the
     best candidate plus a Boltzmann sample of the rest, botorch's ``initialize_q_batch``).  Everything drawn comes from ``generator``.
     Returns (cand (raw_samples, dim), vals (raw_samples,), best0, x0 (R, dim))."""
-    cand = torch.rand(raw_samples, dim, dtype=torch.float64, generator=generator)
+    cand = acqf_draw_candidates(dim, raw_samples, generator)
     vals = af(cand).detach().cpu()
-    R = min(num_restarts, raw_samples)
+    best0, picks = acqf_pick_initial_conditions(vals, num_restarts, generator, eta)
+    return cand, vals, best0, cand[picks]
+
+
+def acqf_draw_candidates(dim: int, raw_samples: int, generator: Optional[torch.Generator]) -> torch.Tensor:
+    """The draw of ``acqf_initial_conditions``: ``raw_samples`` uniform candidates in [0, 1]^dim from ``generator`` (host, float64)."""
+    return torch.rand(raw_samples, dim, dtype=torch.float64, generator=generator)
+
+
+def acqf_pick_initial_conditions(vals: torch.Tensor, num_restarts: int, generator: Optional[torch.Generator], eta: float = 2.0):
+    """The pick of ``acqf_initial_conditions`` from the candidates' values ``vals`` (raw_samples,) on the host: the best candidate plus
+    a Boltzmann sample of the rest (botorch's ``initialize_q_batch``), drawn from ``generator``.  Returns (best0, picks): the index of
+    the best candidate and the indices of the min(num_restarts, raw_samples) initial conditions, best first."""
+    R = min(num_restarts, vals.shape[0])
     best0 = int(vals.argmax())
     picks = [best0]
     if R > 1:
@@ -79,7 +92,7 @@ def acqf_initial_conditions(af: Callable[[torch.Tensor], torch.Tensor], dim: int
         if float(pr.sum()) > 0:
             k = min(R - 1, int((pr > 0).sum()))
             picks += torch.multinomial(pr, k, replacement=False, generator=generator).tolist()
-    return cand, vals, best0, cand[picks]
+    return best0, picks
 
 
 def acqf_local_optimization(af: Callable[[torch.Tensor], torch.Tensor], x0: torch.Tensor, max_iter: int = 50, fd_step: float = 1e-4,
@@ -275,6 +288,13 @@ class ScaMLGPBOStudies:
     choice and the fall-back of the studies the batch does not take are ``"lockstep"``'s.  ``last_suggest_info``: ``batched``,
     ``n_eval`` (rounds enqueued), ``n_calls``, ``evals_per_start`` and ``status`` per start.  ``num_studies=1`` is a legitimate use.
 
+    ``score_mode`` (with ``"lockstep"`` or ``"device"``; ``"sequential"`` refuses ``"batched"``): ``"per_study"`` (default) -- stage 1 as
+    described, every study scores its own candidates; ``"batched"`` -- every batched study draws its candidates from its own ``gen``
+    (``acqf_draw_candidates``), ONE ``StudiesAcquisition.score`` call and one device -> host copy deliver all values (each table padded
+    to whole strips of 16), then every study makes its picks from its own ``gen`` (``acqf_pick_initial_conditions``); the studies'
+    factors come from one batched assemble and one batched Cholesky.  The draws, hence the generators' states, are the per-study
+    mode's.  ``last_suggest_info["score_mode"]`` names the mode.  Not forwarded to the loops.
+
     One source stack PER study (the reference's protocol: ``benchmark_cls(seed=study_seed)`` / ``meta_data_seed=study_seed``,
     scamlgp/benchmarking/local_runner.py:51-65, 178-181 -- every study draws its own meta-tasks): ``source_gps`` may be a sequence of S
     dicts, as ``model.meta_fit_scamlgp_studies`` returns them (slices of one stack fitted in one call).  All three modes work: the
@@ -282,10 +302,15 @@ class ScaMLGPBOStudies:
     (``utils.StudiesAcquisition``).  A single dict keeps meaning "shared"."""
 
     def __init__(self, source_gps: Union[Dict[Hashable, SourceGP], Sequence[Dict[Hashable, SourceGP]]], dim: int, num_studies: int,
-                 seeds: Optional[Sequence[int]] = None, suggest_mode: str = "sequential", **loop_kwargs):
+                 seeds: Optional[Sequence[int]] = None, suggest_mode: str = "sequential", score_mode: str = "per_study", **loop_kwargs):
         if suggest_mode not in ("sequential", "lockstep", "device"):
             raise ValueError(f"suggest_mode must be 'sequential', 'lockstep' or 'device', got {suggest_mode!r}")
-        self.suggest_mode = suggest_mode
+        if score_mode not in ("per_study", "batched"):
+            raise ValueError(f"score_mode must be 'per_study' or 'batched', got {score_mode!r}")
+        if score_mode == "batched" and suggest_mode == "sequential":
+            raise ValueError("score_mode='batched' needs suggest_mode='lockstep' or 'device': the sequential mode runs every study on its own")
+        self.suggest_mode, self.score_mode = suggest_mode, score_mode
+        self.profile_parts = False   # developer timing (tools/dev_studies_time.py): synchronise between the parts of a suggest and time them
         self.last_suggest_info: dict = {}
         S = int(num_studies)
         if S < 1:
@@ -336,21 +361,67 @@ class ScaMLGPBOStudies:
         return (not (st.max_pending_evaluations is not None and st.pending.shape[0] > 0)) and st.model.supports_posterior_grad()
 
     def _suggest_lockstep(self, studies: Sequence[ScaMLGPBOLoop]):
-        out = [None] * len(studies)
-        batch = []   # (position, study, af, cand, vals, best0, x0)
-        for i, st in enumerate(studies):
-            if not self._batched_study(st):
-                out[i] = st.suggest()
-                continue
-            st.model.eval()
-            af = st.acquisition_function()
-            batch.append((i, st, af) + acqf_initial_conditions(af, self.dim, st.raw_samples, st.num_restarts, st.gen))
-        self.last_suggest_info = dict(batched=[b[0] for b in batch], n_eval=0, n_iter=0)
-        if not batch:
-            return out
         from .utils import StudiesAcquisition
 
-        sa = StudiesAcquisition([b[2] for b in batch])
+        out = [None] * len(studies)
+        batch = []   # (position, study, af, cand, vals, best0, x0)
+        parts, t_last = {}, [None]
+
+        def mark(name=None):   # (profile_parts only) a synchronisation at the boundary; the time since the last one goes to `name`
+            if not self.profile_parts:
+                return
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            if name is not None:
+                parts[name] = parts.get(name, 0.0) + now - t_last[0]
+            t_last[0] = now
+
+        mark()
+        if self.score_mode == "batched":
+            drawn = []   # (position, study, af, cand): stage 1's draw per study, the scoring for all of them below
+            for i, st in enumerate(studies):
+                if not self._batched_study(st):
+                    out[i] = st.suggest()
+                    continue
+                st.model.eval()
+                drawn.append((i, st, st.acquisition_function(), acqf_draw_candidates(self.dim, st.raw_samples, st.gen)))
+            sa = None
+            if drawn:
+                # the studies' factors in two launches, then ONE scoring pass over all candidate tables (each padded to whole strips of
+                # 16 with a point of the box, whose values are dropped) and ONE device -> host copy
+                mark("stage1")
+                sa = StudiesAcquisition([d[2] for d in drawn], batched_factors=True)
+                mark("packing")
+                strips = [(d[3].shape[0] + 15) // 16 for d in drawn]
+                table = torch.full((16 * sum(strips), self.dim), 0.5, dtype=torch.float64)
+                o = 0
+                for d, ns in zip(drawn, strips):
+                    table[o:o + d[3].shape[0]] = d[3]
+                    o += 16 * ns
+                vals_all = sa.score(table, sa.group_of(strips))["value"].cpu()
+                o = 0
+                for (i, st, af, cand), ns in zip(drawn, strips):
+                    vals = vals_all[o:o + cand.shape[0]].clone()
+                    o += 16 * ns
+                    best0, pk = acqf_pick_initial_conditions(vals, st.num_restarts, st.gen)
+                    batch.append((i, st, af, cand, vals, best0, cand[pk]))
+        else:
+            for i, st in enumerate(studies):
+                if not self._batched_study(st):
+                    out[i] = st.suggest()
+                    continue
+                st.model.eval()
+                af = st.acquisition_function()
+                batch.append((i, st, af) + acqf_initial_conditions(af, self.dim, st.raw_samples, st.num_restarts, st.gen))
+        mark("stage1")
+        self.last_suggest_info = dict(batched=[b[0] for b in batch], n_eval=0, n_iter=0, score_mode=self.score_mode)
+        if self.profile_parts:
+            self.last_suggest_info["parts"] = parts   # seconds: stage1, packing (with the factors), rounds, stage3
+        if not batch:
+            return out
+        if self.score_mode != "batched":
+            sa = StudiesAcquisition([b[2] for b in batch])
+            mark("packing")
         counts = [b[6].shape[0] for b in batch]
         group = sa.group_of(counts)
         X0 = torch.cat([b[6] for b in batch], 0)
@@ -359,7 +430,11 @@ class ScaMLGPBOStudies:
             res = sa.optimize(X0, group, studies[0].af_max_iter, bounds=(0.0, 1.0))
             self.last_suggest_info.update(n_eval=res["n_eval"], n_calls=res["n_calls"], n_iter=int(res["stats"][:, 0].max()),
                                           evals_per_start=res["stats"][:, 1].tolist(), status=res["stats"][:, 2].tolist())
-            return self._final_choices(batch, out, res["x"].cpu().split(counts), res["f"].cpu().split(counts))
+            xs, fs = res["x"].cpu().split(counts), res["f"].cpu().split(counts)
+            mark("rounds")
+            out = self._final_choices(batch, out, xs, fs)
+            mark("stage3")
+            return out
         vg = lambda X: sa.value_and_grad(X, group)   # noqa: E731
         if studies[0].use_graph:   # one capture per suggest() serves all studies: a single stream, two library launches
             vg = GraphedAcquisition(vg, B, self.dim, sa.device)
@@ -376,7 +451,10 @@ class ScaMLGPBOStudies:
         res = hyper.batched_lbfgs(fun, X0, max_iter=studies[0].af_max_iter, bounds=(0.0, 1.0))
         fin = sa.value(res.x, group).cpu()   # the end points of all studies re-scored in one evaluation
         self.last_suggest_info.update(n_eval=res.n_eval, n_iter=res.n_iter, eval_seconds=t_eval[0])
-        return self._final_choices(batch, out, res.x.split(counts), fin.split(counts))
+        mark("rounds")
+        out = self._final_choices(batch, out, res.x.split(counts), fin.split(counts))
+        mark("stage3")
+        return out
 
     @staticmethod
     def _final_choices(batch, out, xs_per_study, fin_per_study):

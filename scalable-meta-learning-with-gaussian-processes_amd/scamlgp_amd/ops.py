@@ -777,6 +777,128 @@ def target_acqf_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor, 
     return dict(value=value, grad=grad, mu=mu_o, var=var_o)
 
 
+def source_posteriors_grouped(Xq: torch.Tensor, group: torch.Tensor, Xa: torch.Tensor, n_points_a: torch.Tensor, VA_tab: torch.Tensor,
+                              X: torch.Tensor, theta: torch.Tensor, kind: int, Linv: torch.Tensor, alpha: torch.Tensor,
+                              y_mean: Optional[torch.Tensor] = None, y_std: Optional[torch.Tensor] = None,
+                              n_points: Optional[torch.Tensor] = None, task_base: Optional[torch.Tensor] = None,
+                              tasks_per_group: Optional[int] = None, cov_out: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """``source_posteriors_grad_grouped`` without the gradient columns, for a TABLE of candidates: Xq (Mq, D) with Mq a multiple of 16,
+    every strip of 16 consecutive candidates belonging to ONE group; ``group`` (Mq / 16,) int32 names it per strip (negative or out of
+    range: a padding strip, zeros).  ``Xa`` (G, Ma_max, D), ``n_points_a`` (G,) int32 and ``VA_tab`` (G,) int64 are the groups' leading
+    points as in the GRAD sibling.  One launch of scaml_posterior_linv_grouped_f64.  Returns dict(mu, var (T, Mq), cov (T, Ma_max, Mq):
+    rows a < Ma_g of a strip are written, the rest is uninitialised -- or what ``cov_out`` held, when that buffer is given).
+
+    ``task_base`` (G,) int32 with ``tasks_per_group``: every group owns its source tasks (scaml_posterior_linv_grouped_own_f64) -- the
+    source arrays hold Tsrc = X.shape[0] tasks, slot t of group g reads task ``task_base[g] + t``, the outputs have T =
+    ``tasks_per_group`` leading rows."""
+    own = task_base is not None
+    if own != (tasks_per_group is not None):
+        raise ValueError("task_base and tasks_per_group go together")
+    Tsrc, N, D = X.shape
+    T = int(tasks_per_group) if own else Tsrc
+    Mq = Xq.shape[0]
+    if Mq % 16:
+        raise ValueError(f"the candidates come in whole strips of 16, got Mq = {Mq}")
+    G, Ma_max = int(Xa.shape[0]), int(Xa.shape[1])
+    X = _check(X, "X")
+    Xq = _check(Xq, "Xq", (Mq, D))
+    group = _check(group, "group", (Mq // 16,), torch.int32)
+    Xa = _check(Xa, "Xa", (G, Ma_max, D))
+    n_points_a = _check(n_points_a, "n_points_a", (G,), torch.int32)
+    VA_tab = _check(VA_tab, "VA_tab", (G,), torch.int64)
+    theta = _check(theta, "theta", (Tsrc, D + 2))
+    Linv = _check(Linv, "Linv", (Tsrc, N, N))
+    alpha = _check(alpha, "alpha", (Tsrc, N))
+    y_mean = _opt(y_mean, "y_mean", (Tsrc,))
+    y_std = _opt(y_std, "y_std", (Tsrc,))
+    n_points = _opt(n_points, "n_points", (Tsrc,), torch.int32)
+    if own:
+        task_base = _check(task_base, "task_base", (G,), torch.int32)
+    dev = X.device
+    with torch.cuda.device(dev):
+        mu = _empty(dev, T, Mq)
+        var = _empty(dev, T, Mq)
+        cov = _empty(dev, T, Ma_max, Mq) if cov_out is None else _check(cov_out, "cov_out", (T, Ma_max, Mq))
+        head = (_ptr(Xq), _ptr(group), _ptr(Xa), _ptr(n_points_a), _ptr(VA_tab), _ptr(X), _ptr(theta), _ptr(Linv), _ptr(alpha), _ptr(y_mean),
+                _ptr(y_std), _ptr(n_points), T, N, Mq, G, Ma_max, D, int(kind), _ptr(mu), _ptr(var), _ptr(cov))
+        if own:
+            name = "scaml_posterior_linv_grouped_own_f64"
+            rc = _lib.lib.scaml_posterior_linv_grouped_own_f64(*head, _ptr(task_base), Tsrc, _stream_handle())
+        else:
+            name = "scaml_posterior_linv_grouped_f64"
+            rc = _lib.lib.scaml_posterior_linv_grouped_f64(*head, _stream_handle())
+    _lib.check_rc(rc, name)
+    return dict(mu=mu, var=var, cov=cov)
+
+
+def target_score_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor, group: torch.Tensor, Xq: torch.Tensor, w: torch.Tensor,
+                         active: torch.Tensor, Xt: torch.Tensor, theta: torch.Tensor, L: torch.Tensor, Linv_diag: torch.Tensor,
+                         alpha: torch.Tensor, n_points: torch.Tensor, m_all: torch.Tensor, s_all: torch.Tensor, info: torch.Tensor,
+                         acqf_param: torch.Tensor, acqf: int, kind: int, want_posterior: bool = False):
+    """The acquisition value of every candidate of a table from the value-only grouped pass's outputs (``source_posteriors_grouped``:
+    mu, var (T, Mq), cov (T, n_max, Mq)), ``group`` (Mq / 16,) int32 per strip of 16 candidates, and the studies' padded arrays as
+    ``target_acqf_batched`` takes them.  One launch of scaml_target_score_batched_f64: a workgroup per strip, the study's factor staged
+    once for its 16 candidates; per candidate the arithmetic is ``target_acqf_batched``'s, bit for bit.  No gradient.
+    Returns dict(value (Mq,), mu, var (Mq,) or None)."""
+    Mq, D = Xq.shape
+    if Mq % 16:
+        raise ValueError(f"the candidates come in whole strips of 16, got Mq = {Mq}")
+    G, n_max = int(Xt.shape[0]), int(Xt.shape[1])
+    T = int(w.shape[1])
+    mu = _check(mu, "mu", (T, Mq))
+    var = _check(var, "var", (T, Mq))
+    cov = _check(cov, "cov", (T, n_max, Mq))
+    group = _check(group, "group", (Mq // 16,), torch.int32)
+    Xq = _check(Xq, "Xq")
+    w = _check(w, "w", (G, T))
+    active = _check(active, "active", (G, T), torch.uint8)
+    Xt = _check(Xt, "Xt", (G, n_max, D))
+    theta = _check(theta, "theta", (G, D + 2))
+    L = _check(L, "L", (G, n_max, n_max))
+    Linv_diag = _check(Linv_diag, "Linv_diag", (G, (n_max + 15) // 16, 16, 16))
+    alpha = _check(alpha, "alpha", (G, n_max))
+    n_points = _check(n_points, "n_points", (G,), torch.int32)
+    m_all = _check(m_all, "m_all", (G,))
+    s_all = _check(s_all, "s_all", (G,))
+    info = _check(info, "info", (G,), torch.int32)
+    acqf_param = _check(acqf_param, "acqf_param", (G,))
+    dev = Xq.device
+    with torch.cuda.device(dev):
+        value = _empty(dev, Mq)
+        mu_o = _empty(dev, Mq) if want_posterior else None
+        var_o = _empty(dev, Mq) if want_posterior else None
+        rc = _lib.lib.scaml_target_score_batched_f64(_ptr(mu), _ptr(var), _ptr(cov), _ptr(group), _ptr(Xq), _ptr(w), _ptr(active), _ptr(Xt),
+                                                     _ptr(theta), _ptr(L), _ptr(Linv_diag), _ptr(alpha), _ptr(n_points), _ptr(m_all), _ptr(s_all),
+                                                     _ptr(info), _ptr(acqf_param), Mq, G, n_max, T, D, int(kind), int(acqf), _ptr(value),
+                                                     _ptr(mu_o), _ptr(var_o), _stream_handle())
+    _lib.check_rc(rc, "scaml_target_score_batched_f64")
+    return dict(value=value, mu=mu_o, var=var_o)
+
+
+def target_factors_batched(batch: "TargetFitBatch", w: torch.Tensor, active: torch.Tensor, theta: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The jittered Cholesky factors of the training blocks of ALL problems of a ``TargetFitBatch`` in two launches whatever their
+    number: scaml_target_train_block_batched_f64 (Knn, resid per problem from the padded source terms and each problem's pruned
+    ``w`` (S, T), ``active`` (S, T) uint8 and ``theta`` (S, D + 2): what the weighted task sums and the target assemble produce for one
+    model's training block) and ONE ``potrf_batched(Knn, resid, n_points=..., want_linv=True)``.
+    Returns its dict: L (S, n_max, n_max), alpha (S, n_max), Linv_diag, info, jitter, quad, logdet."""
+    S, T, D, n_max = batch.S, batch.T, batch.D, batch.n_max
+    w = _check(w, "w", (S, T))
+    active = _check(active, "active", (S, T), torch.uint8)
+    theta = _check(theta, "theta", (S, D + 2))
+    dev = batch.device
+    with torch.cuda.device(dev):
+        Knn = torch.zeros(S, n_max, n_max, dtype=torch.float64, device=dev)
+        resid = torch.zeros(S, n_max, dtype=torch.float64, device=dev)
+        rc = _lib.lib.scaml_target_train_block_batched_f64(_ptr(batch.means_t), _ptr(batch.covs_p), _ptr(batch.X), _ptr(batch.y),
+                                                           _ptr(batch.n_points), _ptr(batch.m_all), _ptr(batch.s_all), _ptr(w), _ptr(active),
+                                                           _ptr(theta), S, n_max, T, D, int(batch.kind), _ptr(Knn), _ptr(resid),
+                                                           _stream_handle())
+    _lib.check_rc(rc, "scaml_target_train_block_batched_f64")
+    out = potrf_batched(Knn, resid, n_points=batch.n_points, want_linv=True)
+    out["Knn"], out["resid"] = Knn, resid
+    return out
+
+
 def mll_backward_workspace(T: int, N: int, D: int, device) -> Dict[str, torch.Tensor]:
     """Reusable buffers of ``mll_backward`` for a (T, N, D) stack: the explicit inverse factors (T N^2 doubles) and
     the per-tile partial sums.  An optimiser loop allocates them once (scaml_mll_backward_workspace_doubles)."""

@@ -444,7 +444,12 @@ class StudiesAcquisition:
     study g (``scaml_posterior_linv_grad_grouped_own_f64``: a study's query points meet only its own T tasks, the grid stays T x Mq);
     ``w`` / ``active`` stay (G, T) per slice.  ``task_base`` is None on the shared-stack path."""
 
-    def __init__(self, afs: Sequence[Union[UpperConfidenceBound, ExpectedImprovement]]):
+    SCORE_COV_CAP_BYTES = 256 << 20   # `score`: the most the covariance workspace of one chunk of strips may take
+
+    def __init__(self, afs: Sequence[Union[UpperConfidenceBound, ExpectedImprovement]], batched_factors: bool = False):
+        """``batched_factors``: the models that hold no ``_target_factor()`` for their parameter state get it from ONE batched assemble
+        and ONE batched Cholesky for all of them (``ops.target_factors_batched``) instead of a posterior call each; every model keeps its
+        slice (``_keep_target_factor``), so its own later calls reuse it.  False (default): the model's own posterior path, as before."""
         afs = list(afs)
         if not afs:
             raise ValueError("StudiesAcquisition needs at least one acquisition function")
@@ -482,6 +487,8 @@ class StudiesAcquisition:
         self.L, self.Linv_diag, self.alpha = z(G, n_max, n_max), z(G, nbm, 16, 16), z(G, n_max)
         self.info = torch.zeros(G, dtype=torch.int32, device=dev)
         self._VA = []
+        if batched_factors:
+            self._factors_batched([m for m in models if m._target_factor() is None])
         for g, (af, m) in enumerate(zip(afs, models)):
             n = m.n
             f = m._target_factor()
@@ -500,6 +507,60 @@ class StudiesAcquisition:
         self.s_all = host([m._s_all_f for m in models], torch.float64)
         self.acqf_param = host([float(a.beta if self.acqf == ops.ACQF_UCB else a.best_f) for a in afs], torch.float64)
         self.VA_tab = host([v.data_ptr() for v in self._VA], torch.int64)
+
+    @staticmethod
+    def _factors_batched(models: Sequence[ScaMLGP]):
+        """The training-block factors of ``models`` in two launches (``ops.target_factors_batched``), each model keeping its slice in the
+        layout its own ``ops.potrf_batched(Knn, resid, want_linv=True)`` returns.  A model the batch does not take -- no refit problem
+        (``target_problem()`` is None), or source tasks listed in another order than its stack's -- is left without one: the caller's
+        per-model path computes it.  Returns (the models taken, ``ops.target_factors_batched``'s dict for them), or ([], None)."""
+        take = []
+        for m in models:
+            prob = m.target_problem()
+            if prob is not None and [int(i) for i in m._idx] == list(range(m._stack.T)):
+                take.append((m, prob))
+        if not take:
+            return [], None
+        batch = ops.TargetFitBatch([p for _, p in take])
+        act = [m._active_tasks() for m, _ in take]
+        f = ops.target_factors_batched(batch, torch.stack([a[0] for a in act]), torch.stack([a[1] for a in act]).to(torch.uint8),
+                                       torch.stack([m.theta for m, _ in take]))
+        for g, (m, _) in enumerate(take):
+            n, nb = m.n, (m.n + 15) // 16
+            m._keep_target_factor(dict(L=f["L"][g:g + 1, :n, :n].contiguous(), alpha=f["alpha"][g:g + 1, :n].contiguous(),
+                                       quad=f["quad"][g:g + 1], logdet=f["logdet"][g:g + 1], info=f["info"][g:g + 1],
+                                       jitter=f["jitter"][g:g + 1], Linv_diag=f["Linv_diag"][g:g + 1, :nb].contiguous()))
+        return [m for m, _ in take], f
+
+    def score(self, X: torch.Tensor, group_per_strip: torch.Tensor, want_posterior: bool = False) -> Dict[str, torch.Tensor]:
+        """The acquisition value of a TABLE of candidates: X (Mq, D) with Mq a multiple of 16, every 16 consecutive candidates one
+        strip of ONE study, ``group_per_strip`` (Mq / 16,) int32 on the device naming it (negative: a padding strip, zeros).  Two
+        launches for any number of studies -- the value-only grouped source pass (``ops.source_posteriors_grouped``; its OWN form when
+        the models sit on slices of one parent stack) and the strip scoring kernel (``ops.target_score_batched``) --, no gradient.
+        The strips are taken in chunks so that the source pass's covariance workspace, T x n_max x 16 doubles per strip, stays within
+        ``SCORE_COV_CAP_BYTES`` (256 MiB: configs[4] with 32 studies x 1,024 candidates would need 0.67 GB in one piece and runs as three
+        chunks; a chunk still holds ~800 strips, several per CU); two launches per chunk.
+        Returns dict(value (Mq,), mu, var (Mq,) or None)."""
+        Xq = torch.as_tensor(X, dtype=torch.float64).reshape(-1, self.D).to(self.device).contiguous()
+        Mq = Xq.shape[0]
+        if Mq % 16 or tuple(group_per_strip.shape) != (Mq // 16,) or group_per_strip.dtype != torch.int32:
+            raise ValueError("score takes whole strips of 16 candidates and one int32 group per strip")
+        group = group_per_strip.to(self.device)
+        st, f = self.source, self.source.fit
+        T = self.w.shape[1]
+        per_chunk = max(1, self.SCORE_COV_CAP_BYTES // (T * self.n_max * 16 * 8))
+        parts = []
+        for s0 in range(0, Mq // 16, per_chunk):
+            s1 = min(Mq // 16, s0 + per_chunk)
+            xq, gr = Xq[16 * s0:16 * s1], group[s0:s1]
+            g = ops.source_posteriors_grouped(xq, gr, self.Xt, self.n_points, self.VA_tab, st.X, st.theta, st.kind, f["Linv"], f["alpha"],
+                                              st.y_mean, st.y_std, st.n_points, **self._own)
+            parts.append(ops.target_score_batched(g["mu"], g["var"], g["cov"], gr, xq, self.w, self.active, self.Xt, self.theta, self.L,
+                                                  self.Linv_diag, self.alpha, self.n_points, self.m_all, self.s_all, self.info, self.acqf_param,
+                                                  self.acqf, self.kind, want_posterior=want_posterior))
+        if len(parts) == 1:
+            return parts[0]
+        return {k: (torch.cat([p[k] for p in parts]) if parts[0][k] is not None else None) for k in parts[0]}
 
     def group_of(self, counts: Sequence[int]) -> torch.Tensor:
         """(sum counts,) int32 on the device: study s's index ``counts[s]`` times -- the ``group`` of a batch that lists the studies'

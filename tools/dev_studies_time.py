@@ -9,6 +9,8 @@ medians over the timed steps (the first step of a size is a warm-up and is not c
 
   python tools/dev_studies_time.py [--sizes 1,8,32,64] [--steps K] [--out profiles/studies_timings.txt]
   python tools/dev_studies_time.py --suggest [--sweep 1,2,4,8,16] [--evals-per-call K]    suggest() alone, in its three modes
+  python tools/dev_studies_time.py --score [--sizes 1,8,32,64] [--out profiles/studies_score_timings.txt]
+      the device mode's suggest() by score_mode, the split of a suggest into its parts, and StudiesAcquisition.score alone
   python tools/dev_studies_time.py --own-stacks [--sizes 8,32,128] [--out profiles/studies_own_stacks_timings.txt]
       one source stack PER study at hartmann6.py's shape (see own_stacks_table)
 """
@@ -35,6 +37,7 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--suggest", action="store_true", help="time suggest(): suggest_mode='device', 'lockstep' and the default, interleaved in one process")
 ap.add_argument("--sweep", default=None, help="with a list such as 1,2,4,8,16: the device mode's suggest() against ops.ACQF_OPT_EVALS_PER_CALL")
 ap.add_argument("--evals-per-call", type=int, default=None, help="ops.ACQF_OPT_EVALS_PER_CALL for --suggest")
+ap.add_argument("--score", action="store_true", help="device suggest(): score_mode='batched' against 'per_study', its split into parts, and score alone")
 ap.add_argument("--own-stacks", action="store_true", help="per-study source stacks: meta-fit, BO step and the grouped pass against what a caller had before")
 args = ap.parse_args()
 
@@ -270,6 +273,79 @@ def sweep_table():
     ops.ACQF_OPT_EVALS_PER_CALL = default_chunk
 
 
+def score_table():
+    """score_mode="batched" against score_mode="per_study" (the path as it was), both with suggest_mode="device": two ScaMLGPBOStudies
+    on the same data (both are told the per-study side's points), timed alternately step by step, n = 78 .. 80 over the three timed
+    steps; median and min .. max of each side's suggest.  Then, at n = 80 and without reports in between, three more suggests per side
+    with ``profile_parts`` (a device synchronisation at every boundary): the split into stage 1 (draw, scoring, picks), the
+    StudiesAcquisition packing with the factors, the optimiser rounds and stage 3, medians.  Last, ``StudiesAcquisition.score`` alone
+    for S x 1,024 candidates against S per-study scoring passes ``af(cand)`` (median of five, synchronised at the end of each side)."""
+    say(f"# device suggest() of S studies by score_mode, T = {T}, N = {N}, D = {D}, UCB, 1,024 raw candidates and 10 starts per study; ms, median of "
+        f"{args.steps} steps (n = {N_END - args.steps + 1} .. {N_END}), spread = min .. max of that side's suggest over those steps")
+    for S in [int(v) for v in args.sizes.split(",")]:
+        steps = args.steps + 1
+        n0 = N_END - steps
+        seeds = list(range(100, 100 + S))
+        modes = ("per_study", "batched")
+        sides = {k: ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, suggest_mode="device", score_mode=k, **KW) for k in modes}
+        for side in sides.values():
+            for s in range(S):
+                g = torch.Generator().manual_seed(seeds[s])
+                X0 = torch.rand(n0, D, dtype=torch.float64, generator=g)
+                side[s].record(X0, [obj(x) for x in X0])
+            utils.fit_targets_batched([st.model for st in side.studies], RESTARTS, rng=side.fit_gens)
+        ms = {k: [] for k in modes}
+        for step in range(steps):
+            X = {}
+            for k in modes:
+                t, X[k] = timed(sides[k].suggest)
+                if step:
+                    ms[k].append(1e3 * t)
+            ys = [obj(x) for x in X["per_study"]]
+            for side in sides.values():
+                side.report(X["per_study"], ys)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        spread = max(ms["per_study"]) - min(ms["per_study"])
+        gain = med["per_study"] - med["batched"]
+        for k in modes:
+            say(f"  S = {S:>3} {k:>10} suggest {med[k]:9.1f} ms   ({min(ms[k]):.1f} .. {max(ms[k]):.1f})   rounds {sides[k].last_suggest_info['n_eval']}")
+        say(f"#     n = {sides['batched'][0].model.n}; per_study - batched = {gain:.1f} ms against a per_study spread of {spread:.1f} ms: "
+            f"{'faster by more than the spread' if gain > spread else 'NOT faster by more than the spread'}; per_study / batched = {med['per_study'] / med['batched']:.2f}x")
+        for k in modes:
+            sides[k].profile_parts = True
+            got = []
+            for _ in range(3):
+                sides[k].suggest()
+                got.append(dict(sides[k].last_suggest_info["parts"]))
+            sides[k].profile_parts = False
+            p = {name: 1e3 * statistics.median(g_.get(name, 0.0) for g_ in got) for name in ("stage1", "packing", "rounds", "stage3")}
+            say(f"#     split, {k:>9}: stage 1 {p['stage1']:8.2f}   packing + factors {p['packing']:8.2f}   rounds {p['rounds']:8.2f}   stage 3 {p['stage3']:8.2f}   "
+                f"(stage 1 + packing = {p['stage1'] + p['packing']:.2f} of {sum(p.values()):.2f} ms)")
+        # score alone
+        models = [st.model.eval() for st in sides["per_study"].studies]
+        afs = [utils.UpperConfidenceBound(m, 9.0) for m in models]
+        g = torch.Generator().manual_seed(S)
+        cands = [torch.rand(1024, D, dtype=torch.float64, generator=g) for _ in range(S)]
+        sa = utils.StudiesAcquisition(afs, batched_factors=True)
+        table, group = torch.cat(cands).to(dev), sa.group_of([64] * S)
+        tb, tp = [], []
+        for r in range(6):
+            dt, _ = timed(lambda: sa.score(table, group)["value"].cpu())
+            tb.append(1e3 * dt)
+            dt, _ = timed(lambda: [af(c).detach().cpu() for af, c in zip(afs, cands)])
+            tp.append(1e3 * dt)
+        say(f"#     score alone, {S} x 1,024 candidates: StudiesAcquisition.score {statistics.median(tb[1:]):8.2f} ms ({min(tb[1:]):.2f} .. {max(tb[1:]):.2f})   "
+            f"{S} per-study passes {statistics.median(tp[1:]):8.2f} ms ({min(tp[1:]):.2f} .. {max(tp[1:]):.2f})")
+        del sides, sa, afs, models
+        torch.cuda.empty_cache()
+
+
+if args.score:
+    score_table()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 if args.sweep:
     sweep_table()
     if args.out:
