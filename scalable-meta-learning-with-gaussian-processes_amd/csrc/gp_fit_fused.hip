@@ -32,7 +32,9 @@
 //           right-hand side; v_{k+1} = W y rides along
 //       U2  all remaining tiles get the rank-16 update of panel k (4 MFMAs per tile, operands from
 //           the LDS panel) -- the bulk, during which the other waves' F(k+1) results arrive
-//       then column k+1 goes to HBM (128-byte row segments; the mirrored upper tile as zeros).
+//       then column k+1 goes to HBM (16-byte write-through stores, 8 rows x 128 bytes each, where L's rows sit on 16-byte
+//       boundaries; 8-byte stores elsewhere).  The zeros of the strict upper triangle (on request) left during the
+//       kernel-matrix build.
 // Which tile a slot holds is fixed for the whole kernel: every update wave works its schedule out once per attempt
 // (csrc/gf_schedule.hpp: operand offsets per slot and the slot range per column, in the lanes of one VGPR) and the phases
 // above fetch it with v_readlane instead of walking the triangle's columns again for every tile.
@@ -90,10 +92,26 @@ constexpr int PP = 17;
 static_assert(PP == FIT_PP, "gp_fit_params.h sizes the LDS with this pitch");
 static_assert(PP == GF_SCHED_PITCH, "gf_schedule.hpp packs byte offsets at this pitch");
 
+typedef double d2_t __attribute__((ext_vector_type(2)));   // one 16-byte store of L: two neighbours of a row
+
 // 32-bit LDS addresses: a tile's operand rows are (per-lane base) + (byte offset out of the wave's schedule)
 typedef __attribute__((address_space(3))) double lds_f64_t;
 __device__ __forceinline__ unsigned lds_addr(const double* p) { return (unsigned)(size_t)(const lds_f64_t*)p; }
 __device__ __forceinline__ lds_f64_t* lds_ptr(unsigned a) { return (lds_f64_t*)a; }
+
+// One 16-byte store of two neighbours of a row of L, write-through (sc1): nobody reads L again inside the kernel, and a line
+// that does not stay dirty in L2 is not written back at the end of it (plain 16-byte stores measured 6 us per launch slower,
+// profiles/store_path_notes.md).
+// The store sits inside asm, so the compiler's vmcnt bookkeeping does not count it.  That is safe only in one direction: vmcnt
+// comes down in issue order, so an operation the compiler does not know of can make one of its s_waitcnt vmcnt(n) wait for
+// MORE than it meant to, never for less -- as long as nothing ever waits for THIS store with a count.  Nothing does: L is
+// write-only here, no load depends on it, and the end of the kernel waits for all stores.  Do not put a vmcnt(n), n > 0,
+// that is meant to cover a load behind one of these by hand.
+// s_nop 1: the hardware fetches the 16 bytes of store data after issue; the wait state the compiler would put in front of a
+// write to those VGPRs is not added behind asm.
+__device__ __forceinline__ void store16(double* q, d2_t v) {
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(q), "v"(v) : "memory");
+}
 
 __device__ __forceinline__ int opaque_s(int v) {
   asm volatile("" : "+s"(v));  // keeps per-slot address arithmetic from being hoisted out of the panel loop
@@ -423,6 +441,41 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   double* Lg = (p.flags & SCAML_FIT_STORE_L) ? p.L + (size_t)task * b.sL((size_t)N * N) : nullptr;
   const bool zero_upper = (p.flags & SCAML_FIT_ZERO_UPPER) != 0;
   const int lane_idx = lq * LD + lc;  // element offset of this lane inside a 16x16 tile of L (row-major, ld = LD)
+  // 16-byte stores of L: lane -> row lane >> 3 (+ 8 on the second trip), column pair lane & 7 -- 8 rows x 128 bytes per
+  // instruction.  Only when every row of every tile starts on a 16-byte boundary (L is a caller's pointer and LD may be
+  // odd); wave-uniform.
+  // (the test and the lane mapping are worked out where they are used, from operands the compiler cannot trace back: neither
+  //  is kept in a register across the panel loop)
+  auto st16 = [&]() {
+    const int bits = opaque_s(__builtin_amdgcn_readfirstlane((int)(((unsigned)(size_t)Lg) | ((unsigned)LD << 3))));
+    return (bits & 15) == 0;
+  };
+  auto lane16 = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
+  // The strict upper triangle of L as zeros (on request): tile (c, ti), ti > c, mirrors the lower tile (ti, c).  The
+  // zeros depend on nothing the kernel computes, so they leave during the kernel-matrix build, which issues no other
+  // vector-memory instruction, by the wave that builds (ti, c).
+  const bool zfill = Lg && zero_upper;
+  auto zero_mirror = [&](int c, int ti) {
+    double* mb = Lg + ((size_t)(16 * c) * LD + 16 * ti);   // wave-uniform
+    if (16 * ti + 16 <= n) {                               // interior tile: no per-lane bounds
+      if (st16()) {
+        const d2_t z = {0.0, 0.0};
+        const int l = lane16(), lane_idx2 = (l >> 3) * LD + 2 * (l & 7);
+        store16(mb + lane_idx2, z);
+        store16(mb + (size_t)8 * LD + lane_idx2, z);
+      } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) mb[(size_t)g * 4 * LD + lane_idx] = 0.0;
+      }
+    } else if (16 * ti < n) {                              // (nothing of a tile past the n valid points)
+      const int mc = 16 * ti + lc;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int mr = 16 * c + lq + 4 * g;
+        if (mr < n && mc < n) mb[(size_t)g * 4 * LD + lane_idx] = 0.0;
+      }
+    }
+  };
 
   // Tiles in column-major order over the lower triangle: column j starts at tile off(j); this wave
   // owns tiles t = s * WU + wave (slot s), so its tiles of column j are the contiguous slots
@@ -567,6 +620,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
           double kt[4];                                                                            \
           tile_eval(kj, kr, tile_dist(kj, kr), kt);                                                \
           TILE_SET(r0, r1, r2, r3, r4, r5, r6, r7, kt[0], kt[1], kt[2], kt[3]);                    \
+          if (zfill && kr != 0) zero_mirror(kj, kj + kr);                                          \
           kr += WU;                                                                                \
         }                                                                                          \
       }
@@ -583,6 +637,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
         tile_eval(kj, kr, tile_dist(kj, kr), kt);
         double* img = KT + idx * 256 + lane;
         img[0] = kt[0]; img[64] = kt[1]; img[128] = kt[2]; img[192] = kt[3];
+        if (zfill && kr != 0) zero_mirror(kj, kj + kr);
       }
     }
 #ifdef SCAML_STAMPS
@@ -626,35 +681,39 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
     __syncthreads();
     STAMP(2);
 
-    // One finished sub-diagonal tile (ti, c): read back from the LDS column buffer in row segments -> HBM as
-    // 128-byte stores; the mirrored upper tile is written as zeros by the same lanes on request (no
-    // separate zero-fill pass over L).
+    // One finished sub-diagonal tile (ti, c): read back from the LDS column buffer in row segments -> HBM.
     auto store_tile = [&](int c, int ti) {
-      const double* prow = PT + (c % 3) * PANEL + (16 * ti + lq) * PP + lc;
-      const double e[4] = {prow[0], prow[4 * PP], prow[8 * PP], prow[12 * PP]};
       double* tb = Lg + ((size_t)(16 * ti) * LD + 16 * c);   // tile (ti, c), wave-uniform
-      double* mb = Lg + ((size_t)(16 * c) * LD + 16 * ti);   // mirrored tile (c, ti)
-      if (16 * ti + 16 <= n) {                              // interior tile: no per-lane bounds
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          tb[(size_t)g * 4 * LD + lane_idx] = e[g];
-          if (zero_upper) mb[(size_t)g * 4 * LD + lane_idx] = 0.0;
-        }
+      if (16 * ti + 16 <= n && st16()) {
+        // interior tile, rows on 16-byte boundaries: two neighbours of a row per lane (the odd pitch leaves the LDS side
+        // at 8-byte alignment: one two-address read per trip), two stores of 8 rows x 128 bytes
+        const int l = lane16(), lane_idx2 = (l >> 3) * LD + 2 * (l & 7);
+        const double* prow = PT + (c % 3) * PANEL + (16 * ti + (l >> 3)) * PP + 2 * (l & 7);
+        const d2_t e0 = {prow[0], prow[1]}, e1 = {prow[8 * PP], prow[8 * PP + 1]};
+        store16(tb + lane_idx2, e0);
+        store16(tb + (size_t)8 * LD + lane_idx2, e1);
       } else {
-        const int col = 16 * c + lc, mc = 16 * ti + lc;
+        const double* prow = PT + (c % 3) * PANEL + (16 * ti + lq) * PP + lc;
+        const double e[4] = {prow[0], prow[4 * PP], prow[8 * PP], prow[12 * PP]};
+        if (16 * ti + 16 <= n) {                              // interior tile: no per-lane bounds
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int row = 16 * ti + lq + 4 * g, mr = 16 * c + lq + 4 * g;
-          if (row < n && col < n) tb[(size_t)g * 4 * LD + lane_idx] = e[g];
-          if (zero_upper && mr < n && mc < n) mb[(size_t)g * 4 * LD + lane_idx] = 0.0;
+          for (int g = 0; g < 4; ++g) tb[(size_t)g * 4 * LD + lane_idx] = e[g];
+        } else {
+          const int col = 16 * c + lc;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int row = 16 * ti + lq + 4 * g;
+            if (row < n && col < n) tb[(size_t)g * 4 * LD + lane_idx] = e[g];
+          }
         }
       }
     };
     // The first PSTORE columns go to HBM from the panel wave: in the early panels it runs a whole step ahead
     // of the update waves (which are the bottleneck there) and has the time; later it is the bottleneck
-    // itself and the update waves store their own tiles.  (8 columns: re-tuned at the end of round 2; it was 12.)
+    // itself and the update waves store their own tiles.  (5 columns, re-tuned for the write-through 16-byte stores -- 3 .. 7:
+    // 100.4 / 100.3 / 100.1 / 100.7 / 101.6 us, profiles/store_path_timings.txt; it was 8 with 8-byte stores, 12 before.)
 #ifndef SCAML_PSTORE
-#define SCAML_PSTORE 8
+#define SCAML_PSTORE 5
 #endif
     constexpr int PSTORE = (WU == 7 && NB == 16) ? SCAML_PSTORE : 0;
 
@@ -739,24 +798,30 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
           const int c = j - 2;
           int ti = j - 1;
           for (; ti + SCAML_STRIP - 1 < NB && 16 * (ti + SCAML_STRIP) <= n; ti += SCAML_STRIP) {
-            const double* prow = PT + (c % 3) * PANEL + (16 * ti + lq) * PP + lc;
-            double e[4 * SCAML_STRIP];
+            if (st16()) {
+              const int l = lane16(), lane_idx2 = (l >> 3) * LD + 2 * (l & 7);
+              const double* prow = PT + (c % 3) * PANEL + (16 * ti + (l >> 3)) * PP + 2 * (l & 7);
+              d2_t e[2 * SCAML_STRIP];
 #pragma unroll
-            for (int u = 0; u < 4 * SCAML_STRIP; ++u) e[u] = prow[4 * u * PP];
-            double* tb = Lg + ((size_t)(16 * ti) * LD + 16 * c) + lane_idx;
+              for (int u = 0; u < 2 * SCAML_STRIP; ++u) e[u] = d2_t{prow[8 * u * PP], prow[8 * u * PP + 1]};
+              double* tb = Lg + ((size_t)(16 * ti) * LD + 16 * c) + lane_idx2;
 #pragma unroll
-            for (int u = 0; u < 4 * SCAML_STRIP; ++u) tb[(size_t)4 * u * LD] = e[u];
-            if (zero_upper) {
-              double* mb = Lg + ((size_t)(16 * c) * LD + 16 * ti) + lane_idx;
+              for (int u = 0; u < 2 * SCAML_STRIP; ++u) store16(tb + (size_t)8 * u * LD, e[u]);
+            } else {
+              const double* prow = PT + (c % 3) * PANEL + (16 * ti + lq) * PP + lc;
+              double e[4 * SCAML_STRIP];
 #pragma unroll
-              for (int g = 0; g < 4; ++g)
+              for (int u = 0; u < 4 * SCAML_STRIP; ++u) e[u] = prow[4 * u * PP];
+              double* tb = Lg + ((size_t)(16 * ti) * LD + 16 * c) + lane_idx;
 #pragma unroll
-                for (int u = 0; u < SCAML_STRIP; ++u) mb[(size_t)g * 4 * LD + 16 * u] = 0.0;
+              for (int u = 0; u < 4 * SCAML_STRIP; ++u) tb[(size_t)4 * u * LD] = e[u];
             }
           }
           for (; ti < NB; ++ti) store_tile(c, ti);
         }
+        STAMP(6);
         if (j >= 2) fold_column(j - 2);
+        STAMP(7);
         if (j == 1 && lane < WU) {
           // Off the critical path (the chain waits for parked tiles next anyway): which off-diagonal tiles of
           // each block row the update waves hold, for the back-substitution at the end -- lane w lists wave w.

@@ -25,10 +25,11 @@ def run(l, flags):
 for n, l in libs.items():   # sanity line per build: a wrong kernel shows up as failed pivots / a different MLL sum
     run(l, 1); torch.cuda.synchronize()
     print(f"{n:28s} failed tasks {int((info != 0).sum())}  sum(mll) {float(mll.sum()):.12f}  max jitter {float(jit.max()):.1e}")
-res = {(n, f): [] for n in libs for f in (1, 3)}
+FLAGS = (0, 1, 3)   # 0: no L at all (MLL-only mode); 3 - 0 = the whole cost of the output path
+res = {(n, f): [] for n in libs for f in FLAGS}
 for rnd in range(8):
     for n, l in libs.items():
-        for flags in (1, 3):
+        for flags in FLAGS:
             for _ in range(3): run(l, flags)
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -37,4 +38,4 @@ for rnd in range(8):
             e1.record(); torch.cuda.synchronize()
             res[(n, flags)].append(e0.elapsed_time(e1) / 20 * 1e3)
 for (n, f), v in res.items():
-    print(f"{n:28s} flags={f} (zero_upper={'yes' if f & 2 else 'no '}): median {statistics.median(v):7.1f} us  min {min(v):7.1f} us")
+    print(f"{n:28s} flags={f} (store_L={'yes' if f & 1 else 'no '} zero_upper={'yes' if f & 2 else 'no '}): median {statistics.median(v):7.1f} us  min {min(v):7.1f} us")

@@ -18,6 +18,7 @@ lib.scaml_gp_fit_fused_f64.argtypes = [vp]*5 + [ctypes.c_int]*4 + [vp]*8 + [ctyp
 lib.scaml_debug_set_stamp_buffer.restype, lib.scaml_debug_set_stamp_buffer.argtypes = SIGNATURES["scaml_debug_set_stamp_buffer"]
 T, N, D = int(sys.argv[1]) if len(sys.argv) > 1 else 256, int(sys.argv[2]) if len(sys.argv) > 2 else 256, int(sys.argv[3]) if len(sys.argv) > 3 else 8
 kind = int(sys.argv[4]) if len(sys.argv) > 4 else 1
+flags = int(sys.argv[5]) if len(sys.argv) > 5 else 1   # 1: store L; 3: with the upper-triangle zeros (what bench.py runs)
 dev = torch.device("cuda:0")
 d = synthetic.smooth_field_task_stack(T, N, D, seed=1234)
 ys, _, _ = synthetic.standardize_rows(d["Y"])
@@ -28,7 +29,7 @@ q, ld, mll, jit = (torch.empty(T, dtype=torch.float64, device=dev) for _ in rang
 stamps = torch.zeros(T, 2, 16, dtype=torch.int64, device=dev)
 assert lib.scaml_debug_set_stamp_buffer(stamps.data_ptr()) == 0
 for _ in range(3):
-    rc = lib.scaml_gp_fit_fused_f64(X.data_ptr(), y.data_ptr(), th.data_ptr(), None, None, T, N, D, kind, L.data_ptr(), alpha.data_ptr(), q.data_ptr(), ld.data_ptr(), mll.data_ptr(), info.data_ptr(), jit.data_ptr(), None, 1, None)
+    rc = lib.scaml_gp_fit_fused_f64(X.data_ptr(), y.data_ptr(), th.data_ptr(), None, None, T, N, D, kind, L.data_ptr(), alpha.data_ptr(), q.data_ptr(), ld.data_ptr(), mll.data_ptr(), info.data_ptr(), jit.data_ptr(), None, flags, None)
     assert rc == 0
 torch.cuda.synchronize()
 s = stamps.cpu().numpy().astype(np.float64)
@@ -51,7 +52,7 @@ names_u = {0: "load X,y", 9: "K-build (own tiles)", 1: "K-build: barrier + image
            6: "F: v, trsm, panel write, fold", 7: "U2: bulk update", 8: "column k+1 -> HBM", 15: "loop exit barrier", 11: "tail: M_k products+bar",
            12: "-", 13: "backsub: wait alpha + folds", 14: "backsub: barrier", 10: "tail: rest"}
 names_p = {0: "load X,y", 8: "K-build (15 tile images)", 1: "K-build: barrier", 2: "prologue", 3: "wait cntS[j-2] (D_j, R_j)", 4: "own TRSM + diag update", 5: "potf2",
-           9: "dl + publish", 15: "loop exit barrier",
+           9: "dl + publish", 6: "column j-2 -> HBM (first PSTORE)", 7: "fold column j-2 into rhs", 15: "loop exit barrier",
            11: "tail: scalars+bar", 12: "backsub: chain steps", 13: "backsub: wait for w_k", 14: "backsub: barrier", 10: "tail: rest"}
 med = np.median(s[:, 0], 0); medp = np.median(s[:, 1], 0); tot = med.sum(); totp = medp.sum()
 order = [0, 9, 8, 1, 2, 3, 4, 5, 6, 7, 15, 11, 12, 13, 14, 10] if False else [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 15, 11, 12, 13, 14, 10]
