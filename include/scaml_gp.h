@@ -415,6 +415,10 @@ int scaml_posterior_linv_grouped_own_f64(const double* Xq, const int32_t* group,
  *   decrease <= ftol, max_iter iterations), entirely on the device; value (B) = mll at the returned point, stats (B, 4)
  *   (may be NULL) = [iterations, evaluations, status, 0], status 1 / 2 converged (gradient / decrease), 0 max_iter,
  *   3 line search failed, 4 objective not finite at the start point.  workspace: scaml_target_fit_workspace_doubles(...) doubles.
+ * Non-finite inputs: a NaN weight or raw lengthscale in a row of z, or a NaN or infinite coordinate of X, makes every element of the
+ *   matrix that it enters NaN in BOTH kernel families (the Matern clamp and exp(-inf) = 0 do not hide it), so the factorisation
+ *   fails on every rung of the ladder: that row answers info > 0, value NaN and a zero gradient (n >= 2 for a lengthscale or a
+ *   coordinate: a single point has no distance).  The other rows of the launch -- in (8b) the other problems -- are not affected.
  * One workgroup per row of z, the n x n matrix in LDS: n <= scaml_target_fit_max_n(T, D) (128 at T = 32, D = 6),
  * D <= scaml_target_fit_max_d(); SCAML_E_TOOLARGE otherwise.
  */

@@ -141,14 +141,17 @@ TF_DEV double tf_rcp(double x) {
   return 1.0 / x;
 }
 
-// k(x_a, x_b) / os and d(k / os) / d(d2) for the scaled squared distance d2 (a != b)
+// k(x_a, x_b) / os and d(k / os) / d(d2) for the scaled squared distance d2 (a != b).  A d2 that is not finite (a NaN or infinite
+// coordinate, a NaN lengthscale) gives NaN in both families: d2 - d2 is 0 for a finite d2, and adding it changes no bit of a positive
+// number; alone, fmax drops a NaN operand (Matern-5/2: k = 1) and exp(-inf) is 0 (RBF), and the factorisation passed on a matrix that
+// stood for other inputs (include/scaml_gp.h (8), "non-finite inputs").
 TF_DEV void tf_kernel(int kind, double d2, double& kk, double& dk) {
   if (kind == 0) {
-    kk = exp(-0.5 * d2);
+    kk = exp(-0.5 * d2) + (d2 - d2);
     dk = -0.5 * kk;
   } else {
     const double s5 = 2.2360679774997896964;
-    const double r = sqrt(fmax(d2, 1e-30));   // gpytorch clamps the squared distance before the root
+    const double r = sqrt(fmax(d2, 1e-30) + (d2 - d2));   // gpytorch clamps the squared distance before the root
     const double e5 = exp(-s5 * r);
     kk = (1.0 + s5 * r + (5.0 / 3.0) * r * r) * e5;
     dk = -(5.0 / 6.0) * (1.0 + s5 * r) * e5;

@@ -1,7 +1,10 @@
 """The target GP's fused objective / gradient and the on-device refit (scaml_target_mll_f64, scaml_target_fit_f64) on the MI355X,
 through the C ABI, against torch autograd through the oracle's target_train_mll (scamlgp/model.py:360-363, 376-383 +
 scamlgp/utils.py:171-177) and against scipy L-BFGS-B on the oracle objective (the optimiser the reference drives,
-scamlgp/utils.py:175).  Tolerances: 1e-3 relative on the objective (north_star's MLL bound; measured ~1e-12), 1e-4 on the gradient."""
+scamlgp/utils.py:175).  Tolerances: 1e-3 relative on the objective (north_star's MLL bound; measured ~1e-12), 1e-4 on the gradient.
+These comparisons pin the kernel to the oracle's model; its ACCURACY -- the value and every gradient entry against a long-double
+reference under a-priori fp64 error bounds, at the shapes where the loops of csrc/gp_target_fit.hip branch -- is held by
+tests/_target_fit_bounds.py, tests/test_target_fit_bounds.py (CPU) and tests/test_target_fit_bounds_gpu.py."""
 import numpy as np
 import pytest
 import scipy.optimize
