@@ -305,6 +305,9 @@ int scaml_target_posterior_grad_f64(const double* cov_g, const double* mu_g, con
  * inputs Xt (n, D), the queries Xq (M, D) and the target kernel theta (D + 2) of family `kind`, as (5d) takes them; the gradient
  * contracts over the training points once per query with abar = sum_f dA/dmu_f alpha[:, f].  info (1) int32 or NULL: a factorisation
  * that failed even with jitter turns every output into NaN.  One wave per query point, no host synchronisation.
+ * Non-finite queries: a query point with a NaN or infinite coordinate in Xq[q] gives NaN in EVERY entry of grad[q], whatever mu_g /
+ * var_g / cov_g hold (as (5d)), and a query whose value[q] is NaN (a NaN in its column of Knq or Z, in mean_q[q] or var_q[q]) gives NaN
+ * in every entry of grad[q] too; the other query points are not affected.  (value[q] itself reads no coordinate.)
  * Limits: F <= 64, n <= scaml_fit_max_n(); with grad also n <= 96 and D <= 15.  SCAML_E_TOOLARGE beyond them.
  */
 int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q,

@@ -86,6 +86,16 @@ __device__ __forceinline__ void fantasy_acqf_body(const scaml::FantasyAcqfParams
   const double sAmu = wave_sum_all(Amu), sAv = wave_sum_all(Av);
   am[lane] = Amu;
   __syncthreads();
+  // a query point with a NaN / inf coordinate: the clamps of kernel_and_slope_scaled are bare v_max / v_min, which drop a NaN operand --
+  // only that coordinate's df[d] would carry it, the other D - 1 entries would be the gradient at a nonsense distance; and a NaN value
+  // (a NaN column of Knq / Z) leaves UCB's A_mu = -1, A_v = 0 and with them a finite gradient.  val - val and sum_d (x_d - x_d) are 0,
+  // or NaN for such a query: every entry of its gradient is NaN where the results are stored, as in scaml_target_grad_kernel (a
+  // select: finite inputs stay bit for bit what they were)
+  double bad = val - val;
+  for (int d = 0; d < D; ++d) {
+    const double x = p.Xq[(size_t)q * D + d];
+    bad += x - x;
+  }
   // (3) lanes = training points: abar_a = sum_f A_mu,f alpha[a, f]; the kernel slopes at (x_a, x_q), once for all D dimensions
   const double os = p.theta[D], inv_s2 = 1.0 / s2;
   const size_t W = (size_t)M * 16, col0 = (size_t)q * 16 + 1;
@@ -128,7 +138,7 @@ __device__ __forceinline__ void fantasy_acqf_body(const scaml::FantasyAcqfParams
       if (lane == 63) {
         const double gmu = __builtin_fma(sAmu, p.mu_g[col0 + d], s * sm);
         const double gvar = p.var_g[col0 + d] - 2.0 * s2 * sv;
-        p.grad[(size_t)q * D + d] = __builtin_fma(sAv, gvar, gmu) * invF;
+        p.grad[(size_t)q * D + d] = bad == 0.0 ? __builtin_fma(sAv, gvar, gmu) * invF : bad;
       }
     }
   }

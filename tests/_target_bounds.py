@@ -582,4 +582,7 @@ def check_chain(be, kind):
     refs = tgrad_reference(ga)
     within(label, ("chain", fam, "dmu"), dmu, refs["dmu"])
     within(label, ("chain", fam, "dvar"), dvar, refs["dvar"])
-    return dict(mu=mu, var=var, dmu=dmu, dvar=dvar)
+    # ctx: what a further stage on the same pipeline needs (tests/_fantasy_bounds.check_chain)
+    ctx = dict(Knq=asm["Knq"], mean_q=asm["mean_q"], var_q=asm["var_q"], resid=asm["resid"], L=f["L"], W=f["W"], info=int(f["info"]), Z=Z, cov_g=cov_g,
+               mu_g=mu_g, var_g=var_g, theta=a["theta"], Xall=Xall, m=m, s=s)
+    return dict(mu=mu, var=var, dmu=dmu, dvar=dvar, ctx=ctx)
