@@ -561,17 +561,18 @@ int scaml_studies_acqf_opt_own_f64(const double* x0, const int32_t* group, const
 
 /*
  * (7i) The acquisition VALUE of a table of candidates of many studies, behind (5f): one workgroup per strip of 16 candidates of one
- * study; the study's L, Linv_diag and alpha are staged in LDS once per workgroup and serve all 16 columns (csrc/gp_studies_score.h).
+ * study; the study's L, Linv_diag and alpha are staged in LDS once per workgroup and serve all 16 columns (csrc/gp_studies_acqf.h).
  *   mu, var (T, Mq), cov (T, n_max, Mq): (5f)'s outputs; group (Mq / 16) int32 per strip; Xq (Mq, D); Mq a multiple of 16.
  *   w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param: the studies as (7g) takes them.
  *   value (Mq); mu_out, var_out (Mq) or NULL.  No gradient.
- * Per candidate the operations are exactly (7g)'s on column 0 of its 16-column layout, in (7g)'s order, each output by one thread and
- * without atomics: value, mu_out and var_out are a pure function of the inputs and BIT-IDENTICAL to (7g)'s for the same per-task numbers.
+ * (7g) and (7i) are two instantiations of ONE kernel body (sa_block<R> of csrc/gp_studies_acqf.h: R = 1 right-hand side with 15 gradient
+ * columns, or R = 16): per candidate the operations are (7g)'s on column 0 of its 16-column layout, in (7g)'s order, each output by one thread
+ * and without atomics: value, mu_out and var_out are a pure function of the inputs and BIT-IDENTICAL to (7g)'s for the same per-task numbers.
  * info[g] != 0 (or n_points[g] outside 1 .. n_max) gives NaN for the study's candidates, a padding strip zeros; an inactive task is
  * skipped, not multiplied by zero; what lies past n_g in a study's slices is never read; a candidate with a NaN or infinite coordinate
  * gives NaN in its own outputs only.
  * Checks: sizes (Mq < 0 or not a multiple of 16, G < 0, n_max < 1, T < 1, D < 1), NULL required pointers, kind, acqf: SCAML_E_BADARG.
- * Limits: n_max <= 96, D <= 15 and the LDS footprint of a strip (a constexpr of csrc/gp_studies_score.h): SCAML_E_TOOLARGE beyond them
+ * Limits: n_max <= 96, D <= 15 and the LDS footprint of a strip (a constexpr of csrc/gp_studies_acqf.h): SCAML_E_TOOLARGE beyond them
  * (bad arguments answer first).  Mq == 0 or G == 0: nothing is enqueued.  Does not synchronise.
  */
 int scaml_target_score_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,

@@ -18,6 +18,7 @@
 // to LDS; lanes = training points again for abar and the kernel slopes (one slope evaluation serves all D dimensions).
 #include "scaml_common.hpp"
 #include "gp_fantasy_params.h"
+#include "gp_studies_formulas.h"   // sa_acquisition: the one statement of UCB / EI and their chain-rule factors
 
 namespace {
 
@@ -63,21 +64,7 @@ __device__ __forceinline__ void fantasy_acqf_body(const scaml::FantasyAcqfParams
   }
   mu = __builtin_fma(s, mu, p.m_all);
   double A, Amu, Av;
-  if (p.acqf == 0) {   // UCB: -mu + sqrt(beta max(v, 0)); d/dv = beta / (2 sqrt(beta v)), zero where v is clamped
-    const double beta = p.acqf_param;
-    const double sd = sqrt(beta * (v > 0.0 ? v : 0.0));
-    A = sd - mu;
-    Amu = -1.0;
-    Av = v > 0.0 ? 0.5 * beta / (sd > 1e-300 ? sd : 1e-300) : 0.0;
-  } else {             // EI (minimisation): d/dmu = -Phi(u), d/dv = phi(u) / (2 sigma), zero on the 1e-9 floor
-    const double sigma = sqrt(v > 1e-9 ? v : 1e-9);
-    const double u = -(mu - p.acqf_param) / sigma;
-    const double pdf = exp(-0.5 * u * u) * 0.39894228040143267794;   // 1 / sqrt(2 pi)
-    const double cdf = 0.5 * (1.0 + erf(u * 0.70710678118654752440));
-    A = sigma * (pdf + u * cdf);
-    Amu = -cdf;
-    Av = v > 1e-9 ? 0.5 * pdf / sigma : 0.0;
-  }
+  scaml::sa_acquisition(p.acqf, p.acqf_param, mu, v, A, Amu, Av);   // UCB / EI with the clamps: csrc/gp_studies_formulas.h
   if (!live) A = Amu = Av = 0.0;
   const double invF = 1.0 / F;
   const double val = wave_sum_all(A);

@@ -1,5 +1,6 @@
 // gp_studies_acqf.h -- the batched target acquisition of many BO studies (include/scaml_gp.h (7g)): argument block, LDS footprint and
-// the arithmetic of one query point.  One source for the device kernel (csrc/gp_studies_acqf.hip: a workgroup per query point), the
+// the arithmetic of one block of right-hand sides, sa_block<R>.  One source for both device kernels (csrc/gp_studies_acqf.hip: a
+// workgroup per query point, R = 1; csrc/gp_studies_score.hip: a workgroup per strip of 16 candidates, R = 16, value only (7i)), the
 // host launcher and the single-threaded host build the CPU tests check against torch (any compiler but hipcc: tests/host_emul).
 //
 // Per query point q of group g (a study: its weights, target kernel, training inputs, cached factor of Knn, alpha, standardiser):
@@ -9,11 +10,11 @@
 //   z        = Knn^-1 Knq from the cached factor (blocked substitution with the 16 x 16 inverses of L's diagonal blocks)
 //   mu*      = m + s ((S_mu[0] - m) / s + Knq . alpha),   var* = s^2 (S_var[0] / s^2 + os - Knq . z)
 //   dmu*[d]  = S_mu[1 + d] + s sum_a alpha_a dKnq[a][d],   dvar*[d] = S_var[1 + d] - 2 s^2 sum_a z_a dKnq[a][d]
-//   UCB / EI and their chain rule with the clamps of scamlgp_amd/utils.py (csrc/gp_fantasy.hip states them for F fantasies).
+//   UCB / EI and their chain rule with the clamps of scamlgp_amd/utils.py (sa_acquisition, which csrc/gp_fantasy.hip calls for F fantasies).
 // Every sum runs in a fixed order (tasks ascending, training points ascending) by ONE thread per output: no atomics, no wave
 // reductions, so the result is a pure function of the inputs and the host build computes what the device computes.
 #pragma once
-#include "gp_studies_formulas.h"   // SA_DEV / SA_SYNC, sa_kernel_and_slope, sa_acquisition (shared with csrc/gp_studies_score.h)
+#include "gp_studies_formulas.h"   // SA_DEV / SA_SYNC, sa_kernel_and_slope, sa_acquisition
 
 namespace scaml {
 
@@ -46,61 +47,76 @@ struct StudiesAcqfParams {
   int Mq, G, n_max, T, D, kind, acqf, pad_;
 };
 
-// LDS of one query point, in doubles: C [n_max][16] | S_mu, S_var [32] | u, v, alpha [3 np] | W [nb][256] | L [n_max][n_max | 1] | red [48]
-constexpr size_t studies_acqf_lds_doubles(int n_max) {
+// LDS of one block of R right-hand sides, in doubles:
+//   C [n_max][16] | S_mu, S_var [32] | u, v [2][np * R] | alpha [np] | W [nb][256] | L [n_max][n_max | 1] | red [R == 1 ? 48 : 32]
+template <int R>
+constexpr size_t sa_lds_doubles(int n_max) {
   const size_t nb = (size_t)(n_max + 15) / 16, np = nb * 16;
-  return (size_t)n_max * 16 + 32 + 3 * np + nb * 256 + (size_t)n_max * (size_t)(n_max | 1) + 48;
+  return (size_t)n_max * 16 + 32 + 2 * np * R + np + nb * 256 + (size_t)n_max * (size_t)(n_max | 1) + (R == 1 ? 48 : 32);
 }
+constexpr size_t studies_acqf_lds_doubles(int n_max) { return sa_lds_doubles<1>(n_max); }
 
-// One query point by `nthr` cooperating threads (thread `tid`; SA_SYNC between the phases).  `lds`: studies_acqf_lds_doubles(n_max).
-SA_DEV void sa_query(const StudiesAcqfParams& p, double* lds, int q, int tid, int nthr) {
+// One block `blk` of R right-hand sides of one study by `nthr` cooperating threads (thread `tid`; SA_SYNC between the phases).
+// `lds`: sa_lds_doubles<R>(n_max).  The two instantiations are the two layouts of the grouped source pass:
+//   R = 1   a query point in the 16-column GRAD layout: mu, var (T, Mq, 16), cov (T, n_max, Mq * 16), group (Mq) per query.  Column 0
+//           is the right-hand side, columns 1 .. 15 of C are the gradient columns that ride along; `grad` is written where given.
+//   R = 16  a strip of 16 candidates in the value layout: mu, var (T, Mq), cov (T, n_max, Mq), group (Mq / 16) per strip, Mq a
+//           multiple of 16.  The 16 columns of C are 16 right-hand sides against ONE copy of the factor; `grad` is not used.
+// Either way a block owns 16 consecutive columns of a source row and C is [a][16]; element e of an [.][R] array is (e / R, e % R).
+template <int R>
+SA_DEV void sa_block(const StudiesAcqfParams& p, double* lds, int blk, int tid, int nthr) {
+  static_assert(R == 1 || R == 16, "a query point with its gradient columns, or a strip of 16 candidates");
   const int D = p.D, T = p.T, n_max = p.n_max;
-  const int g = p.group[q];
+  const int g = p.group[blk];
+  const size_t q0 = (size_t)blk * R;   // the block's first output
   const double nan = NAN;
   // (every branch up to the first barrier is uniform over the workgroup)
-  if (g < 0 || g >= p.G) {
-    if (tid == 0) {
-      p.value[q] = 0.0;
-      if (p.mu_out) p.mu_out[q] = 0.0;
-      if (p.var_out) p.var_out[q] = 0.0;
+  if (g < 0 || g >= p.G) {   // padding
+    for (int c = tid; c < R; c += nthr) {
+      p.value[q0 + c] = 0.0;
+      if (p.mu_out) p.mu_out[q0 + c] = 0.0;
+      if (p.var_out) p.var_out[q0 + c] = 0.0;
     }
-    if (p.grad) for (int d = tid; d < D; d += nthr) p.grad[(size_t)q * D + d] = 0.0;
+    if constexpr (R == 1)
+      if (p.grad) for (int d = tid; d < D; d += nthr) p.grad[q0 * D + d] = 0.0;
     return;
   }
   const int n = p.n_points[g];
   if (p.info[g] != 0 || n < 1 || n > n_max) {
-    if (tid == 0) {
-      p.value[q] = nan;
-      if (p.mu_out) p.mu_out[q] = nan;
-      if (p.var_out) p.var_out[q] = nan;
+    for (int c = tid; c < R; c += nthr) {
+      p.value[q0 + c] = nan;
+      if (p.mu_out) p.mu_out[q0 + c] = nan;
+      if (p.var_out) p.var_out[q0 + c] = nan;
     }
-    if (p.grad) for (int d = tid; d < D; d += nthr) p.grad[(size_t)q * D + d] = nan;
+    if constexpr (R == 1)
+      if (p.grad) for (int d = tid; d < D; d += nthr) p.grad[q0 * D + d] = nan;
     return;
   }
   const int nbm = (n_max + 15) / 16, np = nbm * 16, nb = (n + 15) / 16, ldl = n_max | 1;
-  double* C = lds;
-  double* Ssum = C + (size_t)n_max * 16;   // S_mu [16] | S_var [16]
-  double* u = Ssum + 32;
-  double* v = u + np;
-  double* al = v + np;
+  double* C = lds;                          // [a][16]: Knq in columns c < R, then (R = 1) dKnq in columns 1 + d
+  double* Ssum = C + (size_t)n_max * 16;    // S_mu [16] | S_var [16]
+  double* u = Ssum + 32;                    // [a][R]
+  double* v = u + (size_t)np * R;
+  double* al = v + (size_t)np * R;
   double* Wd = al + np;
   double* Ls = Wd + (size_t)nbm * 256;
-  double* red = Ls + (size_t)n_max * ldl;
+  double* red = Ls + (size_t)n_max * ldl;   // Knq . alpha [R] | Knq . z [R]; R = 1: then sum_a alpha_a dKnq [2 + d], sum_a z_a dKnq [18 + d]
 
   const double s = p.s_all[g], m = p.m_all[g], s2 = s * s, inv_s2 = 1.0 / s2;
   const double* th = p.theta + (size_t)g * (D + 2);
   const double os = th[D];
   const double* wg = p.w + (size_t)g * T;
   const uint8_t* ag = p.active + (size_t)g * T;
-  const size_t W16 = (size_t)p.Mq * 16, col0 = (size_t)q * 16;
+  const size_t W = (size_t)p.Mq * (R == 1 ? 16 : 1), col0 = (size_t)blk * 16;   // a source row, the block's 16 columns in it
 
-  // ---- phase 1: the weighted task sums (eight tasks' loads in flight), the factor, its block inverses and alpha into LDS
+  // ---- phase 1: the weighted task sums (eight tasks' loads in flight; a row's 16 columns are 128 consecutive bytes), the factor,
+  // its block inverses and alpha into LDS
   for (int e = tid; e < n * 16 + 32; e += nthr) {
     const bool is_cov = e < n * 16;
     const int a = e >> 4, c = e & 15;
     const int which = (e - n * 16) >> 4;   // 0: mu, 1: var
-    const double* src = is_cov ? p.cov + (size_t)a * W16 + col0 + c : (which == 0 ? p.mu : p.var) + col0 + c;
-    const size_t tstride = is_cov ? (size_t)n_max * W16 : W16;
+    const double* src = is_cov ? p.cov + (size_t)a * W + col0 + c : (which == 0 ? p.mu : p.var) + col0 + c;
+    const size_t tstride = is_cov ? (size_t)n_max * W : W;
     const bool lin = !is_cov && which == 0;
     double acc = 0.0;
     for (int t0 = 0; t0 < T; t0 += 8) {
@@ -108,7 +124,7 @@ SA_DEV void sa_query(const StudiesAcqfParams& p, double* lds, int q, int tid, in
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const int t = t0 + k;
-        const bool ok = t < T && ag[t];
+        const bool ok = t < T && ag[t];   // (a masked task is skipped, not multiplied by zero: its values may be NaN)
         val[k] = ok ? src[(size_t)t * tstride] : 0.0;
         const double wt = ok ? wg[t] : 0.0;
         cf[k] = lin ? wt : wt * wt;
@@ -130,10 +146,11 @@ SA_DEV void sa_query(const StudiesAcqfParams& p, double* lds, int q, int tid, in
     for (int a = tid; a < n; a += nthr) al[a] = p.alpha[(size_t)g * n_max + a];
   }
   SA_SYNC();
-  // ---- phase 1b: the target kernel's part of Knq and of its input gradient, one slope evaluation per training point
-  for (int a = tid; a < n; a += nthr) {
+  // ---- phase 1b: the target kernel's part of Knq and (R = 1) of its input gradient, one slope evaluation per (training point, rhs)
+  for (int e = tid; e < n * R; e += nthr) {
+    const int a = e / R, c = e % R;
     const double* xa = p.Xt + ((size_t)g * n_max + a) * D;
-    const double* xq = p.Xq + (size_t)q * D;
+    const double* xq = p.Xq + (q0 + c) * D;
     double d2 = 0.0;
     for (int d = 0; d < D; ++d) {
       const double df = (xq[d] - xa[d]) / th[d];
@@ -142,81 +159,94 @@ SA_DEV void sa_query(const StudiesAcqfParams& p, double* lds, int q, int tid, in
     double k0, dk;
     sa_kernel_and_slope(p.kind, d2, os, k0, dk);
     double* Ca = C + (size_t)a * 16;
-    Ca[0] += k0;
-    for (int d = 0; d < D; ++d) Ca[1 + d] += 2.0 * dk * ((xq[d] - xa[d]) / (th[d] * th[d]));
-    u[a] = Ca[0];
+    Ca[c] += k0;
+    if constexpr (R == 1)
+      for (int d = 0; d < D; ++d) Ca[1 + d] += 2.0 * dk * ((xq[d] - xa[d]) / (th[d] * th[d]));
+    u[e] = Ca[c];
   }
   SA_SYNC();
-  // ---- phase 2: z = Knn^-1 Knq.  Forward L y = Knq by block rows: y_kb = W_kb u_kb, then u_i -= L[i, kb] y_kb below the block
+  // ---- phase 2: z = Knn^-1 Knq, R right-hand sides.  Forward L y = Knq by block rows: y_kb = W_kb u_kb, then
+  // u_i -= L[i, kb] y_kb below the block
   for (int kb = 0; kb < nb; ++kb) {
     const int r0 = 16 * kb, cnt = n - r0 < 16 ? n - r0 : 16;
-    for (int r = tid; r < cnt; r += nthr) {
+    for (int e = tid; e < cnt * R; e += nthr) {
+      const int r = e / R, c = e % R;
       double acc = 0.0;
-      for (int k = 0; k <= r; ++k) acc = fma(Wd[kb * 256 + r * 16 + k], u[r0 + k], acc);
-      v[r0 + r] = acc;
+      for (int k = 0; k <= r; ++k) acc = fma(Wd[kb * 256 + r * 16 + k], u[(r0 + k) * R + c], acc);
+      v[(r0 + r) * R + c] = acc;
     }
     SA_SYNC();
-    for (int i = r0 + 16 + tid; i < n; i += nthr) {
-      double acc = u[i];
-      for (int k = 0; k < 16; ++k) acc = fma(-Ls[(size_t)i * ldl + r0 + k], v[r0 + k], acc);
-      u[i] = acc;
+    for (int e = (r0 + 16) * R + tid; e < n * R; e += nthr) {
+      const int i = e / R, c = e % R;
+      double acc = u[e];
+      for (int k = 0; k < 16; ++k) acc = fma(-Ls[(size_t)i * ldl + r0 + k], v[(r0 + k) * R + c], acc);
+      u[e] = acc;
     }
     SA_SYNC();
   }
   // backward L^T z = y (y in v, z into u): z_kb = W_kb^T v_kb, then v_i -= L[kb, i]^T z_kb above the block
   for (int kb = nb - 1; kb >= 0; --kb) {
     const int r0 = 16 * kb, cnt = n - r0 < 16 ? n - r0 : 16;
-    for (int r = tid; r < cnt; r += nthr) {
+    for (int e = tid; e < cnt * R; e += nthr) {
+      const int r = e / R, c = e % R;
       double acc = 0.0;
-      for (int k = r; k < cnt; ++k) acc = fma(Wd[kb * 256 + k * 16 + r], v[r0 + k], acc);
-      u[r0 + r] = acc;
+      for (int k = r; k < cnt; ++k) acc = fma(Wd[kb * 256 + k * 16 + r], v[(r0 + k) * R + c], acc);
+      u[(r0 + r) * R + c] = acc;
     }
     SA_SYNC();
-    for (int i = tid; i < r0; i += nthr) {
-      double acc = v[i];
-      for (int k = 0; k < cnt; ++k) acc = fma(-Ls[(size_t)(r0 + k) * ldl + i], u[r0 + k], acc);
-      v[i] = acc;
+    for (int e = tid; e < r0 * R; e += nthr) {
+      const int i = e / R, c = e % R;
+      double acc = v[e];
+      for (int k = 0; k < cnt; ++k) acc = fma(-Ls[(size_t)(r0 + k) * ldl + i], u[(r0 + k) * R + c], acc);
+      v[e] = acc;
     }
     SA_SYNC();
   }
   // ---- phase 3: the contractions over the training points, one thread per output, a = 0 .. n-1 in order
-  //   red[0] = Knq . alpha, red[1] = Knq . z, red[2 + d] = sum_a alpha_a dKnq[a][d], red[18 + d] = sum_a z_a dKnq[a][d]
-  for (int o = tid; o < 2 + 2 * D; o += nthr) {
-    const bool with_alpha = o == 0 || (o >= 2 && o < 2 + D);
-    const int col = o < 2 ? 0 : (o < 2 + D ? 1 + (o - 2) : 1 + (o - 2 - D));
-    const double* lhs = with_alpha ? al : u;
+  //   red[c] = Knq . alpha, red[R + c] = Knq . z; R = 1: red[2 + d] = sum_a alpha_a dKnq[a][d], red[18 + d] = sum_a z_a dKnq[a][d]
+  for (int o = tid; o < 2 * R + (R == 1 ? 2 * D : 0); o += nthr) {
+    const bool grad_col = R == 1 && o >= 2;
+    const int og = o - 2;
+    const bool with_alpha = grad_col ? og < D : o < R;
+    const int c = grad_col ? 0 : o % R, col = grad_col ? 1 + (og < D ? og : og - D) : c;
     double acc = 0.0;
-    for (int a = 0; a < n; ++a) acc = fma(lhs[a], C[(size_t)a * 16 + col], acc);
-    red[o < 2 ? o : (o < 2 + D ? 2 + (o - 2) : 18 + (o - 2 - D))] = acc;
+    for (int a = 0; a < n; ++a) acc = fma(with_alpha ? al[a] : u[a * R + c], C[(size_t)a * 16 + col], acc);
+    red[grad_col ? (og < D ? 2 + og : 18 + (og - D)) : o] = acc;
   }
   SA_SYNC();
-  // ---- phase 4: the posterior, the acquisition value and its chain rule (every writing thread restates the scalars)
-  for (int o = tid; o < (D > 1 ? D : 1); o += nthr) {
-    const double mean_q = (Ssum[0] - m) / s, var_q = Ssum[16] * inv_s2 + os;
-    const double mu = fma(s, mean_q + red[0], m);
-    const double vr = s2 * (var_q - red[1]);
+  // ---- phase 4: the posterior, the acquisition value and (R = 1) its chain rule: one thread per right-hand side, or per input
+  // dimension of the one (every writing thread restates the scalars)
+  for (int e = tid; e < (R == 1 ? (D > 1 ? D : 1) : R); e += nthr) {
+    const int c = R == 1 ? 0 : e, o = R == 1 ? e : 0;
+    const double mean_q = (Ssum[c] - m) / s, var_q = Ssum[16 + c] * inv_s2 + os;
+    const double mu = fma(s, mean_q + red[c], m);
+    const double vr = s2 * (var_q - red[R + c]);
     const double par = p.acqf_param[g];
     double A, Amu, Av;
     sa_acquisition(p.acqf, par, mu, vr, A, Amu, Av);
     // a query point with a NaN / inf coordinate: fmax in the Matern branch drops a NaN operand, so only that coordinate's slope
     // would carry it (and nothing at all with source sums that happen to be finite).  sum_d (x_d - x_d) is 0, or NaN for such a
-    // point: every output of the query is NaN, as (5d)'s target gradient has it (a select: finite inputs are untouched)
+    // point: every output of THAT point is NaN, as (5d)'s target gradient has it (a select: finite inputs are untouched)
     double bad = 0.0;
     for (int d = 0; d < D; ++d) {
-      const double x = p.Xq[(size_t)q * D + d];
+      const double x = p.Xq[(q0 + c) * D + d];
       bad += x - x;
     }
     if (o == 0) {
-      p.value[q] = bad == 0.0 ? A : bad;
-      if (p.mu_out) p.mu_out[q] = bad == 0.0 ? mu : bad;
-      if (p.var_out) p.var_out[q] = bad == 0.0 ? vr : bad;
+      p.value[q0 + c] = bad == 0.0 ? A : bad;
+      if (p.mu_out) p.mu_out[q0 + c] = bad == 0.0 ? mu : bad;
+      if (p.var_out) p.var_out[q0 + c] = bad == 0.0 ? vr : bad;
     }
-    if (p.grad && o < D) {
-      const double dmu = fma(s, red[2 + o], Ssum[1 + o]);
-      const double dvar = fma(-2.0 * s2, red[18 + o], Ssum[17 + o]);
-      p.grad[(size_t)q * D + o] = bad == 0.0 ? fma(Av, dvar, Amu * dmu) : bad;
-    }
+    if constexpr (R == 1)
+      if (p.grad && o < D) {
+        const double dmu = fma(s, red[2 + o], Ssum[1 + o]);
+        const double dvar = fma(-2.0 * s2, red[18 + o], Ssum[17 + o]);
+        p.grad[q0 * D + o] = bad == 0.0 ? fma(Av, dvar, Amu * dmu) : bad;
+      }
   }
 }
+
+// One query point (7g): the R = 1 instantiation.
+SA_DEV void sa_query(const StudiesAcqfParams& p, double* lds, int q, int tid, int nthr) { sa_block<1>(p, lds, q, tid, nthr); }
 
 }  // namespace scaml

@@ -1,6 +1,7 @@
 // gp_studies_formulas.h -- the scalar formulas the studies' target kernels share: the target kernel with its slope, and the UCB / EI
-// value with its chain-rule factors.  Included by csrc/gp_studies_acqf.h (a workgroup per query point, value + gradient) and
-// csrc/gp_studies_score.h (a workgroup per strip of 16 candidates, value only): one text, so that both evaluate the same expressions.
+// value with its chain-rule factors.  Included by csrc/gp_studies_acqf.h (sa_block<R>: a workgroup per query point, value + gradient,
+// or per strip of 16 candidates, value only) and by csrc/gp_fantasy.hip (UCB / EI averaged over F fantasies): one text, so that all of
+// them evaluate the same expressions.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -32,7 +33,7 @@ SA_DEV void sa_kernel_and_slope(int kind, double d2, double os, double& k, doubl
 }
 
 // The acquisition value A of a posterior (mu, vr) with its partial derivatives Amu = dA / dmu, Av = dA / dvr; `par`: UCB's beta, EI's
-// best_f.  The clamps are those of scamlgp_amd/utils.py (csrc/gp_fantasy.hip states them for F fantasies).
+// best_f.  The clamps are those of scamlgp_amd/utils.py.
 SA_DEV void sa_acquisition(int acqf, double par, double mu, double vr, double& A, double& Amu, double& Av) {
   if (acqf == 0) {   // UCB: -mu + sqrt(beta max(v, 0)); d/dv = beta / (2 sqrt(beta v)), zero where v is clamped
     const double sd = sqrt(par * (vr > 0.0 ? vr : 0.0));

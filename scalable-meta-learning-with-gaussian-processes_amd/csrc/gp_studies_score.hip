@@ -2,9 +2,9 @@
 // of raw candidates of MANY BO studies in one launch (include/scaml_gp.h (7i)), behind the value-only grouped source pass (5f); and the
 // training blocks of all studies in one launch (7j), whose factors (2) then computes together.
 //
-// (7i) A workgroup of 256 threads per strip of 16 candidates of one study; the arithmetic is csrc/gp_studies_score.h (also built for
-// the host by the CPU tests).  The study's factor, block inverses and alpha go to LDS once and serve 16 right-hand sides: thread <->
-// (row, candidate).  Per candidate the operations are (7g)'s, so the two kernels agree bit for bit; like (7g) the work is latency
+// (7i) A workgroup of 256 threads per strip of 16 candidates of one study; the arithmetic is sa_block<16> of csrc/gp_studies_acqf.h (also built
+// for the host by the CPU tests).  The study's factor, block inverses and alpha go to LDS once and serve 16 right-hand sides: thread <->
+// (row, candidate).  (7g) is sa_block<1>, the same text, so the two kernels agree bit for bit; like (7g) the work is latency
 // bound (T n 16 loads and an n x n substitution, n <= 96) and uses no matrix cores.
 #include "scaml_common.hpp"
 #include "gp_studies_score.h"

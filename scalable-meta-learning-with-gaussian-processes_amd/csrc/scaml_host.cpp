@@ -746,72 +746,103 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
   return launch(grad ? m->tgt_fantasy_grad[kind] : m->tgt_fantasy, dim3((unsigned)M), 64, 0, stream, "target_fantasy_acqf", p);
 }
 
-// ---- (5e) the GRAD pass with the query points divided among groups; (7g) the batched target acquisition behind it ---------------
-// The two launches on checked arguments (non-empty shapes within the kernels' limits): the entry points below check and call them,
-// and (7h) checks once and calls them per round.
+// ---- (5e) the GRAD pass with the query points divided among groups, (5f) the same pass in VALUE mode; (7g), (7i) the batched target
+// acquisition behind them ----
+// Every entry point fills its kernel's argument block once -- the block names each pointer --; one check and one launch per block take
+// it from there.  (7h) builds both blocks once, checks them once and launches them per round.
+// The order of the checks that can be observed: every SCAML_E_BADARG check comes before every SCAML_E_TOOLARGE check, and an empty
+// shape is SCAML_OK only after both.
 namespace {
-int grouped_grad_launch(Module& m, const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
-                        const double* const* VA_tab, const double* X, const double* theta, const double* Linv, const double* alpha,
-                        const double* y_mean, const double* y_std, const int32_t* n_points, int T, int N, int Mq, int G, int Ma_max, int D,
-                        int kind, double* mu, double* var, double* cov, const int32_t* task_base, int Tsrc, void* stream,
-                        bool value = false) {   // (task_base NULL: (5e) as it was; value: (5f), Mq candidates in strips of 16)
-  const size_t lds = scaml::posterior_linv_lds_doubles(N, D) * sizeof(double);
+int sat_int(long long v) { return v > INT32_MAX ? INT32_MAX : (v < INT32_MIN ? INT32_MIN : (int)v); }
+
+// The grouped pass's block.  `value`: (5f), Mq candidates in strips of 16, `group` has one entry per strip; else (5e), 16 columns per
+// query point.  Either way base.M is the row width of mu / var / cov (saturated: grouped_check refuses what does not fit) and base.M / 16
+// the number of strips.  task_base NULL: every group reads the same source tasks; with the table, T = task slots per group.
+scaml::PosteriorGroupedParams grouped_block(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
+                                            const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
+                                            const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T,
+                                            int N, int Mq, int G, int Ma_max, int D, double* mu, double* var, double* cov,
+                                            const int32_t* task_base, int Tsrc, bool value) {
   scaml::PosteriorGroupedParams p{};
-  p.base = scaml::PosteriorParams{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N, value ? Mq : 16 * Mq, D, 0, 0, 0,
-                                  nullptr, cov, Ma_max, 0, nullptr};
-  p.ga = scaml::PosteriorGroupArgs{group, n_points_a, VA_tab, Xa, G, 0, task_base, Tsrc, 0};   // (with the table: T = task slots per group)
-  const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * (unsigned)(value ? Mq / 16 : Mq);   // XCD-aware (task, strip) map inside the kernel
-  hipFunction_t fn = value ? (task_base ? m.post_linv_grouped_val_own[kind] : m.post_linv_grouped_val[kind])
-                           : (task_base ? m.post_linv_grouped_own[kind] : m.post_linv_grouped[kind]);
-  return launch(fn, dim3(blocks), 512, lds, stream, task_base ? "gp_posterior_linv_grouped_own" : "gp_posterior_linv_grouped", p);
+  p.base = scaml::PosteriorParams{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N,
+                                  sat_int((long long)Mq * (value ? 1 : 16)), D, 0, 0, 0, nullptr, cov, Ma_max, 0, nullptr};
+  p.ga = scaml::PosteriorGroupArgs{group, n_points_a, VA_tab, Xa, G, 0, task_base, Tsrc, 0};
+  return p;
 }
-int acqf_batched_launch(Module& m, const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
-                        const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
-                        const double* Linv_diag, const double* alpha, const int32_t* n_points, const double* m_all, const double* s_all,
-                        const int32_t* info, const double* acqf_param, int Mq, int G, int n_max, int T, int D, int kind, int acqf,
-                        double* value, double* grad, double* mu_out, double* var_out, void* stream) {
-  const size_t lds = scaml::studies_acqf_lds_doubles(n_max) * sizeof(double);
-  scaml::StudiesAcqfParams p{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param,
-                             value, grad, mu_out, var_out, Mq, G, n_max, T, D, kind, acqf, 0};
-  return launch(m.tgt_acqf_batched, dim3((unsigned)Mq), scaml::STUDIES_ACQF_THREADS, lds, stream, "target_acqf_batched", p);   // a workgroup per query point
-}
-}  // namespace
-namespace {
-// (5e) and its per-group-source-task form: `own` = the entry point that takes task_base / Tsrc
-int grouped_grad_checked(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a, const double* const* VA_tab,
-                         const double* X, const double* theta, const double* Linv, const double* alpha, const double* y_mean,
-                         const double* y_std, const int32_t* n_points, int T, int N, int Mq, int G, int Ma_max, int D, int kind, double* mu,
-                         double* var, double* cov, bool own, const int32_t* task_base, int Tsrc, void* stream, bool value = false) {
-  if (T < 0 || N < 1 || Mq < 0 || G < 0 || Ma_max < 1 || D < 1) return SCAML_E_BADARG;
-  if (value && (Mq & 15)) return SCAML_E_BADARG;   // (5f): whole strips of 16 candidates
-  if (!Xq || !group || !Xa || !n_points_a || !VA_tab || !X || !theta || !Linv || !alpha || !mu || !var || !cov) return SCAML_E_BADARG;
-  if (own && (!task_base || Tsrc < 1)) return SCAML_E_BADARG;
+// `own`: the entry point takes task_base / Tsrc.  SCAML_OK: the shapes are within the kernel's limits (they may be empty).
+int grouped_check(const scaml::PosteriorGroupedParams& p, int kind, bool value, bool own) {
+  const scaml::PosteriorParams& b = p.base;
+  if (b.T < 0 || b.N < 1 || b.M < 0 || p.ga.G < 0 || b.Ma < 1 || b.D < 1) return SCAML_E_BADARG;
+  if (value && (b.M & 15)) return SCAML_E_BADARG;   // (5f): whole strips of 16 candidates
+  if (!b.Xq || !p.ga.group || !p.ga.Xa || !p.ga.n_a || !p.ga.VA_tab || !b.X || !b.theta || !b.L || !b.alpha || !b.mu || !b.var || !b.cov)
+    return SCAML_E_BADARG;
+  if (own && (!p.ga.task_base || p.ga.Tsrc < 1)) return SCAML_E_BADARG;
   if (!valid_kind(kind)) return SCAML_E_BADARG;
-  if (D > 15 || Ma_max > 96 || Ma_max > N || N > scaml_posterior_max_n() || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
-  const size_t lds = scaml::posterior_linv_lds_doubles(N, D) * sizeof(double);
-  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
-  if (T == 0 || Mq == 0 || G == 0) return SCAML_OK;
+  if (b.D > 15 || b.Ma > 96 || b.Ma > b.N || b.N > scaml_posterior_max_n() || (value ? b.M : b.M / 16) > (1 << 26)) return SCAML_E_TOOLARGE;
+  if (scaml::posterior_linv_lds_doubles(b.N, b.D) * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
+  return SCAML_OK;
+}
+int grouped_launch(Module& m, scaml::PosteriorGroupedParams& p, int kind, bool value, void* stream) {   // a checked, non-empty block
+  const size_t lds = scaml::posterior_linv_lds_doubles(p.base.N, p.base.D) * sizeof(double);
+  const unsigned blocks = (unsigned)(((p.base.T + 7) / 8) * 8) * (unsigned)(p.base.M / 16);   // XCD-aware (task, strip) map inside the kernel
+  const bool own = p.ga.task_base != nullptr;
+  hipFunction_t fn = value ? (own ? m.post_linv_grouped_val_own[kind] : m.post_linv_grouped_val[kind])
+                           : (own ? m.post_linv_grouped_own[kind] : m.post_linv_grouped[kind]);
+  return launch(fn, dim3(blocks), 512, lds, stream, own ? "gp_posterior_linv_grouped_own" : "gp_posterior_linv_grouped", p);
+}
+int grouped_run(scaml::PosteriorGroupedParams p, int kind, bool value, bool own, void* stream) {
+  if (const int rc = grouped_check(p, kind, value, own)) return rc;
+  if (p.base.T == 0 || p.base.M == 0 || p.ga.G == 0) return SCAML_OK;
   Module* m = ready();
-  if (!m) return SCAML_E_LAUNCH;
-  return grouped_grad_launch(*m, Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
-                             mu, var, cov, own ? task_base : nullptr, Tsrc, stream, value);
+  return m ? grouped_launch(*m, p, kind, value, stream) : SCAML_E_LAUNCH;
+}
+
+// The studies' acquisition block (csrc/gp_studies_acqf.h).  `strips`: (7i), the value layout, a workgroup per strip of 16 candidates
+// (sa_block<16>); else (7g), a workgroup per query point (sa_block<1>).
+size_t acqf_lds_bytes(int n_max, bool strips) {
+  return (strips ? scaml::sa_lds_doubles<16>(n_max) : scaml::sa_lds_doubles<1>(n_max)) * sizeof(double);
+}
+int acqf_check(const scaml::StudiesAcqfParams& p, bool strips) {
+  if (p.Mq < 0 || (strips && (p.Mq & 15)) || p.G < 0 || p.n_max < 1 || p.T < 1 || p.D < 1) return SCAML_E_BADARG;
+  if (!p.mu || !p.var || !p.cov || !p.group || !p.Xq || !p.w || !p.active || !p.Xt || !p.theta || !p.L || !p.Linv_diag || !p.alpha ||
+      !p.n_points || !p.m_all || !p.s_all || !p.info || !p.acqf_param || !p.value)
+    return SCAML_E_BADARG;
+  if (!valid_kind(p.kind) || (p.acqf != 0 && p.acqf != 1)) return SCAML_E_BADARG;
+  if (p.n_max > scaml::STUDIES_ACQF_MAX_N || p.D > scaml::STUDIES_ACQF_MAX_D || p.Mq > (1 << 26)) return SCAML_E_TOOLARGE;
+  if (acqf_lds_bytes(p.n_max, strips) > kLdsLimit) return SCAML_E_TOOLARGE;
+  return SCAML_OK;
+}
+static_assert(scaml::sa_lds_doubles<16>(scaml::STUDIES_ACQF_MAX_N) * sizeof(double) <= kLdsLimit, "a strip at n_max = 96 fits the LDS");
+int acqf_launch(Module& m, scaml::StudiesAcqfParams& p, bool strips, void* stream) {   // a checked, non-empty block
+  const size_t lds = acqf_lds_bytes(p.n_max, strips);
+  if (strips) return launch(m.tgt_score_batched, dim3((unsigned)(p.Mq / 16)), scaml::STUDIES_SCORE_THREADS, lds, stream, "target_score_batched", p);
+  return launch(m.tgt_acqf_batched, dim3((unsigned)p.Mq), scaml::STUDIES_ACQF_THREADS, lds, stream, "target_acqf_batched", p);
+}
+int acqf_run(scaml::StudiesAcqfParams p, bool strips, void* stream) {
+  if (const int rc = acqf_check(p, strips)) return rc;
+  if (p.Mq == 0 || p.G == 0) return SCAML_OK;
+  Module* m = ready();
+  return m ? acqf_launch(*m, p, strips, stream) : SCAML_E_LAUNCH;
 }
 }  // namespace
+
 int scaml_posterior_linv_grad_grouped_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
                                           const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
                                           const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T,
                                           int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov,
                                           void* stream) {
-  return grouped_grad_checked(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
-                              mu, var, cov, false, nullptr, 0, stream);
+  return grouped_run(grouped_block(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, mu,
+                                   var, cov, nullptr, 0, false),
+                     kind, false, false, stream);
 }
 int scaml_posterior_linv_grad_grouped_own_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
                                               const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
                                               const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points,
                                               int T, int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var,
                                               double* cov, const int32_t* task_base, int Tsrc, void* stream) {
-  return grouped_grad_checked(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
-                              mu, var, cov, true, task_base, Tsrc, stream);
+  return grouped_run(grouped_block(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, mu,
+                                   var, cov, task_base, Tsrc, false),
+                     kind, false, true, stream);
 }
 
 int scaml_target_acqf_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
@@ -819,19 +850,9 @@ int scaml_target_acqf_batched_f64(const double* mu, const double* var, const dou
                                   const double* Linv_diag, const double* alpha, const int32_t* n_points, const double* m_all,
                                   const double* s_all, const int32_t* info, const double* acqf_param, int Mq, int G, int n_max, int T,
                                   int D, int kind, int acqf, double* value, double* grad, double* mu_out, double* var_out, void* stream) {
-  if (Mq < 0 || G < 0 || n_max < 1 || T < 1 || D < 1) return SCAML_E_BADARG;
-  if (!mu || !var || !cov || !group || !Xq || !w || !active || !Xt || !theta || !L || !Linv_diag || !alpha || !n_points || !m_all || !s_all ||
-      !info || !acqf_param || !value)
-    return SCAML_E_BADARG;
-  if (!valid_kind(kind) || (acqf != 0 && acqf != 1)) return SCAML_E_BADARG;
-  if (n_max > scaml::STUDIES_ACQF_MAX_N || D > scaml::STUDIES_ACQF_MAX_D || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
-  const size_t lds = scaml::studies_acqf_lds_doubles(n_max) * sizeof(double);
-  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
-  if (Mq == 0 || G == 0) return SCAML_OK;
-  Module* m = ready();
-  if (!m) return SCAML_E_LAUNCH;
-  return acqf_batched_launch(*m, mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param, Mq,
-                             G, n_max, T, D, kind, acqf, value, grad, mu_out, var_out, stream);
+  return acqf_run(scaml::StudiesAcqfParams{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info,
+                                           acqf_param, value, grad, mu_out, var_out, Mq, G, n_max, T, D, kind, acqf, 0},
+                  false, stream);
 }
 
 // ---- (5f), (5f') the grouped pass in VALUE mode: a strip is 16 different candidates of one group, `group` has one entry per strip ----
@@ -839,16 +860,18 @@ int scaml_posterior_linv_grouped_f64(const double* Xq, const int32_t* group, con
                                      const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
                                      const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T, int N,
                                      int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov, void* stream) {
-  return grouped_grad_checked(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
-                              mu, var, cov, false, nullptr, 0, stream, true);
+  return grouped_run(grouped_block(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, mu,
+                                   var, cov, nullptr, 0, true),
+                     kind, true, false, stream);
 }
 int scaml_posterior_linv_grouped_own_f64(const double* Xq, const int32_t* group, const double* Xa, const int32_t* n_points_a,
                                          const double* const* VA_tab, const double* X, const double* theta, const double* Linv,
                                          const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points, int T,
                                          int N, int Mq, int G, int Ma_max, int D, int kind, double* mu, double* var, double* cov,
                                          const int32_t* task_base, int Tsrc, void* stream) {
-  return grouped_grad_checked(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, kind,
-                              mu, var, cov, true, task_base, Tsrc, stream, true);
+  return grouped_run(grouped_block(Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points, T, N, Mq, G, Ma_max, D, mu,
+                                   var, cov, task_base, Tsrc, true),
+                     kind, true, true, stream);
 }
 
 // ---- (7i) the acquisition value of a table of candidates of many studies, a workgroup per strip of 16 (csrc/gp_studies_score.hip) ----
@@ -857,22 +880,10 @@ int scaml_target_score_batched_f64(const double* mu, const double* var, const do
                                    const double* Linv_diag, const double* alpha, const int32_t* n_points, const double* m_all,
                                    const double* s_all, const int32_t* info, const double* acqf_param, int Mq, int G, int n_max, int T,
                                    int D, int kind, int acqf, double* value, double* mu_out, double* var_out, void* stream) {
-  if (Mq < 0 || (Mq & 15) || G < 0 || n_max < 1 || T < 1 || D < 1) return SCAML_E_BADARG;
-  if (!mu || !var || !cov || !group || !Xq || !w || !active || !Xt || !theta || !L || !Linv_diag || !alpha || !n_points || !m_all || !s_all ||
-      !info || !acqf_param || !value)
-    return SCAML_E_BADARG;
-  if (!valid_kind(kind) || (acqf != 0 && acqf != 1)) return SCAML_E_BADARG;
-  if (n_max > scaml::STUDIES_ACQF_MAX_N || D > scaml::STUDIES_ACQF_MAX_D || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
-  const size_t lds = scaml::studies_score_lds_doubles(n_max) * sizeof(double);
-  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
-  if (Mq == 0 || G == 0) return SCAML_OK;
-  Module* m = ready();
-  if (!m) return SCAML_E_LAUNCH;
-  scaml::StudiesScoreParams p{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info, acqf_param,
-                              value, nullptr, mu_out, var_out, Mq, G, n_max, T, D, kind, acqf, 0};
-  return launch(m->tgt_score_batched, dim3((unsigned)(Mq / 16)), scaml::STUDIES_SCORE_THREADS, lds, stream, "target_score_batched", p);
+  return acqf_run(scaml::StudiesAcqfParams{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info,
+                                           acqf_param, value, nullptr, mu_out, var_out, Mq, G, n_max, T, D, kind, acqf, 0},
+                  true, stream);
 }
-static_assert(scaml::studies_score_lds_doubles(scaml::STUDIES_ACQF_MAX_N) * sizeof(double) <= kLdsLimit, "a strip at n_max = 96 fits the LDS");
 
 // ---- (7j) the training blocks Knn / resid of G studies in one launch (csrc/gp_studies_score.hip); (2) factors them together ----
 int scaml_target_train_block_batched_f64(const double* means_t, const double* covs_packed, const double* X, const double* y,
@@ -1160,28 +1171,29 @@ int studies_acqf_opt_checked(const double* x0, const int32_t* group, const doubl
                              int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi, int max_iter,
                              int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace,
                              double* x, double* f, int32_t* stats, bool own, const int32_t* task_base, int Tsrc, void* stream) {
-  if (own && (!task_base || Tsrc < 1)) return SCAML_E_BADARG;
-  if (B < 0 || G < 0 || n_max < 1 || T < 1 || N < 1 || D < 1 || n_evals < 0 || max_iter < 0 || max_ls < 1) return SCAML_E_BADARG;
-  if (!x0 || !group || !VA_tab || !X || !theta_s || !Linv || !alpha_s || !w || !active || !Xt || !theta_t || !L || !Linv_diag || !alpha_t ||
-      !n_points_t || !m_all || !s_all || !info || !acqf_param || !lo || !hi || !workspace || !x || !f || !stats)
-    return SCAML_E_BADARG;
-  if (!valid_kind(kind_s) || !valid_kind(kind_t) || (acqf != 0 && acqf != 1) || (flags & ~SCAML_ACQF_OPT_CONTINUE)) return SCAML_E_BADARG;
+  // what is the optimiser's own, and what the workspace layout is sized by
+  if (B < 0 || n_max < 1 || T < 1 || D < 1 || n_evals < 0 || max_iter < 0 || max_ls < 1) return SCAML_E_BADARG;
+  if (!x0 || !group || !lo || !hi || !workspace || !x || !f || !stats) return SCAML_E_BADARG;
+  if (flags & ~SCAML_ACQF_OPT_CONTINUE) return SCAML_E_BADARG;
   if (history < 1 || history > scaml::ACQF_OPT_HMAX || ((uintptr_t)workspace & 15)) return SCAML_E_BADARG;
   if (!(gtol >= 0.0) || !(c1 > 0.0) || ftol != ftol) return SCAML_E_BADARG;
-  // the shapes (5e) and (7g) take
-  if (n_max > scaml::STUDIES_ACQF_MAX_N || D > scaml::ACQF_OPT_MAX_D || n_max > N || N > scaml_posterior_max_n() || B > (1 << 26))
-    return SCAML_E_TOOLARGE;
-  if (scaml::posterior_linv_lds_doubles(N, D) * sizeof(double) > kLdsLimit || scaml::studies_acqf_lds_doubles(n_max) * sizeof(double) > kLdsLimit)
-    return SCAML_E_TOOLARGE;
+  const AcqfOptLayout lay = acqf_opt_layout(B, n_max, T, D, history);
+  auto ws = [workspace](size_t off) { return (double*)((uintptr_t)workspace + off); };
+  double *Xq = ws(lay.Xq), *mu = ws(lay.mu), *var = ws(lay.var), *cov = ws(lay.cov), *value = ws(lay.value), *grad = ws(lay.grad);
+  int32_t* live = (int32_t*)ws(lay.group_live);
+  // the evaluation kernels are handed group_live where they were handed group: a stopped start (and a padding row) returns at once
+  scaml::PosteriorGroupedParams ps = grouped_block(Xq, live, Xt, n_points_t, VA_tab, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, T, N, B, G,
+                                                   n_max, D, mu, var, cov, own ? task_base : nullptr, Tsrc, false);
+  scaml::StudiesAcqfParams pt{mu, var, cov, live, Xq, w, active, Xt, theta_t, L, Linv_diag, alpha_t, n_points_t, m_all, s_all, info, acqf_param,
+                              value, grad, nullptr, nullptr, B, G, n_max, T, D, kind_t, acqf, 0};
+  // the arguments and shapes (5e) and (7g) take: both blocks' SCAML_E_BADARG before either's SCAML_E_TOOLARGE
+  const int rs = grouped_check(ps, kind_s, false, own), rt = acqf_check(pt, false);
+  if (rs == SCAML_E_BADARG || rt == SCAML_E_BADARG) return SCAML_E_BADARG;
+  if (rs != SCAML_OK || rt != SCAML_OK || D > scaml::ACQF_OPT_MAX_D) return SCAML_E_TOOLARGE;
   if (B == 0 || G == 0) return SCAML_OK;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
-  const AcqfOptLayout lay = acqf_opt_layout(B, n_max, T, D, history);
-  char* ws = (char*)workspace;
-  double *Xq = (double*)(ws + lay.Xq), *mu = (double*)(ws + lay.mu), *var = (double*)(ws + lay.var), *cov = (double*)(ws + lay.cov);
-  double *value = (double*)(ws + lay.value), *grad = (double*)(ws + lay.grad);
-  int32_t* live = (int32_t*)(ws + lay.group_live);
-  scaml::AcqfOptParams p{value, grad, group, x0, lo, hi, (double*)(ws + lay.state), Xq, live, x, f, stats, B, G, D, 1, max_iter, history,
+  scaml::AcqfOptParams p{value, grad, group, x0, lo, hi, ws(lay.state), Xq, live, x, f, stats, B, G, D, 1, max_iter, history,
                          max_ls, 0, gtol, ftol, c1};
   int rc = SCAML_OK;
   if (!(flags & SCAML_ACQF_OPT_CONTINUE)) {
@@ -1190,14 +1202,9 @@ int studies_acqf_opt_checked(const double* x0, const int32_t* group, const doubl
     p.mode = 1;
   }
   for (int r = 0; r < n_evals; ++r) {
-    // the evaluation kernels are handed group_live where they were handed group: a stopped start (and a padding row) returns at once.
     // (Arguments and sizes were checked above, once; only a failing launch can end the call here, with the rounds before it enqueued.)
-    if ((rc = grouped_grad_launch(*m, Xq, live, Xt, n_points_t, VA_tab, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, T, N, B, G, n_max,
-                                  D, kind_s, mu, var, cov, own ? task_base : nullptr, Tsrc, stream)) != SCAML_OK)
-      return rc;
-    if ((rc = acqf_batched_launch(*m, mu, var, cov, live, Xq, w, active, Xt, theta_t, L, Linv_diag, alpha_t, n_points_t, m_all, s_all, info,
-                                  acqf_param, B, G, n_max, T, D, kind_t, acqf, value, grad, nullptr, nullptr, stream)) != SCAML_OK)
-      return rc;
+    if ((rc = grouped_launch(*m, ps, kind_s, false, stream)) != SCAML_OK) return rc;
+    if ((rc = acqf_launch(*m, pt, false, stream)) != SCAML_OK) return rc;
     if ((rc = launch(m->acqf_opt_step, dim3((unsigned)B), 64, 0, stream, "acqf_opt_step", p)) != SCAML_OK) return rc;
   }
   return SCAML_OK;

@@ -653,103 +653,79 @@ def target_fantasy_acqf(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor,
     return value, grad
 
 
-def source_posteriors_grad_grouped(Xq: torch.Tensor, group: torch.Tensor, Xa: torch.Tensor, n_points_a: torch.Tensor, VA_tab: torch.Tensor,
-                                   X: torch.Tensor, theta: torch.Tensor, kind: int, Linv: torch.Tensor, alpha: torch.Tensor,
-                                   y_mean: Optional[torch.Tensor] = None, y_std: Optional[torch.Tensor] = None,
-                                   n_points: Optional[torch.Tensor] = None, task_base: Optional[torch.Tensor] = None,
-                                   tasks_per_group: Optional[int] = None) -> Dict[str, torch.Tensor]:
-    """``source_posteriors_grad`` with the query points Xq (Mq, D) divided among G groups, one launch of
-    scaml_posterior_linv_grad_grouped_f64: ``group`` (Mq,) int32 (negative: a padding row, zeros), ``Xa`` (G, Ma_max, D) the groups'
-    leading points, ``n_points_a`` (G,) int32 their counts, ``VA_tab`` (G,) int64: the ADDRESSES of the groups' V (T, N, Ma_g) tensors
-    (``ScaMLGP._train_VA``; the caller keeps them alive).  Returns dict(mu, var (T, Mq, 16), cov (T, Ma_max, Mq * 16): rows
-    a < Ma_{group[q]} of strip q are written, the rest is uninitialised).
-
-    ``task_base`` (G,) int32: every group owns its source tasks (scaml_posterior_linv_grad_grouped_own_f64) -- the source arrays hold
-    Tsrc = X.shape[0] tasks, task slot t of group g reads task ``task_base[g] + t``, and T = ``tasks_per_group`` slots are the leading
-    axis of the outputs and of the groups' V."""
-    if task_base is not None:
-        return _source_posteriors_grad_grouped_own(Xq, group, Xa, n_points_a, VA_tab, X, theta, kind, Linv, alpha, y_mean, y_std, n_points,
-                                                   task_base, tasks_per_group)
-    if tasks_per_group is not None:
-        raise ValueError("tasks_per_group goes with task_base")
-    T, N, D = X.shape
+def _source_pass_grouped(value: bool, Xq, group, Xa, n_points_a, VA_tab, X, theta, kind, Linv, alpha, y_mean, y_std, n_points, task_base,
+                         tasks_per_group, cov_out) -> Dict[str, torch.Tensor]:
+    """The grouped source pass behind ``source_posteriors_grad_grouped`` (``value`` False: 16 columns per query point, ``group`` per query
+    point) and ``source_posteriors_grouped`` (``value`` True: a column per candidate, ``group`` per strip of 16).  With ``task_base`` the
+    source arrays are (Tsrc, ...) and the outputs (T = tasks_per_group, ...): the ``_own`` entry point.  ``cov_out``: the buffer cov is
+    written into (tests prefill it to see which rows a launch writes)."""
+    own = task_base is not None
+    Tsrc, N, D = X.shape
+    T = int(tasks_per_group) if own else Tsrc
     Mq = Xq.shape[0]
     G, Ma_max = int(Xa.shape[0]), int(Xa.shape[1])
     X = _check(X, "X")
     Xq = _check(Xq, "Xq", (Mq, D))
-    group = _check(group, "group", (Mq,), torch.int32)
+    group = _check(group, "group", (Mq // 16 if value else Mq,), torch.int32)
     Xa = _check(Xa, "Xa", (G, Ma_max, D))
     n_points_a = _check(n_points_a, "n_points_a", (G,), torch.int32)
     VA_tab = _check(VA_tab, "VA_tab", (G,), torch.int64)
-    theta = _check(theta, "theta", (T, D + 2))
-    Linv = _check(Linv, "Linv", (T, N, N))
-    alpha = _check(alpha, "alpha", (T, N))
-    y_mean = _opt(y_mean, "y_mean", (T,))
-    y_std = _opt(y_std, "y_std", (T,))
-    n_points = _opt(n_points, "n_points", (T,), torch.int32)
-    dev = X.device
-    with torch.cuda.device(dev):
-        mu = _empty(dev, T, Mq, 16)
-        var = _empty(dev, T, Mq, 16)
-        cov = _empty(dev, T, Ma_max, Mq * 16)
-        rc = _lib.lib.scaml_posterior_linv_grad_grouped_f64(_ptr(Xq), _ptr(group), _ptr(Xa), _ptr(n_points_a), _ptr(VA_tab), _ptr(X), _ptr(theta),
-                                                            _ptr(Linv), _ptr(alpha), _ptr(y_mean), _ptr(y_std), _ptr(n_points), T, N, Mq, G, Ma_max, D,
-                                                            int(kind), _ptr(mu), _ptr(var), _ptr(cov), _stream_handle())
-    _lib.check_rc(rc, "scaml_posterior_linv_grad_grouped_f64")
-    return dict(mu=mu, var=var, cov=cov)
-
-
-def _source_posteriors_grad_grouped_own(Xq, group, Xa, n_points_a, VA_tab, X, theta, kind, Linv, alpha, y_mean, y_std, n_points, task_base,
-                                        tasks_per_group, cov_out=None) -> Dict[str, torch.Tensor]:
-    """``source_posteriors_grad_grouped`` with ``task_base``: the source arrays are (Tsrc, ...), the outputs (T, ...).  ``cov_out``: the
-    (T, Ma_max, Mq * 16) buffer cov is written into (tests prefill it to see which rows a launch writes)."""
-    if tasks_per_group is None:
-        raise ValueError("task_base needs tasks_per_group (the task slots of a group)")
-    Tsrc, N, D = X.shape
-    T, Mq = int(tasks_per_group), Xq.shape[0]
-    G, Ma_max = int(Xa.shape[0]), int(Xa.shape[1])
-    X = _check(X, "X")
-    Xq = _check(Xq, "Xq", (Mq, D))
-    group = _check(group, "group", (Mq,), torch.int32)
-    Xa = _check(Xa, "Xa", (G, Ma_max, D))
-    n_points_a = _check(n_points_a, "n_points_a", (G,), torch.int32)
-    VA_tab = _check(VA_tab, "VA_tab", (G,), torch.int64)
-    task_base = _check(task_base, "task_base", (G,), torch.int32)
     theta = _check(theta, "theta", (Tsrc, D + 2))
     Linv = _check(Linv, "Linv", (Tsrc, N, N))
     alpha = _check(alpha, "alpha", (Tsrc, N))
     y_mean = _opt(y_mean, "y_mean", (Tsrc,))
     y_std = _opt(y_std, "y_std", (Tsrc,))
     n_points = _opt(n_points, "n_points", (Tsrc,), torch.int32)
+    if own:
+        task_base = _check(task_base, "task_base", (G,), torch.int32)
+    row, width = ((Mq,), Mq) if value else ((Mq, 16), Mq * 16)
+    name = "scaml_posterior_linv_" + ("" if value else "grad_") + "grouped_" + ("own_" if own else "") + "f64"
     dev = X.device
     with torch.cuda.device(dev):
-        mu = _empty(dev, T, Mq, 16)
-        var = _empty(dev, T, Mq, 16)
-        cov = _empty(dev, T, Ma_max, Mq * 16) if cov_out is None else _check(cov_out, "cov_out", (T, Ma_max, Mq * 16))
-        rc = _lib.lib.scaml_posterior_linv_grad_grouped_own_f64(_ptr(Xq), _ptr(group), _ptr(Xa), _ptr(n_points_a), _ptr(VA_tab), _ptr(X),
-                                                                _ptr(theta), _ptr(Linv), _ptr(alpha), _ptr(y_mean), _ptr(y_std), _ptr(n_points),
-                                                                T, N, Mq, G, Ma_max, D, int(kind), _ptr(mu), _ptr(var), _ptr(cov),
-                                                                _ptr(task_base), Tsrc, _stream_handle())
-    _lib.check_rc(rc, "scaml_posterior_linv_grad_grouped_own_f64")
+        mu = _empty(dev, T, *row)
+        var = _empty(dev, T, *row)
+        cov = _empty(dev, T, Ma_max, width) if cov_out is None else _check(cov_out, "cov_out", (T, Ma_max, width))
+        rc = getattr(_lib.lib, name)(_ptr(Xq), _ptr(group), _ptr(Xa), _ptr(n_points_a), _ptr(VA_tab), _ptr(X), _ptr(theta), _ptr(Linv), _ptr(alpha),
+                                     _ptr(y_mean), _ptr(y_std), _ptr(n_points), T, N, Mq, G, Ma_max, D, int(kind), _ptr(mu), _ptr(var), _ptr(cov),
+                                     *((_ptr(task_base), Tsrc) if own else ()), _stream_handle())
+    _lib.check_rc(rc, name)
     return dict(mu=mu, var=var, cov=cov)
 
 
-def target_acqf_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor, group: torch.Tensor, Xq: torch.Tensor, w: torch.Tensor,
-                        active: torch.Tensor, Xt: torch.Tensor, theta: torch.Tensor, L: torch.Tensor, Linv_diag: torch.Tensor,
-                        alpha: torch.Tensor, n_points: torch.Tensor, m_all: torch.Tensor, s_all: torch.Tensor, info: torch.Tensor,
-                        acqf_param: torch.Tensor, acqf: int, kind: int, want_grad: bool = True, want_posterior: bool = False):
-    """The acquisition value (and input gradient) of every query point of G studies from the grouped GRAD pass's outputs
-    (``source_posteriors_grad_grouped``: mu, var (T, Mq, 16), cov (T, n_max, Mq * 16)) and the studies' padded arrays: w (G, T),
-    active (G, T) uint8, Xt (G, n_max, D), theta (G, D + 2), L (G, n_max, n_max), Linv_diag (G, ceil(n_max / 16), 16, 16),
-    alpha (G, n_max), n_points, info (G,) int32, m_all, s_all, acqf_param (G,).  One launch of scaml_target_acqf_batched_f64.
-    Returns dict(value (Mq,), grad (Mq, D) or None, mu, var (Mq,) or None)."""
+def source_posteriors_grad_grouped(Xq: torch.Tensor, group: torch.Tensor, Xa: torch.Tensor, n_points_a: torch.Tensor, VA_tab: torch.Tensor,
+                                   X: torch.Tensor, theta: torch.Tensor, kind: int, Linv: torch.Tensor, alpha: torch.Tensor,
+                                   y_mean: Optional[torch.Tensor] = None, y_std: Optional[torch.Tensor] = None,
+                                   n_points: Optional[torch.Tensor] = None, task_base: Optional[torch.Tensor] = None,
+                                   tasks_per_group: Optional[int] = None, cov_out: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """``source_posteriors_grad`` with the query points Xq (Mq, D) divided among G groups, one launch of
+    scaml_posterior_linv_grad_grouped_f64: ``group`` (Mq,) int32 (negative: a padding row, zeros), ``Xa`` (G, Ma_max, D) the groups'
+    leading points, ``n_points_a`` (G,) int32 their counts, ``VA_tab`` (G,) int64: the ADDRESSES of the groups' V (T, N, Ma_g) tensors
+    (``ScaMLGP._train_VA``; the caller keeps them alive).  Returns dict(mu, var (T, Mq, 16), cov (T, Ma_max, Mq * 16): rows
+    a < Ma_{group[q]} of strip q are written, the rest is uninitialised -- or what ``cov_out`` held, when that buffer is given).
+
+    ``task_base`` (G,) int32: every group owns its source tasks (scaml_posterior_linv_grad_grouped_own_f64) -- the source arrays hold
+    Tsrc = X.shape[0] tasks, task slot t of group g reads task ``task_base[g] + t``, and T = ``tasks_per_group`` slots are the leading
+    axis of the outputs and of the groups' V."""
+    if task_base is not None and tasks_per_group is None:
+        raise ValueError("task_base needs tasks_per_group (the task slots of a group)")
+    if task_base is None and tasks_per_group is not None:
+        raise ValueError("tasks_per_group goes with task_base")
+    return _source_pass_grouped(False, Xq, group, Xa, n_points_a, VA_tab, X, theta, kind, Linv, alpha, y_mean, y_std, n_points, task_base,
+                                tasks_per_group, cov_out)
+
+
+def _target_pass_studies(strips: bool, mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info,
+                         acqf_param, acqf, kind, want_grad, want_posterior) -> Dict[str, Optional[torch.Tensor]]:
+    """The studies' target pass behind ``target_acqf_batched`` (``strips`` False: the GRAD layout, ``group`` per query point, the gradient
+    where wanted) and ``target_score_batched`` (``strips`` True: the value layout, ``group`` per strip of 16 candidates, no gradient)."""
     Mq, D = Xq.shape
     G, n_max = int(Xt.shape[0]), int(Xt.shape[1])
     T = int(w.shape[1])
-    mu = _check(mu, "mu", (T, Mq, 16))
-    var = _check(var, "var", (T, Mq, 16))
-    cov = _check(cov, "cov", (T, n_max, Mq * 16))
-    group = _check(group, "group", (Mq,), torch.int32)
+    row, width = ((Mq,), Mq) if strips else ((Mq, 16), Mq * 16)
+    mu = _check(mu, "mu", (T, *row))
+    var = _check(var, "var", (T, *row))
+    cov = _check(cov, "cov", (T, n_max, width))
+    group = _check(group, "group", (Mq // 16 if strips else Mq,), torch.int32)
     Xq = _check(Xq, "Xq")
     w = _check(w, "w", (G, T))
     active = _check(active, "active", (G, T), torch.uint8)
@@ -763,18 +739,32 @@ def target_acqf_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor, 
     s_all = _check(s_all, "s_all", (G,))
     info = _check(info, "info", (G,), torch.int32)
     acqf_param = _check(acqf_param, "acqf_param", (G,))
+    name = "scaml_target_score_batched_f64" if strips else "scaml_target_acqf_batched_f64"
     dev = Xq.device
     with torch.cuda.device(dev):
         value = _empty(dev, Mq)
         grad = _empty(dev, Mq, D) if want_grad else None
         mu_o = _empty(dev, Mq) if want_posterior else None
         var_o = _empty(dev, Mq) if want_posterior else None
-        rc = _lib.lib.scaml_target_acqf_batched_f64(_ptr(mu), _ptr(var), _ptr(cov), _ptr(group), _ptr(Xq), _ptr(w), _ptr(active), _ptr(Xt),
-                                                    _ptr(theta), _ptr(L), _ptr(Linv_diag), _ptr(alpha), _ptr(n_points), _ptr(m_all), _ptr(s_all),
-                                                    _ptr(info), _ptr(acqf_param), Mq, G, n_max, T, D, int(kind), int(acqf), _ptr(value), _ptr(grad),
-                                                    _ptr(mu_o), _ptr(var_o), _stream_handle())
-    _lib.check_rc(rc, "scaml_target_acqf_batched_f64")
+        rc = getattr(_lib.lib, name)(_ptr(mu), _ptr(var), _ptr(cov), _ptr(group), _ptr(Xq), _ptr(w), _ptr(active), _ptr(Xt), _ptr(theta), _ptr(L),
+                                     _ptr(Linv_diag), _ptr(alpha), _ptr(n_points), _ptr(m_all), _ptr(s_all), _ptr(info), _ptr(acqf_param), Mq, G,
+                                     n_max, T, D, int(kind), int(acqf), _ptr(value), *(() if strips else (_ptr(grad),)), _ptr(mu_o), _ptr(var_o),
+                                     _stream_handle())
+    _lib.check_rc(rc, name)
     return dict(value=value, grad=grad, mu=mu_o, var=var_o)
+
+
+def target_acqf_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor, group: torch.Tensor, Xq: torch.Tensor, w: torch.Tensor,
+                        active: torch.Tensor, Xt: torch.Tensor, theta: torch.Tensor, L: torch.Tensor, Linv_diag: torch.Tensor,
+                        alpha: torch.Tensor, n_points: torch.Tensor, m_all: torch.Tensor, s_all: torch.Tensor, info: torch.Tensor,
+                        acqf_param: torch.Tensor, acqf: int, kind: int, want_grad: bool = True, want_posterior: bool = False):
+    """The acquisition value (and input gradient) of every query point of G studies from the grouped GRAD pass's outputs
+    (``source_posteriors_grad_grouped``: mu, var (T, Mq, 16), cov (T, n_max, Mq * 16)) and the studies' padded arrays: w (G, T),
+    active (G, T) uint8, Xt (G, n_max, D), theta (G, D + 2), L (G, n_max, n_max), Linv_diag (G, ceil(n_max / 16), 16, 16),
+    alpha (G, n_max), n_points, info (G,) int32, m_all, s_all, acqf_param (G,).  One launch of scaml_target_acqf_batched_f64.
+    Returns dict(value (Mq,), grad (Mq, D) or None, mu, var (Mq,) or None)."""
+    return _target_pass_studies(False, mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info,
+                                acqf_param, acqf, kind, want_grad, want_posterior)
 
 
 def source_posteriors_grouped(Xq: torch.Tensor, group: torch.Tensor, Xa: torch.Tensor, n_points_a: torch.Tensor, VA_tab: torch.Tensor,
@@ -791,44 +781,12 @@ def source_posteriors_grouped(Xq: torch.Tensor, group: torch.Tensor, Xa: torch.T
     ``task_base`` (G,) int32 with ``tasks_per_group``: every group owns its source tasks (scaml_posterior_linv_grouped_own_f64) -- the
     source arrays hold Tsrc = X.shape[0] tasks, slot t of group g reads task ``task_base[g] + t``, the outputs have T =
     ``tasks_per_group`` leading rows."""
-    own = task_base is not None
-    if own != (tasks_per_group is not None):
+    if (task_base is not None) != (tasks_per_group is not None):
         raise ValueError("task_base and tasks_per_group go together")
-    Tsrc, N, D = X.shape
-    T = int(tasks_per_group) if own else Tsrc
-    Mq = Xq.shape[0]
-    if Mq % 16:
-        raise ValueError(f"the candidates come in whole strips of 16, got Mq = {Mq}")
-    G, Ma_max = int(Xa.shape[0]), int(Xa.shape[1])
-    X = _check(X, "X")
-    Xq = _check(Xq, "Xq", (Mq, D))
-    group = _check(group, "group", (Mq // 16,), torch.int32)
-    Xa = _check(Xa, "Xa", (G, Ma_max, D))
-    n_points_a = _check(n_points_a, "n_points_a", (G,), torch.int32)
-    VA_tab = _check(VA_tab, "VA_tab", (G,), torch.int64)
-    theta = _check(theta, "theta", (Tsrc, D + 2))
-    Linv = _check(Linv, "Linv", (Tsrc, N, N))
-    alpha = _check(alpha, "alpha", (Tsrc, N))
-    y_mean = _opt(y_mean, "y_mean", (Tsrc,))
-    y_std = _opt(y_std, "y_std", (Tsrc,))
-    n_points = _opt(n_points, "n_points", (Tsrc,), torch.int32)
-    if own:
-        task_base = _check(task_base, "task_base", (G,), torch.int32)
-    dev = X.device
-    with torch.cuda.device(dev):
-        mu = _empty(dev, T, Mq)
-        var = _empty(dev, T, Mq)
-        cov = _empty(dev, T, Ma_max, Mq) if cov_out is None else _check(cov_out, "cov_out", (T, Ma_max, Mq))
-        head = (_ptr(Xq), _ptr(group), _ptr(Xa), _ptr(n_points_a), _ptr(VA_tab), _ptr(X), _ptr(theta), _ptr(Linv), _ptr(alpha), _ptr(y_mean),
-                _ptr(y_std), _ptr(n_points), T, N, Mq, G, Ma_max, D, int(kind), _ptr(mu), _ptr(var), _ptr(cov))
-        if own:
-            name = "scaml_posterior_linv_grouped_own_f64"
-            rc = _lib.lib.scaml_posterior_linv_grouped_own_f64(*head, _ptr(task_base), Tsrc, _stream_handle())
-        else:
-            name = "scaml_posterior_linv_grouped_f64"
-            rc = _lib.lib.scaml_posterior_linv_grouped_f64(*head, _stream_handle())
-    _lib.check_rc(rc, name)
-    return dict(mu=mu, var=var, cov=cov)
+    if Xq.shape[0] % 16:
+        raise ValueError(f"the candidates come in whole strips of 16, got Mq = {Xq.shape[0]}")
+    return _source_pass_grouped(True, Xq, group, Xa, n_points_a, VA_tab, X, theta, kind, Linv, alpha, y_mean, y_std, n_points, task_base,
+                                tasks_per_group, cov_out)
 
 
 def target_score_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor, group: torch.Tensor, Xq: torch.Tensor, w: torch.Tensor,
@@ -840,39 +798,11 @@ def target_score_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor,
     ``target_acqf_batched`` takes them.  One launch of scaml_target_score_batched_f64: a workgroup per strip, the study's factor staged
     once for its 16 candidates; per candidate the arithmetic is ``target_acqf_batched``'s, bit for bit.  No gradient.
     Returns dict(value (Mq,), mu, var (Mq,) or None)."""
-    Mq, D = Xq.shape
-    if Mq % 16:
-        raise ValueError(f"the candidates come in whole strips of 16, got Mq = {Mq}")
-    G, n_max = int(Xt.shape[0]), int(Xt.shape[1])
-    T = int(w.shape[1])
-    mu = _check(mu, "mu", (T, Mq))
-    var = _check(var, "var", (T, Mq))
-    cov = _check(cov, "cov", (T, n_max, Mq))
-    group = _check(group, "group", (Mq // 16,), torch.int32)
-    Xq = _check(Xq, "Xq")
-    w = _check(w, "w", (G, T))
-    active = _check(active, "active", (G, T), torch.uint8)
-    Xt = _check(Xt, "Xt", (G, n_max, D))
-    theta = _check(theta, "theta", (G, D + 2))
-    L = _check(L, "L", (G, n_max, n_max))
-    Linv_diag = _check(Linv_diag, "Linv_diag", (G, (n_max + 15) // 16, 16, 16))
-    alpha = _check(alpha, "alpha", (G, n_max))
-    n_points = _check(n_points, "n_points", (G,), torch.int32)
-    m_all = _check(m_all, "m_all", (G,))
-    s_all = _check(s_all, "s_all", (G,))
-    info = _check(info, "info", (G,), torch.int32)
-    acqf_param = _check(acqf_param, "acqf_param", (G,))
-    dev = Xq.device
-    with torch.cuda.device(dev):
-        value = _empty(dev, Mq)
-        mu_o = _empty(dev, Mq) if want_posterior else None
-        var_o = _empty(dev, Mq) if want_posterior else None
-        rc = _lib.lib.scaml_target_score_batched_f64(_ptr(mu), _ptr(var), _ptr(cov), _ptr(group), _ptr(Xq), _ptr(w), _ptr(active), _ptr(Xt),
-                                                     _ptr(theta), _ptr(L), _ptr(Linv_diag), _ptr(alpha), _ptr(n_points), _ptr(m_all), _ptr(s_all),
-                                                     _ptr(info), _ptr(acqf_param), Mq, G, n_max, T, D, int(kind), int(acqf), _ptr(value),
-                                                     _ptr(mu_o), _ptr(var_o), _stream_handle())
-    _lib.check_rc(rc, "scaml_target_score_batched_f64")
-    return dict(value=value, mu=mu_o, var=var_o)
+    if Xq.shape[0] % 16:
+        raise ValueError(f"the candidates come in whole strips of 16, got Mq = {Xq.shape[0]}")
+    out = _target_pass_studies(True, mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info,
+                               acqf_param, acqf, kind, False, want_posterior)
+    return dict(value=out["value"], mu=out["mu"], var=out["var"])
 
 
 def target_factors_batched(batch: "TargetFitBatch", w: torch.Tensor, active: torch.Tensor, theta: torch.Tensor) -> Dict[str, torch.Tensor]:

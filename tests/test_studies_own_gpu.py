@@ -192,9 +192,7 @@ def _raw_pass(sa, X, group, task_base=None, cov_out=None):
     st, f = sa.source, sa.source.fit
     args = (X, group, sa.Xt, sa.n_points, sa.VA_tab, st.X, st.theta, st.kind, f["Linv"], f["alpha"], st.y_mean, st.y_std, st.n_points)
     tb = sa.task_base if task_base is None else task_base
-    if cov_out is None:
-        return ops.source_posteriors_grad_grouped(*args, task_base=tb, tasks_per_group=sa.w.shape[1])
-    return ops._source_posteriors_grad_grouped_own(*args, tb, sa.w.shape[1], cov_out=cov_out)   # (the op's body, writing into a prefilled cov)
+    return ops.source_posteriors_grad_grouped(*args, task_base=tb, tasks_per_group=sa.w.shape[1], cov_out=cov_out)   # (cov_out: a prefilled cov)
 
 
 def _strips(out, sa, group, g):
