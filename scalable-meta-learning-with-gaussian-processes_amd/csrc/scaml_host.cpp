@@ -17,9 +17,7 @@
 
 #include "../../include/scaml_gp.h"
 #include "../../include/scaml_gp_debug.h"
-#include "gp_fit_params.h"
-#include "gp_posterior_params.h"
-#include "gp_target_params.h"
+#include "gp_dispatch.h"       // (dispatch by shape; brings the fit, posterior and target argument blocks and LDS footprints)
 #include "gp_fantasy_params.h"
 #include "gp_stack_fit_params.h"
 #include "gp_studies_acqf.h"   // (argument block and LDS footprint; its arithmetic is not called here)
@@ -38,12 +36,11 @@ void set_error(const char* what, hipError_t e) {
   snprintf(g_last_error, sizeof(g_last_error), "%s: %s", what, hipGetErrorString(e));
 }
 
-constexpr size_t kLdsLimit = 160 * 1024;   // bytes of LDS a workgroup may ask for on gfx950
+constexpr size_t kLdsLimit = scaml::LDS_LIMIT;
 
 bool valid_kind(int kind) { return kind == SCAML_KIND_RBF || kind == SCAML_KIND_MATERN52; }
 
 struct FitVariant {
-  int nb, wu;
   hipFunction_t fn[2][2];  // [dense | blocked addressing][kind]
 };
 
@@ -65,7 +62,7 @@ struct Module {
   bool loaded = false;
   hipModule_t mod = nullptr;
   std::atomic<int> num_cus{0};
-  FitVariant fit[5] = {{2, 1, {}}, {4, 3, {}}, {8, 3, {}}, {16, 7, {}}, {8, 7, {}}};   // [4]: wide variant for 64 < N <= 128
+  FitVariant fit[scaml::FIT_INSTANCES] = {};   // (NB, WU) of each: scaml::fit_instance
   hipFunction_t post[2] = {}, post_cov[2] = {}, post_linv[2] = {}, post_linv_cov[2] = {}, post_linv_grad[2] = {};
   hipFunction_t wsum = nullptr, linv = nullptr, chosolve = nullptr, kmat[2] = {}, mllgrad[2] = {};
   hipFunction_t tgt_assemble[2] = {}, tgt_finish = nullptr, tgt_fit = nullptr, tgt_fit_batched = nullptr, tgt_grad[2] = {};
@@ -126,9 +123,10 @@ struct Module {
         {&blk_solve[0][0], "_ZN5scaml23gp_blocked_solve_kernelILi%dELb%dEEEvNS_16BlockedFitParamsE", kLdsLimit, {K, B}},
         {blk_syrk, "_ZN5scaml22gp_blocked_syrk_kernelILi%dEEEvNS_16BlockedFitParamsE", kLdsLimit, {K}},
     };
-    for (FitVariant& v : fit) {   // the kernels use up to the full 160 KiB of LDS
-      rows.push_back({v.fn[0], "_ZN5scaml19gp_fit_fused_kernelILi%dELi%dELi%dEEEvNS_9FitParamsE", kLdsLimit, {{1, {v.nb}}, {1, {v.wu}}, K}});
-      rows.push_back({v.fn[1], "_ZN5scaml21gp_fit_blocked_kernelILi%dELi%dELi%dEEEvNS_9FitParamsENS_14FitBlockParamsE", kLdsLimit, {{1, {v.nb}}, {1, {v.wu}}, K}});
+    for (int i = 0; i < scaml::FIT_INSTANCES; ++i) {   // the kernels use up to the full 160 KiB of LDS
+      const scaml::FitInstance v = scaml::fit_instance(i);
+      rows.push_back({fit[i].fn[0], "_ZN5scaml19gp_fit_fused_kernelILi%dELi%dELi%dEEEvNS_9FitParamsE", kLdsLimit, {{1, {v.nb}}, {1, {v.wu}}, K}});
+      rows.push_back({fit[i].fn[1], "_ZN5scaml21gp_fit_blocked_kernelILi%dELi%dELi%dEEEvNS_9FitParamsENS_14FitBlockParamsE", kLdsLimit, {{1, {v.nb}}, {1, {v.wu}}, K}});
     }
     for (const KernelRow& r : rows) {
       hipFunction_t* slot = r.slot;
@@ -251,25 +249,16 @@ int scaml_version(void) { return 400; }  // 0.4.0 = 10000 * 0 + 100 * 4 + 0
 const char* scaml_last_error(void) { return g_last_error; }
 int scaml_fit_max_n(void) { return 256; }
 
-int scaml_fit_max_d(int N) {
-  // largest D whose staged point stack fits the 160 KiB LDS next to the vectors
-  const int d = scaml::fit_max_d(N <= 32 ? 32 : (N <= 64 ? 64 : (N <= 128 ? 128 : 256)), (int)(kLdsLimit / sizeof(double)));
-  return d > 1024 ? 1024 : d;
-}
+int scaml_fit_max_d(int N) { return scaml::fit_class_max_d(N); }
 
 static int fit_common(scaml::FitParams p, int kind, void* stream, const scaml::FitBlockParams* blk = nullptr) {
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
-  const int N = p.N;
-  int vi = N <= 32 ? 0 : (N <= 64 ? 1 : (N <= 128 ? 2 : 3));
-  // 64 < N <= 128: four waves per task let two workgroups share a CU; when the stack does not fill the CUs even
-  // once that buys nothing, and eight waves on the task's kernel matrix and trailing update are faster
-  if (vi == 2 && p.T <= num_cus(*m)) vi = 4;
-  const FitVariant& v = m->fit[vi];
-  const size_t lds = scaml::fit_lds_doubles(v.nb, v.wu, p.D) * sizeof(double);
+  const scaml::FitPlan plan = scaml::fit_plan(p.T, p.N, p.D, num_cus(*m));
+  const size_t lds = plan.lds_doubles * sizeof(double);
   if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
   struct { scaml::FitParams p; scaml::FitBlockParams b; } args{p, blk ? *blk : scaml::FitBlockParams{}};   // (kernarg layout: both 8-byte aligned)
-  return launch(v.fn[blk ? 1 : 0][kind], dim3((unsigned)p.T), (unsigned)(v.wu + 1) * 64, lds, stream, "gp_fit_fused", args,
+  return launch(m->fit[plan.variant].fn[blk ? 1 : 0][kind], dim3((unsigned)p.T), plan.block, lds, stream, "gp_fit_fused", args,
                 blk ? sizeof(args) : sizeof(p));
 }
 
@@ -349,34 +338,21 @@ int scaml_gp_fit_blocked_f64(const double* X, const double* y, const double* the
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
   char* ws = (char*)workspace;
-  const int t8 = (T + 7) / 8 * 8;   // tasks ride on grid.x, dealt to the XCDs (bk_task_part)
-  {
-    // Several CUs per task (csrc/gp_fit_coop.hip) while the stack leaves CUs idle: P workgroups per task, ALL resident at once
-    // (one per CU: the dynamic LDS request is kept above half a CU's), so the launch is only taken when T P <= #CUs.
-    const int nbc = (N + 31) / 32;
-    int parts = num_cus(*m) / T;
-    parts = parts > 8 ? 8 : parts;
-    parts = parts > nbc ? nbc : parts;
-    const size_t lds_coop = scaml::coop_fit_lds_doubles(N, D) * sizeof(double);
-    const size_t flag_bytes = (((size_t)T * 44 * 4) + 15) & ~(size_t)15;
-    const size_t need = flag_bytes + (size_t)T * N * 8 + (size_t)T * 64 * 8;
-    // by shape (dev_coop_time.py, profiles/r03_notes.md): three or more workgroups per task always pay; two only while a workgroup's eight
-    // or fewer block columns leave it time to keep up with the diagonal chain (N <= 320)
-    const int path = g_dev.blocked_fit_path.load(kRelaxed);
-    const bool take = path == 2 ? parts >= 1 : (path == 0 && (parts >= 3 || (parts == 2 && nbc <= 10)));
-    if (take && D <= 16 && lds_coop <= kLdsLimit && need <= (size_t)workspace_bytes) {
-      const hipError_t e = hipMemsetAsync(ws, 0, flag_bytes, (hipStream_t)stream);
-      if (e != hipSuccess) { set_error("hipMemsetAsync(coop flags)", e); return SCAML_E_LAUNCH; }
-      scaml::CoopFitParams c{X, y, theta, n_points, jitter_in, L, alpha, quad, logdet, mll, info, jitter_used, Linv_diag,
-                             (unsigned*)ws, (unsigned*)ws + (size_t)T * 32, (unsigned*)ws + (size_t)T * 36, (double*)(ws + flag_bytes), (double*)(ws + flag_bytes) + (size_t)T * N,
-                             T, N, D, flags | (g_dev.coop_far.load(kRelaxed) ? 0x80000000u : 0u), parts};
-      const size_t half_cu = 82 * 1024;   // (more than half a CU's LDS: one workgroup per CU)
-      const int rc = launch(m->coop[kind], dim3((unsigned)(t8 * parts)), 512, lds_coop > half_cu ? lds_coop : half_cu, stream, "gp_fit_coop", c);
-      if (rc == SCAML_OK) g_dev.blocked_fit_last.store(2, kRelaxed);
-      return rc;
-    }
-    g_dev.blocked_fit_last.store(1, kRelaxed);
+  const scaml::BlockedPlan plan =
+      scaml::blocked_plan(T, N, D, num_cus(*m), g_dev.blocked_fit_path.load(kRelaxed), workspace_bytes, (flags & SCAML_FIT_NO_RETRY) != 0);
+  const int t8 = plan.t8;
+  if (plan.path == 2) {
+    const size_t flag_bytes = plan.flag_bytes;
+    const hipError_t e = hipMemsetAsync(ws, 0, flag_bytes, (hipStream_t)stream);
+    if (e != hipSuccess) { set_error("hipMemsetAsync(coop flags)", e); return SCAML_E_LAUNCH; }
+    scaml::CoopFitParams c{X, y, theta, n_points, jitter_in, L, alpha, quad, logdet, mll, info, jitter_used, Linv_diag,
+                           (unsigned*)ws, (unsigned*)ws + (size_t)T * 32, (unsigned*)ws + (size_t)T * 36, (double*)(ws + flag_bytes), (double*)(ws + flag_bytes) + (size_t)T * N,
+                           T, N, D, flags | (g_dev.coop_far.load(kRelaxed) ? 0x80000000u : 0u), plan.parts};
+    const int rc = launch(m->coop[kind], dim3((unsigned)(t8 * plan.parts)), 512, plan.lds_coop, stream, "gp_fit_coop", c);
+    if (rc == SCAML_OK) g_dev.blocked_fit_last.store(2, kRelaxed);
+    return rc;
   }
+  g_dev.blocked_fit_last.store(1, kRelaxed);
   const int N1 = 256, N2 = N - N1, NBT = N / 16;
   scaml::BlockedFitParams p{X, y, theta, n_points, jitter_in, L, alpha, quad, logdet, mll, info, jitter_used, Linv_diag,
                             (double*)(ws + lay.S), (double*)(ws + lay.Vimg), (double*)(ws + lay.r2), (double*)(ws + lay.q12), (double*)(ws + lay.jit_cur),
@@ -388,17 +364,14 @@ int scaml_gp_fit_blocked_f64(const double* X, const double* y, const double* the
   scaml::FitParams f2{nullptr, p.r2 + N1, nullptr, p.n2, nullptr, p.S, L + (size_t)N1 * N + N1, alpha + N1, p.q12 + 2 * (size_t)T, p.q12 + 3 * (size_t)T,
                       nullptr, p.info2, nullptr, Linv_diag + (size_t)(N1 / 16) * 256, T, N2, 1, fl};
   const scaml::FitBlockParams b2{0, N, (long long)N * N, (long long)NBT * 256, p.active, N};
-  const size_t lds_solve = scaml::blocked_solve_lds_doubles(D) * sizeof(double);
-  const size_t lds_syrk = scaml::blocked_syrk_lds_doubles(D) * sizeof(double);
-  const int nt = (N2 + 63) / 64;
-  const int rounds = (flags & SCAML_FIT_NO_RETRY) ? 1 : 4;
+  const int nt = plan.nt;
   int rc = SCAML_OK;
-  for (int r = 0; r < rounds; ++r) {
+  for (int r = 0; r < plan.rounds; ++r) {
     p.round = r;
     if ((rc = launch(m->blk_round, dim3((unsigned)((T + 255) / 256)), 256, 0, stream, "blocked_round", p)) != SCAML_OK) return rc;
     if ((rc = fit_common(f1, kind, stream, &b1)) != SCAML_OK) return rc;
-    if ((rc = launch(m->blk_solve[kind][D <= 8 ? 1 : 0], dim3((unsigned)(t8 * nt)), 512, lds_solve, stream, "gp_blocked_solve", p)) != SCAML_OK) return rc;
-    if ((rc = launch(m->blk_syrk[kind], dim3((unsigned)(t8 * (nt * (nt + 1) / 2))), 512, lds_syrk, stream, "gp_blocked_syrk", p)) != SCAML_OK) return rc;
+    if ((rc = launch(m->blk_solve[kind][plan.solve_small_d], dim3((unsigned)(t8 * nt)), 512, plan.lds_solve, stream, "gp_blocked_solve", p)) != SCAML_OK) return rc;
+    if ((rc = launch(m->blk_syrk[kind], dim3((unsigned)(t8 * (nt * (nt + 1) / 2))), 512, plan.lds_syrk, stream, "gp_blocked_syrk", p)) != SCAML_OK) return rc;
     if ((rc = fit_common(f2, SCAML_KIND_RBF, stream, &b2)) != SCAML_OK) return rc;
   }
   return launch(m->blk_finish, dim3((unsigned)T), 1024, 0, stream, "blocked_finish", p);
@@ -431,13 +404,9 @@ int scaml_posterior_batched_f64(const double* Xq, const double* X, const double*
   if (!valid_kind(kind)) return SCAML_E_BADARG;
   if (N > scaml_posterior_max_n()) return SCAML_E_TOOLARGE;
   if (T == 0 || M == 0) return SCAML_OK;
-  // waves per workgroup / X staging: the largest configuration whose LDS fits 160 KiB
-  int waves = 0;
-  bool xl = true;
-  for (int cand : {4, 2, 1}) {
-    if (scaml::posterior_lds_doubles(N, D, cand, true) * sizeof(double) <= kLdsLimit) { waves = cand; xl = true; break; }
-    if (scaml::posterior_lds_doubles(N, D, cand, false) * sizeof(double) <= kLdsLimit) { waves = cand; xl = false; break; }
-  }
+  const scaml::PosteriorPlan plan = scaml::posterior_plan(N, D);
+  const int waves = plan.waves;
+  const bool xl = plan.xl;
   if (!waves) return SCAML_E_TOOLARGE;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
@@ -490,14 +459,6 @@ int scaml_kernel_matrix_f64(const double* X1, const double* X2, const double* th
 }
 
 // ---- batched Cholesky solve ----------------------------------------------------------------------
-// waves per workgroup of gp_linv_kernel / gp_cho_solve_kernel: as many [np][16] strips as fit the LDS
-static int strip_solve_waves(int np) {
-  for (int waves : {4, 2}) {
-    if (scaml::strip_solve_lds_doubles(np, waves) * sizeof(double) <= kLdsLimit) return waves;
-  }
-  return 1;
-}
-
 static int cho_solve_common(const double* L, const double* Linv_diag, const double* B, const int32_t* n_points,
                            int T, int N, int R, double* Xout, int mode, void* stream) {
   if (T < 0 || N < 1 || R < 0) return SCAML_E_BADARG;
@@ -507,7 +468,7 @@ static int cho_solve_common(const double* L, const double* Linv_diag, const doub
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
   const int nb = (N + 15) / 16, np = nb * 16, strips = (R + 15) / 16;
-  int waves = strip_solve_waves(np);
+  int waves = scaml::strip_solve_waves(np);
   if (waves > strips) waves = strips;
   scaml::ChoSolveParams p{L, Linv_diag, B, n_points, Xout, T, N, R, mode};
   return launch(m->chosolve, dim3((unsigned)((strips + waves - 1) / waves), (unsigned)T), (unsigned)waves * 64,
@@ -539,13 +500,9 @@ int scaml_weighted_prior_reduce_f64(const double* mu, const double* cov, const d
 static int launch_linv(Module& m, const double* L, const double* Linv_diag, const int32_t* n_points, int T, int N,
                        double* Linv, void* stream, int lower_only = 0) {
   const int nb = (N + 15) / 16, np = nb * 16;
-  const int waves = strip_solve_waves(np);
+  const int waves = scaml::strip_solve_waves(np);
   scaml::LinvParams p{L, Linv_diag, n_points, Linv, T, N, lower_only};
-  // one workgroup per task takes all strips (balanced over its waves); small stacks are split over more
-  // workgroups so that the 256 CUs stay busy
-  int groups = 1;
-  while (groups * 2 * waves <= nb && (long long)T * groups * 2 <= 256) groups *= 2;
-  return launch(m.linv, dim3((unsigned)groups, (unsigned)T), (unsigned)waves * 64, scaml::strip_solve_lds_doubles(np, waves) * sizeof(double),
+  return launch(m.linv, dim3((unsigned)scaml::linv_groups(T, nb, waves), (unsigned)T), (unsigned)waves * 64, scaml::strip_solve_lds_doubles(np, waves) * sizeof(double),
                 stream, "gp_linv", p);
 }
 
@@ -640,39 +597,21 @@ int scaml_mll_backward_f64(const double* X, const double* theta, const double* L
   if (T == 0) return SCAML_OK;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
-  const int nb = (N + 15) / 16;
   double* Linv = workspace;
   double* partials = partials_out ? partials_out : workspace + (size_t)T * N * N;
-  // N <= 256, D <= 8: ONE launch, one workgroup per task, K^-1 by column strips held in registers; neither L^-1 nor
-  // K^-1 touches memory (csrc/gp_mll_grad_fused.hip).  Larger problems take the two-launch path below.
-  // (measured, tools/dev_grad_select.py: a stack of at most 64 tasks of more than 64 points leaves most CUs idle with one
-  //  workgroup per task, and there the two launches below -- L^-1 strips and K^-1 tiles spread over the chip -- win: 96 vs 120 us at
-  //  T = 32, N = 256; 44 vs 49 us at T = 64, N = 128)
-  const bool small_stack = N > 64 && T <= 64;
-  const int grad_path = g_dev.grad_path.load(kRelaxed);
-  if (N <= 256 && D <= 8 && grad_path != 1 && !(small_stack && grad_path != 2 && !g_dev.no_grad_split)) {
-    const int sc = N <= 32 ? 0 : (N <= 64 ? 1 : (N <= 128 ? 2 : 3));
-    const int nbt = 2 << sc;
+  const bool aligned16 = ((uintptr_t)L % 16) == 0 && ((uintptr_t)Linv_diag % 16) == 0;
+  const scaml::GradPlan plan =
+      scaml::grad_plan(T, N, D, num_cus(*m), g_dev.grad_path.load(kRelaxed), g_dev.no_grad_split, n_points != nullptr, aligned16);
+  const size_t lds = plan.lds_doubles * sizeof(double);
+  if (plan.single) {
     scaml::MllGradFusedParams p{X, theta, L, Linv_diag, alpha, n_points, partials, T, N, D};
-    // direct-to-LDS staging moves raw 16-byte pieces: only where no element needs masking and every row is 16-byte aligned
-    const int dma = (n_points == nullptr && N % 16 == 0 && ((uintptr_t)L % 16) == 0 && ((uintptr_t)Linv_diag % 16) == 0) ? 1 : 0;
-    // a stack that leaves CUs idle with one workgroup per task is split over 2 or 4 workgroups per task (strips are
-    // independent): BASELINE configs[3] runs 128 tasks per GPU on 256 CUs
-    // (split tasks pay for themselves in the N <= 256 class between 65 and 128 tasks only: 100 vs 105 us at T = 128; in the N <= 128
-    //  class every split measured slower than one workgroup per task: 57 vs 49 us at T = 64)
-    int split = 1;
-    if (sc == 3 && dma && !g_dev.no_grad_split && 2 * T <= num_cus(*m)) split = 2;
-    hipFunction_t fn = split == 1 ? m->mllgrad_fused[sc][kind][dma] : m->mllgrad_split[sc - 2][kind][split == 2 ? 0 : 1];
-    return launch(fn, dim3((unsigned)T, (unsigned)split), (unsigned)(nbt * 32 / split), scaml::mll_grad_fused_lds_doubles(nbt, nbt / 2) * sizeof(double),
-                  stream, "gp_mll_grad_fused", p);
+    hipFunction_t fn = plan.split == 1 ? m->mllgrad_fused[plan.sc][kind][plan.dma] : m->mllgrad_split[plan.sc - 2][kind][plan.split == 2 ? 0 : 1];
+    return launch(fn, dim3(plan.grid_x, plan.grid_y), plan.block, lds, stream, "gp_mll_grad_fused", p);
   }
   const int rc = launch_linv(*m, L, Linv_diag, n_points, T, N, Linv, stream);   // (dense: the 2 x 2 super-tiles of the tile kernel read zero blocks above the diagonal)
   if (rc != SCAML_OK) return rc;
   scaml::MllGradParams p{X, theta, alpha, Linv, n_points, partials, T, N, D};
-  // 1-D grid, XCD-aware (task, tile group) map inside the kernel
-  const int nbs = (nb + 1) / 2, ns = nbs * (nbs + 1) / 2;   // 2 x 2 super-tiles, one per wave
-  const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * (unsigned)((ns + 3) / 4);
-  return launch(m->mllgrad[kind], dim3(blocks), 256, lds_tiles, stream, "gp_mll_grad", p);
+  return launch(m->mllgrad[kind], dim3(plan.grid_x), plan.block, lds, stream, "gp_mll_grad", p);
 }
 
 // ---- target GP: assemble the joint prior block / finish the posterior (a10) -----------------------------------------
@@ -903,15 +842,7 @@ int scaml_target_train_block_batched_f64(const double* means_t, const double* co
 
 // ---- (8) target GP: objective + gradient, and the whole L-BFGS refit, in one launch (csrc/gp_target_fit.hip) -------------
 namespace {
-constexpr int kTargetFitThreads = 512;
-size_t target_fit_lds_bytes(int n, int T, int D, bool mfma) {
-  return scaml::target_fit_lds_doubles(n, T, D, mfma, kTargetFitThreads / 64) * sizeof(double);
-}
-static_assert(scaml::TARGET_FIT_LDS_LIMIT == kLdsLimit, "the matrix-core rule and the launcher count the same LDS");
-// the matrix-core factorisation takes n <= 112 (two block triangles of 16 x 17 tiles in LDS)
-bool target_fit_use_mfma(int n, int T, int D) {
-  return g_dev.target_fit_path.load(kRelaxed) == 0 && scaml::target_fit_mfma_shape(n, T, D, kTargetFitThreads / 64);
-}
+constexpr int kTargetFitThreads = scaml::TARGET_FIT_THREADS;
 // Argument checks of both launchers.  The order that can be observed is kept by both: every SCAML_E_BADARG check (the entry point's,
 // the filler's, the launcher's own, these) comes before every SCAML_E_TOOLARGE check (D here, then the launcher's sizes), and an empty
 // launch is SCAML_OK only after all of them.
@@ -925,8 +856,9 @@ int target_fit_check(const scaml::TargetFitParams& p) {
 int target_fit_launch(scaml::TargetFitParams& p, void* stream) {
   if (!(p.s_all > 0.0)) return SCAML_E_BADARG;
   if (const int rc = target_fit_check(p)) return rc;
-  p.use_mfma = target_fit_use_mfma(p.n, p.T, p.D) ? 1 : 0;
-  const size_t lds = target_fit_lds_bytes(p.n, p.T, p.D, p.use_mfma != 0);
+  const scaml::TargetFitPlan plan = scaml::target_fit_plan(p.n, p.T, p.D, g_dev.target_fit_path.load(kRelaxed));
+  p.use_mfma = plan.use_mfma ? 1 : 0;
+  const size_t lds = plan.lds_doubles * sizeof(double);
   if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
   if (p.B == 0) return SCAML_OK;
   Module* m = ready();
@@ -967,7 +899,7 @@ int scaml_target_fit_max_d(void) { return scaml::TARGET_FIT_DMAX; }
 int scaml_target_fit_max_n(int T, int D) {
   if (T < 1 || D < 1 || D > scaml::TARGET_FIT_DMAX) return 0;
   int n = 0;
-  while (n < 4096 && target_fit_lds_bytes(n + 1, T, D, false) <= kLdsLimit) ++n;
+  while (n < 4096 && scaml::target_fit_plan(n + 1, T, D, 1).lds_doubles * sizeof(double) <= kLdsLimit) ++n;   // (mode 1: column by column)
   return n;
 }
 
@@ -1006,8 +938,9 @@ int target_fit_batched_launch(scaml::TargetFitBatchParams& bp, void* stream) {
   if (const int rc = target_fit_check(p)) return rc;
   if (p.n > scaml_target_fit_max_n(p.T, p.D)) return SCAML_E_TOOLARGE;
   if ((long long)bp.S * p.B > 0x7fffffffLL) return SCAML_E_TOOLARGE;
-  p.use_mfma = g_dev.target_fit_path.load(kRelaxed) == 0 ? 1 : 0;
-  const size_t lds = scaml::target_fit_batched_lds_doubles(p.n, p.T, p.D, p.use_mfma != 0, kTargetFitThreads / 64) * sizeof(double);
+  const scaml::TargetFitPlan plan = scaml::target_fit_batched_plan(p.n, p.T, p.D, g_dev.target_fit_path.load(kRelaxed));
+  p.use_mfma = plan.use_mfma ? 1 : 0;
+  const size_t lds = plan.lds_doubles * sizeof(double);
   if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
   if (bp.S == 0 || p.B == 0) return SCAML_OK;
   Module* m = ready();

@@ -19,13 +19,15 @@ import torch
 
 from oracle import gp_oracle as O
 from scamlgp_amd import synthetic
+from tests._dispatch import narrow_fit_tasks
 
 F64 = torch.float64
 RUNGS = (1e-8, 1e-7, 1e-6)
 JITTER_IN_RETRY = 4.5e-8   # caller-side jitter on a rung-1e-7 task: attempt 0 at -5e-9, rung 1e-8 at +5e-9
 
-# (instance, N, T): shapes that reach each kernel instance (fit_common, csrc/scaml_host.cpp).  T = None: one more than the
-# device's CU count (the narrow instance); the CPU test uses NARROW_T_CPU.
+# (instance, N, T): shapes that reach each kernel instance (fit_plan, csrc/gp_dispatch.h; tests/test_failpath_inputs.py holds the
+# names to the plan).  T = None: the smallest stack the plan sends to the narrow instance on the device's CU count; the CPU test
+# uses NARROW_T_CPU.
 INSTANCES = {
     "nb2_wu1": (32, 9, 2),
     "nb4_wu3": (64, 9, 4),
@@ -34,7 +36,7 @@ INSTANCES = {
     "nb16_wu7_n255": (255, 9, 16),
     "nb16_wu7_n256": (256, 9, 16),
 }
-NARROW_T_CPU = 257      # MI355X: 256 CUs
+NARROW_T_CPU = narrow_fit_tasks(256, N=INSTANCES["nb8_wu3_narrow"][0])      # MI355X: 256 CUs
 RAGGED_SHORT = 5        # the ragged hopeless task has n = N - 5 valid points and fails at its last one
 SMALL_PATTERN = ("clean", 1e-8, "hopeless", 1e-7, "hopeless", 1e-6, "hopeless", "clean", "hopeless")
 CYCLE_PATTERN = ("clean", 1e-8, 1e-7, 1e-6, "hopeless")

@@ -70,7 +70,7 @@ bound at most CAP of S_p = (1 / 2n) sum |G| |dK / dtheta_p| AND at most 1e-6 of 
 
 Input sets: the recipe of make_inputs (X uniform in the unit cube, l = c sqrt(D) (0.5 .. 1.5), os = 1.3, noise 1e-2 or 1e-3, a smooth
 standardised y), ragged_counts(N) = N, N - 1, a multiple of 16, 1, 0 dealt to the tasks in turn (clamped at N for N < 16).  #CUs = 256.
-Fit shapes, the smallest at which the kernels branch (fit_common, scaml_fit_max_d, the blocked dispatch of csrc/scaml_host.cpp):
+Fit shapes, the smallest at which the kernels branch (fit_plan, fit_class_max_d, blocked_plan of csrc/gp_dispatch.h):
   N  1, 2, 15, 16, 17  one and two blocks in the nb = 2 variant;  32 | 33, 64 | 65, 128 | 129 the class edges (nb = 2 | 4 | 8 | 16);
      255, 256 close the fused classes;  272 the first blocked size;  320 | 336 either side of the 4 -> 2 waves-per-workgroup switch of
      the strip kernels that consume the factor (and of `parts == 2 && nbc <= 10` in the blocked dispatch);  512 the limit.  Every
@@ -104,12 +104,13 @@ from collections import namedtuple
 
 import numpy as np
 
+from tests import _dispatch as DP
 from tests import _posterior_bounds as P
 from tests import _target_bounds as TB
 from tests._posterior_bounds import CAP, KIND_MATERN52, KIND_RBF, LD, SENTINEL, U, Quantity, Ratios, _kernel, _S, gamma, inverse_lower, make_inputs, ragged_counts
 from tests._target_bounds import FAMILY, _col, _up, potrf_reference, solve_reference, within
 
-CUS = 256                                                   # compute units of the MI355X: the dispatch thresholds are multiples of it
+CUS = 256                                                   # compute units of the MI355X: the count the cases are chosen for
 LOG_2PI = LD("1.8378770664093454835606594728112353")
 GRAD_CAP_G = 1e-6                                           # second half of the gradient's cap: of the task's largest |g_p|
 FIT_MAX_D = {32: 592, 64: 296, 128: 144, 256: 44}           # scaml_fit_max_d per class (the GPU file asserts them against the library)
@@ -144,16 +145,11 @@ def _f(T, N, D, kind, ragged=None, noise=1e-2, c=0.5, jit=0.0, path=0, refs=None
 
 
 def fit_instance(c: FitCase) -> str:
-    """The kernel instance fit_common / the blocked dispatch sends the case to."""
+    """The kernel instance fit_common / the blocked dispatch sends the case to: the launcher's own plan (tests/_dispatch.py) at CUS."""
     if c.N > 256:
-        return "fit_blocked[launches]" if c.path == 1 else "fit_blocked[coop]"
-    if c.N <= 32:
-        return "fit_fused[nb2,wu1]"
-    if c.N <= 64:
-        return "fit_fused[nb4,wu3]"
-    if c.N <= 128:
-        return "fit_fused[nb8,wu7]" if c.T <= CUS else "fit_fused[nb8,wu3]"
-    return "fit_fused[nb16,wu7]"
+        return "fit_blocked[launches]" if DP.blocked_plan(c.T, c.N, c.D, CUS, mode=c.path).path == 1 else "fit_blocked[coop]"
+    p = DP.fit_plan(c.T, c.N, c.D, CUS)
+    return f"fit_fused[nb{p.nb},wu{p.wu}]"
 
 
 def _fit_shapes():
@@ -428,20 +424,20 @@ def _g(path, T, N, D, kind, ragged=None, noise=1e-2, refs=None):
     return GradCase(path, T, N, D, kind, ragged, noise, refs)
 
 
+GRAD_MODE = {"default": 0, "two": 1, "single": 2}      # a case's path as scaml_debug_force_two_launch_grad's mode
+
+
 def grad_instance(c: GradCase, path=None) -> str:
-    """The kernel instance scaml_mll_backward_f64 sends the case to (csrc/scaml_host.cpp)."""
+    """The kernel instance scaml_mll_backward_f64 sends the case to: the launcher's own plan (grad_plan, csrc/gp_dispatch.h) at CUS."""
     path = path or c.path
     fam = FAMILY[c.kind]
-    if path == "default":
-        single = c.N <= 256 and c.D <= 8 and not (c.N > 64 and c.T <= 64)
-        return "default->" + grad_instance(c, "single" if single else "two")
-    if path == "two":
-        return f"mllgrad[{fam}]"
-    sc = 0 if c.N <= 32 else (1 if c.N <= 64 else (2 if c.N <= 128 else 3))
-    dma = int(c.ragged is None and c.N % 16 == 0)
-    if sc == 3 and dma and 2 * c.T <= CUS:
-        return f"mllgrad_split[1][{fam}][0]"
-    return f"mllgrad_fused[{sc}][{fam}][{dma}]"
+    p = DP.grad_plan(c.T, c.N, c.D, CUS, mode=GRAD_MODE[path], ragged=c.ragged is not None)      # (the backends' buffers are 16-byte aligned)
+    pre = "default->" if path == "default" else ""
+    if not p.single:
+        return f"{pre}mllgrad[{fam}]"
+    if p.split > 1:
+        return f"{pre}mllgrad_split[{p.sc - 2}][{fam}][{0 if p.split == 2 else 1}]"
+    return f"{pre}mllgrad_fused[{p.sc}][{fam}][{p.dma}]"
 
 
 # single-launch ragged sets: T = 4, ragged = 4 -> counts 0, N, N - 1, a multiple of 16 (no single point, see the header)
@@ -482,7 +478,7 @@ def grad_reference(c: GradCase, inp, fit, t, form):
         Lfull[:n, :n] = Ln
         q = solve_reference(Lfull, np.eye(N), n)
         Kinv, E_Kinv = q.ref[:n, :n], q.bound[:n, :n]
-        NP = 16 * (2 if N <= 32 else (4 if N <= 64 else (8 if N <= 128 else 16)))
+        NP = 16 * (2 << DP.fit_class(N))
         m = NP + 32
     else:
         Li = inverse_lower(Ln)

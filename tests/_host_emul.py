@@ -12,9 +12,10 @@ CSRC = os.path.join(ROOT, "scalable-meta-learning-with-gaussian-processes_amd", 
 DP, IP, BP = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8)
 
 
-def build(tmp_path_factory, name: str) -> ctypes.CDLL:
-    """tests/host_emul/<name>.cpp -> a shared object in a temporary directory, loaded."""
-    so = str(tmp_path_factory.mktemp("emul") / (name + ".so"))
+def build(tmp_path_factory, name: str, out_dir=None) -> ctypes.CDLL:
+    """tests/host_emul/<name>.cpp -> a shared object in a temporary directory (or in out_dir, for a module that builds once outside
+    a fixture), loaded."""
+    so = os.path.join(out_dir, name + ".so") if out_dir else str(tmp_path_factory.mktemp("emul") / (name + ".so"))
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-I", CSRC,
                     os.path.join(ROOT, "tests", "host_emul", name + ".cpp"), "-o", so], check=True)
     return ctypes.CDLL(so)

@@ -84,6 +84,7 @@ from collections import namedtuple
 import numpy as np
 
 from tests import _fit_bounds as FB
+from tests._dispatch import target_fit_plan
 from tests._fit_bounds import GRAD_CAP_G, LOG_2PI, grad_within
 from tests._posterior_bounds import CAP, KIND_MATERN52, KIND_RBF, LD, SENTINEL, U, Quantity, Ratios, _kernel, _S, gamma, inverse_lower
 from tests._target_bounds import FAMILY, within
@@ -392,9 +393,10 @@ def assert_caps(label, ref: Ref):
         f"{label}: gradient caps, bound / S_p {float((ref.E_grad / ref.S_grad).max()):.3e}, bound / max |g| {float((ref.E_grad / gmax).max()):.3e}")
 
 
-def device_path(n):
-    """The factorisation the device's dispatch takes by shape (every shape here fits the matrix-core footprint up to n = 112)."""
-    return "mfma" if n <= 112 else "col"
+def device_path(n, T, D, forced=False):
+    """The factorisation the launcher's plan takes (forced: through scaml_debug_target_fit_path(1)).  By shape every set here fits the
+    matrix-core footprint up to n = 112, which tests/test_target_fit_bounds.py asserts."""
+    return "mfma" if target_fit_plan(n, T, D, mode=1 if forced else 0).use_mfma else "col"
 
 
 def resolve(be, c: Case) -> Case:

@@ -9,6 +9,7 @@ import torch
 
 from oracle import gp_oracle as O
 from scamlgp_amd import _lib, ops
+from tests._dispatch import blocked_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -35,13 +36,15 @@ def _took():
 
 
 def test_path_choice_by_shape(device):
-    """Default: the one-launch kernel while a task can have three workgroups (two for N <= 320), the sequence of launches beyond."""
+    """Default: the one-launch kernel while a task can have three workgroups (two for N <= 320), the sequence of launches beyond;
+    and the path taken is the one the launcher's plan (tests/_dispatch.py) names for the shape on this device."""
     cus = torch.cuda.get_device_properties(device).multi_processor_count
     kind = O.KIND_MATERN52
     for T, N, want in [(2, 512, 2), (cus // 3, 512, 2), (cus // 2, 512, 1), (cus // 2, 320, 2), (cus // 2 + 8, 320, 1)]:
         X, y, theta = (t.to(device) for t in _stack(T, N, 3, T + N))
         out = ops.gp_fit_fused(X, y, theta, kind)
         assert _took() == want, (T, N)
+        assert _took() == blocked_plan(T, N, 3, cus).path, (T, N)
         assert not out["info"].cpu().any()
 
 

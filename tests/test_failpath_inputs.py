@@ -13,6 +13,7 @@ import torch
 
 from oracle import gp_oracle as O
 from tests import _failpath_cases as C
+from tests._dispatch import fit_plan
 
 KINDS = [O.KIND_RBF, O.KIND_MATERN52]
 U = 2.0 ** -53
@@ -83,6 +84,17 @@ def test_fit_stacks(N, NB, T, part, kind):
     for t, s in enumerate(case["plan"]):
         if s["what"] == "rescued":
             assert float(torch.linalg.cond(C.task_matrix_fit(case, t, s["rung"]))) < 5.0
+
+
+@pytest.mark.parametrize("name", list(C.INSTANCES))
+def test_name_is_the_instance_the_launcher_picks(name):
+    """At the 256 CUs the CPU shapes are chosen for, the launcher's plan for (T, N) is the instance the name and NB say, and the narrow
+    stack is one task past the last the wide instance takes."""
+    N, T, NB = C.INSTANCES[name]
+    p = fit_plan(T or C.NARROW_T_CPU, N, 1, 256)
+    assert p.nb == NB and name.startswith(f"nb{p.nb}_wu{p.wu}"), (name, p)
+    if T is None:
+        assert C.NARROW_T_CPU == 257 and fit_plan(C.NARROW_T_CPU - 1, N, 1, 256)[1:3] == (8, 7)
 
 
 @pytest.mark.parametrize("name", list(C.INSTANCES))

@@ -14,6 +14,7 @@ import torch
 from oracle import gp_oracle as O
 from scamlgp_amd import ops
 from tests import _failpath_cases as C
+from tests._dispatch import narrow_fit_tasks
 
 pytestmark = pytest.mark.gpu
 
@@ -55,10 +56,8 @@ def _idx(case, *what):
 
 
 def _narrow_T(device):
-    cus = torch.cuda.get_device_properties(device).multi_processor_count
-    T = cus + 1
-    assert T > cus   # fit_common takes the four-wave (8, 3) instance only for stacks larger than the CU count
-    return T
+    """The smallest stack the launcher's plan sends to the four-wave (8, 3) instance on this device (asserted there)."""
+    return narrow_fit_tasks(torch.cuda.get_device_properties(device).multi_processor_count, N=C.INSTANCES[NARROW][0])
 
 
 def _narrow_sample(plan_):

@@ -8,31 +8,26 @@ Per case: L, alpha, MLL and logdet against the oracle at the tolerances of tests
 test_fit_matches_oracle: north-star tolerances against the reference's formulation, the tight ones against the kernel's
 own distance formulation); two launches agree bit for bit; fit mode and POTRF mode (the same kernel handed the matrix)
 agree on the factor and are each reproducible, the checks of tools/dev_race_check.py."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import gp_oracle as O
 from scamlgp_amd import _lib, ops
+from tests._dispatch import narrow_fit_tasks
 from tests.test_fit_gpu import RTOL_MLL, RTOL_POST, _rel, _stack
 
 pytestmark = pytest.mark.gpu
 
-HOST_CPP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                        "scalable-meta-learning-with-gaussian-processes_amd", "csrc", "scaml_host.cpp")
 D = 3
 
 
 def _narrow_kernel_task_count(device):
     """64 < N <= 128 runs the (8, 3) instance only when the stack has more tasks than the device has CUs; up to that
-    count the launcher takes the wide (8, 7) instance.  The rule is read from the launcher's source so that the test
-    fails, rather than silently testing (8, 7) twice, when it changes."""
-    src = open(HOST_CPP).read()
-    assert re.search(r"if \(vi == 2 && p\.T <= num_cus\(\*m\)\) vi = 4;", src), "the launcher's switch-over rule has changed"
-    return torch.cuda.get_device_properties(device).multi_processor_count + 1
+    count the launcher takes the wide (8, 7) instance.  The count is asked of the launcher's own plan (tests/_dispatch.py)
+    with the device's CU count, which asserts the instance, so that the test fails, rather than silently testing (8, 7)
+    twice, when the rule changes."""
+    return narrow_fit_tasks(torch.cuda.get_device_properties(device).multi_processor_count, N=128, D=D)
 
 
 # (instance, N, tasks, blocked): tasks None = just above the launcher's switch-over count

@@ -291,7 +291,9 @@ def test_dispatch_by_shape_is_by_n_alone_on_these_sets(emul):
     f = emul.lib.emul_target_fit_problem_lds_doubles
     shapes = [(c.n, c.T, c.D) for c in TF.CASES + TF.NAN_CASES + TF.REFIT_CASES if c.n] + [(n, TF.RAGGED["T"], TF.RAGGED["D"]) for n in TF.RAGGED["sizes"]]
     for n, T, D in shapes:
-        assert (f(n, T, D, 8, 1) != f(n, T, D, 8, 0)) == (TF.device_path(n) == "mfma"), (n, T, D)
+        path = TF.device_path(n, T, D)
+        assert (path == "mfma") == (n <= 112), (n, T, D)
+        assert (f(n, T, D, 8, 1) != f(n, T, D, 8, 0)) == (path == "mfma"), (n, T, D)
         assert f(n, T, D, 8, 1) * 8 <= LDS_LIMIT
 
 
@@ -307,7 +309,7 @@ def test_caps_hold_for_the_device_on_every_input_set(emul):
         for s, n in enumerate(TF.RAGGED["sizes"]):
             prob = TF.make_problem(n, TF.RAGGED["T"], TF.RAGGED["D"], kind, seed=5 + s)
             for b, z in enumerate(TF.starts(prob, 2, seed=5)):
-                TF.assert_caps(f"ragged n{n} kind {kind} start {b}", TF.reference(prob, z, TF.device_path(n), TF.DEVICE_ARITH))
+                TF.assert_caps(f"ragged n{n} kind {kind} start {b}", TF.reference(prob, z, TF.device_path(n, TF.RAGGED["T"], TF.RAGGED["D"]), TF.DEVICE_ARITH))
 
 
 @pytest.mark.parametrize("kind", [KIND_RBF, KIND_MATERN52])

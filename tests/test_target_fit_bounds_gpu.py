@@ -37,7 +37,7 @@ class Device:
 
     def path_of(self, n, T, D, forced):
         """(tests/test_target_fit_bounds.py checks target_fit_mfma_shape for every n <= 112 of the input sets)"""
-        return "col" if forced else TF.device_path(n)
+        return TF.device_path(n, T, D, forced)
 
     @property
     def stream(self):
