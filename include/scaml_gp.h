@@ -597,6 +597,66 @@ int scaml_target_train_block_batched_f64(const double* means_t, const double* co
                                          const uint8_t* active, const double* theta, int G, int n_max, int T, int D, int kind, double* Knn,
                                          double* resid, void* stream);
 
+/*
+ * (7k) (7g) and (7i) for studies of which some hold PENDING evaluations (scamlgp_amd.bo.ScaMLGPBOStudies with pending_mode="batched"):
+ * such a study is a fantasy model as in (7f) -- its training block holds the pending inputs too (n_g counts them), and UCB / EI are
+ * averaged over its F_g sampled outcomes, which differ in alpha only.  The arguments are (7g)'s / (7i)'s with `alpha` replaced by
+ *   alpha_f (G, n_max, F_max): row a of study g holds its F_g values Knn^-1 [resid_0 .. resid_{F_g - 1}][a] contiguously (the (n, F)
+ *       layout of (7f), row stride F_max);  n_fant (G) int32, 1 <= F_g <= F_max;  F_max >= 1.
+ * Per right-hand side, with Knq, dKnq, z = Knn^-1 Knq, mean_q, var_q, S_mu, S_var as (7g) forms them:
+ *   r_f = sum_a Knq[a] alpha_f[a][f],  mu_f = m + s (mean_q + r_f),  vr = s^2 (var_q - Knq . z)  (shared by the fantasies),
+ *   value = (sum_f A(mu_f, vr)) / F_g, and with the chain-rule factors Amu_f, Av_f of A:  abar[a] = sum_f Amu_f alpha_f[a][f],
+ *   grad[d] = ((sum_f Amu_f) S_mu[1 + d] + s sum_a abar[a] dKnq[a][d] + (sum_f Av_f) (S_var[1 + d] - 2 s^2 sum_a z[a] dKnq[a][d])) / F_g.
+ * Every sum is formed by one thread in a fixed order (tasks, training points, fantasies ascending), without atomics: the outputs are
+ * a pure function of the inputs.  A study with F_g == 1 is an ordinary one -- alpha_f[g, :, 0] is its alpha -- and its value and grad are
+ * BIT-IDENTICAL to (7g)'s / (7i)'s: the workgroup takes their statements, so a mixed launch does not perturb the studies that have
+ * nothing pending.  The strip layout gives the value of the query layout bit for bit, as (7i) does of (7g).
+ *   value (Mq); grad (Mq, D) or NULL in the query layout.  No mu_out / var_out: a fantasy model has F_g posterior means.
+ * The refusals are (7g)'s: a padding query (strip) gives zeros; info[g] != 0, n_points[g] outside 1 .. n_max or n_fant[g] outside
+ * 1 .. F_max gives NaN for that study; a query with a NaN or infinite coordinate gives NaN in all of its own outputs; nothing past n_g
+ * or F_g in a study's slices is read.
+ * Checks: (7g)'s / (7i)'s, and F_max < 1 or a NULL alpha_f / n_fant: SCAML_E_BADARG.  Limits: n_max <= 96, D <= 15, F_max <= 64 (all at
+ * once, in both layouts) and the LDS footprint (sa_fantasy_lds_doubles of csrc/gp_studies_acqf.h; alpha_f is read from global memory):
+ * SCAML_E_TOOLARGE beyond them (bad arguments answer first).  Mq == 0 or G == 0: nothing is enqueued.  Neither call synchronises;
+ * every status stays on the device (both can be stream-captured).
+ */
+int scaml_target_fantasy_acqf_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
+                                          const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
+                                          const double* Linv_diag, const double* alpha_f, const int32_t* n_fant, const int32_t* n_points,
+                                          const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int Mq,
+                                          int G, int n_max, int F_max, int T, int D, int kind, int acqf, double* value, double* grad,
+                                          void* stream);
+int scaml_target_fantasy_score_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
+                                           const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
+                                           const double* Linv_diag, const double* alpha_f, const int32_t* n_fant, const int32_t* n_points,
+                                           const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int Mq,
+                                           int G, int n_max, int F_max, int T, int D, int kind, int acqf, double* value, void* stream);
+
+/*
+ * (7l) (7h) on (7k)'s block: the acquisition optimiser of many studies' start points where studies may hold pending evaluations.  The
+ * same rounds of { grouped GRAD source pass, acquisition launch ((7k) in the query layout), optimiser step }, the same step kernel,
+ * workspace (scaml_studies_acqf_opt_workspace_bytes) and state layout, the same flags, outputs and stats as (7h).
+ * The source pass of a round is (5e) / (5e') in an instantiation of its own that adds the waves' shares of a mean and of a variance in
+ * wave order instead of with LDS float atomics: with (7k) and the step kernel every round is then a pure function of the state, and
+ * x, f and stats do not depend on how the rounds are divided among calls, BIT FOR BIT ((7h) is chunking-independent only within the
+ * run-to-run scatter of its pass).
+ *   alpha_f, n_fant, F_max: as (7k) takes them, in place of (7h)'s alpha_t; n_points_t counts the pending inputs of a study, which
+ *       are the last rows of its slice of Xt and columns of VA_tab[g].
+ *   task_base (G) int32 / Tsrc: as (7h') takes them; task_base == NULL: every study reads the same source stack (Tsrc is ignored), as
+ *       (7h) -- one entry serves both.
+ * Checks and limits: those of (7h) / (7h') and (7k), bad arguments first, everything before the first launch.  B == 0 or G == 0:
+ * nothing is enqueued.  Does not synchronise.
+ */
+int scaml_studies_fantasy_acqf_opt_f64(const double* x0, const int32_t* group, const double* const* VA_tab, const double* X, const double* theta_s,
+                                       const double* Linv, const double* alpha_s, const double* y_mean, const double* y_std,
+                                       const int32_t* n_points_s, const double* w, const uint8_t* active, const double* Xt,
+                                       const double* theta_t, const double* L, const double* Linv_diag, const double* alpha_f,
+                                       const int32_t* n_fant, const int32_t* n_points_t, const double* m_all, const double* s_all,
+                                       const int32_t* info, const double* acqf_param, int B, int G, int n_max, int F_max, int T, int N, int D,
+                                       int kind_s, int kind_t, int acqf, const double* lo, const double* hi, int max_iter, int history, int max_ls,
+                                       double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace, double* x, double* f,
+                                       int32_t* stats, const int32_t* task_base, int Tsrc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,9 +169,14 @@ struct PosteriorArgs<true> {
 // GROUPED without GRAD (scaml_posterior_linv_grouped_f64 and its OWN twin): a strip holds 16 DIFFERENT query points of one
 // group -- the raw candidates of a study's stage 1 --, the group table has one entry per strip, and the outputs are the value layout
 // mu / var (T, Mq), cov (T, Ma_max, Mq).  Nothing else differs: the group is still uniform per workgroup.
-template <int KIND, bool COV, bool GRAD, bool GROUPED = false, bool OWN = false>
+// DET (the rounds of scaml_studies_fantasy_acqf_opt_f64): the waves' shares of a mean and of a variance are laid side by side in LDS
+// and added in wave order by one thread per column instead of with LDS float atomics, whose order of arrival differs from run to run:
+// mu and var are then a pure function of the inputs, like cov, and an optimisation does not depend on how its rounds are chunked.  An
+// instantiation of its own: the other passes keep their instruction streams.
+template <int KIND, bool COV, bool GRAD, bool GROUPED = false, bool OWN = false, bool DET = false>
 __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename PosteriorArgs<GROUPED>::type pp) {
   static_assert(!GROUPED || COV, "the grouped pass comes with its covariance block");
+  static_assert(!DET || (GROUPED && GRAD), "the ordered sums are built for the grouped GRAD pass");
   static_assert(!OWN || GROUPED, "per-group source tasks belong to the grouped pass");
   const PosteriorParams& p = PosteriorArgs<GROUPED>::base(pp);
   // eight waves share one K_*^T strip (the row blocks are dealt 8 ways: twice the waves per byte of LDS to hide the L^-1 segment loads)
@@ -324,7 +329,18 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
     }
   }
   mean_part = sum_lane_groups(mean_part);
-  if (lq == 0) __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double*)(red + lc), mean_part);
+  if constexpr (DET) {
+    __shared__ double shares[NW * 16];
+    if (lq == 0) shares[wave * 16 + lc] = mean_part;
+    __syncthreads();
+    if (tid < 16) {
+      double sum = 0.0;
+      for (int w = 0; w < NW; ++w) sum += shares[w * 16 + tid];
+      red[tid] = sum;
+    }
+  } else {
+    if (lq == 0) __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double*)(red + lc), mean_part);
+  }
   __syncthreads();
 
   // ---- phase 2: V = L^-1 K_*^T by row blocks, the variance on the fly
@@ -386,7 +402,18 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
       }
     }
     var_part = sum_lane_groups(var_part);
-    if (lq == 0) __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double*)(red + 16 + lc), var_part);
+    if constexpr (DET) {
+      __shared__ double shares[NW * 16];
+      if (lq == 0) shares[wave * 16 + lc] = var_part;
+      __syncthreads();
+      if (tid < 16) {
+        double sum = 0.0;
+        for (int w = 0; w < NW; ++w) sum += shares[w * 16 + tid];
+        red[16 + tid] = sum;
+      }
+    } else {
+      if (lq == 0) __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double*)(red + 16 + lc), var_part);
+    }
     __syncthreads();
   }
   if (tid < 16 && qc < M) {
@@ -717,6 +744,10 @@ template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, true>(sc
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, true>(scaml::PosteriorGroupedParams);
 template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, true, true>(scaml::PosteriorGroupedParams);   // (5e')
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, true, true>(scaml::PosteriorGroupedParams);
+template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, true, false, true>(scaml::PosteriorGroupedParams);   // (7l)'s rounds
+template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, true, false, true>(scaml::PosteriorGroupedParams);
+template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, true, true, true>(scaml::PosteriorGroupedParams);
+template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, true, true, true>(scaml::PosteriorGroupedParams);
 template __global__ void scaml::gp_posterior_linv_kernel<0, true, false, true>(scaml::PosteriorGroupedParams);   // (5f)
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, false, true>(scaml::PosteriorGroupedParams);
 template __global__ void scaml::gp_posterior_linv_kernel<0, true, false, true, true>(scaml::PosteriorGroupedParams);   // (5f')

@@ -13,7 +13,13 @@
 //   UCB / EI and their chain rule with the clamps of scamlgp_amd/utils.py (sa_acquisition, which csrc/gp_fantasy.hip calls for F fantasies).
 // Every sum runs in a fixed order (tasks ascending, training points ascending) by ONE thread per output: no atomics, no wave
 // reductions, so the result is a pure function of the inputs and the host build computes what the device computes.
+//
+// Studies with pending evaluations (include/scaml_gp.h (7k)): the block's argument type is the second template parameter.  With
+// StudiesFantasyParams a group is a fantasy model (ScaMLGP.fantasize) of F_g fantasies: phases 1 and 2 are the text above, the alpha
+// load, phase 3 and phase 4 differ at `if constexpr (FANT)`, where UCB / EI are averaged over the group's columns of alpha_f with
+// (7f)'s formula (sa_fantasy_tail).  A group with F_g == 1 takes the statements of the ordinary block.
 #pragma once
+#include <type_traits>
 #include "gp_studies_formulas.h"   // SA_DEV / SA_SYNC, sa_kernel_and_slope, sa_acquisition
 
 namespace scaml {
@@ -47,6 +53,15 @@ struct StudiesAcqfParams {
   int Mq, G, n_max, T, D, kind, acqf, pad_;
 };
 
+// The block of a launch in which studies hold pending evaluations: (7g)'s block and, per group, the F_g columns of alpha that its
+// fantasies differ in.  `alpha` of the base block is not read.
+constexpr int STUDIES_FANTASY_MAX_F = 64;   // fantasies per study (csrc/gp_fantasy_params.h has the same limit for (7f))
+struct StudiesFantasyParams : StudiesAcqfParams {
+  const double* alpha_f;      // (G, n_max, F_max) Knn^-1 [resid_0 .. resid_{F_g - 1}]: row a of group g holds its F_g values contiguously
+  const int32_t* n_fant;      // (G) 1 <= F_g <= F_max; 1: an ordinary model, alpha_f[g, :, 0] is its alpha
+  int F_max, pad2_;
+};
+
 // LDS of one block of R right-hand sides, in doubles:
 //   C [n_max][16] | S_mu, S_var [32] | u, v [2][np * R] | alpha [np] | W [nb][256] | L [n_max][n_max | 1] | red [R == 1 ? 48 : 32]
 template <int R>
@@ -55,6 +70,17 @@ constexpr size_t sa_lds_doubles(int n_max) {
   return (size_t)n_max * 16 + 32 + 2 * np * R + np + nb * 256 + (size_t)n_max * (size_t)(n_max | 1) + (R == 1 ? 48 : 32);
 }
 constexpr size_t studies_acqf_lds_doubles(int n_max) { return sa_lds_doubles<1>(n_max); }
+// ... and of a block with fantasies: the above, then (alpha_f stays in global memory: at n_max = 96, F_max = 64 it alone is 6,144 doubles)
+//   R == 1:  A, Amu, Av [3][F_max] | abar [np] | sum_f A, Amu, Av [4]        R == 16:  r_f, then A_f [16][F_max]
+template <int R>
+constexpr size_t sa_fantasy_lds_doubles(int n_max, int F_max) {
+  const size_t np = ((size_t)(n_max + 15) / 16) * 16;
+  return sa_lds_doubles<R>(n_max) + (R == 1 ? 3 * (size_t)F_max + np + 4 : 16 * (size_t)F_max);
+}
+
+// a count of fantasies outside 1 .. F_max turns the group's outputs into NaN; the ordinary block has none to refuse
+SA_DEV bool sa_fantasies_refused(const StudiesAcqfParams&, int) { return false; }
+SA_DEV bool sa_fantasies_refused(const StudiesFantasyParams& p, int F) { return F < 1 || F > p.F_max; }
 
 // One block `blk` of R right-hand sides of one study by `nthr` cooperating threads (thread `tid`; SA_SYNC between the phases).
 // `lds`: sa_lds_doubles<R>(n_max).  The two instantiations are the two layouts of the grouped source pass:
@@ -63,9 +89,13 @@ constexpr size_t studies_acqf_lds_doubles(int n_max) { return sa_lds_doubles<1>(
 //   R = 16  a strip of 16 candidates in the value layout: mu, var (T, Mq), cov (T, n_max, Mq), group (Mq / 16) per strip, Mq a
 //           multiple of 16.  The 16 columns of C are 16 right-hand sides against ONE copy of the factor; `grad` is not used.
 // Either way a block owns 16 consecutive columns of a source row and C is [a][16]; element e of an [.][R] array is (e / R, e % R).
-template <int R>
-SA_DEV void sa_block(const StudiesAcqfParams& p, double* lds, int blk, int tid, int nthr) {
+// `Params`: StudiesAcqfParams, or StudiesFantasyParams (`lds`: sa_fantasy_lds_doubles<R>(n_max, F_max)) -- the sites that differ are
+// the refusal of a bad F_g, the alpha load and, for a group with F_g > 1, phases 3 and 4.
+template <int R, class Params>
+SA_DEV void sa_block(const Params& p, double* lds, int blk, int tid, int nthr) {
   static_assert(R == 1 || R == 16, "a query point with its gradient columns, or a strip of 16 candidates");
+  constexpr bool FANT = std::is_same<Params, StudiesFantasyParams>::value;
+  static_assert(FANT || std::is_same<Params, StudiesAcqfParams>::value, "one of the two argument blocks");
   const int D = p.D, T = p.T, n_max = p.n_max;
   const int g = p.group[blk];
   const size_t q0 = (size_t)blk * R;   // the block's first output
@@ -82,7 +112,9 @@ SA_DEV void sa_block(const StudiesAcqfParams& p, double* lds, int blk, int tid, 
     return;
   }
   const int n = p.n_points[g];
-  if (p.info[g] != 0 || n < 1 || n > n_max) {
+  [[maybe_unused]] int F = 1;   // the group's fantasies, 1 .. F_max
+  if constexpr (FANT) F = p.n_fant[g];
+  if (p.info[g] != 0 || n < 1 || n > n_max || sa_fantasies_refused(p, F)) {
     for (int c = tid; c < R; c += nthr) {
       p.value[q0 + c] = nan;
       if (p.mu_out) p.mu_out[q0 + c] = nan;
@@ -143,7 +175,12 @@ SA_DEV void sa_block(const StudiesAcqfParams& p, double* lds, int blk, int tid, 
     }
     const double* Wg = p.Linv_diag + (size_t)g * nbm * 256;
     for (int e = tid; e < nb * 256; e += nthr) Wd[e] = Wg[e];
-    for (int a = tid; a < n; a += nthr) al[a] = p.alpha[(size_t)g * n_max + a];
+    if constexpr (FANT) {   // column 0: all there is of a group with F_g == 1 (a group with more reads alpha_f where it is, not `al`)
+      if (F == 1)
+        for (int a = tid; a < n; a += nthr) al[a] = p.alpha_f[((size_t)g * n_max + a) * p.F_max];
+    } else {
+      for (int a = tid; a < n; a += nthr) al[a] = p.alpha[(size_t)g * n_max + a];
+    }
   }
   SA_SYNC();
   // ---- phase 1b: the target kernel's part of Knq and (R = 1) of its input gradient, one slope evaluation per (training point, rhs)
@@ -202,6 +239,109 @@ SA_DEV void sa_block(const StudiesAcqfParams& p, double* lds, int blk, int tid, 
     }
     SA_SYNC();
   }
+  // ---- phases 3 and 4 of a fantasy model with F > 1 fantasies (uniform over the workgroup): (7f)'s formula on this block's Knq, dKnq
+  // and z.  Every sum by one thread, a ascending, f ascending:
+  //   r_f = sum_a alpha_f[a][f] Knq[a],  mu_f = fma(s, mean_q + r_f, m),  vr = s^2 (var_q - Knq . z),  (A_f, Amu_f, Av_f) = sa_acquisition
+  //   value = (sum_f A_f) / F;  R = 1: sAmu = sum_f Amu_f, sAv = sum_f Av_f, abar[a] = sum_f Amu_f alpha_f[a][f],
+  //   gm[d] = sum_a abar[a] dKnq[a][d], gv[d] = sum_a z[a] dKnq[a][d],
+  //   grad[d] = fma(sAv, fma(-2 s^2, gv[d], S_var[1 + d]), fma(s, gm[d], sAmu S_mu[1 + d])) / F
+  if constexpr (FANT) {
+    if (F > 1) {
+      const int Fm = p.F_max, nr = R * F;
+      const double* af = p.alpha_f + (size_t)g * n_max * Fm;   // row a at af + a * Fm, read where it is: columns f < F of rows a < n
+      double* fA = red + (R == 1 ? 48 : 32);   // [c][F]: r_f, then A_f
+      double* fAmu = fA + Fm;                  // (R = 1) [F]
+      double* fAv = fAmu + Fm;                 //         [F]
+      double* abar = fAv + Fm;                 //         [np]
+      double* fsum = abar + np;                //         sum_f A_f | Amu_f | Av_f
+      // phase 3: fA[c][f] = r_f of right-hand side c, eight rows of alpha_f in flight (consecutive threads, consecutive f);
+      // red[R + c] = Knq . z; R = 1: red[18 + d] = sum_a z_a dKnq[a][d]
+      for (int o = tid; o < nr + R + (R == 1 ? D : 0); o += nthr) {
+        if (o < nr) {
+          const int c = o / F, f = o - c * F;
+          double acc = 0.0;
+          for (int a0 = 0; a0 < n; a0 += 8) {
+            double av[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) av[k] = a0 + k < n ? af[(size_t)(a0 + k) * Fm + f] : 0.0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+              if (a0 + k < n) acc = fma(av[k], C[(size_t)(a0 + k) * 16 + c], acc);
+          }
+          fA[o] = acc;
+        } else {
+          const int og = o - nr;   // R = 16: the right-hand side; R = 1: 0 for Knq . z, 1 + d for the gradient column d
+          const int c = R == 1 ? 0 : og, col = og;
+          double acc = 0.0;
+          for (int a = 0; a < n; ++a) acc = fma(u[a * R + c], C[(size_t)a * 16 + col], acc);
+          red[R == 1 ? (og == 0 ? 1 : 17 + og) : R + c] = acc;
+        }
+      }
+      SA_SYNC();
+      // phase 4a: one thread per (right-hand side, fantasy)
+      const double par = p.acqf_param[g];
+      for (int e = tid; e < nr; e += nthr) {
+        const int c = e / F;
+        const double mean_q = (Ssum[c] - m) / s, var_q = Ssum[16 + c] * inv_s2 + os;
+        const double mu = fma(s, mean_q + fA[e], m);
+        const double vr = s2 * (var_q - red[R + c]);
+        double A, Amu, Av;
+        sa_acquisition(p.acqf, par, mu, vr, A, Amu, Av);
+        fA[e] = A;
+        if constexpr (R == 1) {
+          fAmu[e] = Amu;
+          fAv[e] = Av;
+        }
+      }
+      SA_SYNC();
+      // phase 4b: the averages, one thread per right-hand side; R = 1 with a gradient: and one per training point for abar
+      for (int e = tid; e < (R == 1 ? 1 + (p.grad ? n : 0) : R); e += nthr) {
+        if (R == 16 || e == 0) {
+          const int c = R == 1 ? 0 : e;
+          double sA = 0.0;
+          for (int f = 0; f < F; ++f) sA += fA[c * F + f];
+          if constexpr (R == 1) {
+            double sAmu = 0.0, sAv = 0.0;
+            for (int f = 0; f < F; ++f) sAmu += fAmu[f];
+            for (int f = 0; f < F; ++f) sAv += fAv[f];
+            fsum[0] = sA;
+            fsum[1] = sAmu;
+            fsum[2] = sAv;
+          }
+          double bad = 0.0;   // (the rule of phase 4 below: a NaN / inf coordinate makes every output of THAT point NaN)
+          for (int d = 0; d < D; ++d) {
+            const double x = p.Xq[(q0 + c) * D + d];
+            bad += x - x;
+          }
+          p.value[q0 + c] = bad == 0.0 ? sA / F : bad;
+        } else {
+          const int a = e - 1;
+          double acc = 0.0;
+          for (int f = 0; f < F; ++f) acc = fma(fAmu[f], af[(size_t)a * Fm + f], acc);
+          abar[a] = acc;
+        }
+      }
+      if constexpr (R == 1) {
+        if (p.grad) {
+          SA_SYNC();
+          // phase 4c: one thread per input dimension
+          for (int o = tid; o < D; o += nthr) {
+            double gm = 0.0;
+            for (int a = 0; a < n; ++a) gm = fma(abar[a], C[(size_t)a * 16 + 1 + o], gm);
+            double bad = 0.0;
+            for (int d = 0; d < D; ++d) {
+              const double x = p.Xq[q0 * D + d];
+              bad += x - x;
+            }
+            const double dmu = fma(s, gm, fsum[1] * Ssum[1 + o]);
+            const double dvar = fma(-2.0 * s2, red[18 + o], Ssum[17 + o]);
+            p.grad[q0 * D + o] = bad == 0.0 ? fma(fsum[2], dvar, dmu) / F : bad;
+          }
+        }
+      }
+      return;
+    }
+  }
   // ---- phase 3: the contractions over the training points, one thread per output, a = 0 .. n-1 in order
   //   red[c] = Knq . alpha, red[R + c] = Knq . z; R = 1: red[2 + d] = sum_a alpha_a dKnq[a][d], red[18 + d] = sum_a z_a dKnq[a][d]
   for (int o = tid; o < 2 * R + (R == 1 ? 2 * D : 0); o += nthr) {
@@ -248,5 +388,9 @@ SA_DEV void sa_block(const StudiesAcqfParams& p, double* lds, int blk, int tid, 
 
 // One query point (7g): the R = 1 instantiation.
 SA_DEV void sa_query(const StudiesAcqfParams& p, double* lds, int q, int tid, int nthr) { sa_block<1>(p, lds, q, tid, nthr); }
+
+// The same two layouts for studies with pending evaluations (7k): a query point, a strip of 16 candidates.
+SA_DEV void sa_fantasy_query(const StudiesFantasyParams& p, double* lds, int q, int tid, int nthr) { sa_block<1>(p, lds, q, tid, nthr); }
+SA_DEV void sa_fantasy_strip(const StudiesFantasyParams& p, double* lds, int strip, int tid, int nthr) { sa_block<16>(p, lds, strip, tid, nthr); }
 
 }  // namespace scaml

@@ -37,6 +37,8 @@ void set_error(const char* what, hipError_t e) {
 }
 
 constexpr size_t kLdsLimit = scaml::LDS_LIMIT;
+// static LDS of the grouped GRAD pass with ordered sums (DET of csrc/gp_posterior.hip): the eight waves' shares of 16 means and of 16 variances
+constexpr size_t kOrderedSumsLds = 2 * 8 * 16 * sizeof(double);
 
 bool valid_kind(int kind) { return kind == SCAML_KIND_RBF || kind == SCAML_KIND_MATERN52; }
 
@@ -69,8 +71,10 @@ struct Module {
   hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {};   // value only; value + gradient per kind
   hipFunction_t post_linv_grouped[2] = {}, tgt_acqf_batched = nullptr;   // lock-step studies: grouped GRAD pass, batched acquisition
   hipFunction_t post_linv_grouped_own[2] = {};                           // the grouped pass with per-group source tasks
+  hipFunction_t post_linv_grouped_det[2] = {}, post_linv_grouped_det_own[2] = {};   // the GRAD grouped pass with ordered sums: (7l)'s rounds
   hipFunction_t post_linv_grouped_val[2] = {}, post_linv_grouped_val_own[2] = {};   // the value-only grouped pass (16 candidates per strip)
   hipFunction_t tgt_score_batched = nullptr, tgt_train_block[2] = {};     // studies' stage 1: strip scoring; the training blocks of all studies
+  hipFunction_t tgt_fantasy_acqf_batched = nullptr, tgt_fantasy_score_batched = nullptr;   // both with pending evaluations (7k)
   hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {}, stack_step = nullptr, acqf_opt_step = nullptr;
   hipFunction_t blk_solve[2][2] = {}, blk_syrk[2] = {};   // solve: [kind][D <= 8]
   hipFunction_t mllgrad_fused[4][2][2] = {};   // [size class NBT = 2, 4, 8, 16][kind][LDS-DMA staging]
@@ -89,15 +93,19 @@ struct Module {
     std::vector<KernelRow> rows = {
         {post, "_ZN5scaml19gp_posterior_kernelILi%dEEEvNS_15PosteriorParamsE", kLdsLimit, {K}},
         {post_cov, "_ZN5scaml23gp_posterior_cov_kernelILi%dEEEvNS_18PosteriorCovParamsE", 0, {K}},
-        {post_linv, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_cov, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped_val, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped_val_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb0ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_cov, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_det, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit - kOrderedSumsLds, {K}},   // (static LDS: the waves' shares)
+        {post_linv_grouped_det_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit - kOrderedSumsLds, {K}},   // (static LDS: the waves' shares)
+        {post_linv_grouped_val, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_val_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
         {&tgt_acqf_batched, "scaml_target_acqf_batched_kernel", kLdsLimit, {}},
         {&tgt_score_batched, "scaml_target_score_batched_kernel", kLdsLimit, {}},
+        {&tgt_fantasy_acqf_batched, "scaml_target_fantasy_acqf_batched_kernel", kLdsLimit, {}},
+        {&tgt_fantasy_score_batched, "scaml_target_fantasy_score_batched_kernel", kLdsLimit, {}},
         {&tgt_train_block[0], "scaml_target_train_block_rbf_kernel", 0, {}},
         {&tgt_train_block[1], "scaml_target_train_block_matern_kernel", 0, {}},
         {&wsum, "scaml_weighted_task_sum_kernel", 0, {}},
@@ -721,12 +729,14 @@ int grouped_check(const scaml::PosteriorGroupedParams& p, int kind, bool value, 
   if (scaml::posterior_linv_lds_doubles(b.N, b.D) * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
   return SCAML_OK;
 }
-int grouped_launch(Module& m, scaml::PosteriorGroupedParams& p, int kind, bool value, void* stream) {   // a checked, non-empty block
+// `ordered`: the GRAD pass whose mu / var do not depend on the order in which the waves finish (DET of csrc/gp_posterior.hip)
+int grouped_launch(Module& m, scaml::PosteriorGroupedParams& p, int kind, bool value, void* stream, bool ordered = false) {   // a checked, non-empty block
   const size_t lds = scaml::posterior_linv_lds_doubles(p.base.N, p.base.D) * sizeof(double);
   const unsigned blocks = (unsigned)(((p.base.T + 7) / 8) * 8) * (unsigned)(p.base.M / 16);   // XCD-aware (task, strip) map inside the kernel
   const bool own = p.ga.task_base != nullptr;
   hipFunction_t fn = value ? (own ? m.post_linv_grouped_val_own[kind] : m.post_linv_grouped_val[kind])
                            : (own ? m.post_linv_grouped_own[kind] : m.post_linv_grouped[kind]);
+  if (ordered && !value) fn = own ? m.post_linv_grouped_det_own[kind] : m.post_linv_grouped_det[kind];
   return launch(fn, dim3(blocks), 512, lds, stream, own ? "gp_posterior_linv_grouped_own" : "gp_posterior_linv_grouped", p);
 }
 int grouped_run(scaml::PosteriorGroupedParams p, int kind, bool value, bool own, void* stream) {
@@ -762,6 +772,43 @@ int acqf_run(scaml::StudiesAcqfParams p, bool strips, void* stream) {
   if (p.Mq == 0 || p.G == 0) return SCAML_OK;
   Module* m = ready();
   return m ? acqf_launch(*m, p, strips, stream) : SCAML_E_LAUNCH;
+}
+
+// The same block for studies with pending evaluations (7k): (7g)'s arguments with alpha_f (handed to the base block's check as its
+// `alpha`), n_fant and F_max.
+scaml::StudiesFantasyParams fantasy_block(const scaml::StudiesAcqfParams& base, const double* alpha_f, const int32_t* n_fant, int F_max) {
+  scaml::StudiesFantasyParams p{};
+  static_cast<scaml::StudiesAcqfParams&>(p) = base;
+  p.alpha = alpha_f;
+  p.alpha_f = alpha_f;
+  p.n_fant = n_fant;
+  p.F_max = F_max;
+  return p;
+}
+size_t fantasy_lds_bytes(int n_max, int F_max, bool strips) {
+  return (strips ? scaml::sa_fantasy_lds_doubles<16>(n_max, F_max) : scaml::sa_fantasy_lds_doubles<1>(n_max, F_max)) * sizeof(double);
+}
+int fantasy_check(const scaml::StudiesFantasyParams& p, bool strips) {
+  const int rb = acqf_check(p, strips);
+  if (rb == SCAML_E_BADARG || p.F_max < 1 || !p.alpha_f || !p.n_fant) return SCAML_E_BADARG;
+  if (rb != SCAML_OK || p.F_max > scaml::STUDIES_FANTASY_MAX_F) return SCAML_E_TOOLARGE;
+  if (fantasy_lds_bytes(p.n_max, p.F_max, strips) > kLdsLimit) return SCAML_E_TOOLARGE;
+  return SCAML_OK;
+}
+static_assert(scaml::sa_fantasy_lds_doubles<16>(scaml::STUDIES_ACQF_MAX_N, scaml::STUDIES_FANTASY_MAX_F) * sizeof(double) <= kLdsLimit &&
+                  scaml::sa_fantasy_lds_doubles<1>(scaml::STUDIES_ACQF_MAX_N, scaml::STUDIES_FANTASY_MAX_F) * sizeof(double) <= kLdsLimit,
+              "n_max = 96 with F_max = 64 fits the LDS in both layouts");
+int fantasy_launch(Module& m, scaml::StudiesFantasyParams& p, bool strips, void* stream) {   // a checked, non-empty block
+  const size_t lds = fantasy_lds_bytes(p.n_max, p.F_max, strips);
+  if (strips)
+    return launch(m.tgt_fantasy_score_batched, dim3((unsigned)(p.Mq / 16)), scaml::STUDIES_ACQF_THREADS, lds, stream, "target_fantasy_score_batched", p);
+  return launch(m.tgt_fantasy_acqf_batched, dim3((unsigned)p.Mq), scaml::STUDIES_ACQF_THREADS, lds, stream, "target_fantasy_acqf_batched", p);
+}
+int fantasy_run(scaml::StudiesFantasyParams p, bool strips, void* stream) {
+  if (const int rc = fantasy_check(p, strips)) return rc;
+  if (p.Mq == 0 || p.G == 0) return SCAML_OK;
+  Module* m = ready();
+  return m ? fantasy_launch(*m, p, strips, stream) : SCAML_E_LAUNCH;
 }
 }  // namespace
 
@@ -822,6 +869,30 @@ int scaml_target_score_batched_f64(const double* mu, const double* var, const do
   return acqf_run(scaml::StudiesAcqfParams{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info,
                                            acqf_param, value, nullptr, mu_out, var_out, Mq, G, n_max, T, D, kind, acqf, 0},
                   true, stream);
+}
+
+// ---- (7k) (7g) / (7i) for studies of which some hold pending evaluations: UCB / EI averaged over a study's fantasies
+// (csrc/gp_studies_fantasy.hip) ----
+int scaml_target_fantasy_acqf_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
+                                          const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
+                                          const double* Linv_diag, const double* alpha_f, const int32_t* n_fant, const int32_t* n_points,
+                                          const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int Mq,
+                                          int G, int n_max, int F_max, int T, int D, int kind, int acqf, double* value, double* grad,
+                                          void* stream) {
+  return fantasy_run(fantasy_block(scaml::StudiesAcqfParams{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, nullptr, n_points, m_all,
+                                                            s_all, info, acqf_param, value, grad, nullptr, nullptr, Mq, G, n_max, T, D, kind, acqf, 0},
+                                   alpha_f, n_fant, F_max),
+                     false, stream);
+}
+int scaml_target_fantasy_score_batched_f64(const double* mu, const double* var, const double* cov, const int32_t* group, const double* Xq,
+                                           const double* w, const uint8_t* active, const double* Xt, const double* theta, const double* L,
+                                           const double* Linv_diag, const double* alpha_f, const int32_t* n_fant, const int32_t* n_points,
+                                           const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int Mq,
+                                           int G, int n_max, int F_max, int T, int D, int kind, int acqf, double* value, void* stream) {
+  return fantasy_run(fantasy_block(scaml::StudiesAcqfParams{mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, nullptr, n_points, m_all,
+                                                            s_all, info, acqf_param, value, nullptr, nullptr, nullptr, Mq, G, n_max, T, D, kind, acqf, 0},
+                                   alpha_f, n_fant, F_max),
+                     true, stream);
 }
 
 // ---- (7j) the training blocks Knn / resid of G studies in one launch (csrc/gp_studies_score.hip); (2) factors them together ----
@@ -1095,7 +1166,13 @@ long long scaml_studies_acqf_opt_workspace_bytes(int B, int G, int n_max, int T,
 }
 
 namespace {
-// (7h) and its per-group-source-task form (`own`): only the evaluation launch of a round is handed the table
+// (7h) and its per-group-source-task form (`own`): only the evaluation launch of a round is handed the table.  `fant` non-NULL: (7l),
+// the rounds' acquisition launch is (7k)'s with these fantasy arrays (alpha_t is not read then).
+struct AcqfOptFantasy {
+  const double* alpha_f;
+  const int32_t* n_fant;
+  int F_max;
+};
 int studies_acqf_opt_checked(const double* x0, const int32_t* group, const double* const* VA_tab, const double* X, const double* theta_s,
                              const double* Linv, const double* alpha_s, const double* y_mean, const double* y_std,
                              const int32_t* n_points_s, const double* w, const uint8_t* active, const double* Xt, const double* theta_t,
@@ -1103,7 +1180,8 @@ int studies_acqf_opt_checked(const double* x0, const int32_t* group, const doubl
                              const double* m_all, const double* s_all, const int32_t* info, const double* acqf_param, int B, int G,
                              int n_max, int T, int N, int D, int kind_s, int kind_t, int acqf, const double* lo, const double* hi, int max_iter,
                              int history, int max_ls, double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace,
-                             double* x, double* f, int32_t* stats, bool own, const int32_t* task_base, int Tsrc, void* stream) {
+                             double* x, double* f, int32_t* stats, bool own, const int32_t* task_base, int Tsrc, void* stream,
+                             const AcqfOptFantasy* fant = nullptr) {
   // what is the optimiser's own, and what the workspace layout is sized by
   if (B < 0 || n_max < 1 || T < 1 || D < 1 || n_evals < 0 || max_iter < 0 || max_ls < 1) return SCAML_E_BADARG;
   if (!x0 || !group || !lo || !hi || !workspace || !x || !f || !stats) return SCAML_E_BADARG;
@@ -1120,9 +1198,13 @@ int studies_acqf_opt_checked(const double* x0, const int32_t* group, const doubl
   scaml::StudiesAcqfParams pt{mu, var, cov, live, Xq, w, active, Xt, theta_t, L, Linv_diag, alpha_t, n_points_t, m_all, s_all, info, acqf_param,
                               value, grad, nullptr, nullptr, B, G, n_max, T, D, kind_t, acqf, 0};
   // the arguments and shapes (5e) and (7g) take: both blocks' SCAML_E_BADARG before either's SCAML_E_TOOLARGE
-  const int rs = grouped_check(ps, kind_s, false, own), rt = acqf_check(pt, false);
+  scaml::StudiesFantasyParams pf = fant ? fantasy_block(pt, fant->alpha_f, fant->n_fant, fant->F_max) : scaml::StudiesFantasyParams{};
+  const int rs = grouped_check(ps, kind_s, false, own), rt = fant ? fantasy_check(pf, false) : acqf_check(pt, false);
   if (rs == SCAML_E_BADARG || rt == SCAML_E_BADARG) return SCAML_E_BADARG;
   if (rs != SCAML_OK || rt != SCAML_OK || D > scaml::ACQF_OPT_MAX_D) return SCAML_E_TOOLARGE;
+  // (7l)'s pass keeps the waves' shares in static LDS next to the dynamic block that grouped_check admits (no N within
+  // scaml_posterior_max_n() comes near it today; the rule stands for the day that limit rises)
+  if (fant && scaml::posterior_linv_lds_doubles(N, D) * sizeof(double) > kLdsLimit - kOrderedSumsLds) return SCAML_E_TOOLARGE;
   if (B == 0 || G == 0) return SCAML_OK;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
@@ -1136,8 +1218,9 @@ int studies_acqf_opt_checked(const double* x0, const int32_t* group, const doubl
   }
   for (int r = 0; r < n_evals; ++r) {
     // (Arguments and sizes were checked above, once; only a failing launch can end the call here, with the rounds before it enqueued.)
-    if ((rc = grouped_launch(*m, ps, kind_s, false, stream)) != SCAML_OK) return rc;
-    if ((rc = acqf_launch(*m, pt, false, stream)) != SCAML_OK) return rc;
+    // ((7l): the pass with ordered sums, so that a round is a pure function of the state and chunking cannot change the result)
+    if ((rc = grouped_launch(*m, ps, kind_s, false, stream, fant != nullptr)) != SCAML_OK) return rc;
+    if ((rc = fant ? fantasy_launch(*m, pf, false, stream) : acqf_launch(*m, pt, false, stream)) != SCAML_OK) return rc;
     if ((rc = launch(m->acqf_opt_step, dim3((unsigned)B), 64, 0, stream, "acqf_opt_step", p)) != SCAML_OK) return rc;
   }
   return SCAML_OK;
@@ -1168,6 +1251,23 @@ int scaml_studies_acqf_opt_own_f64(const double* x0, const int32_t* group, const
   return studies_acqf_opt_checked(x0, group, VA_tab, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, w, active, Xt, theta_t, L, Linv_diag,
                                   alpha_t, n_points_t, m_all, s_all, info, acqf_param, B, G, n_max, T, N, D, kind_s, kind_t, acqf, lo, hi,
                                   max_iter, history, max_ls, gtol, ftol, c1, n_evals, flags, workspace, x, f, stats, true, task_base, Tsrc, stream);
+}
+
+// ---- (7l) (7h) / (7h') on (7k)'s block: the studies may hold pending evaluations; task_base NULL: a shared source stack ----
+int scaml_studies_fantasy_acqf_opt_f64(const double* x0, const int32_t* group, const double* const* VA_tab, const double* X, const double* theta_s,
+                                       const double* Linv, const double* alpha_s, const double* y_mean, const double* y_std,
+                                       const int32_t* n_points_s, const double* w, const uint8_t* active, const double* Xt,
+                                       const double* theta_t, const double* L, const double* Linv_diag, const double* alpha_f,
+                                       const int32_t* n_fant, const int32_t* n_points_t, const double* m_all, const double* s_all,
+                                       const int32_t* info, const double* acqf_param, int B, int G, int n_max, int F_max, int T, int N, int D,
+                                       int kind_s, int kind_t, int acqf, const double* lo, const double* hi, int max_iter, int history, int max_ls,
+                                       double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace, double* x, double* f,
+                                       int32_t* stats, const int32_t* task_base, int Tsrc, void* stream) {
+  const AcqfOptFantasy fant{alpha_f, n_fant, F_max};
+  return studies_acqf_opt_checked(x0, group, VA_tab, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, w, active, Xt, theta_t, L, Linv_diag,
+                                  alpha_f, n_points_t, m_all, s_all, info, acqf_param, B, G, n_max, T, N, D, kind_s, kind_t, acqf, lo, hi,
+                                  max_iter, history, max_ls, gtol, ftol, c1, n_evals, flags, workspace, x, f, stats, task_base != nullptr, task_base,
+                                  Tsrc, stream, &fant);
 }
 
 }  // extern "C"

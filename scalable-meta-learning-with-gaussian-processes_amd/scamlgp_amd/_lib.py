@@ -128,6 +128,12 @@ SIGNATURES = {
     "scaml_studies_acqf_opt_f64": (_i, [_dp] * 22 + [_i] * 9 + [_dp, _dp] + [_i] * 3 + [_f] * 3 + [_i, _u] + [_dp] * 4 + [c_void_p]),
     # (7h') (7h)'s arguments; task_base, Tsrc
     "scaml_studies_acqf_opt_own_f64": (_i, [_dp] * 22 + [_i] * 9 + [_dp, _dp] + [_i] * 3 + [_f] * 3 + [_i, _u] + [_dp] * 4 + [_dp, _i, c_void_p]),
+    # (7k) (7g)'s arrays with alpha_f, n_fant for alpha (18); Mq, G, n_max, F_max, T, D, kind, acqf; value, grad -- and (7i)'s likewise: value
+    "scaml_target_fantasy_acqf_batched_f64": (_i, [_dp] * 18 + [_i] * 8 + [_dp] * 2 + [c_void_p]),
+    "scaml_target_fantasy_score_batched_f64": (_i, [_dp] * 18 + [_i] * 8 + [_dp] + [c_void_p]),
+    # (7l) (7h)'s arguments with alpha_f, n_fant for alpha_t and F_max after n_max; task_base (or NULL), Tsrc
+    "scaml_studies_fantasy_acqf_opt_f64": (_i, [_dp] * 23 + [_i] * 10 + [_dp, _dp] + [_i] * 3 + [_f] * 3 + [_i, _u] + [_dp] * 4
+                                           + [_dp, _i, c_void_p]),
     "scaml_debug_target_fit_path": (_i, [_i]),
     "scaml_debug_blocked_fit_path": (_i, [_i]),
     "scaml_debug_coop_far": (_i, [_i]),

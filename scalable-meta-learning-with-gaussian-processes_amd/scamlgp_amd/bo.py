@@ -295,6 +295,15 @@ class ScaMLGPBOStudies:
     factors come from one batched assemble and one batched Cholesky.  The draws, hence the generators' states, are the per-study
     mode's.  ``last_suggest_info["score_mode"]`` names the mode.  Not forwarded to the loops.
 
+    ``pending_mode`` (with ``"lockstep"`` or ``"device"``; ``"sequential"`` refuses ``"batched"``): ``"per_study"`` (default) -- a study
+    with pending evaluations takes its own ``ScaMLGPBOLoop.suggest()``, as described; ``"batched"`` -- it stays in the batch, with both
+    ``score_mode``s: its acquisition function is built on its fantasy model as the single loop builds it (``fantasize`` from its own
+    ``gen``, the set-up of the conditioned model per study), and ``utils.StudiesAcquisition`` evaluates it with the others, UCB / EI
+    averaged over its fantasies (``scaml_target_fantasy_acqf_batched_f64`` and its siblings).  Whether a study stays is decided before
+    its fantasies are drawn: n >= 1, n + p <= 96 and <= the stack's N, D <= 15, ``num_fantasies`` <= 64; any other study falls back as
+    in the default mode.  Per study the order of the draws is the single loop's (fantasies, raw candidates, picks), so the generators
+    end where a ``"per_study"`` twin's do; ``last_suggest_info`` has the keys it always had.  Not forwarded to the loops.
+
     One source stack PER study (the reference's protocol: ``benchmark_cls(seed=study_seed)`` / ``meta_data_seed=study_seed``,
     scamlgp/benchmarking/local_runner.py:51-65, 178-181 -- every study draws its own meta-tasks): ``source_gps`` may be a sequence of S
     dicts, as ``model.meta_fit_scamlgp_studies`` returns them (slices of one stack fitted in one call).  All three modes work: the
@@ -302,14 +311,19 @@ class ScaMLGPBOStudies:
     (``utils.StudiesAcquisition``).  A single dict keeps meaning "shared"."""
 
     def __init__(self, source_gps: Union[Dict[Hashable, SourceGP], Sequence[Dict[Hashable, SourceGP]]], dim: int, num_studies: int,
-                 seeds: Optional[Sequence[int]] = None, suggest_mode: str = "sequential", score_mode: str = "per_study", **loop_kwargs):
+                 seeds: Optional[Sequence[int]] = None, suggest_mode: str = "sequential", score_mode: str = "per_study",
+                 pending_mode: str = "per_study", **loop_kwargs):
         if suggest_mode not in ("sequential", "lockstep", "device"):
             raise ValueError(f"suggest_mode must be 'sequential', 'lockstep' or 'device', got {suggest_mode!r}")
         if score_mode not in ("per_study", "batched"):
             raise ValueError(f"score_mode must be 'per_study' or 'batched', got {score_mode!r}")
         if score_mode == "batched" and suggest_mode == "sequential":
             raise ValueError("score_mode='batched' needs suggest_mode='lockstep' or 'device': the sequential mode runs every study on its own")
-        self.suggest_mode, self.score_mode = suggest_mode, score_mode
+        if pending_mode not in ("per_study", "batched"):
+            raise ValueError(f"pending_mode must be 'per_study' or 'batched', got {pending_mode!r}")
+        if pending_mode == "batched" and suggest_mode == "sequential":
+            raise ValueError("pending_mode='batched' needs suggest_mode='lockstep' or 'device': the sequential mode runs every study on its own")
+        self.suggest_mode, self.score_mode, self.pending_mode = suggest_mode, score_mode, pending_mode
         self.profile_parts = False   # developer timing (tools/dev_studies_time.py): synchronise between the parts of a suggest and time them
         self.last_suggest_info: dict = {}
         S = int(num_studies)
@@ -360,6 +374,19 @@ class ScaMLGPBOStudies:
         pending evaluations make it a fantasy model.)"""
         return (not (st.max_pending_evaluations is not None and st.pending.shape[0] > 0)) and st.model.supports_posterior_grad()
 
+    def _takes_study(self, st: ScaMLGPBOLoop) -> bool:
+        """``_batched_study``, and with ``pending_mode="batched"`` also a study whose pending evaluations make it a fantasy model the
+        batched acquisition takes.  Asked BEFORE ``st.acquisition_function()`` draws the fantasies from ``st.gen``: a study that fell
+        back afterwards would draw them twice."""
+        if self._batched_study(st):
+            return True
+        p = st.pending.shape[0]
+        if self.pending_mode != "batched" or st.max_pending_evaluations is None or p == 0:
+            return False
+        m = st.model
+        return (m.num_fantasies is None and m.supports_posterior_grad() and m.n + p <= 96 and m.n + p <= m._stack.N
+                and 1 <= int(st.num_fantasies) <= 64)
+
     def _suggest_lockstep(self, studies: Sequence[ScaMLGPBOLoop]):
         from .utils import StudiesAcquisition
 
@@ -380,7 +407,7 @@ class ScaMLGPBOStudies:
         if self.score_mode == "batched":
             drawn = []   # (position, study, af, cand): stage 1's draw per study, the scoring for all of them below
             for i, st in enumerate(studies):
-                if not self._batched_study(st):
+                if not self._takes_study(st):
                     out[i] = st.suggest()
                     continue
                 st.model.eval()
@@ -407,7 +434,7 @@ class ScaMLGPBOStudies:
                     batch.append((i, st, af, cand, vals, best0, cand[pk]))
         else:
             for i, st in enumerate(studies):
-                if not self._batched_study(st):
+                if not self._takes_study(st):
                     out[i] = st.suggest()
                     continue
                 st.model.eval()

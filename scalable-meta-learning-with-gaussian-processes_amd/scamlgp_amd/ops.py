@@ -715,9 +715,11 @@ def source_posteriors_grad_grouped(Xq: torch.Tensor, group: torch.Tensor, Xa: to
 
 
 def _target_pass_studies(strips: bool, mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info,
-                         acqf_param, acqf, kind, want_grad, want_posterior) -> Dict[str, Optional[torch.Tensor]]:
+                         acqf_param, acqf, kind, want_grad, want_posterior, fantasy=None) -> Dict[str, Optional[torch.Tensor]]:
     """The studies' target pass behind ``target_acqf_batched`` (``strips`` False: the GRAD layout, ``group`` per query point, the gradient
-    where wanted) and ``target_score_batched`` (``strips`` True: the value layout, ``group`` per strip of 16 candidates, no gradient)."""
+    where wanted) and ``target_score_batched`` (``strips`` True: the value layout, ``group`` per strip of 16 candidates, no gradient).
+    ``fantasy`` = (alpha_f (G, n_max, F_max), n_fant (G,) int32): their ``target_fantasy_*`` siblings for studies with pending
+    evaluations -- ``alpha`` is not used and the posterior is not returned."""
     Mq, D = Xq.shape
     G, n_max = int(Xt.shape[0]), int(Xt.shape[1])
     T = int(w.shape[1])
@@ -733,7 +735,14 @@ def _target_pass_studies(strips: bool, mu, var, cov, group, Xq, w, active, Xt, t
     theta = _check(theta, "theta", (G, D + 2))
     L = _check(L, "L", (G, n_max, n_max))
     Linv_diag = _check(Linv_diag, "Linv_diag", (G, (n_max + 15) // 16, 16, 16))
-    alpha = _check(alpha, "alpha", (G, n_max))
+    if fantasy is None:
+        alpha = _check(alpha, "alpha", (G, n_max))
+    else:
+        if fantasy[0].dim() != 3:
+            raise ValueError("alpha_f must be (G, n_max, F_max)")
+        F_max = int(fantasy[0].shape[2])
+        alpha_f = _check(fantasy[0], "alpha_f", (G, n_max, F_max))
+        n_fant = _check(fantasy[1], "n_fant", (G,), torch.int32)
     n_points = _check(n_points, "n_points", (G,), torch.int32)
     m_all = _check(m_all, "m_all", (G,))
     s_all = _check(s_all, "s_all", (G,))
@@ -744,6 +753,14 @@ def _target_pass_studies(strips: bool, mu, var, cov, group, Xq, w, active, Xt, t
     with torch.cuda.device(dev):
         value = _empty(dev, Mq)
         grad = _empty(dev, Mq, D) if want_grad else None
+        if fantasy is not None:
+            name = "scaml_target_fantasy_score_batched_f64" if strips else "scaml_target_fantasy_acqf_batched_f64"
+            rc = getattr(_lib.lib, name)(_ptr(mu), _ptr(var), _ptr(cov), _ptr(group), _ptr(Xq), _ptr(w), _ptr(active), _ptr(Xt), _ptr(theta),
+                                         _ptr(L), _ptr(Linv_diag), _ptr(alpha_f), _ptr(n_fant), _ptr(n_points), _ptr(m_all), _ptr(s_all),
+                                         _ptr(info), _ptr(acqf_param), Mq, G, n_max, F_max, T, D, int(kind), int(acqf), _ptr(value),
+                                         *(() if strips else (_ptr(grad),)), _stream_handle())
+            _lib.check_rc(rc, name)
+            return dict(value=value, grad=grad, mu=None, var=None)
         mu_o = _empty(dev, Mq) if want_posterior else None
         var_o = _empty(dev, Mq) if want_posterior else None
         rc = getattr(_lib.lib, name)(_ptr(mu), _ptr(var), _ptr(cov), _ptr(group), _ptr(Xq), _ptr(w), _ptr(active), _ptr(Xt), _ptr(theta), _ptr(L),
@@ -765,6 +782,34 @@ def target_acqf_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor, 
     Returns dict(value (Mq,), grad (Mq, D) or None, mu, var (Mq,) or None)."""
     return _target_pass_studies(False, mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, alpha, n_points, m_all, s_all, info,
                                 acqf_param, acqf, kind, want_grad, want_posterior)
+
+
+def target_fantasy_acqf_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor, group: torch.Tensor, Xq: torch.Tensor, w: torch.Tensor,
+                                active: torch.Tensor, Xt: torch.Tensor, theta: torch.Tensor, L: torch.Tensor, Linv_diag: torch.Tensor,
+                                alpha_f: torch.Tensor, n_fant: torch.Tensor, n_points: torch.Tensor, m_all: torch.Tensor, s_all: torch.Tensor,
+                                info: torch.Tensor, acqf_param: torch.Tensor, acqf: int, kind: int, want_grad: bool = True):
+    """``target_acqf_batched`` for studies of which some hold pending evaluations: alpha_f (G, n_max, F_max) holds, per study, the F_g =
+    ``n_fant[g]`` columns of alpha of its fantasies (row a: F_g values contiguously), and a study's training block -- Xt, L, Linv_diag,
+    n_points, the rows of cov -- includes its pending inputs.  UCB / EI are averaged over the fantasies as ``target_fantasy_acqf`` does
+    for one model; a study with F_g == 1 gives ``target_acqf_batched``'s bits.  One launch of scaml_target_fantasy_acqf_batched_f64.
+    Returns dict(value (Mq,), grad (Mq, D) or None)."""
+    out = _target_pass_studies(False, mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, None, n_points, m_all, s_all, info,
+                               acqf_param, acqf, kind, want_grad, False, fantasy=(alpha_f, n_fant))
+    return dict(value=out["value"], grad=out["grad"])
+
+
+def target_fantasy_score_batched(mu: torch.Tensor, var: torch.Tensor, cov: torch.Tensor, group: torch.Tensor, Xq: torch.Tensor, w: torch.Tensor,
+                                 active: torch.Tensor, Xt: torch.Tensor, theta: torch.Tensor, L: torch.Tensor, Linv_diag: torch.Tensor,
+                                 alpha_f: torch.Tensor, n_fant: torch.Tensor, n_points: torch.Tensor, m_all: torch.Tensor, s_all: torch.Tensor,
+                                 info: torch.Tensor, acqf_param: torch.Tensor, acqf: int, kind: int):
+    """``target_score_batched`` for studies of which some hold pending evaluations (the arrays of ``target_fantasy_acqf_batched``, the
+    value layout of ``source_posteriors_grouped``): per candidate the value of ``target_fantasy_acqf_batched``, bit for bit.  One launch
+    of scaml_target_fantasy_score_batched_f64.  Returns dict(value (Mq,))."""
+    if Xq.shape[0] % 16:
+        raise ValueError(f"the candidates come in whole strips of 16, got Mq = {Xq.shape[0]}")
+    out = _target_pass_studies(True, mu, var, cov, group, Xq, w, active, Xt, theta, L, Linv_diag, None, n_points, m_all, s_all, info,
+                               acqf_param, acqf, kind, False, False, fantasy=(alpha_f, n_fant))
+    return dict(value=out["value"])
 
 
 def source_posteriors_grouped(Xq: torch.Tensor, group: torch.Tensor, Xa: torch.Tensor, n_points_a: torch.Tensor, VA_tab: torch.Tensor,
@@ -1226,11 +1271,12 @@ class StudiesAcqfOpt:
     be enqueued in chunks (``enqueue``; the first call resets, the later ones continue).  ``arrays``: the 22 device arrays of the C
     signature from ``x0`` to ``acqf_param``, in its order (None for the optional y_mean / y_std / n_points_s).  ``task_base`` (G,)
     int32: every study owns its source tasks (scaml_studies_acqf_opt_own_f64) -- the eight source arrays then hold ``Tsrc`` tasks and T
-    is the tasks per study."""
+    is the tasks per study.  ``fantasy`` = (alpha_f (G, n_max, F_max), n_fant (G,) int32): studies may hold pending evaluations
+    (scaml_studies_fantasy_acqf_opt_f64, with or without ``task_base``); the ``alpha_t`` slot of ``arrays`` is then not used (None)."""
 
     def __init__(self, arrays, B: int, G: int, n_max: int, T: int, N: int, D: int, kind_s: int, kind_t: int, acqf: int, lo: torch.Tensor, hi: torch.Tensor,
                  max_iter: int, history: int = 10, max_ls: int = ACQF_OPT_MAX_LS, gtol: float = 1e-5, ftol: float = 2.2e-9, c1: float = 1e-4,
-                 task_base: Optional[torch.Tensor] = None, Tsrc: Optional[int] = None):
+                 task_base: Optional[torch.Tensor] = None, Tsrc: Optional[int] = None, fantasy=None):
         dev = arrays[0].device
         i32, u8, i64, f64, nbm = torch.int32, torch.uint8, torch.int64, torch.float64, (n_max + 15) // 16
         if (task_base is None) != (Tsrc is None):
@@ -1244,10 +1290,19 @@ class StudiesAcqfOpt:
                 ("m_all", (G,), f64), ("s_all", (G,), f64), ("info", (G,), i32), ("acqf_param", (G,), f64)]
         if len(arrays) != len(spec):
             raise ValueError(f"expected {len(spec)} arrays, got {len(arrays)}")
+        self._fantasy = fantasy is not None
+        if self._fantasy:
+            if fantasy[0].dim() != 3:
+                raise ValueError("alpha_f must be (G, n_max, F_max)")
+            F_max = int(fantasy[0].shape[2])
+            arrays = list(arrays)
+            arrays[16:17] = fantasy   # alpha_f and n_fant stand where alpha_t stood
+            spec[16:17] = [("alpha_f", (G, n_max, F_max), f64), ("n_fant", (G,), i32)]
         arrays = [_opt(a, name, shape, dt) for a, (name, shape, dt) in zip(arrays, spec)]
         self._keep = arrays
         self._ptrs = [_ptr(a) for a in arrays]
-        self._shape = (B, G, n_max, T, N, D, int(kind_s), int(kind_t), int(acqf))
+        self._shape = (B, G, n_max, *((F_max,) if self._fantasy else ()), T, N, D, int(kind_s), int(kind_t), int(acqf))
+        self._dims = (B, G, D)
         self._opts = (int(max_iter), int(history), int(max_ls), float(gtol), float(ftol), float(c1))
         self.lo, self.hi = _check(lo, "lo", (D,)), _check(hi, "hi", (D,))
         self.device, self.n_calls, self.n_eval = dev, 0, 0
@@ -1262,6 +1317,8 @@ class StudiesAcqfOpt:
 
     def enqueue(self, n_evals: int) -> None:
         fn, own = ("scaml_studies_acqf_opt_f64", ()) if self._own is None else ("scaml_studies_acqf_opt_own_f64", (_ptr(self._own[0]), self._own[1]))
+        if self._fantasy:   # one entry for both: task_base NULL is the shared stack
+            fn, own = "scaml_studies_fantasy_acqf_opt_f64", own or (None, 0)
         with torch.cuda.device(self.device):
             rc = getattr(_lib.lib, fn)(*self._ptrs, *self._shape, _ptr(self.lo), _ptr(self.hi), *self._opts, int(n_evals),
                                        _lib.ACQF_OPT_CONTINUE if self.n_calls else 0, _ptr(self.ws), _ptr(self.x), _ptr(self.f),
@@ -1276,12 +1333,12 @@ class StudiesAcqfOpt:
         most ``1 + max_iter * max_ls`` evaluations: then every start has stopped).  Returns dict(x (B, D), f (B,) the acquisition value
         there, stats (B, 4) int32 [iterations, evaluations, status, pairs] on the host, n_eval rounds enqueued, n_calls, state)."""
         out = _lbfgs_rounds(lambda k, _: self.enqueue(k), self.stats, int(evals_per_call or ACQF_OPT_EVALS_PER_CALL), self.budget,
-                            self._shape[0] > 0 and self._shape[1] > 0, self.n_eval, self.n_calls)
+                            self._dims[0] > 0 and self._dims[1] > 0, self.n_eval, self.n_calls)
         return dict(x=self.x, f=self.f, state=self.state(), **out)
 
     def state(self) -> torch.Tensor:
         """(B, studies_acqf_opt_state_doubles(D, history)): the per-start state that opens the workspace (a view)."""
-        return _lbfgs_state(self.ws, self._shape[0], self._shape[5], self._opts[1])
+        return _lbfgs_state(self.ws, self._dims[0], self._dims[2], self._opts[1])
 
 
 def studies_acqf_opt(arrays, B: int, G: int, n_max: int, T: int, N: int, D: int, kind_s: int, kind_t: int, acqf: int, lo: torch.Tensor, hi: torch.Tensor,

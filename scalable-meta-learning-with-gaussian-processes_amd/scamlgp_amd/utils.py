@@ -433,7 +433,7 @@ class StudiesAcquisition:
     captured into a HIP graph (``bo.GraphedAcquisition``).
 
     ``afs``: one ``UpperConfidenceBound`` or ``ExpectedImprovement`` per study, all of the same class, on models that share the source
-    stack and the kernel family, ``supports_posterior_grad()`` and are no fantasy models.  Built once per parameter state: the per-study
+    stack and the kernel family and ``supports_posterior_grad()``.  Built once per parameter state: the per-study
     arrays (pruned weights and mask, theta, training inputs, standardiser, the factor ``_target_factor()`` -- computed through the
     model's own posterior path where it is absent --, alpha, beta or best_f) are packed from the models' caches here, padded to the
     largest n.  The models' ``_train_VA()`` tensors are passed by address (10 MB each at configs[4]: no padded copy); this object
@@ -442,7 +442,14 @@ class StudiesAcquisition:
     Per-study source stacks: the models' stacks may instead be slices of one parent with an equal number of tasks T
     (``model.meta_fit_scamlgp_studies``).  The source pass then reads the PARENT's arrays with ``task_base[g]`` = the first task of
     study g (``scaml_posterior_linv_grad_grouped_own_f64``: a study's query points meet only its own T tasks, the grid stays T x Mq);
-    ``w`` / ``active`` stay (G, T) per slice.  ``task_base`` is None on the shared-stack path."""
+    ``w`` / ``active`` stay (G, T) per slice.  ``task_base`` is None on the shared-stack path.
+
+    Studies with pending evaluations: a model may be a fantasy model (``ScaMLGP.fantasize``, at most 64 fantasies, n + p <= 96 training
+    and pending points).  It is packed with its n + p inputs, the factor of that block, its ``_train_VA()`` of the n + p points and the
+    F columns of alpha (``alpha_f`` (G, n_max, F_max), ``n_fant``; an ordinary model is F = 1 with its alpha in column 0), which it gets
+    through its own ``fantasy_acqf``.  A set with a fantasy model (``self.fantasy``) goes through the ``ops.target_fantasy_*`` entry
+    points and ``scaml_studies_fantasy_acqf_opt_f64`` -- UCB / EI averaged over a study's fantasies, the ordinary studies' results bit for
+    bit what they are without the fantasy models --; a set without one makes the calls it always made."""
 
     SCORE_COV_CAP_BYTES = 256 << 20   # `score`: the most the covariance workspace of one chunk of strips may take
 
@@ -470,8 +477,9 @@ class StudiesAcquisition:
                 raise ValueError("the studies' models must share one source stack and one kernel family")
             if m._shard is not None:
                 raise NotImplementedError("the batched acquisition is not implemented for a task-sharded source stack (shard=True)")
-            if m.num_fantasies is not None or not m.supports_posterior_grad():
-                raise NotImplementedError("the batched acquisition takes ordinary models with 1 <= n <= 96 training points and D <= 15")
+            if not m.supports_posterior_grad():
+                raise NotImplementedError("the batched acquisition takes models with 1 <= n <= 96 training (and pending) points, D <= 15 "
+                                          "and at most 64 fantasies")
         self.models, self.kind, self.device = models, m0.kind, m0.device
         st = m0._stack
         self.source = parent if own else st0   # whose arrays the source pass reads
@@ -487,25 +495,39 @@ class StudiesAcquisition:
         self.L, self.Linv_diag, self.alpha = z(G, n_max, n_max), z(G, nbm, 16, 16), z(G, n_max)
         self.info = torch.zeros(G, dtype=torch.int32, device=dev)
         self._VA = []
+        fant = [m.num_fantasies or 1 for m in models]
+        self.fantasy = any(m.num_fantasies is not None for m in models)
+        self.alpha_f = z(G, n_max, max(fant)) if self.fantasy else None
+        param = lambda a: float(a.beta if self.acqf == ops.ACQF_UCB else a.best_f)   # noqa: E731
         if batched_factors:
-            self._factors_batched([m for m in models if m._target_factor() is None])
+            self._factors_batched([m for m in models if m.num_fantasies is None and m._target_factor() is None])
         for g, (af, m) in enumerate(zip(afs, models)):
             n = m.n
             f = m._target_factor()
             if f is None:   # (present after the study's scoring pass; otherwise the model's own path computes and caches it)
-                m.posterior_with_grad(m.train_X[:1])
+                if m.num_fantasies is not None:
+                    m.fantasy_acqf(m.train_X[:1], self.acqf, param(af))
+                else:
+                    m.posterior_with_grad(m.train_X[:1])
                 f = m._target_factor()
             w_full, act = m._active_tasks()
             self.w[g], self.active[g] = w_full, act.to(torch.uint8)
             self.Xt[g, :n], self.theta[g] = m.train_X, m.theta
-            self.L[g, :n, :n], self.Linv_diag[g, :(n + 15) // 16], self.alpha[g, :n] = f["L"][0], f["Linv_diag"][0], f["alpha"][0]
+            self.L[g, :n, :n], self.Linv_diag[g, :(n + 15) // 16] = f["L"][0], f["Linv_diag"][0]
+            if m.num_fantasies is not None:
+                self.alpha_f[g, :n, :fant[g]] = f["alpha_f"]
+            else:
+                self.alpha[g, :n] = f["alpha"][0]
+                if self.fantasy:
+                    self.alpha_f[g, :n, 0] = f["alpha"][0]
             self.info[g] = f["info"][0]
             self._VA.append(m._train_VA().contiguous())
         host = lambda vals, dt: torch.tensor(vals, dtype=dt).to(dev)   # noqa: E731
         self.n_points = host(ns, torch.int32)
         self.m_all = host([m._m_all_f for m in models], torch.float64)
         self.s_all = host([m._s_all_f for m in models], torch.float64)
-        self.acqf_param = host([float(a.beta if self.acqf == ops.ACQF_UCB else a.best_f) for a in afs], torch.float64)
+        self.acqf_param = host([param(a) for a in afs], torch.float64)
+        self.n_fant = host(fant, torch.int32) if self.fantasy else None
         self.VA_tab = host([v.data_ptr() for v in self._VA], torch.int64)
 
     @staticmethod
@@ -545,6 +567,8 @@ class StudiesAcquisition:
         Mq = Xq.shape[0]
         if Mq % 16 or tuple(group_per_strip.shape) != (Mq // 16,) or group_per_strip.dtype != torch.int32:
             raise ValueError("score takes whole strips of 16 candidates and one int32 group per strip")
+        if self.fantasy and want_posterior:
+            raise ValueError("a set with fantasy models has no single posterior per candidate")
         group = group_per_strip.to(self.device)
         st, f = self.source, self.source.fit
         T = self.w.shape[1]
@@ -555,6 +579,12 @@ class StudiesAcquisition:
             xq, gr = Xq[16 * s0:16 * s1], group[s0:s1]
             g = ops.source_posteriors_grouped(xq, gr, self.Xt, self.n_points, self.VA_tab, st.X, st.theta, st.kind, f["Linv"], f["alpha"],
                                               st.y_mean, st.y_std, st.n_points, **self._own)
+            if self.fantasy:
+                v = ops.target_fantasy_score_batched(g["mu"], g["var"], g["cov"], gr, xq, self.w, self.active, self.Xt, self.theta, self.L,
+                                                     self.Linv_diag, self.alpha_f, self.n_fant, self.n_points, self.m_all, self.s_all,
+                                                     self.info, self.acqf_param, self.acqf, self.kind)
+                parts.append(dict(value=v["value"], mu=None, var=None))
+                continue
             parts.append(ops.target_score_batched(g["mu"], g["var"], g["cov"], gr, xq, self.w, self.active, self.Xt, self.theta, self.L,
                                                   self.Linv_diag, self.alpha, self.n_points, self.m_all, self.s_all, self.info, self.acqf_param,
                                                   self.acqf, self.kind, want_posterior=want_posterior))
@@ -574,6 +604,13 @@ class StudiesAcquisition:
         st, f = self.source, self.source.fit
         g = ops.source_posteriors_grad_grouped(Xq, group, self.Xt, self.n_points, self.VA_tab, st.X, st.theta, st.kind, f["Linv"], f["alpha"],
                                                st.y_mean, st.y_std, st.n_points, **self._own)
+        if self.fantasy:
+            if want_posterior:
+                raise ValueError("a set with fantasy models has no single posterior per query point")
+            out = ops.target_fantasy_acqf_batched(g["mu"], g["var"], g["cov"], group, Xq, self.w, self.active, self.Xt, self.theta, self.L,
+                                                  self.Linv_diag, self.alpha_f, self.n_fant, self.n_points, self.m_all, self.s_all, self.info,
+                                                  self.acqf_param, self.acqf, self.kind, want_grad=want_grad)
+            return dict(value=out["value"], grad=out["grad"], mu=None, var=None)
         return ops.target_acqf_batched(g["mu"], g["var"], g["cov"], group, Xq, self.w, self.active, self.Xt, self.theta, self.L, self.Linv_diag,
                                        self.alpha, self.n_points, self.m_all, self.s_all, self.info, self.acqf_param, self.acqf, self.kind,
                                        want_grad=want_grad, want_posterior=want_posterior)
@@ -604,6 +641,9 @@ class StudiesAcquisition:
         T, N = self.w.shape[1], st.X.shape[1]
         if self.task_base is not None:   # per-study source tasks: T slots per study of the Tsrc tasks in the parent's arrays
             options = dict(options, task_base=self.task_base, Tsrc=st.X.shape[0])
+        if self.fantasy:
+            arrays[16] = None   # (alpha_t: not read; alpha_f and n_fant stand in its place)
+            options = dict(options, fantasy=(self.alpha_f, self.n_fant))
         return ops.StudiesAcqfOpt(arrays, B, self.G, self.n_max, T, N, D, st.kind, self.kind, self.acqf, lo.to(dev), hi.to(dev), max_iter, **options)
 
     def optimize(self, X0: torch.Tensor, group: torch.Tensor, max_iter: int, bounds=(0.0, 1.0), evals_per_call: Optional[int] = None,

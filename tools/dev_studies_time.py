@@ -13,6 +13,8 @@ medians over the timed steps (the first step of a size is a warm-up and is not c
       the device mode's suggest() by score_mode, the split of a suggest into its parts, and StudiesAcquisition.score alone
   python tools/dev_studies_time.py --own-stacks [--sizes 8,32,128] [--out profiles/studies_own_stacks_timings.txt]
       one source stack PER study at hartmann6.py's shape (see own_stacks_table)
+  python tools/dev_studies_time.py --pending [--sizes 8,32] [--steps K] [--out profiles/studies_pending_timings.txt]
+      every study holds pending evaluations: pending_mode='batched' against 'per_study' (see pending_table)
 """
 import argparse
 import os
@@ -39,6 +41,7 @@ ap.add_argument("--sweep", default=None, help="with a list such as 1,2,4,8,16: t
 ap.add_argument("--evals-per-call", type=int, default=None, help="ops.ACQF_OPT_EVALS_PER_CALL for --suggest")
 ap.add_argument("--score", action="store_true", help="device suggest(): score_mode='batched' against 'per_study', its split into parts, and score alone")
 ap.add_argument("--own-stacks", action="store_true", help="per-study source stacks: meta-fit, BO step and the grouped pass against what a caller had before")
+ap.add_argument("--pending", action="store_true", help="studies with pending evaluations: pending_mode='batched' against 'per_study', and the evaluation launch alone")
 args = ap.parse_args()
 
 T, N, D, N_END, RESTARTS = 32, 512, 6, 80, 2
@@ -340,6 +343,112 @@ def score_table():
         torch.cuda.empty_cache()
 
 
+def pending_table():
+    """Every study holds p pending evaluations (p = 1, then 4; F = 16 fantasies, n = 80 observed points, 10 starts per study):
+    ``pending_mode="batched"`` against ``"per_study"`` -- the parent's behaviour, every study its own ``ScaMLGPBOLoop.suggest()`` --, in
+    suggest_mode "device" and "lockstep".  Two ScaMLGPBOStudies on the same data, timed alternately call by call in one process; after
+    every suggest the pending lists are put back to the p points, so every call sees the same shapes (each draws new fantasies and
+    starts from the studies' generators).  The first call of a row is a warm-up and is not counted; median and min .. max per side.
+    Then the split of the batched side's suggest (``profile_parts``: "stage1" holds the per-study set-up -- fantasize with the
+    conditioned model's source pass, factor and alpha, through the study's own scoring pass).  Last, the evaluation launch alone on one
+    grouped source pass's outputs: scaml_target_fantasy_acqf_batched_f64 against scaml_target_acqf_batched_f64 at F = 1 (the same
+    ordinary studies) and at F = 16 (the fantasy models; (7g) on their arrays with column 0 of alpha_f, for the time only)."""
+    F, starts = 16, 10
+    kw = dict(KW, max_pending_evaluations=8, num_fantasies=F)
+    say(f"# suggest() of S studies that all hold p pending evaluations, T = {T}, N = {N}, D = {D}, n = {N_END}, F = {F}, UCB, 1,024 raw candidates and "
+        f"{starts} starts per study; ms, median of {args.steps} calls, (min .. max) per side")
+    for S in [int(v) for v in args.sizes.split(",")]:
+        seeds = list(range(100, 100 + S))
+        sides = {k: ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, suggest_mode="device", pending_mode=k, **kw) for k in ("batched", "per_study")}
+        for side in sides.values():
+            for s in range(S):
+                g = torch.Generator().manual_seed(seeds[s])
+                X0 = torch.rand(N_END, D, dtype=torch.float64, generator=g)
+                side[s].record(X0, [obj(x) for x in X0])
+            utils.fit_targets_batched([st.model for st in side.studies], RESTARTS, rng=side.fit_gens)
+        for p in (1, 4):
+            g = torch.Generator().manual_seed(1000 + S + p)
+            pend = [torch.rand(p, D, dtype=torch.float64, generator=g) for _ in range(S)]
+
+            def reset():
+                for side in sides.values():
+                    for s in range(S):
+                        side[s].pending = pend[s].clone()
+
+            for mode in ("device", "lockstep"):
+                ms = {k: [] for k in sides}
+                for r in range(args.steps + 1):
+                    for k, side in sides.items():
+                        side.suggest_mode = mode
+                        reset()
+                        t, _ = timed(side.suggest)
+                        if r:
+                            ms[k].append(1e3 * t)
+                        assert len(side.last_suggest_info["batched"]) == (S if k == "batched" else 0)
+                med = {k: statistics.median(v) for k, v in ms.items()}
+                gain, spread = med["per_study"] - med["batched"], max(ms["per_study"]) - min(ms["per_study"])
+                say(f"  S = {S:>3} p = {p} {mode:>8}: batched {med['batched']:9.1f} ({min(ms['batched']):.1f} .. {max(ms['batched']):.1f})   per_study "
+                    f"{med['per_study']:9.1f} ({min(ms['per_study']):.1f} .. {max(ms['per_study']):.1f})   per_study / batched = {med['per_study'] / med['batched']:5.2f}x   "
+                    f"gain {gain:.1f} ms against a per_study spread of {spread:.1f} ms: "
+                    f"{'faster by more than the spread' if gain > spread else ('a LOSS' if gain < 0 else 'INSIDE the spread')}")
+                side = sides["batched"]
+                side.profile_parts = True
+                got = []
+                for _ in range(3):
+                    reset()
+                    side.suggest()
+                    got.append(dict(side.last_suggest_info["parts"]))
+                side.profile_parts = False
+                q = {name: 1e3 * statistics.median(g_.get(name, 0.0) for g_ in got) for name in ("stage1", "packing", "rounds", "stage3")}
+                say(f"#       split, batched {mode:>8}: stage 1 with the per-study set-up {q['stage1']:8.2f}   packing {q['packing']:8.2f}   rounds {q['rounds']:8.2f}   "
+                    f"stage 3 {q['stage3']:8.2f}   ({q['stage1'] / S:.2f} ms of stage 1 per study)")
+        # the evaluation launch alone, on one source pass's outputs
+        reset()
+        studies = sides["batched"].studies
+        ordinary = [utils.UpperConfidenceBound(st.model.eval(), 9.0) for st in studies]
+        fantasy = [st.acquisition_function() for st in studies]
+        Xq = torch.rand(S * starts, D, dtype=torch.float64, generator=torch.Generator().manual_seed(S)).to(dev)
+        for name, afs in (("F = 1", ordinary), (f"F = {F}, p = 4", fantasy)):
+            sa = utils.StudiesAcquisition(afs)
+            group = sa.group_of([starts] * S)
+            st, f = sa.source, sa.source.fit
+            src = ops.source_posteriors_grad_grouped(Xq, group, sa.Xt, sa.n_points, sa.VA_tab, st.X, st.theta, st.kind, f["Linv"], f["alpha"], st.y_mean,
+                                                     st.y_std, st.n_points)
+            alpha_f = sa.alpha_f if sa.fantasy else sa.alpha.unsqueeze(-1).contiguous()
+            n_fant = sa.n_fant if sa.fantasy else torch.ones(S, dtype=torch.int32, device=dev)
+            head = (src["mu"], src["var"], src["cov"], group, Xq, sa.w, sa.active, sa.Xt, sa.theta, sa.L, sa.Linv_diag)
+            tail = (sa.n_points, sa.m_all, sa.s_all, sa.info, sa.acqf_param, sa.acqf, sa.kind)
+            a7 = alpha_f[:, :, 0].contiguous()
+            calls = {"(7g)": lambda: ops.target_acqf_batched(*head, a7, *tail),
+                     "(7k)": lambda: ops.target_fantasy_acqf_batched(*head, alpha_f, n_fant, *tail)}
+            reps, inner = 8, 20
+            got = {k: [] for k in calls}
+            for r in range(reps + 1):
+                for k, fn in calls.items():
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    ev0.record()
+                    for _ in range(inner):
+                        fn()
+                    ev1.record()
+                    torch.cuda.synchronize()
+                    if r:
+                        got[k].append(1e3 * ev0.elapsed_time(ev1) / inner)
+            say(f"#     evaluation launch alone, {S * starts} query points, n' = {sa.n_max}, {name}: (7k) {statistics.median(got['(7k)']):8.1f} us "
+                f"({min(got['(7k)']):.1f} .. {max(got['(7k)']):.1f})   (7g) {statistics.median(got['(7g)']):8.1f} us ({min(got['(7g)']):.1f} .. {max(got['(7g)']):.1f})   "
+                f"[device events over {inner} calls, allocation of the outputs included]")
+        del sides, studies, ordinary, fantasy, sa
+        torch.cuda.empty_cache()
+
+
+if args.pending:
+    if args.sizes == ap.get_default("sizes"):
+        args.sizes = "8,32"
+    pending_table()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 if args.score:
     score_table()
     if args.out:
