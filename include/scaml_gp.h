@@ -657,6 +657,58 @@ int scaml_studies_fantasy_acqf_opt_f64(const double* x0, const int32_t* group, c
                                        double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace, double* x, double* f,
                                        int32_t* stats, const int32_t* task_base, int Tsrc, void* stream);
 
+/*
+ * (7m), (7n) The fantasy SET-UP of G studies with pending evaluations in a constant number of launches
+ * (scamlgp_amd.model.fantasize_studies; bo.ScaMLGPBOStudies with fantasy_setup="batched"), in place of, per study, ScaMLGP.fantasize,
+ * condition_on_observations and the conditioned model's first pass.  With X' = cat(train_X, X_pend), n' = n + p points, K' the training
+ * block of the conditioned model (standardised units, noise on the diagonal), mean' the standardised weighted source mean at X' and
+ * L' = chol(K') = [[L_nn, 0], [L_pn, L_pp]]:  v = L_nn^-1 (y~_n - mean'_n);  the posterior mean at the pending points is
+ * mean'_p + L_pn v and L_pp L_pp^T their posterior covariance with observation noise, so the fantasy targets are
+ * y~_p^f = mean'_p + L_pn v + L_pp eps_f;  the residual of fantasy f is L' [v ; eps_f], hence alpha_f[:, f] = L'^-T [v ; eps_f].
+ * The calls: (5f) / (5f') ONCE with every study's own X' as its query strips, (7m), (2) with n_points and Linv_diag, (7n).
+ *
+ * (7m) scaml_studies_condition_block_f64: the training blocks of the conditioned models -- (7j) on (5f)'s layout.
+ *   mu (T, Mq), cov (T, n_max, Mq): (5f)'s outputs (its var is not needed: the diagonal of K' comes from cov, as its other elements do).
+ *       Strip j of study g holds points 16 j .. 16 j + 15 of X'_g, padded with any point of the box; Mq a multiple of 16.
+ *   strip_base (G) int32: the first strip of study g;  w, active (G, T), Xt (G, n_max, D) = X'_g, theta (G, D + 2): as (7g) takes them;
+ *   y (G, n_max): standardised targets of the observed rows (rows >= n_obs are not read);  n_points (G) int32 = n'_g;  n_obs (G) int32
+ *       = n_g, 1 <= n_g <= n'_g <= n_max (n_g == n'_g: nothing pending);  m_all, s_all (G).
+ *   Knn (G, n_max, n_max): the leading n'_g block.  Element (i, c) with c <= i is
+ *       sum_t w_t^2 cov[t][i][16 strip_base[g] + c] / s^2 + os k(x_i, x_c) (+ noise if i == c) -- the ROW of the later point, the COLUMN
+ *       of the earlier one -- and (c, i) is its copy; (2) reads the lower triangle only.
+ *   resid (G, n_max): y_i - mean'_i for i < n_obs, ZERO for the pending rows;  mean_p (G, n_max): mean'_i at rows n_obs .. n' - 1.
+ *   The task sums run in (6)'s order, masked tasks skipped.  Nothing past n'_g in a study's slices is read or written.  A point of
+ *   X'_g with a NaN or infinite coordinate, n_obs[g] outside 1 .. n'_g or strips outside the Mq columns make THAT study's outputs NaN;
+ *   n_points[g] outside 1 .. n_max: nothing is written for the study ((7n) answers NaN for it).
+ *   Checks: Mq < 0 or not a multiple of 16, G < 0, n_max < 1, T < 1, D < 1, a NULL pointer, kind: SCAML_E_BADARG.  Limits: n_max <= 96,
+ *   D <= 15, Mq <= 2^26 (as (7g)) and the LDS footprint (sc_block_lds_doubles of csrc/gp_studies_condition.h): SCAML_E_TOOLARGE (bad arguments answer first).
+ *
+ * (7n) scaml_studies_fantasy_condition_f64: the fantasies and alpha_f from the factor.
+ *   L (G, n_max, n_max), info (G) int32: (2)'s outputs for Knn;  resid, mean_p, n_points, n_obs, m_all, s_all: as (7m);
+ *   eps (G, p_max, F_max): standard-normal draws, row i of study g holds the F_g values of pending point i contiguously;
+ *   n_fant (G) int32, 1 <= F_g <= F_max;  p_max >= 1, every n'_g - n_g <= p_max.
+ *   alpha_f (G, n_max, F_max): exactly (7k)'s layout;  y_fant (G, p_max, F_max): the fantasy targets in original units, m + s y~;
+ *   mu_p (G, p_max): the posterior mean at the pending points in original units.
+ *   Per study: v by forward substitution against the leading n_g block, the samples by the formula above, L'^T x = [v ; eps_f] by
+ *   backward substitution, one thread per fantasy column.  A study with n_g == n'_g is an ordinary one: F_g must be 1, column 0 of
+ *   alpha_f is L'^-T v = K^-1 resid and nothing is written to y_fant / mu_p.
+ *   info[g] != 0, n_points[g] outside 1 .. n_max, n_obs[g] outside 1 .. n'_g, n_fant[g] outside 1 .. F_max, more than p_max pending points
+ *   or an ordinary study with F_g != 1: that study's outputs are NaN (and (7k) answers NaN for it).  Nothing past n'_g, p_g or F_g is
+ *   read or written.
+ *   Checks: G < 0, n_max < 1, p_max < 1, F_max < 1, a NULL pointer: SCAML_E_BADARG.  Limits: n_max <= 96, p_max <= 96, F_max <= 64 and the
+ *   LDS footprint (sc_fantasy_lds_doubles): SCAML_E_TOOLARGE (bad arguments answer first).
+ * Both: fp64, a workgroup of 256 threads per study, every sum formed by one thread in a fixed ascending order, no atomics -- the outputs
+ * are a pure function of the inputs.  Everything is checked before the first HIP call; G == 0: nothing is enqueued.  Neither call
+ * synchronises and both can be stream-captured.
+ */
+int scaml_studies_condition_block_f64(const double* mu, const double* cov, const int32_t* strip_base, const double* w, const uint8_t* active,
+                                      const double* Xt, const double* theta, const double* y, const int32_t* n_points, const int32_t* n_obs,
+                                      const double* m_all, const double* s_all, int Mq, int G, int n_max, int T, int D, int kind, double* Knn,
+                                      double* resid, double* mean_p, void* stream);
+int scaml_studies_fantasy_condition_f64(const double* L, const double* resid, const double* mean_p, const int32_t* n_points, const int32_t* n_obs,
+                                        const int32_t* info, const double* eps, const int32_t* n_fant, const double* m_all, const double* s_all,
+                                        int G, int n_max, int p_max, int F_max, double* alpha_f, double* y_fant, double* mu_p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

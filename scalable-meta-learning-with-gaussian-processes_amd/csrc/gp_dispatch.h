@@ -9,6 +9,7 @@
 #include "gp_fit_params.h"
 #include "gp_posterior_params.h"
 #include "gp_target_params.h"
+#include "gp_studies_condition.h"
 
 namespace scaml {
 
@@ -184,6 +185,18 @@ constexpr TargetFitPlan target_fit_plan(int n, int T, int D, int mode) {
 }
 constexpr TargetFitPlan target_fit_batched_plan(int n_max, int T, int D, int mode) {
   return {mode == 0, target_fit_batched_lds_doubles(n_max, T, D, mode == 0, TARGET_FIT_THREADS / 64)};
+}
+
+// ---- studies' batched fantasy set-up (7m), (7n): a workgroup per study ---------------------------------------------------------
+struct StudiesConditionPlan {
+  unsigned grid, block;
+  size_t lds_doubles;   // more than LDS_LIMIT: the shape is too large
+};
+constexpr StudiesConditionPlan studies_condition_block_plan(int G, int n_max, int D) {
+  return {(unsigned)G, (unsigned)STUDIES_CONDITION_THREADS, sc_block_lds_doubles(n_max, D)};
+}
+constexpr StudiesConditionPlan studies_fantasy_condition_plan(int G, int n_max, int F_max) {
+  return {(unsigned)G, (unsigned)STUDIES_CONDITION_THREADS, sc_fantasy_lds_doubles(n_max, F_max)};
 }
 
 }  // namespace scaml

@@ -75,6 +75,7 @@ struct Module {
   hipFunction_t post_linv_grouped_val[2] = {}, post_linv_grouped_val_own[2] = {};   // the value-only grouped pass (16 candidates per strip)
   hipFunction_t tgt_score_batched = nullptr, tgt_train_block[2] = {};     // studies' stage 1: strip scoring; the training blocks of all studies
   hipFunction_t tgt_fantasy_acqf_batched = nullptr, tgt_fantasy_score_batched = nullptr;   // both with pending evaluations (7k)
+  hipFunction_t cond_block = nullptr, cond_fantasy = nullptr;   // the batched fantasy set-up of studies with pending evaluations (7m), (7n)
   hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {}, stack_step = nullptr, acqf_opt_step = nullptr;
   hipFunction_t blk_solve[2][2] = {}, blk_syrk[2] = {};   // solve: [kind][D <= 8]
   hipFunction_t mllgrad_fused[4][2][2] = {};   // [size class NBT = 2, 4, 8, 16][kind][LDS-DMA staging]
@@ -106,6 +107,8 @@ struct Module {
         {&tgt_score_batched, "scaml_target_score_batched_kernel", kLdsLimit, {}},
         {&tgt_fantasy_acqf_batched, "scaml_target_fantasy_acqf_batched_kernel", kLdsLimit, {}},
         {&tgt_fantasy_score_batched, "scaml_target_fantasy_score_batched_kernel", kLdsLimit, {}},
+        {&cond_block, "scaml_studies_condition_block_kernel", kLdsLimit, {}},
+        {&cond_fantasy, "scaml_studies_fantasy_condition_kernel", kLdsLimit, {}},
         {&tgt_train_block[0], "scaml_target_train_block_rbf_kernel", 0, {}},
         {&tgt_train_block[1], "scaml_target_train_block_matern_kernel", 0, {}},
         {&wsum, "scaml_weighted_task_sum_kernel", 0, {}},
@@ -909,6 +912,45 @@ int scaml_target_train_block_batched_f64(const double* means_t, const double* co
   if (!m) return SCAML_E_LAUNCH;
   scaml::TrainBlockParams p{means_t, covs_packed, X, y, n_points, m_all, s_all, w, active, theta, Knn, resid, G, n_max, T, D};
   return launch(m->tgt_train_block[kind], dim3((unsigned)G), 256, 0, stream, "target_train_block_batched", p);
+}
+
+// ---- (7m), (7n) the fantasy set-up of G studies with pending evaluations (csrc/gp_studies_condition.hip); (2) factors the blocks between them ----
+static_assert(scaml::studies_condition_block_plan(1, scaml::STUDIES_ACQF_MAX_N, scaml::STUDIES_ACQF_MAX_D).lds_doubles * sizeof(double) <= kLdsLimit &&
+                  scaml::studies_fantasy_condition_plan(1, scaml::STUDIES_ACQF_MAX_N, scaml::STUDIES_FANTASY_MAX_F).lds_doubles * sizeof(double) <= kLdsLimit,
+              "n_max = 96 with D = 15 and with F_max = 64 fits the LDS");
+int scaml_studies_condition_block_f64(const double* mu, const double* cov, const int32_t* strip_base, const double* w, const uint8_t* active,
+                                      const double* Xt, const double* theta, const double* y, const int32_t* n_points, const int32_t* n_obs,
+                                      const double* m_all, const double* s_all, int Mq, int G, int n_max, int T, int D, int kind, double* Knn,
+                                      double* resid, double* mean_p, void* stream) {
+  if (Mq < 0 || (Mq & 15) || G < 0 || n_max < 1 || T < 1 || D < 1) return SCAML_E_BADARG;
+  if (!mu || !cov || !strip_base || !w || !active || !Xt || !theta || !y || !n_points || !n_obs || !m_all || !s_all || !Knn || !resid || !mean_p)
+    return SCAML_E_BADARG;
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (n_max > scaml::STUDIES_ACQF_MAX_N || D > scaml::STUDIES_ACQF_MAX_D || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
+  const scaml::StudiesConditionPlan plan = scaml::studies_condition_block_plan(G, n_max, D);
+  if (plan.lds_doubles * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (G == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  scaml::StudiesConditionBlockParams p{mu, cov, strip_base, w, active, Xt, theta, y, n_points, n_obs, m_all, s_all, Knn, resid, mean_p,
+                                       Mq, G, n_max, T, D, kind};
+  return launch(m->cond_block, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "studies_condition_block", p);
+}
+
+int scaml_studies_fantasy_condition_f64(const double* L, const double* resid, const double* mean_p, const int32_t* n_points, const int32_t* n_obs,
+                                        const int32_t* info, const double* eps, const int32_t* n_fant, const double* m_all, const double* s_all,
+                                        int G, int n_max, int p_max, int F_max, double* alpha_f, double* y_fant, double* mu_p, void* stream) {
+  if (G < 0 || n_max < 1 || p_max < 1 || F_max < 1) return SCAML_E_BADARG;
+  if (!L || !resid || !mean_p || !n_points || !n_obs || !info || !eps || !n_fant || !m_all || !s_all || !alpha_f || !y_fant || !mu_p)
+    return SCAML_E_BADARG;
+  if (n_max > scaml::STUDIES_ACQF_MAX_N || p_max > scaml::STUDIES_ACQF_MAX_N || F_max > scaml::STUDIES_FANTASY_MAX_F) return SCAML_E_TOOLARGE;
+  const scaml::StudiesConditionPlan plan = scaml::studies_fantasy_condition_plan(G, n_max, F_max);
+  if (plan.lds_doubles * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (G == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  scaml::StudiesFantasyConditionParams p{L, resid, mean_p, n_points, n_obs, info, eps, n_fant, m_all, s_all, alpha_f, y_fant, mu_p, G, n_max, p_max, F_max};
+  return launch(m->cond_fantasy, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "studies_fantasy_condition", p);
 }
 
 // ---- (8) target GP: objective + gradient, and the whole L-BFGS refit, in one launch (csrc/gp_target_fit.hip) -------------

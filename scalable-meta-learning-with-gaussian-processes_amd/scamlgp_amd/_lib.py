@@ -134,6 +134,10 @@ SIGNATURES = {
     # (7l) (7h)'s arguments with alpha_f, n_fant for alpha_t and F_max after n_max; task_base (or NULL), Tsrc
     "scaml_studies_fantasy_acqf_opt_f64": (_i, [_dp] * 23 + [_i] * 10 + [_dp, _dp] + [_i] * 3 + [_f] * 3 + [_i, _u] + [_dp] * 4
                                            + [_dp, _i, c_void_p]),
+    # (7m) mu, cov, strip_base, w, active, Xt, theta, y, n_points, n_obs, m_all, s_all; Mq, G, n_max, T, D, kind; Knn, resid, mean_p
+    "scaml_studies_condition_block_f64": (_i, [_dp] * 12 + [_i] * 6 + [_dp] * 3 + [c_void_p]),
+    # (7n) L, resid, mean_p, n_points, n_obs, info, eps, n_fant, m_all, s_all; G, n_max, p_max, F_max; alpha_f, y_fant, mu_p
+    "scaml_studies_fantasy_condition_f64": (_i, [_dp] * 10 + [_i] * 4 + [_dp] * 3 + [c_void_p]),
     "scaml_debug_target_fit_path": (_i, [_i]),
     "scaml_debug_blocked_fit_path": (_i, [_i]),
     "scaml_debug_coop_far": (_i, [_i]),

@@ -29,7 +29,7 @@ import scipy.optimize
 import torch
 
 from . import hyper
-from .model import ScaMLGP, SourceGP
+from .model import ScaMLGP, SourceGP, fantasize_studies
 from .utils import ExpectedImprovement, UpperConfidenceBound, capture_graph, fit_targets_batched, optimize_marginal_likelihood
 
 
@@ -227,9 +227,13 @@ class ScaMLGPBOLoop:
             covar_module=self.model.covar_module,
         )
 
-    def acquisition_function(self) -> Callable[[torch.Tensor], torch.Tensor]:
+    def acquisition_function(self, fantasy_model: Optional[ScaMLGP] = None) -> Callable[[torch.Tensor], torch.Tensor]:
+        """``fantasy_model``: the fantasy model of the pending evaluations where the caller has built it already
+        (``model.fantasize_studies`` for many studies at once: the draws from ``gen`` are made there)."""
         model = self.model
-        if self.max_pending_evaluations is not None and self.pending.shape[0] > 0:
+        if fantasy_model is not None:
+            model = fantasy_model
+        elif self.max_pending_evaluations is not None and self.pending.shape[0] > 0:
             model = self.model.eval().fantasize(self.pending, self.num_fantasies, generator=self.gen)
         if self.acquisition == "ei":
             Yf = self.Y[torch.isfinite(self.Y)]
@@ -308,11 +312,22 @@ class ScaMLGPBOStudies:
     scamlgp/benchmarking/local_runner.py:51-65, 178-181 -- every study draws its own meta-tasks): ``source_gps`` may be a sequence of S
     dicts, as ``model.meta_fit_scamlgp_studies`` returns them (slices of one stack fitted in one call).  All three modes work: the
     batched refit takes its source terms per study anyway, and the grouped source pass reads study s's tasks only
-    (``utils.StudiesAcquisition``).  A single dict keeps meaning "shared"."""
+    (``utils.StudiesAcquisition``).  A single dict keeps meaning "shared".
+
+    ``fantasy_setup`` (with ``pending_mode="batched"``; anything else refuses ``"batched"``): ``"per_study"`` (default) -- the fantasy
+    model of a study with pending evaluations is built by its own ``fantasize`` call, as described; ``"batched"`` -- the studies that
+    stay in the batch and hold pending points get their fantasy models from ONE ``model.fantasize_studies`` call before any raw
+    candidate is drawn (one grouped source pass, ``scaml_studies_condition_block_f64``, one batched Cholesky,
+    ``scaml_studies_fantasy_condition_f64``, one status read-back; per study only the V launch of its n + p points is left).  Per study
+    the order of the draws stays fantasies, raw candidates, picks, so every ``gen`` ends where a ``"per_study"`` twin's does; the
+    fantasies are the same samples up to rounding (one factor of the joint block in place of the Schur complement's).
+    ``last_suggest_info`` gains the key ``"fantasy_setup"`` in this mode (the default mode's record keeps exactly its keys); with
+    ``profile_parts`` the part ``"setup"`` is timed apart from ``"stage1"``.
+    Not forwarded to the loops."""
 
     def __init__(self, source_gps: Union[Dict[Hashable, SourceGP], Sequence[Dict[Hashable, SourceGP]]], dim: int, num_studies: int,
                  seeds: Optional[Sequence[int]] = None, suggest_mode: str = "sequential", score_mode: str = "per_study",
-                 pending_mode: str = "per_study", **loop_kwargs):
+                 pending_mode: str = "per_study", fantasy_setup: str = "per_study", **loop_kwargs):
         if suggest_mode not in ("sequential", "lockstep", "device"):
             raise ValueError(f"suggest_mode must be 'sequential', 'lockstep' or 'device', got {suggest_mode!r}")
         if score_mode not in ("per_study", "batched"):
@@ -323,7 +338,11 @@ class ScaMLGPBOStudies:
             raise ValueError(f"pending_mode must be 'per_study' or 'batched', got {pending_mode!r}")
         if pending_mode == "batched" and suggest_mode == "sequential":
             raise ValueError("pending_mode='batched' needs suggest_mode='lockstep' or 'device': the sequential mode runs every study on its own")
-        self.suggest_mode, self.score_mode, self.pending_mode = suggest_mode, score_mode, pending_mode
+        if fantasy_setup not in ("per_study", "batched"):
+            raise ValueError(f"fantasy_setup must be 'per_study' or 'batched', got {fantasy_setup!r}")
+        if fantasy_setup == "batched" and pending_mode != "batched":
+            raise ValueError("fantasy_setup='batched' needs pending_mode='batched': otherwise a study with pending evaluations runs on its own")
+        self.suggest_mode, self.score_mode, self.pending_mode, self.fantasy_setup = suggest_mode, score_mode, pending_mode, fantasy_setup
         self.profile_parts = False   # developer timing (tools/dev_studies_time.py): synchronise between the parts of a suggest and time them
         self.last_suggest_info: dict = {}
         S = int(num_studies)
@@ -387,6 +406,19 @@ class ScaMLGPBOStudies:
         return (m.num_fantasies is None and m.supports_posterior_grad() and m.n + p <= 96 and m.n + p <= m._stack.N
                 and 1 <= int(st.num_fantasies) <= 64)
 
+    def _fantasy_models(self, studies: Sequence[ScaMLGPBOLoop]) -> dict:
+        """``fantasy_setup="batched"``: the fantasy models of the studies that stay in the batch and hold pending points, from ONE
+        ``fantasize_studies`` call -- each study's fantasies drawn from its own ``gen`` before its raw candidates, as its own
+        ``acquisition_function()`` would.  {position in ``studies``: model}; empty in the default mode."""
+        if self.fantasy_setup != "batched":
+            return {}
+        take = [(i, st) for i, st in enumerate(studies) if self._takes_study(st) and not self._batched_study(st)]
+        if not take:
+            return {}
+        models = fantasize_studies([st.model.eval() for _, st in take], [st.pending for _, st in take], [int(st.num_fantasies) for _, st in take],
+                                   [st.gen for _, st in take])
+        return {i: m for (i, _), m in zip(take, models)}
+
     def _suggest_lockstep(self, studies: Sequence[ScaMLGPBOLoop]):
         from .utils import StudiesAcquisition
 
@@ -404,6 +436,13 @@ class ScaMLGPBOStudies:
             t_last[0] = now
 
         mark()
+        fmodel = self._fantasy_models(studies)   # fantasy_setup="batched": {position: fantasy model}, all of them from one call
+        if fmodel:
+            mark("setup")
+
+        def build_af(i, st):   # (a study without a model from the batch builds its own, as before)
+            return st.acquisition_function(fmodel[i]) if i in fmodel else st.acquisition_function()
+
         if self.score_mode == "batched":
             drawn = []   # (position, study, af, cand): stage 1's draw per study, the scoring for all of them below
             for i, st in enumerate(studies):
@@ -411,7 +450,7 @@ class ScaMLGPBOStudies:
                     out[i] = st.suggest()
                     continue
                 st.model.eval()
-                drawn.append((i, st, st.acquisition_function(), acqf_draw_candidates(self.dim, st.raw_samples, st.gen)))
+                drawn.append((i, st, build_af(i, st), acqf_draw_candidates(self.dim, st.raw_samples, st.gen)))
             sa = None
             if drawn:
                 # the studies' factors in two launches, then ONE scoring pass over all candidate tables (each padded to whole strips of
@@ -438,12 +477,14 @@ class ScaMLGPBOStudies:
                     out[i] = st.suggest()
                     continue
                 st.model.eval()
-                af = st.acquisition_function()
+                af = build_af(i, st)
                 batch.append((i, st, af) + acqf_initial_conditions(af, self.dim, st.raw_samples, st.num_restarts, st.gen))
         mark("stage1")
         self.last_suggest_info = dict(batched=[b[0] for b in batch], n_eval=0, n_iter=0, score_mode=self.score_mode)
+        if self.fantasy_setup != "per_study":   # (the default mode's record keeps exactly the keys it had)
+            self.last_suggest_info["fantasy_setup"] = self.fantasy_setup
         if self.profile_parts:
-            self.last_suggest_info["parts"] = parts   # seconds: stage1, packing (with the factors), rounds, stage3
+            self.last_suggest_info["parts"] = parts   # seconds: setup (fantasy_setup="batched"), stage1, packing (with the factors), rounds, stage3
         if not batch:
             return out
         if self.score_mode != "batched":

@@ -665,6 +665,54 @@ class ScaMLGP:
     def batch_shape(self) -> torch.Size:
         return torch.Size([self.num_fantasies]) if self.num_fantasies is not None else torch.Size()
 
+    # the cached source posteriors at the training inputs: tensors, or -- a model from ``fantasize_studies`` -- a callable that cuts them
+    # out of the batch's source pass on first read (a fantasy model is not fitted: only ``forward`` in training mode reads them)
+    def _resolved(self, name: str) -> torch.Tensor:
+        v = self.__dict__.get(name)
+        if v is None:
+            raise AttributeError(f"'ScaMLGP' object has no attribute '{name[1:]}' (a model without training data caches no source terms)")
+        if callable(v):
+            v = self.__dict__[name] = v()
+        return v
+
+    source_means = property(lambda self: self._resolved("_source_means"), lambda self, v: self.__dict__.__setitem__("_source_means", v))
+    source_covs = property(lambda self: self._resolved("_source_covs"), lambda self, v: self.__dict__.__setitem__("_source_covs", v))
+
+    @classmethod
+    def _fantasy_of(cls, parent: "ScaMLGP", train_X: torch.Tensor, y_fant: torch.Tensor, VA: torch.Tensor, factor: dict,
+                    source_means, source_covs) -> "ScaMLGP":
+        """The fantasy model ``parent.fantasize`` would build for the pending points that close ``train_X`` (n + p, D), WITHOUT
+        ``__init__``'s source launches (``fantasize_studies``): y_fant (F, p) the sampled outcomes in original units, ``VA`` its
+        ``_train_VA()``, ``factor`` its target factor with alpha_f, the source terms as callables.  Everything else is what
+        ``condition_on_observations`` leaves: copied modules, the parent's weights and transform kept fixed; ``spec`` is the parent's
+        object (the constraints and priors are the same; a fantasy model is not fitted, so the init values are not used)."""
+        new = cls.__new__(cls)
+        F, n = int(y_fant.shape[0]), int(train_X.shape[0])
+        new._weight_pruning_threshold = parent._weight_pruning_threshold
+        new.source_gps, new._stack, new._idx, new._idx_dev, new._shard = parent.source_gps, parent._stack, parent._idx, parent._idx_dev, None
+        new.device, new.n, new.T, new.kind, new.spec = parent.device, n, parent.T, parent.kind, parent.spec
+        new.likelihood, new.covar_module = copy.deepcopy(parent.likelihood), copy.deepcopy(parent.covar_module)
+        new.has_transform = parent.has_transform
+        new.m_all, new.s_all = parent.m_all.clone(), parent.s_all.clone()
+        new._m_all_f, new._s_all_f = parent._m_all_f, parent._s_all_f
+        new.outcome_transform = _OutcomeTransform(new.m_all, new.s_all) if new.has_transform else None
+        new.train_X = train_X
+        new.train_inputs = (train_X,)
+        new.train_Y = torch.cat([parent.train_Y.unsqueeze(0).expand(F, -1, -1), y_fant.unsqueeze(-1)], 1)   # (F, n + p, 1)
+        new.train_targets = ((new.train_Y - new.m_all) / new.s_all).squeeze(-1).contiguous()                # (F, n + p)
+        new._cache = _StateCache()
+        new._stds_all, new._VA, new._tprob = parent._stds_all, VA, None
+        new.source_means, new.source_covs = source_means, source_covs
+        new.raw_weights = parent.raw_weights.detach().clone()
+        new.weights_prior, new.weights_lower_bound = parent.weights_prior, parent.weights_lower_bound
+        new.training = parent.training
+        new.num_fantasies = F
+        # equal parameters, equal derived values: the parent's constrained theta and pruned weights serve the copy's parameter state
+        new._cache.put("theta", new._param_tensors(), parent.theta)
+        new._cache.put("active", (new.weights,), parent._active_tasks())
+        new._keep_target_factor(factor)
+        return new
+
     # -- conditioning on new observations and fantasies (pending evaluations) ----------------------------------------------
     def condition_on_observations(self, X: torch.Tensor, Y: torch.Tensor) -> "ScaMLGP":
         """The model with (X (p, D), Y) appended to its target training set, Y (p, 1) or (F, p, 1) in original units: same
@@ -1062,3 +1110,142 @@ class ScaMLGP:
                 return TargetPosterior(mu_o.reshape(*batch, 1), var_o.reshape(*batch, 1), lambda: var_o.reshape(*batch, 1, 1))
             return TargetPosterior(mu_o.reshape(*batch, q), var_o.reshape(*batch, q), lambda: _batch_blocks(full_cov(), batch, q))
         return TargetPosterior(mu_o, var_o, full_cov)
+
+
+def _fantasy_batch(models: Sequence[ScaMLGP], Xp: Sequence[torch.Tensor], Fs: Sequence[int], eps: torch.Tensor, own: bool) -> dict:
+    """The device work of ``fantasize_studies`` for checked arguments: ``Xp[s]`` = cat(train_X, pending) of study s on the device, ``eps``
+    (S, p_max, F_max) the draws (host or device), ``own``: the models sit on slices of one parent stack.  Per study the V' launch, then
+    the grouped value pass over the studies' X' strips, ``ops.studies_condition_block``, ``ops.potrf_batched``,
+    ``ops.studies_fantasy_condition``.  Nothing is read back.  Returns dict(VA, pass (mu, var, cov), block (Knn, resid, mean_p), factor
+    (``potrf_batched``'s dict), out (alpha_f, y_fant, mu_p), strip_base (host list) and the packed arrays by name)."""
+    S = len(models)
+    m0 = models[0]
+    st0 = m0._stack
+    parent = getattr(st0, "parent", None)
+    D, dev = st0.D, m0.device
+    ns, nps = [m.n for m in models], [int(x.shape[0]) for x in Xp]
+    n_max = max(nps)
+    # V' per study, on its own stack object (step 1 of fantasize_studies)
+    VA = []
+    for m, x in zip(models, Xp):
+        st, f = m._stack, m._stack.fit
+        VA.append(ops.source_posteriors(x, st.X, st.theta, st.kind, f["L"], f["Linv_diag"], f["alpha"], st.y_mean, st.y_std,
+                                        n_points=st.n_points, want_var=False, keep_V=True, Linv=f["Linv"])["V"].contiguous())
+    # the batch (step 3): the studies' X' as query strips of 16 (filled up with a point of the box) and as leading points
+    strips = [(n + 15) // 16 for n in nps]
+    fill = torch.full((16, D), 0.5, dtype=torch.float64, device=dev)
+    Xq = torch.cat([t for x, k in zip(Xp, strips) for t in (x, fill[:16 * k - x.shape[0]])], 0)
+    pad = torch.nn.utils.rnn.pad_sequence
+    Xt = pad(Xp, batch_first=True)
+    y = torch.nn.functional.pad(pad([m.train_targets for m in models], batch_first=True), (0, n_max - max(ns)))
+    act = [m._active_tasks() for m in models]
+    w, active = torch.stack([a[0] for a in act]), torch.stack([a[1] for a in act]).to(torch.uint8)
+    theta = torch.stack([m.theta for m in models])
+    host = lambda vals, dt: torch.tensor(vals, dtype=dt).to(dev)   # noqa: E731
+    base = [sum(strips[:s]) for s in range(S)]
+    n_points, n_obs, n_fant = host(nps, torch.int32), host(ns, torch.int32), host(Fs, torch.int32)
+    strip_base = host(base, torch.int32)
+    group = host([s for s, k in enumerate(strips) for _ in range(k)], torch.int32)
+    m_all, s_all = host([m._m_all_f for m in models], torch.float64), host([m._s_all_f for m in models], torch.float64)
+    VA_tab = host([v.data_ptr() for v in VA], torch.int64)
+    src = parent if own else st0
+    fs = src.fit
+    own_kw = dict(task_base=host([m._stack.lo for m in models], torch.int32), tasks_per_group=st0.T) if own else {}
+    g = ops.source_posteriors_grouped(Xq, group, Xt, n_points, VA_tab, src.X, src.theta, src.kind, fs["Linv"], fs["alpha"], src.y_mean, src.y_std,
+                                      src.n_points, **own_kw)
+    blk = ops.studies_condition_block(g["mu"], g["cov"], strip_base, w, active, Xt, theta, y, n_points, n_obs, m_all, s_all, m0.kind)
+    fac = ops.potrf_batched(blk["Knn"], None, n_points=n_points, want_linv=True)
+    eps = eps.to(dev)
+    out = ops.studies_fantasy_condition(fac["L"], blk["resid"], blk["mean_p"], n_points, n_obs, fac["info"], eps, n_fant, m_all, s_all)
+    arrays = dict(Xq=Xq, group=group, Xt=Xt, y=y, w=w, active=active, theta=theta, n_points=n_points, n_obs=n_obs, n_fant=n_fant,
+                  strip_base=strip_base, m_all=m_all, s_all=s_all, eps=eps)
+    return dict(VA=VA, strip_base=base, arrays=arrays, block=blk, factor=fac, out=out, **{"pass": g})
+
+
+def fantasize_studies(models: Sequence[ScaMLGP], pending: Sequence[torch.Tensor], num_fantasies, generators: Sequence[Optional[torch.Generator]],
+                      observation_noise: bool = True) -> List[ScaMLGP]:
+    """``models[s].fantasize(pending[s], num_fantasies, generator=generators[s])`` for S studies at once: S fantasy models from a
+    constant number of launches and ONE host round trip, where every ``fantasize`` call makes several dozen launches and three.
+
+    ``models``: S ordinary ScaMLGP on one shared source stack, or on equal-T slices of one parent stack
+    (``meta_fit_scamlgp_studies``) -- the rule of ``utils.StudiesAcquisition``; ``pending[s]`` (p_s, D) with p_s >= 1 and
+    n_s + p_s <= 96; ``num_fantasies`` an int or one per study, at most 64; ``generators[s]`` as ``fantasize`` takes it.
+
+    Everything follows from ONE Cholesky factor L' of the joint block K' over X' = cat(train_X, pending) (csrc/gp_studies_condition.h):
+    the posterior at the pending points with observation noise has mean mean'_p + L_pn v, v = L_nn^-1 resid, and covariance
+    L_pp L_pp^T, so the samples are mean'_p + L_pn v + L_pp eps_f and alpha_f = L'^-T [v ; eps_f].  The steps:
+      1. per study the source-pass launch for V' = ``_train_VA`` of X'_s on the study's own stack -- the launch the conditioned model
+         makes today, the same bits; these S asynchronous launches are the per-study device work that is left;
+      2. per study ``eps_s = torch.randn(F, p_s, generator=...)`` with ``TargetPosterior.rsample``'s shape, dtype and device, so that a
+         generator ends where a ``fantasize`` call leaves it;
+      3. ONE value-mode grouped source pass over all studies' X' strips, ``ops.studies_condition_block``, ONE ``ops.potrf_batched``
+         (ragged sizes, the jitter ladder per study), ``ops.studies_fantasy_condition``;
+      4. one read-back of the studies' status: a block that fails on every rung raises ``ops.NotPSDError`` naming the study, as
+         ``fantasize`` does through ``psd_safe_cholesky``; the jitter a study's block needed is in its model's ``last_condition_info``
+         (its samples come from the jittered block);
+      5. the models, without ``ScaMLGP.__init__``'s source launches (``ScaMLGP._fantasy_of``): ``_VA`` = V'_s, the study's slice of the
+         factor with alpha_f kept as its target factor, ``source_means`` / ``source_covs`` cut out of the pass's outputs on first read.
+    ``observation_noise=False`` is not implemented: L_pp L_pp^T is the covariance WITH the noise."""
+    models, pending, generators = list(models), list(pending), list(generators)
+    S = len(models)
+    if S == 0:
+        return []
+    if len(pending) != S or len(generators) != S:
+        raise ValueError(f"got {len(pending)} pending sets and {len(generators)} generators for {S} models")
+    if not observation_noise:
+        raise NotImplementedError("fantasize_studies samples with observation noise (the factor of the joint block holds it)")
+    Fs = [int(num_fantasies)] * S if not isinstance(num_fantasies, (list, tuple)) else [int(v) for v in num_fantasies]
+    if len(Fs) != S:
+        raise ValueError(f"got {len(Fs)} fantasy counts for {S} models")
+    m0 = models[0]
+    st0 = m0._stack
+    parent = getattr(st0, "parent", None)
+    shared = all(m._stack is st0 for m in models)
+    own = (not shared) and parent is not None and all(getattr(m._stack, "parent", None) is parent and m._stack.T == st0.T for m in models)
+    D, dev = st0.D, m0.device
+    Xp = []
+    for s, m in enumerate(models):
+        if not (shared or own) or m.kind != m0.kind or m.T != m0.T:
+            raise ValueError("the studies' models must share one source stack and one kernel family")
+        if m._shard is not None:
+            raise NotImplementedError("fantasies are not implemented for a task-sharded source stack (shard=True)")
+        if m.num_fantasies is not None:
+            raise NotImplementedError("a fantasy model cannot be conditioned further")
+        x = torch.as_tensor(pending[s], dtype=torch.float64).to(dev).reshape(-1, D)
+        if not m.supports_posterior_grad() or x.shape[0] < 1 or m.n + x.shape[0] > 96 or m.n + x.shape[0] > st0.N or not 1 <= Fs[s] <= 64:
+            raise NotImplementedError(f"study {s}: fantasize_studies takes 1 <= n, p >= 1, n + p <= 96 (and <= the stack's N), D <= 15 and "
+                                      "at most 64 fantasies; use ScaMLGP.fantasize")
+        Xp.append(torch.cat([m.train_X, x], 0))
+    ns, nps = [m.n for m in models], [int(x.shape[0]) for x in Xp]
+    # 2. the draws, one host table for the batch
+    eps = torch.zeros(S, max(b - a for a, b in zip(ns, nps)), max(Fs), dtype=torch.float64)
+    for s, gen in enumerate(generators):
+        gdev = gen.device if gen is not None else torch.device("cpu")
+        e = torch.randn(Fs[s], nps[s] - ns[s], dtype=torch.float64, generator=gen, device=gdev)
+        eps[s, :nps[s] - ns[s], :Fs[s]] = e.transpose(0, 1).cpu()
+    # 1. and 3. on the device
+    b = _fantasy_batch(models, Xp, Fs, eps, own)
+    g, fac, out, VA, base = b["pass"], b["factor"], b["out"], b["VA"], b["strip_base"]
+    # 4. the one round trip
+    status = torch.cat([fac["info"].to(torch.float64), fac["jitter"]]).cpu()
+    info, jitter = status[:S].to(torch.int64).tolist(), status[S:].tolist()
+    bad = [s for s in range(S) if info[s] != 0]
+    if bad:
+        raise ops.NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to 1.0e-06 (the conditioned block of "
+                              f"stud{'ies' if len(bad) > 1 else 'y'} {bad[:8]}{'...' if len(bad) > 8 else ''}).")
+    # 5. the models
+    fantasies = []
+    for s, m in enumerate(models):
+        n, F, c0 = nps[s], Fs[s], 16 * base[s]
+        nb = (n + 15) // 16
+        alpha_f = out["alpha_f"][s, :n, :F].contiguous()
+        factor = dict(L=fac["L"][s:s + 1, :n, :n].contiguous(), alpha=alpha_f[:, 0].unsqueeze(0).contiguous(), quad=None,
+                      logdet=fac["logdet"][s:s + 1], info=fac["info"][s:s + 1], jitter=fac["jitter"][s:s + 1],
+                      Linv_diag=fac["Linv_diag"][s:s + 1, :nb].contiguous(), alpha_f=alpha_f)
+        rows = m._idx_dev   # (the model's tasks among the pass's rows: the stack's tasks, or the T slots of the study's slice)
+        means = lambda rows=rows, c0=c0, n=n: g["mu"][rows, c0:c0 + n].transpose(0, 1).contiguous()              # noqa: E731  (n', T)
+        covs = lambda rows=rows, c0=c0, n=n: g["cov"][rows, :n, c0:c0 + n].permute(1, 2, 0).contiguous()          # noqa: E731  (n', n', T)
+        fm = ScaMLGP._fantasy_of(m, Xp[s], out["y_fant"][s, :n - ns[s], :F].transpose(0, 1), VA[s], factor, means, covs)
+        fm.last_condition_info = dict(info=info[s], jitter=jitter[s])
+        fantasies.append(fm)
+    return fantasies

@@ -874,6 +874,80 @@ def target_factors_batched(batch: "TargetFitBatch", w: torch.Tensor, active: tor
     return out
 
 
+def studies_condition_block(mu: torch.Tensor, cov: torch.Tensor, strip_base: torch.Tensor, w: torch.Tensor, active: torch.Tensor,
+                            Xt: torch.Tensor, theta: torch.Tensor, y: torch.Tensor, n_points: torch.Tensor, n_obs: torch.Tensor,
+                            m_all: torch.Tensor, s_all: torch.Tensor, kind: int) -> Dict[str, torch.Tensor]:
+    """The training blocks of the CONDITIONED models of G studies from the value-mode grouped pass's outputs at the studies' own
+    X' = cat(train_X, X_pend) strips (``source_posteriors_grouped``: mu (T, Mq), cov (T, n_max, Mq); ``strip_base`` (G,) int32 the first
+    strip of a study) and the studies' padded arrays: w (G, T), active (G, T) uint8, Xt (G, n_max, D), theta (G, D + 2), y (G, n_max)
+    standardised targets of the observed rows, n_points (G,) int32 = n + p, n_obs (G,) int32 = n, m_all, s_all (G,).  One launch of
+    scaml_studies_condition_block_f64.  Returns dict(Knn (G, n_max, n_max), resid (G, n_max): zero in the pending rows, mean_p (G, n_max):
+    the prior mean at the pending rows); what lies past a study's n + p is zero."""
+    if mu.dim() != 2 or Xt.dim() != 3:
+        raise ValueError("mu must be (T, Mq) and Xt (G, n_max, D)")
+    T, Mq = (int(v) for v in mu.shape)
+    G, n_max, D = (int(v) for v in Xt.shape)
+    if Mq % 16:
+        raise ValueError(f"the query points come in whole strips of 16, got Mq = {Mq}")
+    mu = _check(mu, "mu", (T, Mq))
+    cov = _check(cov, "cov", (T, n_max, Mq))
+    strip_base = _check(strip_base, "strip_base", (G,), torch.int32)
+    w = _check(w, "w", (G, T))
+    active = _check(active, "active", (G, T), torch.uint8)
+    Xt = _check(Xt, "Xt", (G, n_max, D))
+    theta = _check(theta, "theta", (G, D + 2))
+    y = _check(y, "y", (G, n_max))
+    n_points = _check(n_points, "n_points", (G,), torch.int32)
+    n_obs = _check(n_obs, "n_obs", (G,), torch.int32)
+    m_all = _check(m_all, "m_all", (G,))
+    s_all = _check(s_all, "s_all", (G,))
+    dev = Xt.device
+    with torch.cuda.device(dev):
+        Knn = torch.zeros(G, n_max, n_max, dtype=torch.float64, device=dev)
+        resid = torch.zeros(G, n_max, dtype=torch.float64, device=dev)
+        mean_p = torch.zeros(G, n_max, dtype=torch.float64, device=dev)
+        rc = _lib.lib.scaml_studies_condition_block_f64(_ptr(mu), _ptr(cov), _ptr(strip_base), _ptr(w), _ptr(active), _ptr(Xt), _ptr(theta),
+                                                        _ptr(y), _ptr(n_points), _ptr(n_obs), _ptr(m_all), _ptr(s_all), Mq, G, n_max, T, D,
+                                                        int(kind), _ptr(Knn), _ptr(resid), _ptr(mean_p), _stream_handle())
+    _lib.check_rc(rc, "scaml_studies_condition_block_f64")
+    return dict(Knn=Knn, resid=resid, mean_p=mean_p)
+
+
+def studies_fantasy_condition(L: torch.Tensor, resid: torch.Tensor, mean_p: torch.Tensor, n_points: torch.Tensor, n_obs: torch.Tensor,
+                              info: torch.Tensor, eps: torch.Tensor, n_fant: torch.Tensor, m_all: torch.Tensor,
+                              s_all: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The fantasies and alpha_f of G studies from the factors L (G, n_max, n_max) / info (G,) int32 that ``potrf_batched`` returns for
+    ``studies_condition_block``'s Knn, its resid and mean_p, and the standard-normal draws eps (G, p_max, F_max) (row i of a study: the
+    F_g = ``n_fant[g]`` values of pending point i).  One launch of scaml_studies_fantasy_condition_f64.  Returns dict(alpha_f
+    (G, n_max, F_max) in ``target_fantasy_acqf_batched``'s layout, y_fant (G, p_max, F_max) the fantasy targets and mu_p (G, p_max) the
+    posterior mean at the pending points, both in original units); what lies past a study's n + p, p or F_g is zero.  A study with
+    ``info != 0`` or counts out of range holds NaN."""
+    if L.dim() != 3 or eps.dim() != 3:
+        raise ValueError("L must be (G, n_max, n_max) and eps (G, p_max, F_max)")
+    G, n_max = int(L.shape[0]), int(L.shape[1])
+    p_max, F_max = int(eps.shape[1]), int(eps.shape[2])
+    L = _check(L, "L", (G, n_max, n_max))
+    resid = _check(resid, "resid", (G, n_max))
+    mean_p = _check(mean_p, "mean_p", (G, n_max))
+    n_points = _check(n_points, "n_points", (G,), torch.int32)
+    n_obs = _check(n_obs, "n_obs", (G,), torch.int32)
+    info = _check(info, "info", (G,), torch.int32)
+    eps = _check(eps, "eps", (G, p_max, F_max))
+    n_fant = _check(n_fant, "n_fant", (G,), torch.int32)
+    m_all = _check(m_all, "m_all", (G,))
+    s_all = _check(s_all, "s_all", (G,))
+    dev = L.device
+    with torch.cuda.device(dev):
+        alpha_f = torch.zeros(G, n_max, F_max, dtype=torch.float64, device=dev)
+        y_fant = torch.zeros(G, p_max, F_max, dtype=torch.float64, device=dev)
+        mu_p = torch.zeros(G, p_max, dtype=torch.float64, device=dev)
+        rc = _lib.lib.scaml_studies_fantasy_condition_f64(_ptr(L), _ptr(resid), _ptr(mean_p), _ptr(n_points), _ptr(n_obs), _ptr(info), _ptr(eps),
+                                                          _ptr(n_fant), _ptr(m_all), _ptr(s_all), G, n_max, p_max, F_max, _ptr(alpha_f),
+                                                          _ptr(y_fant), _ptr(mu_p), _stream_handle())
+    _lib.check_rc(rc, "scaml_studies_fantasy_condition_f64")
+    return dict(alpha_f=alpha_f, y_fant=y_fant, mu_p=mu_p)
+
+
 def mll_backward_workspace(T: int, N: int, D: int, device) -> Dict[str, torch.Tensor]:
     """Reusable buffers of ``mll_backward`` for a (T, N, D) stack: the explicit inverse factors (T N^2 doubles) and
     the per-tile partial sums.  An optimiser loop allocates them once (scaml_mll_backward_workspace_doubles)."""

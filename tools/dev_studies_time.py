@@ -14,7 +14,7 @@ medians over the timed steps (the first step of a size is a warm-up and is not c
   python tools/dev_studies_time.py --own-stacks [--sizes 8,32,128] [--out profiles/studies_own_stacks_timings.txt]
       one source stack PER study at hartmann6.py's shape (see own_stacks_table)
   python tools/dev_studies_time.py --pending [--sizes 8,32] [--steps K] [--out profiles/studies_pending_timings.txt]
-      every study holds pending evaluations: pending_mode='batched' against 'per_study' (see pending_table)
+      every study holds pending evaluations: fantasy_setup='batched' and pending_mode='batched' against 'per_study' (see pending_table)
 """
 import argparse
 import os
@@ -41,7 +41,7 @@ ap.add_argument("--sweep", default=None, help="with a list such as 1,2,4,8,16: t
 ap.add_argument("--evals-per-call", type=int, default=None, help="ops.ACQF_OPT_EVALS_PER_CALL for --suggest")
 ap.add_argument("--score", action="store_true", help="device suggest(): score_mode='batched' against 'per_study', its split into parts, and score alone")
 ap.add_argument("--own-stacks", action="store_true", help="per-study source stacks: meta-fit, BO step and the grouped pass against what a caller had before")
-ap.add_argument("--pending", action="store_true", help="studies with pending evaluations: pending_mode='batched' against 'per_study', and the evaluation launch alone")
+ap.add_argument("--pending", action="store_true", help="studies with pending evaluations: fantasy_setup='batched' against pending_mode='batched' against 'per_study', and the evaluation launch alone")
 args = ap.parse_args()
 
 T, N, D, N_END, RESTARTS = 32, 512, 6, 80, 2
@@ -344,22 +344,30 @@ def score_table():
 
 
 def pending_table():
-    """Every study holds p pending evaluations (p = 1, then 4; F = 16 fantasies, n = 80 observed points, 10 starts per study):
-    ``pending_mode="batched"`` against ``"per_study"`` -- the parent's behaviour, every study its own ``ScaMLGPBOLoop.suggest()`` --, in
-    suggest_mode "device" and "lockstep".  Two ScaMLGPBOStudies on the same data, timed alternately call by call in one process; after
-    every suggest the pending lists are put back to the p points, so every call sees the same shapes (each draws new fantasies and
-    starts from the studies' generators).  The first call of a row is a warm-up and is not counted; median and min .. max per side.
-    Then the split of the batched side's suggest (``profile_parts``: "stage1" holds the per-study set-up -- fantasize with the
-    conditioned model's source pass, factor and alpha, through the study's own scoring pass).  Last, the evaluation launch alone on one
-    grouped source pass's outputs: scaml_target_fantasy_acqf_batched_f64 against scaml_target_acqf_batched_f64 at F = 1 (the same
-    ordinary studies) and at F = 16 (the fantasy models; (7g) on their arrays with column 0 of alpha_f, for the time only)."""
+    """Every study holds p pending evaluations (p = 1, then 4; F = 16 fantasies, n = 80 observed points, 10 starts per study), three
+    sides: ``pending_mode="batched"`` with ``fantasy_setup="batched"`` (all fantasy models from one ``model.fantasize_studies`` call),
+    ``pending_mode="batched"`` alone (the fantasy model of every study from its own ``fantasize`` call: the yardstick of the first side)
+    and ``"per_study"`` (every study its own ``ScaMLGPBOLoop.suggest()``), with both ``score_mode``s, in suggest_mode "device" and
+    "lockstep".  Three ScaMLGPBOStudies on the same data, timed alternately call by call in one process; after every suggest the pending
+    lists are put back to the p points, so every call sees the same shapes (each draws new fantasies and starts from the studies'
+    generators).  The first call of a row is a warm-up and is not counted; median and min .. max per side.  A side counts as faster than
+    its yardstick only if the gain exceeds the yardstick's own min .. max spread.
+    Then the split of the two batched sides' suggest (``profile_parts``: "setup" is the ``fantasize_studies`` call; without it "stage1"
+    holds the per-study set-up -- fantasize with the conditioned model's source pass, factor and alpha, through the study's own scoring
+    pass), and the split of one ``fantasize_studies`` call: the S V' launches, the module copies, the rest.  Last, the evaluation launch
+    alone on one grouped source pass's outputs: scaml_target_fantasy_acqf_batched_f64 against scaml_target_acqf_batched_f64 at F = 1
+    (the same ordinary studies) and at F = 16 (the fantasy models; (7g) on their arrays with column 0 of alpha_f, for the time only)."""
+    import copy
+
     F, starts = 16, 10
     kw = dict(KW, max_pending_evaluations=8, num_fantasies=F)
     say(f"# suggest() of S studies that all hold p pending evaluations, T = {T}, N = {N}, D = {D}, n = {N_END}, F = {F}, UCB, 1,024 raw candidates and "
         f"{starts} starts per study; ms, median of {args.steps} calls, (min .. max) per side")
+    say("# sides: setup = pending_mode='batched' with fantasy_setup='batched'; batched = pending_mode='batched' (its yardstick); per_study")
     for S in [int(v) for v in args.sizes.split(",")]:
         seeds = list(range(100, 100 + S))
-        sides = {k: ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, suggest_mode="device", pending_mode=k, **kw) for k in ("batched", "per_study")}
+        make = {"setup": dict(pending_mode="batched", fantasy_setup="batched"), "batched": dict(pending_mode="batched"), "per_study": dict()}
+        sides = {k: ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, suggest_mode="device", **o, **kw) for k, o in make.items()}
         for side in sides.values():
             for s in range(S):
                 g = torch.Generator().manual_seed(seeds[s])
@@ -375,36 +383,61 @@ def pending_table():
                     for s in range(S):
                         side[s].pending = pend[s].clone()
 
-            for mode in ("device", "lockstep"):
+            for score_mode, mode in (("per_study", "device"), ("batched", "device"), ("per_study", "lockstep"), ("batched", "lockstep")):
                 ms = {k: [] for k in sides}
                 for r in range(args.steps + 1):
                     for k, side in sides.items():
-                        side.suggest_mode = mode
+                        side.suggest_mode, side.score_mode = mode, score_mode
                         reset()
                         t, _ = timed(side.suggest)
                         if r:
                             ms[k].append(1e3 * t)
-                        assert len(side.last_suggest_info["batched"]) == (S if k == "batched" else 0)
+                        assert len(side.last_suggest_info["batched"]) == (0 if k == "per_study" else S)
                 med = {k: statistics.median(v) for k, v in ms.items()}
-                gain, spread = med["per_study"] - med["batched"], max(ms["per_study"]) - min(ms["per_study"])
-                say(f"  S = {S:>3} p = {p} {mode:>8}: batched {med['batched']:9.1f} ({min(ms['batched']):.1f} .. {max(ms['batched']):.1f})   per_study "
-                    f"{med['per_study']:9.1f} ({min(ms['per_study']):.1f} .. {max(ms['per_study']):.1f})   per_study / batched = {med['per_study'] / med['batched']:5.2f}x   "
-                    f"gain {gain:.1f} ms against a per_study spread of {spread:.1f} ms: "
+                cell = lambda k: f"{k} {med[k]:9.1f} ({min(ms[k]):.1f} .. {max(ms[k]):.1f})"   # noqa: E731
+                gain, spread = med["batched"] - med["setup"], max(ms["batched"]) - min(ms["batched"])
+                say(f"  S = {S:>3} p = {p} score {score_mode:>9} {mode:>8}: {cell('setup')}   {cell('batched')}   {cell('per_study')}   "
+                    f"batched / setup = {med['batched'] / med['setup']:5.2f}x   gain {gain:.1f} ms against a batched spread of {spread:.1f} ms: "
                     f"{'faster by more than the spread' if gain > spread else ('a LOSS' if gain < 0 else 'INSIDE the spread')}")
-                side = sides["batched"]
-                side.profile_parts = True
-                got = []
-                for _ in range(3):
-                    reset()
-                    side.suggest()
-                    got.append(dict(side.last_suggest_info["parts"]))
-                side.profile_parts = False
-                q = {name: 1e3 * statistics.median(g_.get(name, 0.0) for g_ in got) for name in ("stage1", "packing", "rounds", "stage3")}
-                say(f"#       split, batched {mode:>8}: stage 1 with the per-study set-up {q['stage1']:8.2f}   packing {q['packing']:8.2f}   rounds {q['rounds']:8.2f}   "
-                    f"stage 3 {q['stage3']:8.2f}   ({q['stage1'] / S:.2f} ms of stage 1 per study)")
+                for k in ("setup", "batched"):
+                    side = sides[k]
+                    side.profile_parts = True
+                    got = []
+                    for _ in range(3):
+                        reset()
+                        side.suggest()
+                        got.append(dict(side.last_suggest_info["parts"]))
+                    side.profile_parts = False
+                    q = {name: 1e3 * statistics.median(g_.get(name, 0.0) for g_ in got) for name in ("setup", "stage1", "packing", "rounds", "stage3")}
+                    say(f"#       split, {k:>7} {mode:>8}: set-up {q['setup']:8.2f}   stage 1 {q['stage1']:8.2f}   packing {q['packing']:8.2f}   "
+                        f"rounds {q['rounds']:8.2f}   stage 3 {q['stage3']:8.2f}   ({(q['setup'] + q['stage1']) / S:.2f} ms of set-up + stage 1 per study)")
+            # one fantasize_studies call, and what of it stays per study
+            reset()
+            studies = sides["setup"].studies
+            models = [st.model.eval() for st in studies]
+            gens = [torch.Generator().manual_seed(7 + s) for s in range(S)]
+            whole, va, cp = [], [], []
+            for r in range(args.steps + 1):
+                t0, _ = timed(lambda: M.fantasize_studies(models, [st.pending for st in studies], F, gens))
+                Xp = [torch.cat([m.train_X, st.pending.to(dev)], 0) for m, st in zip(models, studies)]
+
+                def v_launches():
+                    for m, x in zip(models, Xp):
+                        stk, f = m._stack, m._stack.fit
+                        ops.source_posteriors(x, stk.X, stk.theta, stk.kind, f["L"], f["Linv_diag"], f["alpha"], stk.y_mean, stk.y_std,
+                                              n_points=stk.n_points, want_var=False, keep_V=True, Linv=f["Linv"])
+
+                t1, _ = timed(v_launches)
+                t2, _ = timed(lambda: [(copy.deepcopy(m.likelihood), copy.deepcopy(m.covar_module)) for m in models])
+                if r:
+                    whole.append(1e3 * t0), va.append(1e3 * t1), cp.append(1e3 * t2)
+            w_, v_, c_ = statistics.median(whole), statistics.median(va), statistics.median(cp)
+            say(f"#     fantasize_studies alone, S = {S}, p = {p}: {w_:8.2f} ms ({min(whole):.2f} .. {max(whole):.2f}), {w_ / S:.3f} ms per study; of it the S V' "
+                f"launches {v_:.2f} ms ({100 * v_ / w_:.0f} %), the module copies {c_:.2f} ms ({100 * c_ / w_:.0f} %)")
         # the evaluation launch alone, on one source pass's outputs
         reset()
         studies = sides["batched"].studies
+        models = gens = Xp = None
         ordinary = [utils.UpperConfidenceBound(st.model.eval(), 9.0) for st in studies]
         fantasy = [st.acquisition_function() for st in studies]
         Xq = torch.rand(S * starts, D, dtype=torch.float64, generator=torch.Generator().manual_seed(S)).to(dev)
