@@ -23,7 +23,10 @@
 //       D_j -= L L^T by 8 MFMAs of its own -> factor D_j (16 rank-1 MFMA updates on the symmetric
 //       block, the next pivot formed ahead on the VALU so the 64-cycle MFMA latency stays off the
 //       pivot chain; a second accumulator receives the same row operations and ends as
-//       W_j = L_jj^-1) -> publish flagW[j].  It runs ahead of the update waves.
+//       W_j = L_jj^-1) -> publish flagW[j].  It runs ahead of the update waves.  Steps 0 and 1 run INSIDE the kernel-matrix
+//       build ("early chain"): D_0, R_1 and D_1 are the first tiles anyone builds, their owners park them at once (cntE),
+//       and the panel wave factors them between two of the tile images it builds for the others -- the update waves find
+//       flagW[0] and flagW[1] published when they leave the build's barriers.
 //   update waves, iteration k (column k final in LDS = cntT[k] complete):
 //       U1  column k+1 and the diagonal tile D_{k+2} get the rank-16 update of panel k first; D_{k+2}
 //           and R_{k+2} are parked for the panel wave (cntS[k])
@@ -124,6 +127,9 @@ __device__ __forceinline__ int opaque_s(int v) {
 // traffic (on gfx950 that is s_waitcnt lgkmcnt(0) around the atomic; HBM stores are not waited for).
 #ifndef SCAML_SLEEP
 #define SCAML_SLEEP 1   // s_sleep argument of the pollers (64-cycle units); A/B-tuned
+#endif
+#ifndef SCAML_EARLY_CHAIN
+#define SCAML_EARLY_CHAIN 1   // panel steps j = 0, 1 run during the kernel-matrix build (0: after it, as before; A/B builds)
 #endif
 typedef __attribute__((address_space(3))) int lds_int_t;
 __device__ __forceinline__ int sync_peek(const int* p) {
@@ -399,6 +405,10 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   const int XROWS = ((p.D + 3) & ~3) + 4;   // staged point stack: D rounded up to the MFMA k-step + 4 tail rows
   const int buildA = XROWS * NP + ((WU == 7 && NB == 16) ? 24 * 256 : 0);
   const int regionA = (buildA > REGION_A) ? buildA : REGION_A;
+  // Early chain: while xsT and the tile images end in front of WAll, the panel wave's outputs of steps 0 and 1 (W_0, W_1, LT) and
+  // the parked tiles (DG, CR) can go to their final places during the build, and those two steps run inside it.  Uniform over the
+  // workgroup.  (N = 256: D <= 20; the other instances: D <= 44.)
+  const bool early = SCAML_EARLY_CHAIN && buildA <= 3 * PANEL;
   double* ytil = lds + regionA;   // [NP] running right-hand side
   double* vv = ytil + NP;         // [NP] v = L^-1 y
   double* ww = PT + 2 * PANEL;    // [NP] back-substitution workspace -> alpha: tail only, on the (then free) third column buffer
@@ -414,7 +424,8 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   int* cntY = cntS + NB;         // [NB] update waves done folding column k into the right-hand side
   int* cntU = cntY + NB;         // [NB] update waves done with U2(k): nobody reads column k any more
   int* cntB = cntU + NB;         // [NB] back-substitution: tiles (i, k), i > k, already folded into w_k
-  // End of the carve, cntB + NB: the launcher asks for fit_lds_doubles(NB, WU, D) (gp_fit_params.h) -- change both together.
+  int* cntE = cntB + NB;         // [2] early chain: D_0 parked during the build (1 arrival); R_1 and D_1 parked (2 arrivals)
+  // End of the carve, cntE + 2: the launcher asks for fit_lds_doubles(NB, WU, D) (gp_fit_params.h) -- change both together.
   // (D is a run-time extent, so the end is no constant to assert on, and taking the offsets from the header would alter
   // the address arithmetic of a kernel whose instruction stream is kept as it is.)
 
@@ -491,7 +502,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
     if (!from_matrix)   // strided: the workgroup may have fewer threads than D (128 threads at N <= 32, D up to ~588)
       for (int d = tid; d < D; d += NTHREADS) invl[d] = 1.4142135623730951 / th[d];
     if (tid < 2) flagp[tid] = 0;
-    if (tid < 6 * NB) flagW[tid] = 0;
+    if (tid < 6 * NB + 2) flagW[tid] = 0;   // every hand-off counter, cntE included
     exp2_table_init(exptab, tid);
     __syncthreads();
     // ---- stage x' = sqrt(2) X / l transposed into LDS: xsT[d][row], rows D .. D4-1 zero, then the tail rows
@@ -594,21 +605,83 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
         }
       }
     };
+    // Panel wave, step j without its wait: D_j and R_j from where their owners parked them -> L_j,j-1, D_j -= L L^T -> factor
+    // -> diag(L), flagW[j].  Returns what potf2_inv_block returns (a failed pivot is published as flagW[j] = 2).
+    auto panel_factor = [&](int j) __attribute__((always_inline)) -> int {
+      double* Wj = WAll + j * 16 * PP;
+      d4_t a;
+      {
+        const double* dg = DG + (j & 1) * 256 + lane;   // symmetric: the transposed image is the block
+#pragma unroll
+        for (int g = 0; g < 4; ++g) a[g] = dg[64 * g];
+      }
+      if (j >= 1) {
+        // tm = W_{j-1} R_j^T = (L_j,j-1)^T: in the C/D layout that is L_j,j-1 in operand position,
+        // so D_j -= L L^T follows without a transpose through LDS
+        const double* pw = WAll + (j - 1) * 16 * PP + lq * PP + lc;   // W[lc][lq + 4m] out of the transposed copy
+        const double* pr = CR + (j & 1) * 256 + lane;   // register image of the transposed tile = R[lc][lq + 4m]
+        d4_t tm = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int m = 0; m < 4; ++m) tm = __builtin_amdgcn_mfma_f64_16x16x4f64(pw[4 * m * PP], pr[64 * m], tm, 0, 0, 0);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) a = __builtin_amdgcn_mfma_f64_16x16x4f64(tm[m], tm[m], a, 0, 0, 1);
+      }
+      STAMP(4);
+      double* LTj = LT + (j & 1) * 16 * PP;
+      const int bad = potf2_inv_block(a, LTj, Wj, trash, j, lane);
+      STAMP(5);
+      if (lq == 0) dl[16 * j + lc] = LTj[lc * PP + lc];   // diag(L) for logdet
+      if (bad) {
+        if (lane == 0) flagp[0] = bad;
+        sync_publish(flagW + j, 2, lane);
+      } else {
+        sync_publish(flagW + j, 1, lane);
+      }
+      return bad;
+    };
+    // Which off-diagonal tiles of each block row the update waves hold, for the back-substitution at the end -- lane w lists
+    // wave w (panel wave, behind an early step of its loop: off the critical path, the chain waits for parked tiles next anyway).
+    auto list_rows = [&]() __attribute__((always_inline)) {
+      if (lane < WU) {
+        int* rl = rowlist + lane * NB * 8;
+#pragma clang loop unroll(disable)
+        for (int i = 0; i < NB; ++i) rl[8 * i] = 0;
+        int jj = 0, r = lane;
+#pragma clang loop unroll(disable)
+        for (int sl = 0; sl < SLOTS; ++sl) {
+          while (jj < NB && r >= NB - jj) { r -= NB - jj; ++jj; }
+          if (jj >= NB) break;
+          if (r > 0) {
+            const int i = jj + r, c = rl[8 * i];
+            if (c < 7) { rl[8 * i + 1 + c] = ((jj == i - 1) << 16) | (sl << 8) | jj; rl[8 * i] = c + 1; }   // bit 16: next to the diagonal
+          }
+          r += WU;
+        }
+      }
+    };
     // The build is VALU work, two waves per SIMD -- except on the SIMD of the (otherwise idle) panel
     // wave.  With 7 update waves the panel wave therefore builds the last slots of the six update waves that
     // do not share its SIMD into LDS images, which their owners pick up after the barrier.  The second wave
     // of a SIMD (4, 5, 6) only gets the issue slots its older mate leaves (measured 3.0 k cycles per tile
     // against 2.6 k; the panel wave 3.8 k), so it hands over two tiles (slots 17, 18) and the first waves
-    // one (slot 19): 9 of the 136 tiles.  (Round 1: three and one, 12 tiles; re-tuned at the end of round 2 together with
-    // PSTORE below, after the panel loop had changed: 106.8 -> 105.3 us in interleaved A/B runs.)
+    // none: 6 of the 136 tiles.  (Round 1: three and one, 12 tiles; two and one, 9 tiles, from the end of round 2 on; re-tuned
+    // with the early chain, which gives the panel wave two panel steps to do inside the build: 20 / 17 97.0 us, 19 / 18 97.4,
+    // 20 / 18 97.6, 19 / 17 99.2, 20 / 16 99.4, 18 / 17 102.0 against 99.8 before, profiles/early_chain_timings.txt.)
+    constexpr int JE = NB > 1 ? 2 : 1;   // panel steps of the early chain
     constexpr bool PANEL_BUILDS = (WU == 7 && NB == 16);
     constexpr int KMATE = 3;   // wave KMATE shares the panel wave's SIMD (waves go round-robin)
 #ifndef SCAML_KOLD
-#define SCAML_KOLD 19
+#define SCAML_KOLD 20
 #define SCAML_KYOUNG 17
 #endif
     auto kslot_of = [](int w) { return w < KMATE ? SCAML_KOLD : SCAML_KYOUNG; };
     double* KT = lds + XROWS * NP;   // [6][4][256] register images, behind xsT
+    // Early chain: the owners of D_0, R_1 and D_1 park their tile (the register image park_slot writes) the moment it is
+    // built and arrive on cntE; the LDS unit takes a wave's instructions in order, so the image is there before the count.
+    auto park_early = [&](double* dst, int* cnt, const double (&kt)[4]) __attribute__((always_inline)) {
+      dst[lane] = kt[0]; dst[64 + lane] = kt[1]; dst[128 + lane] = kt[2]; dst[192 + lane] = kt[3];
+      sync_arrive(cnt, lane);
+    };
     if (!is_panel) {
       int kj = 0, kr = wave;  // column / row-in-column of the current slot's tile
       // (issuing the distances of the next tile ahead of the evaluation of this one was tried: no gain, the
@@ -620,14 +693,36 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
           double kt[4];                                                                            \
           tile_eval(kj, kr, tile_dist(kj, kr), kt);                                                \
           TILE_SET(r0, r1, r2, r3, r4, r5, r6, r7, kt[0], kt[1], kt[2], kt[3]);                    \
+          if (early) {                                                                             \
+            if (S == 0 && wave == 0) park_early(DG, cntE, kt);                   /* D_0 */         \
+            if (NB > 1 && S == 1 / WU && wave == 1 % WU) park_early(CR + 256, cntE + 1, kt);   /* R_1 = tile 1 */  \
+            if (NB > 1 && S == NB / WU && wave == NB % WU) park_early(DG + 256, cntE + 1, kt); /* D_1 = tile off(1) */ \
+          }                                                                                        \
           if (zfill && kr != 0) zero_mirror(kj, kj + kr);                                          \
           kr += WU;                                                                                \
         }                                                                                          \
       }
       SCAML_TILE_LIST(SCAML_KBUILD_)
 #undef SCAML_KBUILD_
-    } else if (PANEL_BUILDS) {
-      for (int idx = 0; idx < 6 * 4; ++idx) {
+    } else if (PANEL_BUILDS || early) {
+      // The panel wave: its tile images, and between two of them (early chain) step 0 as soon as D_0 is parked, step 1 as
+      // soon as R_1 and D_1 are; what is left of the two steps after the last image waits for its tiles here.
+      constexpr int NIMG = PANEL_BUILDS ? 6 * 4 : 0;
+      int jdone = early ? 0 : JE, next = 0;
+      while (next < NIMG || jdone < JE) {
+        if (jdone < JE) {
+          if (sync_peek(cntE + jdone) > jdone) {
+            STAMP(8);
+            __builtin_amdgcn_s_setprio(3);   // (as in the chain; 0 and 1 measured the same, the steps behind the last image 3 us slower)
+            const int bad = panel_factor(jdone);
+            STAMP(9);
+            __builtin_amdgcn_s_setprio(0);
+            jdone = bad ? JE : jdone + 1;   // (a failed pivot ends the chain: flagp[0] tells after the barriers)
+            continue;
+          }
+          if (next >= NIMG) { __builtin_amdgcn_s_sleep(SCAML_SLEEP); continue; }
+        }
+        const int idx = next++;
         const int w6 = idx >> 2, w = w6 + (w6 >= KMATE), sl = kslot_of(w) + (idx & 3);
         const int t = sl * WU + w;
         if (sl >= SLOTS || t >= NT) continue;
@@ -671,14 +766,17 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
     auto park_tile = [&](int t, double* dst) {
       if (t % WU == wave) park_slot(t / WU, dst);
     };
-    if (!is_panel) {
-      park_tile(off(0), DG);
-      if (NB > 1) {
-        park_tile(off(1), DG + 256);
-        park_tile(off(0) + 1, CR + 256);   // R_1 = tile (1, 0)
+    // (early chain: all three were parked during the build, and the panel wave is done with them)
+    if (!early) {
+      if (!is_panel) {
+        park_tile(off(0), DG);
+        if (NB > 1) {
+          park_tile(off(1), DG + 256);
+          park_tile(off(0) + 1, CR + 256);   // R_1 = tile (1, 0)
+        }
       }
+      __syncthreads();
     }
-    __syncthreads();
     STAMP(2);
 
     // One finished sub-diagonal tile (ti, c): read back from the LDS column buffer in row segments -> HBM.
@@ -751,40 +849,16 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
       // (it is the youngest wave on its SIMD and would lose every issue slot to the update wave
       //  streaming MFMAs next to it: raised priority for the whole chain)
       __builtin_amdgcn_s_setprio(3);
-      for (int j = 0; j < NB; ++j) {
-        double* Wj = WAll + j * 16 * PP;
+      // (early chain: steps 0 and 1 ran during the build -- on from step 2, or not at all after a failed pivot there)
+      int j0 = 0;
+      if (early) j0 = flagp[0] ? NB : JE;
+      if (early && NB <= JE) list_rows();   // (no step left to attach it to)
+      for (int j = j0; j < NB; ++j) {
         // D_j (updates of panels <= j-2 applied) and the raw tile R_j = A[j][j-1] were parked by their
         // owners during U1(j-2): one whole step of slack, the chain does not wait in steady state
         if (j >= 2) sync_wait_ge(cntS + j - 2, WU);
         STAMP(3);
-        d4_t a;
-        {
-          const double* dg = DG + (j & 1) * 256 + lane;   // symmetric: the transposed image is the block
-#pragma unroll
-          for (int g = 0; g < 4; ++g) a[g] = dg[64 * g];
-        }
-        if (j >= 1) {
-          // tm = W_{j-1} R_j^T = (L_j,j-1)^T: in the C/D layout that is L_j,j-1 in operand position,
-          // so D_j -= L L^T follows without a transpose through LDS
-          const double* pw = WAll + (j - 1) * 16 * PP + lq * PP + lc;   // W[lc][lq + 4m] out of the transposed copy
-          const double* pr = CR + (j & 1) * 256 + lane;   // register image of the transposed tile = R[lc][lq + 4m]
-          d4_t tm = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-          for (int m = 0; m < 4; ++m) tm = __builtin_amdgcn_mfma_f64_16x16x4f64(pw[4 * m * PP], pr[64 * m], tm, 0, 0, 0);
-#pragma unroll
-          for (int m = 0; m < 4; ++m) a = __builtin_amdgcn_mfma_f64_16x16x4f64(tm[m], tm[m], a, 0, 0, 1);
-        }
-        STAMP(4);
-        double* LTj = LT + (j & 1) * 16 * PP;
-        const int bad = potf2_inv_block(a, LTj, Wj, trash, j, lane);
-        STAMP(5);
-        if (lq == 0) dl[16 * j + lc] = LTj[lc * PP + lc];   // diag(L) for logdet
-        if (bad) {
-          if (lane == 0) flagp[0] = bad;
-          sync_publish(flagW + j, 2, lane);
-          break;
-        }
-        sync_publish(flagW + j, 1, lane);
+        if (panel_factor(j)) break;
         STAMP_AT(j);
         STAMP(9);
         // Column j-2 (final in its LDS buffer since cntS[j-2]) goes to HBM and into the running right-hand side AFTER
@@ -822,24 +896,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
         STAMP(6);
         if (j >= 2) fold_column(j - 2);
         STAMP(7);
-        if (j == 1 && lane < WU) {
-          // Off the critical path (the chain waits for parked tiles next anyway): which off-diagonal tiles of
-          // each block row the update waves hold, for the back-substitution at the end -- lane w lists wave w.
-          int* rl = rowlist + lane * NB * 8;
-#pragma clang loop unroll(disable)
-          for (int i = 0; i < NB; ++i) rl[8 * i] = 0;
-          int jj = 0, r = lane;
-#pragma clang loop unroll(disable)
-          for (int sl = 0; sl < SLOTS; ++sl) {
-            while (jj < NB && r >= NB - jj) { r -= NB - jj; ++jj; }
-            if (jj >= NB) break;
-            if (r > 0) {
-              const int i = jj + r, c = rl[8 * i];
-              if (c < 7) { rl[8 * i + 1 + c] = ((jj == i - 1) << 16) | (sl << 8) | jj; rl[8 * i] = c + 1; }   // bit 16: next to the diagonal
-            }
-            r += WU;
-          }
-        }
+        if (j == (early ? JE : 1)) list_rows();   // (next to the first step of this loop that has slack behind it)
       }
       if (!flagp[0]) {
         // the last two columns: column NB-2 once every update wave has finalised its tiles of it (nothing reuses its
@@ -861,6 +918,8 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
       // This wave's tile schedule (csrc/gf_schedule.hpp), one word per lane, worked out once per attempt in the shadow of
       // the panel wave's first diagonal block: which tile a slot holds never changes, so the phases below fetch a
       // slot's operand offsets and a column's slot range with one v_readlane instead of walking the columns again.
+      // (With the early chain nothing hides it any more; working it out in front of the build's barrier instead measured
+      //  1.0 us slower, profiles/early_chain_timings.txt.)
       // (from a copy of the lane number that the compiler cannot trace back: nothing of this is computed ahead of the
       //  branch that separates the update waves from the panel wave, where it would cost the panel wave a register)
       int ul = lane;
@@ -973,7 +1032,9 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
           int fw;
           while ((fw = sync_peek(flagW + c)) == 0) __builtin_amdgcn_s_sleep(SCAML_SLEEP);
           STAMP_K(k, 4);
-          STAMP(5);
+#ifdef SCAML_STAMPS
+          if (k <= 0) { STAMP(12); } else { STAMP(5); }   // (diagnostic build: the waits for flagW[0] and flagW[1] on their own)
+#endif
           if (fw == 2) break;
           const double* Wc = WAll + c * 16 * PP;
           const int sa = slo_at(c), sb = slo_at(c + 1), offc = off(c);

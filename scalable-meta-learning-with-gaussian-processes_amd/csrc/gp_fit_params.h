@@ -105,7 +105,7 @@ constexpr size_t fit_lds_doubles(int nb, int wu, int D) {
   const size_t np = (size_t)nb * 16;
   const size_t regionA = 3 * np * FIT_PP + (size_t)(nb + 2) * 16 * FIT_PP + 4 * 256;   // PT[3], WAll[nb], LT[2], DG[2], CR[2]
   const size_t buildA = (size_t)(((D + 3) & ~3) + 4) * np + (nb == 16 ? 24 * 256 : 0);   // staged points (+ tail rows) + the panel wave's tile images (N > 128 only)
-  // + vectors, trash/exp table, row lists, 1/l, fail flag + 6 nb hand-off counters (ints)
+  // + vectors, trash/exp table, row lists, 1/l, fail flag (2 ints) + 6 nb hand-off counters + the 2 of the early chain (ints)
   return (buildA > regionA ? buildA : regionA) + 3 * np + 160 + (size_t)wu * nb * 4 + D + (D & 1) + 2 + 3 * (size_t)nb;
 }
 

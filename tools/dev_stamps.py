@@ -48,9 +48,9 @@ if PER_PANEL:
         print(f"{k:2d} {med[k]:12.0f} {med[k]-(med[k-1] if k else 0):8.0f}   | {medp[k]:12.0f} {medp[k]-(medp[k-1] if k else 0):8.0f}")
     sys.exit(0)
 # stamp slots: 0-2 common; 3-9 differ per role; 10-15 tail
-names_u = {0: "load X,y", 9: "K-build (own tiles)", 1: "K-build: barrier + image loads", 2: "prologue (park tiles)", 3: "wait cntT[k]", 4: "U1: col k+1, D_k+2 + park", 5: "wait flagW[k+1]",
+names_u = {0: "load X,y", 9: "K-build (own tiles)", 1: "K-build: barrier + image loads", 2: "prologue (park tiles)", 3: "wait cntT[k]", 4: "U1: col k+1, D_k+2 + park", 5: "wait flagW[k+1], k >= 1",
            6: "F: v, trsm, panel write, fold", 7: "U2: bulk update", 8: "column k+1 -> HBM", 15: "loop exit barrier", 11: "tail: M_k products+bar",
-           12: "-", 13: "backsub: wait alpha + folds", 14: "backsub: barrier", 10: "tail: rest"}
+           12: "wait flagW[0], flagW[1]", 13: "backsub: wait alpha + folds", 14: "backsub: barrier", 10: "tail: rest"}
 names_p = {0: "load X,y", 8: "K-build (15 tile images)", 1: "K-build: barrier", 2: "prologue", 3: "wait cntS[j-2] (D_j, R_j)", 4: "own TRSM + diag update", 5: "potf2",
            9: "dl + publish", 6: "column j-2 -> HBM (first PSTORE)", 7: "fold column j-2 into rhs", 15: "loop exit barrier",
            11: "tail: scalars+bar", 12: "backsub: chain steps", 13: "backsub: wait for w_k", 14: "backsub: barrier", 10: "tail: rest"}
