@@ -35,6 +35,11 @@ extern "C" {
 #define SCAML_KIND_RBF 0      /* gpytorch RBFKernel:    exp(-r^2/2)                        */
 #define SCAML_KIND_MATERN52 1 /* gpytorch MaternKernel(nu=2.5): (1+√5r+5r²/3)exp(-√5r)      */
 
+/* acquisition codes (`acqf`): UCB, EI, and EI | LOG = 17 for LogEI; SCAML_ACQF_LOG alone is refused */
+#define SCAML_ACQF_UCB 0
+#define SCAML_ACQF_EI 1
+#define SCAML_ACQF_LOG 0x10
+
 #define SCAML_OK 0
 #define SCAML_E_BADARG -1      /* NULL pointer / negative size                              */
 #define SCAML_E_TOOLARGE -2    /* N or D beyond what the kernels support (see *_max_*)      */
@@ -301,6 +306,14 @@ int scaml_target_posterior_grad_f64(const double* cov_g, const double* mu_g, con
  *   value[q] = (1/F) sum_f A(mu_f[q], v[q])
  * acqf 0: UCB, A = -mu + sqrt(beta max(v, 0)), acqf_param = beta; acqf 1: EI (minimisation), sigma = sqrt(max(v, 1e-9)),
  * u = -(mu - best_f) / sigma, A = sigma (phi(u) + u Phi(u)), acqf_param = best_f.  Knq, Z (n, M), mean_q, var_q (M) as in (7).
+ * acqf 17 (SCAML_ACQF_EI | SCAML_ACQF_LOG): LogEI, the logarithm of EI, with EI's clamp and acqf_param:
+ *   A = log sigma + g(u),  g(u) = log(phi(u) + u Phi(u)),  dA/dmu = -g'(u) / sigma,  dA/dv = (1 - u g'(u)) / (2 sigma^2) above the
+ *   floor and exactly 0 on it (v <= 1e-9), as EI has it.  g and g' are evaluated without cancellation (a continued fraction of the
+ *   Mills ratio below u = -2, csrc/gp_studies_formulas.h): finite and accurate to a few ulp for u in [-1e8, 40], where EI and its
+ *   gradient are exactly 0 below u of about -38.  Over the fantasies the average is taken in the log domain, the log of the mean EI:
+ *   value[q] = mx + log(sum_f exp(A_f - mx)) - log F with mx = max_f A_f, and the gradient weights each fantasy's chain-rule factors
+ *   by exp(A_f - mx) / sum_f' exp(A_f' - mx) in place of the 1 / F.  F = 1 gives A_0 and its gradient bit for bit.
+ * Any other code (2, 3, 0x10 alone, 0x12, negative) is SCAML_E_BADARG, here and on every entry point that takes `acqf`.
  * grad (M, D) or NULL: d value / d x_q from the GRAD pass's weighted sums (cov_g (n, M * 16), mu_g / var_g (M * 16)), the training
  * inputs Xt (n, D), the queries Xq (M, D) and the target kernel theta (D + 2) of family `kind`, as (5d) takes them; the gradient
  * contracts over the training points once per query with abar = sum_f dA/dmu_f alpha[:, f].  info (1) int32 or NULL: a factorisation
@@ -314,6 +327,17 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
                                   double m_all, double s_all, double noise_add, const int32_t* info, int acqf, double acqf_param,
                                   const double* cov_g, const double* mu_g, const double* var_g, const double* Xt, const double* Xq,
                                   const double* theta, int n, int M, int F, int D, int kind, double* value, double* grad, void* stream);
+
+/*
+ * (7o) The acquisition function of M given posteriors, elementwise: A[i] and its partial derivatives Amu[i] = dA / dmu, Av[i] = dA / dv
+ * at (mu[i], var[i]) (original units), i = 0 .. M-1, one thread per element -- the statement (7f), (7g), (7i) and (7k) evaluate
+ * (sa_acquisition of csrc/gp_studies_formulas.h), with their clamps.  acqf: SCAML_ACQF_UCB (acqf_param = beta), SCAML_ACQF_EI or
+ * SCAML_ACQF_EI | SCAML_ACQF_LOG (acqf_param = best_f); anything else is SCAML_E_BADARG.  Amu and Av may be NULL.  The input gradient
+ * of an ordinary model's acquisition value is Amu * dmu + Av * dvar with (5d)'s dmu, dvar.  A NaN mu or var gives NaN.
+ * M == 0 enqueues nothing; M < 0 or a NULL mu / var / A with M > 0: SCAML_E_BADARG.  No host synchronisation.
+ */
+int scaml_acqf_transform_f64(const double* mu, const double* var, double acqf_param, int M, int acqf, double* A, double* Amu, double* Av,
+                             void* stream);
 
 /*
  * (5e), (7g) The acquisition function of MANY Bayesian-optimisation studies against one source stack, evaluated in two launches

@@ -6,7 +6,7 @@
 // Z = Knn^-1 Knq; only alpha_f = Knn^-1 r_f differs.  So per query point q:
 //   mu_f(q)  = m + s (mean_q[q] + Knq[:, q] . alpha[:, f])
 //   v(q)     = s^2 (var_q[q] - Knq[:, q] . Z[:, q] + noise_add)        (the same for every f)
-//   value(q) = (1/F) sum_f A(mu_f(q), v(q))
+//   value(q) = (1/F) sum_f A(mu_f(q), v(q))        LogEI: log((1/F) sum_f exp A(mu_f(q), v(q))), A = log EI
 // with A the UCB (-mu + sqrt(beta v)) or EI (sigma (phi(u) + u Phi(u)), sigma = sqrt(max(v, 1e-9)), u = -(mu - best_f) / sigma) of
 // scamlgp_amd/utils.py, same clamps.  The gradient uses
 //   sum_f A_mu,f grad mu_f = (sum_f A_mu,f) grad mu_prior + s sum_a (sum_f A_mu,f alpha[a, f]) grad k_a
@@ -24,6 +24,12 @@ namespace {
 
 __device__ __forceinline__ double wave_sum_all(double x) {
   return __shfl(scaml::wave_sum_to_lane15(x), 63);   // (the total lands in lanes 15, 31, 47, 63)
+}
+
+__device__ __forceinline__ double wave_max_all(double x) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) x = fmax(x, __shfl_xor(x, o));
+  return x;
 }
 
 template <int KIND, bool GRAD>
@@ -66,8 +72,23 @@ __device__ __forceinline__ void fantasy_acqf_body(const scaml::FantasyAcqfParams
   double A, Amu, Av;
   scaml::sa_acquisition(p.acqf, p.acqf_param, mu, v, A, Amu, Av);   // UCB / EI with the clamps: csrc/gp_studies_formulas.h
   if (!live) A = Amu = Av = 0.0;
-  const double invF = 1.0 / F;
-  const double val = wave_sum_all(A);
+  double invF = 1.0 / F;
+  double val;
+  if (p.acqf & scaml::SA_ACQF_LOG) {
+    // LogEI: the average in the log domain, log((sum_f exp l_f) / F) of the l_f = A.  With mx = max_f l_f and S = sum_f exp(l_f - mx):
+    // value = mx + log S - log F, and the chain-rule factors carry the weights w_f = exp(l_f - mx) / S in place of the 1 / F.
+    // (F = 1: exp 0 = 1, S = 1, log 1 = 0, w = 1 -- l_0 and its factors bit for bit.  fmax drops a NaN l_f: A - A puts it back.)
+    const double mx = wave_max_all(live ? A : -__builtin_inf());
+    const double e = live ? exp(A - mx) : 0.0;
+    const double S = wave_sum_all(e);
+    const double w = e / S;
+    Amu *= w;
+    Av *= w;
+    val = (mx + log(S) - log((double)F)) + wave_sum_all(A - A);
+    invF = 1.0;
+  } else {
+    val = wave_sum_all(A);
+  }
   if (lane == 0) p.value[q] = val * invF;
   if (!GRAD) return;
   const double sAmu = wave_sum_all(Amu), sAv = wave_sum_all(Av);

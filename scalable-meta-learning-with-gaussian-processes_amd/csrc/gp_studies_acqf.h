@@ -245,6 +245,7 @@ SA_DEV void sa_block(const Params& p, double* lds, int blk, int tid, int nthr) {
   //   value = (sum_f A_f) / F;  R = 1: sAmu = sum_f Amu_f, sAv = sum_f Av_f, abar[a] = sum_f Amu_f alpha_f[a][f],
   //   gm[d] = sum_a abar[a] dKnq[a][d], gv[d] = sum_a z[a] dKnq[a][d],
   //   grad[d] = fma(sAv, fma(-2 s^2, gv[d], S_var[1 + d]), fma(s, gm[d], sAmu S_mu[1 + d])) / F
+  // LogEI (acqf & SA_ACQF_LOG): value = log((sum_f exp A_f) / F) and Amu_f, Av_f weighted by exp A_f / sum_f' exp A_f' in place of the 1 / F.
   if constexpr (FANT) {
     if (F > 1) {
       const int Fm = p.F_max, nr = R * F;
@@ -294,12 +295,47 @@ SA_DEV void sa_block(const Params& p, double* lds, int blk, int tid, int nthr) {
         }
       }
       SA_SYNC();
+      // LogEI: the average in the log domain, log((sum_f exp l_f) / F) of the l_f = A_f:
+      //   mx = max_f l_f,  e_f = exp(l_f - mx),  S = sum_f e_f (f ascending),  value = mx + log S - log F,  w_f = e_f / S;
+      //   R = 1: Amu_f, Av_f *= w_f
+      // mx by one thread per right-hand side into red[c] (free in this branch); e_f by one thread per (right-hand side, fantasy), in
+      // place of l_f; then, R = 1, every thread f sums S for itself (the same F additions in the same order: the same bits) and
+      // weights its own factors, and thread f = 0 leaves the value in red[c].  Phase 4b sums the weighted factors and divides by 1.
+      const bool logdom = (p.acqf & SA_ACQF_LOG) != 0;   // (uniform over the launch)
+      if (logdom) {
+        for (int c = tid; c < R; c += nthr) {
+          const double* l = fA + c * F;
+          double mx = l[0], any = 0.0;   // (the comparisons drop a NaN l_f: l - l puts it back, and with it NaN into every output)
+          for (int f = 1; f < F; ++f) mx = l[f] > mx ? l[f] : mx;
+          for (int f = 0; f < F; ++f) any += l[f] - l[f];
+          red[c] = mx + any;
+        }
+        SA_SYNC();
+        for (int e = tid; e < nr; e += nthr) fA[e] = exp(fA[e] - red[e / F]);
+        SA_SYNC();
+        for (int e = tid; e < nr; e += nthr) {
+          const int c = e / F, f = e - c * F;
+          if (R == 16 && f != 0) continue;
+          const double* ex = fA + c * F;
+          double S = 0.0;
+          for (int k = 0; k < F; ++k) S += ex[k];
+          if constexpr (R == 1) {
+            const double wf = ex[f] / S;
+            fAmu[f] *= wf;
+            fAv[f] *= wf;
+          }
+          if (f == 0) red[c] = red[c] + log(S) - log((double)F);
+        }
+        SA_SYNC();
+      }
+      const double Fdiv = logdom ? 1.0 : (double)F;
       // phase 4b: the averages, one thread per right-hand side; R = 1 with a gradient: and one per training point for abar
       for (int e = tid; e < (R == 1 ? 1 + (p.grad ? n : 0) : R); e += nthr) {
         if (R == 16 || e == 0) {
           const int c = R == 1 ? 0 : e;
           double sA = 0.0;
-          for (int f = 0; f < F; ++f) sA += fA[c * F + f];
+          if (logdom) sA = red[c];
+          else for (int f = 0; f < F; ++f) sA += fA[c * F + f];
           if constexpr (R == 1) {
             double sAmu = 0.0, sAv = 0.0;
             for (int f = 0; f < F; ++f) sAmu += fAmu[f];
@@ -313,7 +349,7 @@ SA_DEV void sa_block(const Params& p, double* lds, int blk, int tid, int nthr) {
             const double x = p.Xq[(q0 + c) * D + d];
             bad += x - x;
           }
-          p.value[q0 + c] = bad == 0.0 ? sA / F : bad;
+          p.value[q0 + c] = bad == 0.0 ? sA / Fdiv : bad;
         } else {
           const int a = e - 1;
           double acc = 0.0;
@@ -335,7 +371,7 @@ SA_DEV void sa_block(const Params& p, double* lds, int blk, int tid, int nthr) {
             }
             const double dmu = fma(s, gm, fsum[1] * Ssum[1 + o]);
             const double dvar = fma(-2.0 * s2, red[18 + o], Ssum[17 + o]);
-            p.grad[q0 * D + o] = bad == 0.0 ? fma(fsum[2], dvar, dmu) / F : bad;
+            p.grad[q0 * D + o] = bad == 0.0 ? fma(fsum[2], dvar, dmu) / Fdiv : bad;
           }
         }
       }

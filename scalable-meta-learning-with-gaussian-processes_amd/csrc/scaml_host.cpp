@@ -69,6 +69,7 @@ struct Module {
   hipFunction_t wsum = nullptr, linv = nullptr, chosolve = nullptr, kmat[2] = {}, mllgrad[2] = {};
   hipFunction_t tgt_assemble[2] = {}, tgt_finish = nullptr, tgt_fit = nullptr, tgt_fit_batched = nullptr, tgt_grad[2] = {};
   hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {};   // value only; value + gradient per kind
+  hipFunction_t acqf_transform = nullptr;                          // the elementwise acquisition of given posteriors (7o)
   hipFunction_t post_linv_grouped[2] = {}, tgt_acqf_batched = nullptr;   // lock-step studies: grouped GRAD pass, batched acquisition
   hipFunction_t post_linv_grouped_own[2] = {};                           // the grouped pass with per-group source tasks
   hipFunction_t post_linv_grouped_det[2] = {}, post_linv_grouped_det_own[2] = {};   // the GRAD grouped pass with ordered sums: (7l)'s rounds
@@ -124,6 +125,7 @@ struct Module {
         {&tgt_fantasy, "scaml_target_fantasy_acqf_kernel", 0, {}},
         {&tgt_fantasy_grad[0], "scaml_target_fantasy_acqf_grad_rbf_kernel", 0, {}},
         {&tgt_fantasy_grad[1], "scaml_target_fantasy_acqf_grad_matern_kernel", 0, {}},
+        {&acqf_transform, "scaml_acqf_transform_kernel", 0, {}},
         {&tgt_fit, "scaml_target_fit_kernel", kLdsLimit, {}},
         {&tgt_fit_batched, "scaml_target_fit_batched_kernel", kLdsLimit, {}},
         {coop, "_ZN5scaml18gp_fit_coop_kernelILi%dEEEvNS_13CoopFitParamsE", kLdsLimit, {K}},
@@ -679,7 +681,7 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
                                   const double* theta, int n, int M, int F, int D, int kind, double* value, double* grad, void* stream) {
   if (n < 1 || M < 0 || F < 1) return SCAML_E_BADARG;
   if (!Knq || !Z || !alpha || !mean_q || !var_q || !value) return SCAML_E_BADARG;
-  if (acqf != 0 && acqf != 1) return SCAML_E_BADARG;
+  if (!scaml::sa_acqf_valid(acqf)) return SCAML_E_BADARG;
   if (!(s_all > 0.0)) return SCAML_E_BADARG;
   if (grad) {
     if (D < 1 || !cov_g || !mu_g || !var_g || !Xt || !Xq || !theta) return SCAML_E_BADARG;
@@ -694,6 +696,18 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
                              value, grad, n, M, F, grad ? D : 0, acqf, 0};
   // one wave per query point
   return launch(grad ? m->tgt_fantasy_grad[kind] : m->tgt_fantasy, dim3((unsigned)M), 64, 0, stream, "target_fantasy_acqf", p);
+}
+
+// ---- (7o) the acquisition value and chain-rule factors of M given posteriors, elementwise (csrc/gp_acqf_transform.hip) ----------
+int scaml_acqf_transform_f64(const double* mu, const double* var, double acqf_param, int M, int acqf, double* A, double* Amu, double* Av,
+                             void* stream) {
+  if (M < 0 || !scaml::sa_acqf_valid(acqf)) return SCAML_E_BADARG;
+  if (M == 0) return SCAML_OK;
+  if (!mu || !var || !A) return SCAML_E_BADARG;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  void* args[] = {(void*)&mu, (void*)&var, (void*)&acqf_param, (void*)&M, (void*)&acqf, (void*)&A, (void*)&Amu, (void*)&Av};
+  return launch_args(m->acqf_transform, dim3(((unsigned)M + 255u) / 256u), 256, stream, "acqf_transform", args);   // one thread per element (unsigned: no overflow near INT_MAX)
 }
 
 // ---- (5e) the GRAD pass with the query points divided among groups, (5f) the same pass in VALUE mode; (7g), (7i) the batched target
@@ -759,7 +773,7 @@ int acqf_check(const scaml::StudiesAcqfParams& p, bool strips) {
   if (!p.mu || !p.var || !p.cov || !p.group || !p.Xq || !p.w || !p.active || !p.Xt || !p.theta || !p.L || !p.Linv_diag || !p.alpha ||
       !p.n_points || !p.m_all || !p.s_all || !p.info || !p.acqf_param || !p.value)
     return SCAML_E_BADARG;
-  if (!valid_kind(p.kind) || (p.acqf != 0 && p.acqf != 1)) return SCAML_E_BADARG;
+  if (!valid_kind(p.kind) || !scaml::sa_acqf_valid(p.acqf)) return SCAML_E_BADARG;
   if (p.n_max > scaml::STUDIES_ACQF_MAX_N || p.D > scaml::STUDIES_ACQF_MAX_D || p.Mq > (1 << 26)) return SCAML_E_TOOLARGE;
   if (acqf_lds_bytes(p.n_max, strips) > kLdsLimit) return SCAML_E_TOOLARGE;
   return SCAML_OK;

@@ -96,6 +96,8 @@ SIGNATURES = {
     "scaml_posterior_linv_grad_f64": (_i, [_dp] * 10 + [_i] * 6 + [_dp, _dp, _dp, _u, c_void_p]),
     "scaml_target_posterior_grad_f64": (_i, [_dp] * 8 + [_f, _dp, _i, _i, _i, _i, _dp, _dp, c_void_p]),
     "scaml_target_fantasy_acqf_f64": (_i, [_dp] * 5 + [_f, _f, _f, _dp, _i, _f] + [_dp] * 6 + [_i] * 5 + [_dp, _dp, c_void_p]),
+    # (7o) mu, var; acqf_param, M, acqf; A, Amu, Av
+    "scaml_acqf_transform_f64": (_i, [_dp, _dp, _f, _i, _i, _dp, _dp, _dp, c_void_p]),
     # (5e) Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points; T, N, Mq, G, Ma_max, D, kind; mu, var, cov
     "scaml_posterior_linv_grad_grouped_f64": (_i, [_dp] * 12 + [_i] * 7 + [_dp, _dp, _dp, c_void_p]),
     # (5e') (5e)'s arrays and shapes; mu, var, cov; task_base, Tsrc

@@ -30,7 +30,7 @@ import torch
 
 from . import hyper
 from .model import ScaMLGP, SourceGP, fantasize_studies
-from .utils import ExpectedImprovement, UpperConfidenceBound, capture_graph, fit_targets_batched, optimize_marginal_likelihood
+from .utils import ExpectedImprovement, LogExpectedImprovement, UpperConfidenceBound, capture_graph, fit_targets_batched, optimize_marginal_likelihood
 
 
 class OptimizerNotReady(RuntimeError):
@@ -235,11 +235,11 @@ class ScaMLGPBOLoop:
             model = fantasy_model
         elif self.max_pending_evaluations is not None and self.pending.shape[0] > 0:
             model = self.model.eval().fantasize(self.pending, self.num_fantasies, generator=self.gen)
-        if self.acquisition == "ei":
+        if self.acquisition in ("ei", "logei"):   # one best_f rule: the incumbent over the observed values
             Yf = self.Y[torch.isfinite(self.Y)]
             if Yf.numel() == 0:
                 raise ValueError("EI needs at least one evaluation")
-            return ExpectedImprovement(model, float(Yf.min()))
+            return (ExpectedImprovement if self.acquisition == "ei" else LogExpectedImprovement)(model, float(Yf.min()))
         return UpperConfidenceBound(model, self.beta)
 
     def suggest(self) -> torch.Tensor:

@@ -999,7 +999,7 @@ class ScaMLGP:
 
     def fantasy_acqf(self, X: torch.Tensor, acqf: int, acqf_param: float, want_grad: bool = False):
         """The acquisition function of a fantasy model, averaged over its fantasies, at X (M, D): (value (M,), d value / d X (M, D) or
-        None).  ``acqf``: ops.ACQF_UCB (acqf_param = beta) or ops.ACQF_EI (acqf_param = best_f).  The source pass at cat(X', Xq), the
+        None).  ``acqf``: ops.ACQF_UCB (acqf_param = beta), ops.ACQF_EI or ops.ACQF_LOGEI (acqf_param = best_f).  The source pass at cat(X', Xq), the
         assemble and Z = Knn^-1 Knq are those of an ordinary model (the training block's factor and the F columns of alpha are computed
         once per parameter state and cached); then ONE launch of scaml_target_fantasy_acqf_f64 in place of the finish and gradient
         kernels: no per-fantasy work outside it."""

@@ -569,6 +569,26 @@ def target_posterior_grad(cov_g: Optional[torch.Tensor], mu_g: torch.Tensor, var
 
 ACQF_UCB = 0
 ACQF_EI = 1
+ACQF_LOG = 0x10
+ACQF_LOGEI = ACQF_EI | ACQF_LOG   # 17: the logarithm of EI, stable in the tails (include/scaml_gp.h (7f))
+
+
+def acqf_transform(mu: torch.Tensor, var: torch.Tensor, acqf: int, acqf_param: float, want_factors: bool = True):
+    """The acquisition value of M posteriors (mu, var (M,), original units) and its partial derivatives, elementwise: one launch of
+    scaml_acqf_transform_f64 (7o), the statement the fantasy and the studies' kernels evaluate.  ``acqf``: ACQF_UCB (acqf_param = beta),
+    ACQF_EI or ACQF_LOGEI (best_f).  Returns (A, dA/dmu, dA/dvar), each (M,); the last two None with ``want_factors=False``."""
+    M = int(mu.numel())
+    mu = _check(mu.reshape(-1), "mu", (M,))
+    var = _check(var.reshape(-1), "var", (M,))
+    dev = mu.device
+    with torch.cuda.device(dev):
+        A = _empty(dev, M)
+        Amu = _empty(dev, M) if want_factors else None
+        Av = _empty(dev, M) if want_factors else None
+        rc = _lib.lib.scaml_acqf_transform_f64(_ptr(mu), _ptr(var), float(acqf_param), M, int(acqf), _ptr(A), _ptr(Amu), _ptr(Av),
+                                               _stream_handle())
+    _lib.check_rc(rc, "scaml_acqf_transform_f64")
+    return A, Amu, Av
 
 
 def target_fantasy_block(cov_s: torch.Tensor, mean_s: torch.Tensor, var_s: torch.Tensor, Xall: torch.Tensor, theta: torch.Tensor,

@@ -424,6 +424,34 @@ class ExpectedImprovement:
         return sigma * (pdf + u * cdf), -cdf.unsqueeze(-1) * dmu + pdf.unsqueeze(-1) * dsig
 
 
+class LogExpectedImprovement:
+    """botorch LogExpectedImprovement(model, best_f, maximize=False): the logarithm of ``ExpectedImprovement``, with its clamp,
+    log sigma + g(u), g(u) = log(phi(u) + u Phi(u)), evaluated without cancellation so that value and gradient stay finite and
+    accurate where EI underflows to an exact 0 (u below about -38).  The transform of the posterior is the library's
+    (``ops.acqf_transform``, include/scaml_gp.h (7o)) for every n, the prior-only model included.  On a fantasy model: the log of the
+    MEAN EI over the fantasies (a log-sum-exp of the per-fantasy values), ``ScaMLGP.fantasy_acqf`` with ``ops.ACQF_LOGEI``."""
+
+    def __init__(self, model: ScaMLGP, best_f: float):
+        self.model, self.best_f = model, best_f
+
+    def __call__(self, X: torch.Tensor) -> torch.Tensor:
+        if self.model.num_fantasies is not None:
+            return _fantasy_value(self.model, _single_q(X), ops.ACQF_LOGEI, self.best_f)
+        mvn = self.model.posterior(_single_q(X)).mvn
+        mu = mvn.mean
+        A, _, _ = ops.acqf_transform(mu.detach(), mvn.variance.detach(), ops.ACQF_LOGEI, self.best_f, want_factors=False)
+        return _drop_q(X, A.reshape(mu.shape))
+
+    def value_and_grad(self, X: torch.Tensor):
+        """(LogEI (M,), d LogEI / d X (M, D)) = dA/dmu d mu + dA/dvar d var from the model's analytic posterior gradients; on a
+        fantasy model the log of the mean EI over the fantasies and its exact gradient."""
+        if self.model.num_fantasies is not None:
+            return self.model.fantasy_acqf(X, ops.ACQF_LOGEI, self.best_f, want_grad=True)
+        mu, var, dmu, dvar = self.model.posterior_with_grad(X)
+        A, Amu, Av = ops.acqf_transform(mu, var, ops.ACQF_LOGEI, self.best_f)
+        return A, Amu.unsqueeze(-1) * dmu + Av.unsqueeze(-1) * dvar
+
+
 class StudiesAcquisition:
     """The acquisition functions of S ScaMLGP models on ONE source stack (or on slices of one: see below), evaluated together: ``value_and_grad(X, group)`` is two
     library launches whatever S is -- the grouped GRAD source pass (``ops.source_posteriors_grad_grouped``: a query point's covariance
@@ -432,7 +460,7 @@ class StudiesAcquisition:
     ``af.value_and_grad`` is about fifteen.  Nothing is read back and every status stays on the device, so an evaluation can be
     captured into a HIP graph (``bo.GraphedAcquisition``).
 
-    ``afs``: one ``UpperConfidenceBound`` or ``ExpectedImprovement`` per study, all of the same class, on models that share the source
+    ``afs``: one ``UpperConfidenceBound``, ``ExpectedImprovement`` or ``LogExpectedImprovement`` per study, all of the same class, on models that share the source
     stack and the kernel family and ``supports_posterior_grad()``.  Built once per parameter state: the per-study
     arrays (pruned weights and mask, theta, training inputs, standardiser, the factor ``_target_factor()`` -- computed through the
     model's own posterior path where it is absent --, alpha, beta or best_f) are packed from the models' caches here, padded to the
@@ -453,7 +481,7 @@ class StudiesAcquisition:
 
     SCORE_COV_CAP_BYTES = 256 << 20   # `score`: the most the covariance workspace of one chunk of strips may take
 
-    def __init__(self, afs: Sequence[Union[UpperConfidenceBound, ExpectedImprovement]], batched_factors: bool = False):
+    def __init__(self, afs: Sequence[Union[UpperConfidenceBound, ExpectedImprovement, LogExpectedImprovement]], batched_factors: bool = False):
         """``batched_factors``: the models that hold no ``_target_factor()`` for their parameter state get it from ONE batched assemble
         and ONE batched Cholesky for all of them (``ops.target_factors_batched``) instead of a posterior call each; every model keeps its
         slice (``_keep_target_factor``), so its own later calls reuse it.  False (default): the model's own posterior path, as before."""
@@ -461,9 +489,11 @@ class StudiesAcquisition:
         if not afs:
             raise ValueError("StudiesAcquisition needs at least one acquisition function")
         kinds = {type(a) for a in afs}
-        if len(kinds) != 1 or not kinds <= {UpperConfidenceBound, ExpectedImprovement}:
-            raise TypeError("the acquisition functions must all be UpperConfidenceBound or all ExpectedImprovement")
-        self.acqf = ops.ACQF_UCB if isinstance(afs[0], UpperConfidenceBound) else ops.ACQF_EI
+        codes = {UpperConfidenceBound: ops.ACQF_UCB, ExpectedImprovement: ops.ACQF_EI, LogExpectedImprovement: ops.ACQF_LOGEI}
+        if len(kinds) != 1 or not kinds <= set(codes):
+            raise TypeError("the acquisition functions must all be UpperConfidenceBound, all ExpectedImprovement or all "
+                            "LogExpectedImprovement")
+        self.acqf = codes[type(afs[0])]
         models = [a.model for a in afs]
         m0 = models[0]
         # the source stacks: one object shared by all studies, or slices of one parent with an equal number of tasks (per-study stacks,

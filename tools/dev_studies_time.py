@@ -15,6 +15,8 @@ medians over the timed steps (the first step of a size is a warm-up and is not c
       one source stack PER study at hartmann6.py's shape (see own_stacks_table)
   python tools/dev_studies_time.py --pending [--sizes 8,32] [--steps K] [--out profiles/studies_pending_timings.txt]
       every study holds pending evaluations: fantasy_setup='batched' and pending_mode='batched' against 'per_study' (see pending_table)
+  python tools/dev_studies_time.py --acqf ucb,ei,logei [--against LIB] [--out profiles/logei_timings.txt]
+      the evaluation launches per acquisition code (and against a second build of the library), EI against LogEI in suggest() (see acqf_table)
 """
 import argparse
 import os
@@ -42,6 +44,8 @@ ap.add_argument("--evals-per-call", type=int, default=None, help="ops.ACQF_OPT_E
 ap.add_argument("--score", action="store_true", help="device suggest(): score_mode='batched' against 'per_study', its split into parts, and score alone")
 ap.add_argument("--own-stacks", action="store_true", help="per-study source stacks: meta-fit, BO step and the grouped pass against what a caller had before")
 ap.add_argument("--pending", action="store_true", help="studies with pending evaluations: fantasy_setup='batched' against pending_mode='batched' against 'per_study', and the evaluation launch alone")
+ap.add_argument("--acqf", default=None, help="with a list such as ucb,ei,logei: the evaluation launches (7g) / (7k) per acquisition code, and the device suggest() of EI against LogEI")
+ap.add_argument("--against", default=None, help="with --acqf: a second build of the library (the parent commit's), timed in turn with this one")
 args = ap.parse_args()
 
 T, N, D, N_END, RESTARTS = 32, 512, 6, 80, 2
@@ -474,6 +478,124 @@ def pending_table():
         torch.cuda.empty_cache()
 
 
+def acqf_table():
+    """The acquisition codes against each other (``--acqf ucb,ei,logei``) and, with ``--against LIB``, this build against a second one
+    (the parent commit's, which refuses LogEI), everything alternating in one process.
+      (1) the evaluation launch alone on one grouped source pass's outputs, 32 studies x 10 starts = 320 query points, n = 80:
+          scaml_target_acqf_batched_f64 (7g) and scaml_target_fantasy_acqf_batched_f64 (7k) at F = 1 (ordinary studies) and at F = 16
+          (fantasy models of p = 4 pending points; (7g) on their arrays with column 0 of alpha_f, for the time only).  Device events
+          over 20 calls, median of 5 rounds with min .. max, the first round a warm-up; the order of the calls turns round by round.
+      (2) suggest() with suggest_mode="device" of S = 8 and 32 studies, acquisition "ei" against "logei" on the same data, median of
+          5 calls with min .. max and the rounds enqueued (EI stops the starts whose gradient is exactly 0; LogEI moves them)."""
+    import ctypes
+
+    from scamlgp_amd import _lib
+
+    names = args.acqf.split(",")
+    libs = {"this": _lib.lib}
+    if args.against:
+        other = ctypes.CDLL(os.path.abspath(args.against))
+        for name, (restype, argtypes) in _lib.SIGNATURES.items():
+            if hasattr(other, name):
+                fn = getattr(other, name)
+                fn.restype, fn.argtypes = restype, argtypes
+        libs["parent"] = other
+    S, F, starts, p = 32, 16, 10, 4
+    say(f"# acquisition codes {names}, builds {list(libs)}; T = {T}, N = {N}, D = {D}, n = {N_END}")
+    seeds = list(range(100, 100 + S))
+    side = ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, suggest_mode="device", **dict(KW, max_pending_evaluations=8, num_fantasies=F))
+    for s in range(S):
+        g = torch.Generator().manual_seed(seeds[s])
+        X0 = torch.rand(N_END, D, dtype=torch.float64, generator=g)
+        side[s].record(X0, [obj(x) for x in X0])
+    utils.fit_targets_batched([st.model for st in side.studies], RESTARTS, rng=side.fit_gens)
+    g = torch.Generator().manual_seed(1000 + S + p)
+    pend = [torch.rand(p, D, dtype=torch.float64, generator=g) for _ in range(S)]
+    Xq = torch.rand(S * starts, D, dtype=torch.float64, generator=torch.Generator().manual_seed(S)).to(dev)
+    for label, pending in (("F = 1", False), (f"F = {F}, p = {p}", True)):
+        calls = {}
+        for name in names:
+            for s, st in enumerate(side.studies):
+                st.acquisition = name
+                st.pending = pend[s].clone() if pending else pend[s][:0].clone()
+                st.gen.manual_seed(seeds[s])    # the same fantasies for every code
+            sa = utils.StudiesAcquisition([st.acquisition_function() for st in side.studies])
+            group = sa.group_of([starts] * S)
+            stk, f = sa.source, sa.source.fit
+            src = ops.source_posteriors_grad_grouped(Xq, group, sa.Xt, sa.n_points, sa.VA_tab, stk.X, stk.theta, stk.kind, f["Linv"], f["alpha"],
+                                                     stk.y_mean, stk.y_std, stk.n_points)
+            alpha_f = sa.alpha_f if sa.fantasy else sa.alpha.unsqueeze(-1).contiguous()
+            n_fant = sa.n_fant if sa.fantasy else torch.ones(S, dtype=torch.int32, device=dev)
+            head = (src["mu"], src["var"], src["cov"], group, Xq, sa.w, sa.active, sa.Xt, sa.theta, sa.L, sa.Linv_diag)
+            tail = (sa.n_points, sa.m_all, sa.s_all, sa.info, sa.acqf_param, sa.acqf, sa.kind)
+            a7 = alpha_f[:, :, 0].contiguous()
+            for build in libs:
+                if build == "parent" and name == "logei":
+                    continue
+                calls[("(7g)", name, build)] = lambda head=head, a7=a7, tail=tail: ops.target_acqf_batched(*head, a7, *tail)
+                calls[("(7k)", name, build)] = lambda head=head, alpha_f=alpha_f, n_fant=n_fant, tail=tail: ops.target_fantasy_acqf_batched(
+                    *head, alpha_f, n_fant, *tail)
+        reps, inner = 5, 20
+        got = {k: [] for k in calls}
+        for r in range(reps + 1):
+            for k, fn in (list(calls.items()) if r % 2 else reversed(list(calls.items()))):   # the order turns round by round
+                _lib.lib = libs[k[2]]
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                ev0.record()
+                for _ in range(inner):
+                    fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                if r:
+                    got[k].append(1e3 * ev0.elapsed_time(ev1) / inner)
+        _lib.lib = libs["this"]
+        say(f"# (1) evaluation launch alone, {S * starts} query points, {label}; us, median of {reps} rounds (min .. max) [device events over {inner} calls, "
+            f"allocation of the outputs included]")
+        for k, v in got.items():
+            note = ""
+            base = got.get((k[0], k[1], "parent"))
+            if k[2] == "this" and base:
+                inside = min(base) <= statistics.median(v) <= max(base)
+                note = f"   this / parent = {statistics.median(v) / statistics.median(base):5.3f}: {'INSIDE' if inside else 'OUTSIDE'} the parent's min .. max"
+            elif k[2] == "this" and k[1] == "logei" and (k[0], "ei", "this") in got:
+                note = f"   logei / ei = {statistics.median(v) / statistics.median(got[(k[0], 'ei', 'this')]):5.3f}"
+            say(f"  {k[0]} {k[1]:>5} {k[2]:>6} {statistics.median(v):8.1f} ({min(v):.1f} .. {max(v):.1f}){note}")
+    del side
+    torch.cuda.empty_cache()
+    pair = [n_ for n_ in ("ei", "logei") if n_ in names]
+    if len(pair) < 2:
+        return
+    say("# (2) suggest(), suggest_mode='device', no pending evaluations; ms, median of 5 calls (min .. max), rounds enqueued in the last call")
+    for S in (8, 32):
+        seeds = list(range(100, 100 + S))
+        sides = {k: ScaMLGPBOStudies(gps, D, num_studies=S, seeds=seeds, suggest_mode="device", **dict(KW, acquisition=k)) for k in pair}
+        for sd in sides.values():
+            for s in range(S):
+                g = torch.Generator().manual_seed(seeds[s])
+                X0 = torch.rand(N_END, D, dtype=torch.float64, generator=g)
+                sd[s].record(X0, [obj(x) for x in X0])
+            utils.fit_targets_batched([st.model for st in sd.studies], RESTARTS, rng=sd.fit_gens)
+        ms = {k: [] for k in pair}
+        for r in range(6):
+            for k, sd in sides.items():
+                t, _ = timed(sd.suggest)
+                if r:
+                    ms[k].append(1e3 * t)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        for k in pair:
+            say(f"  S = {S:>3} {k:>5} suggest {med[k]:9.1f} ms ({min(ms[k]):.1f} .. {max(ms[k]):.1f})   rounds {sides[k].last_suggest_info['n_eval']}")
+        say(f"#     logei / ei = {med['logei'] / med['ei']:5.2f}x")
+        del sides
+        torch.cuda.empty_cache()
+
+
+if args.acqf:
+    acqf_table()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 if args.pending:
     if args.sizes == ap.get_default("sizes"):
         args.sizes = "8,32"

@@ -3,6 +3,7 @@ tests/_fantasy_bounds.py, in units of the fp64 spacing at the reference value, a
 max(2, ceil(2 x largest observed ulp error)) -- the factor 2 because the sweep samples the domain rather than exhausting it.
 
     python tools/libm_ulp_read.py /tmp/libm_ulp.bin
+    python tools/libm_ulp_read.py /tmp/libm_ulp_logei.bin logei     (the probe run with a third argument "logei")
 """
 import math
 import os
@@ -24,10 +25,25 @@ def _line(name, x, ulp, sel):
     return float(u[i])
 
 
-def main(path):
+def main_logei(xe, ye, xx, yx):
+    """The "logei" mode of the probe: erfc and log for ERFC_U / LOG_U of tests/_logei_bounds.py.  Reference erfc = 1 - erf in long
+    double: over [-29, 1.4143] erfc >= 0.0455, so the subtraction loses at most a factor 22 of eps_LD (0.01 ulp of fp64)."""
+    from tests import _logei_bounds as LB
+    ulp_c = FB.ulp_errors(xe, ye, 1 - FB.erf_ld(xe))
+    worst_c = _line("erfc, [-29, 1.4143] grid and 1e-300 .. 1 log-spaced", xe, ulp_c, np.ones(xe.size, dtype=bool))
+    ulp_l = FB.ulp_errors(xx, yx, np.log(FB.LD(xx)))
+    worst_l = _line("log, [1e-20, 100] log-spaced", xx, ulp_l, np.ones(xx.size, dtype=bool))
+    print(f"ERFC_U = max(2, ceil(2 x {worst_c:.4f})) = {max(2, math.ceil(2 * worst_c))}")
+    print(f"LOG_U = max(2, ceil(2 x {worst_l:.4f})) = {max(2, math.ceil(2 * worst_l))}")
+    print(f"module constants: ERFC_U = {LB.ERFC_U}, LOG_U = {LB.LOG_U}")
+
+
+def main(path, mode=""):
     raw = np.fromfile(path, dtype=np.float64)
     assert raw.size % 4 == 0 and raw.size, f"{path}: {raw.size} doubles"
     xe, ye, xx, yx = raw.reshape(4, -1)
+    if mode == "logei":
+        return main_logei(xe, ye, xx, yx)
     n = xe.size
     nu = n - n // 8
     grid = np.arange(n) < nu
@@ -48,4 +64,4 @@ def main(path):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main(*sys.argv[1:3])
