@@ -45,30 +45,6 @@ struct StudiesConditionBlockParams {
 // LDS in doubles:  X' [n_max][D] | bad [n_max]
 constexpr size_t sc_block_lds_doubles(int n_max, int D) { return (size_t)n_max * (size_t)D + (size_t)n_max; }
 
-// sum_t c_t in[t tstride], c_t = w_t (power 1) or w_t^2 (power 2), in (6)'s order: four quarters of the task axis, each ascending in
-// chunks of eight, met as (q0 + q1) + (q2 + q3); a masked task is skipped
-SA_DEV double sc_weighted_sum(const double* in, size_t tstride, const double* w, const uint8_t* active, int T, int power) {
-  const int chunk = (T + 3) / 4;
-  double part[4];
-  for (int q = 0; q < 4; ++q) {
-    const int t_lo = q * chunk, t_hi = t_lo + chunk < T ? t_lo + chunk : T;
-    double s = 0.0;
-    for (int t0 = t_lo; t0 < t_hi; t0 += 8) {
-      double v[8], c[8];
-      for (int k = 0; k < 8; ++k) {
-        const int t = t0 + k;
-        const bool ok = t < t_hi && active[t];
-        v[k] = ok ? in[(size_t)t * tstride] : 0.0;
-        const double wt = ok ? w[t] : 0.0;
-        c[k] = power == 2 ? wt * wt : wt;
-      }
-      for (int k = 0; k < 8; ++k) s = fma(c[k], v[k], s);
-    }
-    part[q] = s;
-  }
-  return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
 // Study g by `nthr` cooperating threads.  Element (i, c), c <= i, of K' is fed by cov[t][a = i][column of point c]: the row of the LATER
 // point, the column of the earlier one (consecutive threads, consecutive columns); (c, i) is its mirror image.
 //   n'_g outside 1 .. n_max: nothing is known about the study's extent and nothing is written ((7n) answers NaN for it).
@@ -113,7 +89,7 @@ SA_DEV void sc_condition_block(const StudiesConditionBlockParams& p, double* lds
   for (int e = tid; e < n * n; e += nthr) {
     const int i = e / n, c = e - i * n;
     if (c > i) continue;
-    const double cov_s = sc_weighted_sum(p.cov + (size_t)i * W + col0 + c, (size_t)n_max * W, wg, ag, T, 2);
+    const double cov_s = sa_weighted_sum(p.cov + (size_t)i * W + col0 + c, (size_t)n_max * W, wg, ag, T, 2);
     double d2 = 0.0;
     for (int d = 0; d < D; ++d) {
       const double df = (Xs[i * D + d] - Xs[c * D + d]) / th[d];
@@ -126,7 +102,7 @@ SA_DEV void sc_condition_block(const StudiesConditionBlockParams& p, double* lds
     if (i != c) Kg[(size_t)c * n_max + i] = v;
   }
   for (int i = tid; i < n; i += nthr) {
-    const double mean_s = sc_weighted_sum(p.mu + col0 + i, W, wg, ag, T, 1);
+    const double mean_s = sa_weighted_sum(p.mu + col0 + i, W, wg, ag, T, 1);
     const double mean = (mean_s - m) / s;
     if (i < no) {
       rg[i] = p.y[(size_t)g * n_max + i] - mean;

@@ -34,6 +34,34 @@ SA_DEV void sa_kernel_and_slope(int kind, double d2, double os, double& k, doubl
   }
 }
 
+// sum_t c_t in[t tstride], c_t = w_t (power 1) or w_t^2 (power 2), in (6)'s order: four quarters of the task axis, each ascending in
+// chunks of eight, met as (q0 + q1) + (q2 + q3).  The training blocks of (7j) and (7m) are built from it.
+SA_DEV double sa_weighted_sum(const double* __restrict__ in, size_t tstride, const double* __restrict__ w, const uint8_t* __restrict__ active,
+                              int T, int power) {
+  const int chunk = (T + 3) / 4;
+  double part[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int t_lo = q * chunk, t_hi = t_lo + chunk < T ? t_lo + chunk : T;
+    double s = 0.0;
+    for (int t0 = t_lo; t0 < t_hi; t0 += 8) {
+      double v[8], c[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int t = t0 + k;
+        const bool ok = t < t_hi && active[t];   // (a masked task is skipped, not multiplied by zero: its values may be NaN)
+        v[k] = ok ? in[(size_t)t * tstride] : 0.0;
+        const double wt = ok ? w[t] : 0.0;
+        c[k] = power == 2 ? wt * wt : wt;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) s = fma(c[k], v[k], s);
+    }
+    part[q] = s;
+  }
+  return (part[0] + part[1]) + (part[2] + part[3]);
+}
+
 // The acquisition codes of include/scaml_gp.h (SCAML_ACQF_*): UCB, EI, and EI in the log domain (EI | LOG).
 constexpr int SA_ACQF_UCB = 0, SA_ACQF_EI = 1, SA_ACQF_LOG = 0x10, SA_ACQF_LOGEI = SA_ACQF_EI | SA_ACQF_LOG;
 SA_DEV bool sa_acqf_valid(int acqf) { return acqf == SA_ACQF_UCB || acqf == SA_ACQF_EI || acqf == SA_ACQF_LOGEI; }

@@ -20,32 +20,6 @@ extern "C" __global__ __launch_bounds__(scaml::STUDIES_SCORE_THREADS) void scaml
 // holds the lower triangle, which is the triangle (2) reads; the upper one is its mirror image.
 namespace scaml {
 
-__device__ __forceinline__ double tb_weighted_sum(const double* __restrict__ in, size_t tstride, const double* __restrict__ w,
-                                                  const uint8_t* __restrict__ active, int T, int power) {
-  const int chunk = (T + 3) / 4;
-  double part[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int t_lo = q * chunk, t_hi = t_lo + chunk < T ? t_lo + chunk : T;
-    double s = 0.0;
-    for (int t0 = t_lo; t0 < t_hi; t0 += 8) {
-      double v[8], c[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int t = t0 + k;
-        const bool ok = t < t_hi && active[t];   // (a masked task is skipped, not multiplied by zero: its values may be NaN)
-        v[k] = ok ? in[(size_t)t * tstride] : 0.0;
-        const double wt = ok ? w[t] : 0.0;
-        c[k] = power == 2 ? wt * wt : wt;
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) s = __builtin_fma(c[k], v[k], s);
-    }
-    part[q] = s;
-  }
-  return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
 template <int KIND>
 __device__ __forceinline__ void target_train_block(const TrainBlockParams& p) {
   __shared__ double exptab[64];
@@ -70,7 +44,7 @@ __device__ __forceinline__ void target_train_block(const TrainBlockParams& p) {
     while ((i + 1) * (i + 2) / 2 <= e) ++i;
     while (i * (i + 1) / 2 > e) --i;
     const int c = e - i * (i + 1) / 2;
-    const double cov_s = tb_weighted_sum(cp + e, packed, wg, ag, T, 2);
+    const double cov_s = sa_weighted_sum(cp + e, packed, wg, ag, T, 2);
     double d2 = 0.0;
     for (int d = 0; d < D; ++d) {
       const double df = (Xg[(size_t)i * D + d] - Xg[(size_t)c * D + d]) / th[d];
@@ -81,7 +55,7 @@ __device__ __forceinline__ void target_train_block(const TrainBlockParams& p) {
     if (i != c) Kg[(size_t)c * n_max + i] = v;
   }
   for (int e = threadIdx.x; e < n; e += blockDim.x) {
-    const double mean_s = tb_weighted_sum(mt + e, (size_t)n_max, wg, ag, T, 1);
+    const double mean_s = sa_weighted_sum(mt + e, (size_t)n_max, wg, ag, T, 1);
     p.resid[(size_t)g * n_max + e] = p.y[(size_t)g * n_max + e] - (mean_s - m_all) / s_all;
   }
 }

@@ -29,8 +29,9 @@ import scipy.optimize
 import torch
 
 from . import hyper
+from . import studies as _studies
 from .model import ScaMLGP, SourceGP, fantasize_studies
-from .utils import ExpectedImprovement, LogExpectedImprovement, UpperConfidenceBound, capture_graph, fit_targets_batched, optimize_marginal_likelihood
+from .utils import ExpectedImprovement, LogExpectedImprovement, StudiesAcquisition, UpperConfidenceBound, capture_graph, fit_targets_batched, optimize_marginal_likelihood
 
 
 class OptimizerNotReady(RuntimeError):
@@ -262,6 +263,45 @@ class ScaMLGPBOLoop:
         return self.X, self.Y
 
 
+_NEEDS_LOCKSTEP = ("suggest_mode", ("lockstep", "device"), "suggest_mode='lockstep' or 'device': the sequential mode runs every study on its own")
+# (mode, its values, what its value "batched" needs: (another mode, that mode's values that serve, the refusal's words))
+_STUDIES_MODES = (
+    ("suggest_mode", ("sequential", "lockstep", "device"), None),
+    ("score_mode", ("per_study", "batched"), _NEEDS_LOCKSTEP),
+    ("pending_mode", ("per_study", "batched"), _NEEDS_LOCKSTEP),
+    ("fantasy_setup", ("per_study", "batched"),
+     ("pending_mode", ("batched",), "pending_mode='batched': otherwise a study with pending evaluations runs on its own")),
+)
+
+
+def _check_modes(modes: Dict[str, str]) -> None:
+    """``ScaMLGPBOStudies``'s mode strings against ``_STUDIES_MODES``, in its order."""
+    for name, values, needs in _STUDIES_MODES:
+        quoted = [repr(v) for v in values]
+        if modes[name] not in values:
+            raise ValueError(f"{name} must be {', '.join(quoted[:-1])} or {quoted[-1]}, got {modes[name]!r}")
+        if needs is not None and modes[name] == "batched" and modes[needs[0]] not in needs[1]:
+            raise ValueError(f"{name}='batched' needs {needs[2]}")
+
+
+class _PartTimer:
+    """``profile_parts`` (developer timing): called at a boundary between the parts of a suggest it synchronises, and the time since the
+    last call goes to ``seconds[name]``.  Switched off it does nothing."""
+
+    def __init__(self, on: bool):
+        self.on, self.seconds, self.last = on, {}, None
+        self()
+
+    def __call__(self, name: Optional[str] = None) -> None:
+        if not self.on:
+            return
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        if name is not None:
+            self.seconds[name] = self.seconds.get(name, 0.0) + now - self.last
+        self.last = now
+
+
 class ScaMLGPBOStudies:
     """S independent Bayesian-optimisation studies against ONE fitted source stack, stepped in lock-step on one GPU -- the repeated
     runs behind a regret curve (scamlgp/benchmarking/local_runner.py:174-181 fans them out over a process pool, one study per core).
@@ -328,20 +368,7 @@ class ScaMLGPBOStudies:
     def __init__(self, source_gps: Union[Dict[Hashable, SourceGP], Sequence[Dict[Hashable, SourceGP]]], dim: int, num_studies: int,
                  seeds: Optional[Sequence[int]] = None, suggest_mode: str = "sequential", score_mode: str = "per_study",
                  pending_mode: str = "per_study", fantasy_setup: str = "per_study", **loop_kwargs):
-        if suggest_mode not in ("sequential", "lockstep", "device"):
-            raise ValueError(f"suggest_mode must be 'sequential', 'lockstep' or 'device', got {suggest_mode!r}")
-        if score_mode not in ("per_study", "batched"):
-            raise ValueError(f"score_mode must be 'per_study' or 'batched', got {score_mode!r}")
-        if score_mode == "batched" and suggest_mode == "sequential":
-            raise ValueError("score_mode='batched' needs suggest_mode='lockstep' or 'device': the sequential mode runs every study on its own")
-        if pending_mode not in ("per_study", "batched"):
-            raise ValueError(f"pending_mode must be 'per_study' or 'batched', got {pending_mode!r}")
-        if pending_mode == "batched" and suggest_mode == "sequential":
-            raise ValueError("pending_mode='batched' needs suggest_mode='lockstep' or 'device': the sequential mode runs every study on its own")
-        if fantasy_setup not in ("per_study", "batched"):
-            raise ValueError(f"fantasy_setup must be 'per_study' or 'batched', got {fantasy_setup!r}")
-        if fantasy_setup == "batched" and pending_mode != "batched":
-            raise ValueError("fantasy_setup='batched' needs pending_mode='batched': otherwise a study with pending evaluations runs on its own")
+        _check_modes(dict(suggest_mode=suggest_mode, score_mode=score_mode, pending_mode=pending_mode, fantasy_setup=fantasy_setup))
         self.suggest_mode, self.score_mode, self.pending_mode, self.fantasy_setup = suggest_mode, score_mode, pending_mode, fantasy_setup
         self.profile_parts = False   # developer timing (tools/dev_studies_time.py): synchronise between the parts of a suggest and time them
         self.last_suggest_info: dict = {}
@@ -402,9 +429,7 @@ class ScaMLGPBOStudies:
         p = st.pending.shape[0]
         if self.pending_mode != "batched" or st.max_pending_evaluations is None or p == 0:
             return False
-        m = st.model
-        return (m.num_fantasies is None and m.supports_posterior_grad() and m.n + p <= 96 and m.n + p <= m._stack.N
-                and 1 <= int(st.num_fantasies) <= 64)
+        return _studies.takes(st.model, p, int(st.num_fantasies))
 
     def _fantasy_models(self, studies: Sequence[ScaMLGPBOLoop]) -> dict:
         """``fantasy_setup="batched"``: the fantasy models of the studies that stay in the batch and hold pending points, from ONE
@@ -420,93 +445,76 @@ class ScaMLGPBOStudies:
         return {i: m for (i, _), m in zip(take, models)}
 
     def _suggest_lockstep(self, studies: Sequence[ScaMLGPBOLoop]):
-        from .utils import StudiesAcquisition
-
         out = [None] * len(studies)
-        batch = []   # (position, study, af, cand, vals, best0, x0)
-        parts, t_last = {}, [None]
-
-        def mark(name=None):   # (profile_parts only) a synchronisation at the boundary; the time since the last one goes to `name`
-            if not self.profile_parts:
-                return
-            torch.cuda.synchronize()
-            now = time.perf_counter()
-            if name is not None:
-                parts[name] = parts.get(name, 0.0) + now - t_last[0]
-            t_last[0] = now
-
-        mark()
+        mark = _PartTimer(self.profile_parts)
         fmodel = self._fantasy_models(studies)   # fantasy_setup="batched": {position: fantasy model}, all of them from one call
         if fmodel:
             mark("setup")
-
-        def build_af(i, st):   # (a study without a model from the batch builds its own, as before)
-            return st.acquisition_function(fmodel[i]) if i in fmodel else st.acquisition_function()
-
-        if self.score_mode == "batched":
-            drawn = []   # (position, study, af, cand): stage 1's draw per study, the scoring for all of them below
-            for i, st in enumerate(studies):
-                if not self._takes_study(st):
-                    out[i] = st.suggest()
-                    continue
-                st.model.eval()
-                drawn.append((i, st, build_af(i, st), acqf_draw_candidates(self.dim, st.raw_samples, st.gen)))
-            sa = None
-            if drawn:
-                # the studies' factors in two launches, then ONE scoring pass over all candidate tables (each padded to whole strips of
-                # 16 with a point of the box, whose values are dropped) and ONE device -> host copy
-                mark("stage1")
-                sa = StudiesAcquisition([d[2] for d in drawn], batched_factors=True)
-                mark("packing")
-                strips = [(d[3].shape[0] + 15) // 16 for d in drawn]
-                table = torch.full((16 * sum(strips), self.dim), 0.5, dtype=torch.float64)
-                o = 0
-                for d, ns in zip(drawn, strips):
-                    table[o:o + d[3].shape[0]] = d[3]
-                    o += 16 * ns
-                vals_all = sa.score(table, sa.group_of(strips))["value"].cpu()
-                o = 0
-                for (i, st, af, cand), ns in zip(drawn, strips):
-                    vals = vals_all[o:o + cand.shape[0]].clone()
-                    o += 16 * ns
-                    best0, pk = acqf_pick_initial_conditions(vals, st.num_restarts, st.gen)
-                    batch.append((i, st, af, cand, vals, best0, cand[pk]))
-        else:
-            for i, st in enumerate(studies):
-                if not self._takes_study(st):
-                    out[i] = st.suggest()
-                    continue
-                st.model.eval()
-                af = build_af(i, st)
-                batch.append((i, st, af) + acqf_initial_conditions(af, self.dim, st.raw_samples, st.num_restarts, st.gen))
+        batch, sa = self._stage1(studies, fmodel, out, mark)   # batch: (position, study, af, cand, vals, best0, x0)
         mark("stage1")
         self.last_suggest_info = dict(batched=[b[0] for b in batch], n_eval=0, n_iter=0, score_mode=self.score_mode)
         if self.fantasy_setup != "per_study":   # (the default mode's record keeps exactly the keys it had)
             self.last_suggest_info["fantasy_setup"] = self.fantasy_setup
         if self.profile_parts:
-            self.last_suggest_info["parts"] = parts   # seconds: setup (fantasy_setup="batched"), stage1, packing (with the factors), rounds, stage3
+            # seconds: setup (fantasy_setup="batched"), stage1, packing (with the factors), rounds, stage3
+            self.last_suggest_info["parts"] = mark.seconds
         if not batch:
             return out
-        if self.score_mode != "batched":
+        if sa is None:   # (score_mode="batched" has packed the studies for its scoring pass)
             sa = StudiesAcquisition([b[2] for b in batch])
             mark("packing")
         counts = [b[6].shape[0] for b in batch]
-        group = sa.group_of(counts)
-        X0 = torch.cat([b[6] for b in batch], 0)
-        B = X0.shape[0]
-        if self.suggest_mode == "device":   # the optimiser on the device: end points and THEIR values in one status read per chunk
-            res = sa.optimize(X0, group, studies[0].af_max_iter, bounds=(0.0, 1.0))
-            self.last_suggest_info.update(n_eval=res["n_eval"], n_calls=res["n_calls"], n_iter=int(res["stats"][:, 0].max()),
-                                          evals_per_start=res["stats"][:, 1].tolist(), status=res["stats"][:, 2].tolist())
-            xs, fs = res["x"].cpu().split(counts), res["f"].cpu().split(counts)
-            mark("rounds")
-            out = self._final_choices(batch, out, xs, fs)
-            mark("stage3")
-            return out
-        vg = lambda X: sa.value_and_grad(X, group)   # noqa: E731
-        if studies[0].use_graph:   # one capture per suggest() serves all studies: a single stream, two library launches
-            vg = GraphedAcquisition(vg, B, self.dim, sa.device)
+        X0, group = torch.cat([b[6] for b in batch], 0), sa.group_of(counts)
+        xs, fs = (self._rounds_device if self.suggest_mode == "device" else self._rounds_host)(sa, X0, group, counts, studies[0])
+        mark("rounds")
+        out = self._final_choices(batch, out, xs, fs)
+        mark("stage3")
+        return out
 
+    def _stage1(self, studies: Sequence[ScaMLGPBOLoop], fmodel: dict, out: list, mark):
+        """Stage 1 of every study's ``optimize_acqf``.  A study the batch does not take makes its own ``suggest()`` into ``out``; every
+        other one builds its acquisition function (on ``fmodel[position]`` where the batch has built its fantasy model) and draws its raw
+        candidates from its own ``gen``.  ``score_mode="per_study"``: it scores and picks at once (``acqf_initial_conditions``).
+        ``"batched"``: the studies' factors in two launches, then ONE scoring pass over all candidate tables and ONE device -> host copy,
+        then every study's picks.  Returns (batch, the ``StudiesAcquisition`` the scoring pass has built or None)."""
+        batch, drawn = [], []   # drawn: (position, study, af, cand) whose scoring is still to come
+        for i, st in enumerate(studies):
+            if not self._takes_study(st):
+                out[i] = st.suggest()
+                continue
+            st.model.eval()
+            af = st.acquisition_function(fmodel[i]) if i in fmodel else st.acquisition_function()   # (without a model from the batch: its own)
+            if self.score_mode == "batched":
+                drawn.append((i, st, af, acqf_draw_candidates(self.dim, st.raw_samples, st.gen)))
+            else:
+                batch.append((i, st, af) + acqf_initial_conditions(af, self.dim, st.raw_samples, st.num_restarts, st.gen))
+        if not drawn:
+            return batch, None
+        mark("stage1")
+        sa = StudiesAcquisition([d[2] for d in drawn], batched_factors=True)
+        mark("packing")
+        table, strips, first = sa.strip_table([d[3] for d in drawn])
+        vals_all = sa.score(table, sa.group_of(strips))["value"].cpu()
+        for (i, st, af, cand), o in zip(drawn, first):
+            vals = vals_all[o:o + cand.shape[0]].clone()
+            best0, pk = acqf_pick_initial_conditions(vals, st.num_restarts, st.gen)
+            batch.append((i, st, af, cand, vals, best0, cand[pk]))
+        return batch, sa
+
+    def _rounds_device(self, sa, X0: torch.Tensor, group: torch.Tensor, counts, loop: ScaMLGPBOLoop):
+        """The optimiser on the device: end points and THEIR values in one status read per chunk of rounds.  Returns (x, f) per study."""
+        res = sa.optimize(X0, group, loop.af_max_iter, bounds=(0.0, 1.0))
+        self.last_suggest_info.update(n_eval=res["n_eval"], n_calls=res["n_calls"], n_iter=int(res["stats"][:, 0].max()),
+                                      evals_per_start=res["stats"][:, 1].tolist(), status=res["stats"][:, 2].tolist())
+        return res["x"].cpu().split(counts), res["f"].cpu().split(counts)
+
+    def _rounds_host(self, sa, X0: torch.Tensor, group: torch.Tensor, counts, loop: ScaMLGPBOLoop):
+        """ONE ``hyper.batched_lbfgs`` on the host over the starts of all studies, every evaluation two library launches, then the end
+        points of all studies re-scored in one evaluation.  Returns (x, f) per study."""
+        B = X0.shape[0]
+        vg = lambda X: sa.value_and_grad(X, group)   # noqa: E731
+        if loop.use_graph:   # one capture per suggest() serves all studies: a single stream, two library launches
+            vg = GraphedAcquisition(vg, B, self.dim, sa.device)
         t_eval = [0.0]
 
         def fun(x: torch.Tensor):
@@ -516,13 +524,10 @@ class ScaMLGPBOStudies:
             t_eval[0] += time.perf_counter() - t0   # (the copy has waited for the evaluation)
             return -o[:, 0], -o[:, 1:]
 
-        res = hyper.batched_lbfgs(fun, X0, max_iter=studies[0].af_max_iter, bounds=(0.0, 1.0))
-        fin = sa.value(res.x, group).cpu()   # the end points of all studies re-scored in one evaluation
+        res = hyper.batched_lbfgs(fun, X0, max_iter=loop.af_max_iter, bounds=(0.0, 1.0))
+        fin = sa.value(res.x, group).cpu()
         self.last_suggest_info.update(n_eval=res.n_eval, n_iter=res.n_iter, eval_seconds=t_eval[0])
-        mark("rounds")
-        out = self._final_choices(batch, out, res.x.split(counts), fin.split(counts))
-        mark("stage3")
-        return out
+        return res.x.split(counts), fin.split(counts)
 
     @staticmethod
     def _final_choices(batch, out, xs_per_study, fin_per_study):

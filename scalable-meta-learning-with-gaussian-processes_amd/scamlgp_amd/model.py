@@ -24,7 +24,7 @@ from typing import Dict, Hashable, List, Optional, Sequence, Tuple
 import torch
 
 from . import dist as sdist
-from . import hyper, ops
+from . import hyper, ops, studies
 from ._lib import KIND_MATERN52, KIND_RBF
 
 _LOG_2PI = math.log(2.0 * math.pi)
@@ -650,7 +650,7 @@ class ScaMLGP:
         # cached source posteriors at the target inputs, all tasks, no pruning (scamlgp/model.py:279-289)
         if self.n > 0:
             # (V of the training points: computed once here, reused by every later posterior / gradient call of this model)
-            va = self._train_VA() if (self.n <= 96 and self._stack.fit.get("Linv") is not None) else None
+            va = self._train_VA() if (self.n <= studies.MAX_N and self._stack.fit.get("Linv") is not None) else None
             p = self._stack.posterior(self.train_X, cov_first=self.n, VA=va)
             # (sharded: every rank contributes its tasks' columns, one all-reduce each -- n <= ~80, tiny)
             self.source_means = sdist.gather_task_axis(p["mean"][self._idx].transpose(0, 1).contiguous(), self._shard)   # (n, T)
@@ -837,7 +837,7 @@ class ScaMLGP:
         and -- sharded -- ONE all-reduce of the fused buffer [mu_s || Sigma_s || var_s]."""
         w_full, active = self._active_tasks()
         # (the leading points of a joint evaluation are the model's training inputs: their V is computed once per model)
-        va = self._train_VA() if (train_first and 0 < cov_first == self.n <= 96 and x.shape[0] > self.n and self._stack.fit.get("Linv") is not None) else None
+        va = self._train_VA() if (train_first and 0 < cov_first == self.n <= studies.MAX_N and x.shape[0] > self.n and self._stack.fit.get("Linv") is not None) else None
         p = self._stack.posterior(x, cov_first=cov_first, VA=va)
         mu_s, cov_s = ops.weighted_prior_reduce(p["mean"], p["cov"], w_full, active)
         var_s = ops.weighted_task_sum(p["var"], w_full, 2, active)
@@ -930,8 +930,7 @@ class ScaMLGP:
     def supports_posterior_grad(self) -> bool:
         """The analytic input-gradient path needs training data within the fused covariance block (n <= 96), D <= 15 and the
         explicit inverse factors of the source stack (SourceGPStack.refresh caches them)."""
-        return (1 <= self.n <= 96 and self._stack.D <= 15 and self._stack.N <= 512 and self.device.type == "cuda"
-                and (self.num_fantasies is None or self.num_fantasies <= 64))
+        return studies.takes(self)
 
     def _train_VA(self) -> torch.Tensor:
         """V = L^-1 K(X_t, train_X) of every source task (T, N, n): fixed for the model's lifetime (sources and training inputs are)."""
@@ -965,7 +964,7 @@ class ScaMLGP:
         (scaml_target_posterior_grad_f64) -- an L-BFGS-B evaluation over R starts scores R points instead of the (2 D + 1) R of a
         central-difference stencil, with exact gradients."""
         if not self.supports_posterior_grad():
-            raise NotImplementedError("analytic posterior gradients need 1 <= n <= 96 training points and D <= 15")
+            raise NotImplementedError(f"analytic posterior gradients need {studies.LIMITS}")
         if self.num_fantasies is not None:
             raise NotImplementedError("a fantasy model's acquisition gradient comes from fantasy_acqf (the acquisition-function classes)")
         Xq = torch.as_tensor(X, dtype=torch.float64).reshape(-1, self._stack.D).to(self.device).contiguous()
@@ -1005,14 +1004,14 @@ class ScaMLGP:
         kernels: no per-fantasy work outside it."""
         if self.num_fantasies is None:
             raise ValueError("fantasy_acqf needs a fantasy model (ScaMLGP.fantasize)")
-        if self.num_fantasies > 64:
-            raise NotImplementedError("the fantasy acquisition kernel takes at most 64 fantasies")
+        if self.num_fantasies > studies.MAX_FANTASIES:
+            raise NotImplementedError(f"the fantasy acquisition kernel takes at most {studies.MAX_FANTASIES} fantasies")
         Xq = torch.as_tensor(X, dtype=torch.float64).reshape(-1, self._stack.D).to(self.device).contiguous()
         n = self.n
         grad_inputs = None
         if want_grad:
             if not self.supports_posterior_grad():
-                raise NotImplementedError("analytic acquisition gradients need 1 <= n <= 96 training points and D <= 15")
+                raise NotImplementedError(f"analytic acquisition gradients need {studies.LIMITS}")
             cov_s, mean_s, var_s, xall, cov_g, mu_g, var_g = self._grad_pass(Xq)
             grad_inputs = dict(cov_g=cov_g, mu_g=mu_g, var_g=var_g, Xt=self.train_X, Xq=Xq, theta=self.theta)
         else:
@@ -1114,17 +1113,13 @@ class ScaMLGP:
 
 def _fantasy_batch(models: Sequence[ScaMLGP], Xp: Sequence[torch.Tensor], Fs: Sequence[int], eps: torch.Tensor, own: bool) -> dict:
     """The device work of ``fantasize_studies`` for checked arguments: ``Xp[s]`` = cat(train_X, pending) of study s on the device, ``eps``
-    (S, p_max, F_max) the draws (host or device), ``own``: the models sit on slices of one parent stack.  Per study the V' launch, then
-    the grouped value pass over the studies' X' strips, ``ops.studies_condition_block``, ``ops.potrf_batched``,
-    ``ops.studies_fantasy_condition``.  Nothing is read back.  Returns dict(VA, pass (mu, var, cov), block (Knn, resid, mean_p), factor
-    (``potrf_batched``'s dict), out (alpha_f, y_fant, mu_p), strip_base (host list) and the packed arrays by name)."""
-    S = len(models)
+    (S, p_max, F_max) the draws (host or device), ``own``: the models sit on slices of one parent stack (``studies.source_stack`` finds
+    the same).  Per study the V' launch, then the grouped value pass over the studies' X' strips, ``ops.studies_condition_block``,
+    ``ops.potrf_batched``, ``ops.studies_fantasy_condition``.  Nothing is read back.  Returns dict(VA, pass (mu, var, cov), block (Knn,
+    resid, mean_p), factor (``potrf_batched``'s dict), out (alpha_f, y_fant, mu_p), strip_base (host list) and the packed arrays by name)."""
     m0 = models[0]
-    st0 = m0._stack
-    parent = getattr(st0, "parent", None)
-    D, dev = st0.D, m0.device
+    D, dev = m0._stack.D, m0.device
     ns, nps = [m.n for m in models], [int(x.shape[0]) for x in Xp]
-    n_max = max(nps)
     # V' per study, on its own stack object (step 1 of fantasize_studies)
     VA = []
     for m, x in zip(models, Xp):
@@ -1135,31 +1130,22 @@ def _fantasy_batch(models: Sequence[ScaMLGP], Xp: Sequence[torch.Tensor], Fs: Se
     strips = [(n + 15) // 16 for n in nps]
     fill = torch.full((16, D), 0.5, dtype=torch.float64, device=dev)
     Xq = torch.cat([t for x, k in zip(Xp, strips) for t in (x, fill[:16 * k - x.shape[0]])], 0)
-    pad = torch.nn.utils.rnn.pad_sequence
-    Xt = pad(Xp, batch_first=True)
-    y = torch.nn.functional.pad(pad([m.train_targets for m in models], batch_first=True), (0, n_max - max(ns)))
-    act = [m._active_tasks() for m in models]
-    w, active = torch.stack([a[0] for a in act]), torch.stack([a[1] for a in act]).to(torch.uint8)
-    theta = torch.stack([m.theta for m in models])
-    host = lambda vals, dt: torch.tensor(vals, dtype=dt).to(dev)   # noqa: E731
-    base = [sum(strips[:s]) for s in range(S)]
-    n_points, n_obs, n_fant = host(nps, torch.int32), host(ns, torch.int32), host(Fs, torch.int32)
-    strip_base = host(base, torch.int32)
-    group = host([s for s, k in enumerate(strips) for _ in range(k)], torch.int32)
-    m_all, s_all = host([m._m_all_f for m in models], torch.float64), host([m._s_all_f for m in models], torch.float64)
-    VA_tab = host([v.data_ptr() for v in VA], torch.int64)
-    src = parent if own else st0
+    a = studies.pack(models, VA, Xp)
+    y = torch.nn.functional.pad(torch.nn.utils.rnn.pad_sequence([m.train_targets for m in models], batch_first=True), (0, max(nps) - max(ns)))
+    host = lambda vals: torch.tensor(vals, dtype=torch.int32).to(dev)   # noqa: E731
+    base = [sum(strips[:s]) for s in range(len(models))]
+    a.update(Xq=Xq, y=y, n_obs=host(ns), n_fant=host(Fs), strip_base=host(base), group=host([s for s, k in enumerate(strips) for _ in range(k)]),
+             eps=eps.to(dev))
+    src, own_kw = studies.source_stack(models, "fantasies are")
     fs = src.fit
-    own_kw = dict(task_base=host([m._stack.lo for m in models], torch.int32), tasks_per_group=st0.T) if own else {}
-    g = ops.source_posteriors_grouped(Xq, group, Xt, n_points, VA_tab, src.X, src.theta, src.kind, fs["Linv"], fs["alpha"], src.y_mean, src.y_std,
-                                      src.n_points, **own_kw)
-    blk = ops.studies_condition_block(g["mu"], g["cov"], strip_base, w, active, Xt, theta, y, n_points, n_obs, m_all, s_all, m0.kind)
-    fac = ops.potrf_batched(blk["Knn"], None, n_points=n_points, want_linv=True)
-    eps = eps.to(dev)
-    out = ops.studies_fantasy_condition(fac["L"], blk["resid"], blk["mean_p"], n_points, n_obs, fac["info"], eps, n_fant, m_all, s_all)
-    arrays = dict(Xq=Xq, group=group, Xt=Xt, y=y, w=w, active=active, theta=theta, n_points=n_points, n_obs=n_obs, n_fant=n_fant,
-                  strip_base=strip_base, m_all=m_all, s_all=s_all, eps=eps)
-    return dict(VA=VA, strip_base=base, arrays=arrays, block=blk, factor=fac, out=out, **{"pass": g})
+    g = ops.source_posteriors_grouped(Xq, a["group"], a["Xt"], a["n_points"], a["VA_tab"], src.X, src.theta, src.kind, fs["Linv"], fs["alpha"],
+                                      src.y_mean, src.y_std, src.n_points, **own_kw)
+    blk = ops.studies_condition_block(g["mu"], g["cov"], a["strip_base"], a["w"], a["active"], a["Xt"], a["theta"], y, a["n_points"], a["n_obs"],
+                                      a["m_all"], a["s_all"], m0.kind)
+    fac = ops.potrf_batched(blk["Knn"], None, n_points=a["n_points"], want_linv=True)
+    out = ops.studies_fantasy_condition(fac["L"], blk["resid"], blk["mean_p"], a["n_points"], a["n_obs"], fac["info"], a["eps"], a["n_fant"],
+                                        a["m_all"], a["s_all"])
+    return dict(VA=VA, strip_base=base, arrays=a, block=blk, factor=fac, out=out, **{"pass": g})
 
 
 def fantasize_studies(models: Sequence[ScaMLGP], pending: Sequence[torch.Tensor], num_fantasies, generators: Sequence[Optional[torch.Generator]],
@@ -1197,24 +1183,16 @@ def fantasize_studies(models: Sequence[ScaMLGP], pending: Sequence[torch.Tensor]
     Fs = [int(num_fantasies)] * S if not isinstance(num_fantasies, (list, tuple)) else [int(v) for v in num_fantasies]
     if len(Fs) != S:
         raise ValueError(f"got {len(Fs)} fantasy counts for {S} models")
-    m0 = models[0]
-    st0 = m0._stack
-    parent = getattr(st0, "parent", None)
-    shared = all(m._stack is st0 for m in models)
-    own = (not shared) and parent is not None and all(getattr(m._stack, "parent", None) is parent and m._stack.T == st0.T for m in models)
-    D, dev = st0.D, m0.device
+    _, own = studies.source_stack(models, "fantasies are")
+    st0, dev = models[0]._stack, models[0].device
     Xp = []
     for s, m in enumerate(models):
-        if not (shared or own) or m.kind != m0.kind or m.T != m0.T:
-            raise ValueError("the studies' models must share one source stack and one kernel family")
-        if m._shard is not None:
-            raise NotImplementedError("fantasies are not implemented for a task-sharded source stack (shard=True)")
         if m.num_fantasies is not None:
             raise NotImplementedError("a fantasy model cannot be conditioned further")
-        x = torch.as_tensor(pending[s], dtype=torch.float64).to(dev).reshape(-1, D)
-        if not m.supports_posterior_grad() or x.shape[0] < 1 or m.n + x.shape[0] > 96 or m.n + x.shape[0] > st0.N or not 1 <= Fs[s] <= 64:
-            raise NotImplementedError(f"study {s}: fantasize_studies takes 1 <= n, p >= 1, n + p <= 96 (and <= the stack's N), D <= 15 and "
-                                      "at most 64 fantasies; use ScaMLGP.fantasize")
+        x = torch.as_tensor(pending[s], dtype=torch.float64).to(dev).reshape(-1, st0.D)
+        if x.shape[0] < 1 or not studies.takes(m, x.shape[0], Fs[s]):
+            raise NotImplementedError(f"study {s}: fantasize_studies takes 1 <= n, p >= 1, n + p <= {studies.MAX_N} (and <= the stack's N), "
+                                      f"D <= {studies.MAX_D} and at most {studies.MAX_FANTASIES} fantasies; use ScaMLGP.fantasize")
         Xp.append(torch.cat([m.train_X, x], 0))
     ns, nps = [m.n for m in models], [int(x.shape[0]) for x in Xp]
     # 2. the draws, one host table for the batch
@@ -1224,7 +1202,7 @@ def fantasize_studies(models: Sequence[ScaMLGP], pending: Sequence[torch.Tensor]
         e = torch.randn(Fs[s], nps[s] - ns[s], dtype=torch.float64, generator=gen, device=gdev)
         eps[s, :nps[s] - ns[s], :Fs[s]] = e.transpose(0, 1).cpu()
     # 1. and 3. on the device
-    b = _fantasy_batch(models, Xp, Fs, eps, own)
+    b = _fantasy_batch(models, Xp, Fs, eps, bool(own))
     g, fac, out, VA, base = b["pass"], b["factor"], b["out"], b["VA"], b["strip_base"]
     # 4. the one round trip
     status = torch.cat([fac["info"].to(torch.float64), fac["jitter"]]).cpu()
@@ -1237,11 +1215,7 @@ def fantasize_studies(models: Sequence[ScaMLGP], pending: Sequence[torch.Tensor]
     fantasies = []
     for s, m in enumerate(models):
         n, F, c0 = nps[s], Fs[s], 16 * base[s]
-        nb = (n + 15) // 16
-        alpha_f = out["alpha_f"][s, :n, :F].contiguous()
-        factor = dict(L=fac["L"][s:s + 1, :n, :n].contiguous(), alpha=alpha_f[:, 0].unsqueeze(0).contiguous(), quad=None,
-                      logdet=fac["logdet"][s:s + 1], info=fac["info"][s:s + 1], jitter=fac["jitter"][s:s + 1],
-                      Linv_diag=fac["Linv_diag"][s:s + 1, :nb].contiguous(), alpha_f=alpha_f)
+        factor = studies.factor_slice(fac, s, n, alpha_f=out["alpha_f"][s, :n, :F].contiguous())
         rows = m._idx_dev   # (the model's tasks among the pass's rows: the stack's tasks, or the T slots of the study's slice)
         means = lambda rows=rows, c0=c0, n=n: g["mu"][rows, c0:c0 + n].transpose(0, 1).contiguous()              # noqa: E731  (n', T)
         covs = lambda rows=rows, c0=c0, n=n: g["cov"][rows, :n, c0:c0 + n].permute(1, 2, 0).contiguous()          # noqa: E731  (n', n', T)

@@ -18,7 +18,7 @@ import torch
 
 from . import dist as sdist
 from . import hyper
-from . import ops
+from . import ops, studies
 from .model import ScaMLGP, SourceGP, SourceGPStack
 
 logger = logging.getLogger("scamlgp_amd")
@@ -365,26 +365,41 @@ def _fantasy_value(model: ScaMLGP, X: torch.Tensor, acqf: int, param: float) -> 
     return _drop_q(X, v.reshape(X.shape[:-1]))
 
 
+class _AnalyticAcquisition:
+    """What the three acquisition classes share: ``code`` (the library's ops.ACQF_*) and ``param`` (UCB's beta, best_f of EI and LogEI)
+    for the library's kernels, and the fantasy-model branch of ``__call__`` / ``value_and_grad``.  A class states its formulas on an
+    ordinary model in ``_value`` / ``_value_and_grad``."""
 
-class UpperConfidenceBound:
+    def __call__(self, X: torch.Tensor) -> torch.Tensor:
+        X = _single_q(X)
+        if self.model.num_fantasies is not None:
+            return _fantasy_value(self.model, X, self.code, self.param)
+        return _drop_q(X, self._value(X))
+
+    def value_and_grad(self, X: torch.Tensor):
+        """(value (M,), d value / d X (M, D)) from the model's analytic posterior gradients (ScaMLGP.posterior_with_grad); on a fantasy
+        model the value over the fantasies (``ScaMLGP.fantasy_acqf``) and its exact gradient."""
+        if self.model.num_fantasies is not None:
+            return self.model.fantasy_acqf(X, self.code, self.param, want_grad=True)
+        return self._value_and_grad(X)
+
+
+class UpperConfidenceBound(_AnalyticAcquisition):
     """botorch UpperConfidenceBound(model, beta=9.0, maximize=False) (scamlgp/utils.py:215-224):
     value = -mu + sqrt(beta * var) per query point; X (M, D) -> (M,).  On a fantasy model (ScaMLGP.fantasize) the value is the
     mean over the fantasies of the per-fantasy value (``ScaMLGP.fantasy_acqf``)."""
 
+    code = ops.ACQF_UCB
+    param = property(lambda self: self.beta)
+
     def __init__(self, model: ScaMLGP, beta: float = 9.0):
         self.model, self.beta = model, beta
 
-    def __call__(self, X: torch.Tensor) -> torch.Tensor:
-        if self.model.num_fantasies is not None:
-            return _fantasy_value(self.model, _single_q(X), ops.ACQF_UCB, self.beta)
-        mvn = self.model.posterior(_single_q(X)).mvn
-        return _drop_q(X, -mvn.mean + torch.sqrt(self.beta * mvn.variance.clamp_min(0.0)))
+    def _value(self, X: torch.Tensor) -> torch.Tensor:
+        mvn = self.model.posterior(X).mvn
+        return -mvn.mean + torch.sqrt(self.beta * mvn.variance.clamp_min(0.0))
 
-    def value_and_grad(self, X: torch.Tensor):
-        """(value (M,), d value / d X (M, D)) from the model's analytic posterior gradients (ScaMLGP.posterior_with_grad); on a fantasy
-        model the mean over the fantasies and its exact gradient."""
-        if self.model.num_fantasies is not None:
-            return self.model.fantasy_acqf(X, ops.ACQF_UCB, self.beta, want_grad=True)
+    def _value_and_grad(self, X: torch.Tensor):
         mu, var, dmu, dvar = self.model.posterior_with_grad(X)
         sd = torch.sqrt(self.beta * var.clamp_min(0.0))
         # d sqrt(beta var) = beta dvar / (2 sqrt(beta var)); zero where the variance is clamped
@@ -392,29 +407,27 @@ class UpperConfidenceBound:
         return -mu + sd, -dmu + coef.unsqueeze(-1) * dvar
 
 
-class ExpectedImprovement:
+class ExpectedImprovement(_AnalyticAcquisition):
     """botorch analytic ExpectedImprovement(model, best_f, maximize=False) (scamlgp/optimizer.py:96-98):
     sigma = sqrt(max(var, 1e-9)), u = -(mu - best_f) / sigma, EI = sigma (phi(u) + u Phi(u)).  On a fantasy model: the mean over the
     fantasies of the per-fantasy EI, best_f still the caller's incumbent over observed data."""
 
+    code = ops.ACQF_EI
+    param = property(lambda self: self.best_f)
+
     def __init__(self, model: ScaMLGP, best_f: float):
         self.model, self.best_f = model, best_f
 
-    def __call__(self, X: torch.Tensor) -> torch.Tensor:
-        if self.model.num_fantasies is not None:
-            return _fantasy_value(self.model, _single_q(X), ops.ACQF_EI, self.best_f)
-        mvn = self.model.posterior(_single_q(X)).mvn
+    def _value(self, X: torch.Tensor) -> torch.Tensor:
+        mvn = self.model.posterior(X).mvn
         sigma = mvn.variance.clamp_min(1e-9).sqrt()
         u = -(mvn.mean - self.best_f) / sigma
         pdf = torch.exp(-0.5 * u * u) / math.sqrt(2.0 * math.pi)
         cdf = 0.5 * (1.0 + torch.erf(u / math.sqrt(2.0)))
-        return _drop_q(X, sigma * (pdf + u * cdf))
+        return sigma * (pdf + u * cdf)
 
-    def value_and_grad(self, X: torch.Tensor):
-        """(EI (M,), d EI / d X (M, D)): d EI = -Phi(u) d mu + phi(u) d sigma, d sigma = d var / (2 sigma) (zero where the variance
-        sits on the 1e-9 floor), from the model's analytic posterior gradients; on a fantasy model the mean over the fantasies."""
-        if self.model.num_fantasies is not None:
-            return self.model.fantasy_acqf(X, ops.ACQF_EI, self.best_f, want_grad=True)
+    def _value_and_grad(self, X: torch.Tensor):
+        """d EI = -Phi(u) d mu + phi(u) d sigma, d sigma = d var / (2 sigma) (zero where the variance sits on the 1e-9 floor)."""
         mu, var, dmu, dvar = self.model.posterior_with_grad(X)
         sigma = var.clamp_min(1e-9).sqrt()
         u = -(mu - self.best_f) / sigma
@@ -424,29 +437,27 @@ class ExpectedImprovement:
         return sigma * (pdf + u * cdf), -cdf.unsqueeze(-1) * dmu + pdf.unsqueeze(-1) * dsig
 
 
-class LogExpectedImprovement:
+class LogExpectedImprovement(_AnalyticAcquisition):
     """botorch LogExpectedImprovement(model, best_f, maximize=False): the logarithm of ``ExpectedImprovement``, with its clamp,
     log sigma + g(u), g(u) = log(phi(u) + u Phi(u)), evaluated without cancellation so that value and gradient stay finite and
     accurate where EI underflows to an exact 0 (u below about -38).  The transform of the posterior is the library's
     (``ops.acqf_transform``, include/scaml_gp.h (7o)) for every n, the prior-only model included.  On a fantasy model: the log of the
     MEAN EI over the fantasies (a log-sum-exp of the per-fantasy values), ``ScaMLGP.fantasy_acqf`` with ``ops.ACQF_LOGEI``."""
 
+    code = ops.ACQF_LOGEI
+    param = property(lambda self: self.best_f)
+
     def __init__(self, model: ScaMLGP, best_f: float):
         self.model, self.best_f = model, best_f
 
-    def __call__(self, X: torch.Tensor) -> torch.Tensor:
-        if self.model.num_fantasies is not None:
-            return _fantasy_value(self.model, _single_q(X), ops.ACQF_LOGEI, self.best_f)
-        mvn = self.model.posterior(_single_q(X)).mvn
+    def _value(self, X: torch.Tensor) -> torch.Tensor:
+        mvn = self.model.posterior(X).mvn
         mu = mvn.mean
         A, _, _ = ops.acqf_transform(mu.detach(), mvn.variance.detach(), ops.ACQF_LOGEI, self.best_f, want_factors=False)
-        return _drop_q(X, A.reshape(mu.shape))
+        return A.reshape(mu.shape)
 
-    def value_and_grad(self, X: torch.Tensor):
-        """(LogEI (M,), d LogEI / d X (M, D)) = dA/dmu d mu + dA/dvar d var from the model's analytic posterior gradients; on a
-        fantasy model the log of the mean EI over the fantasies and its exact gradient."""
-        if self.model.num_fantasies is not None:
-            return self.model.fantasy_acqf(X, ops.ACQF_LOGEI, self.best_f, want_grad=True)
+    def _value_and_grad(self, X: torch.Tensor):
+        """d LogEI = dA/dmu d mu + dA/dvar d var."""
         mu, var, dmu, dvar = self.model.posterior_with_grad(X)
         A, Amu, Av = ops.acqf_transform(mu, var, ops.ACQF_LOGEI, self.best_f)
         return A, Amu.unsqueeze(-1) * dmu + Av.unsqueeze(-1) * dvar
@@ -489,46 +500,31 @@ class StudiesAcquisition:
         if not afs:
             raise ValueError("StudiesAcquisition needs at least one acquisition function")
         kinds = {type(a) for a in afs}
-        codes = {UpperConfidenceBound: ops.ACQF_UCB, ExpectedImprovement: ops.ACQF_EI, LogExpectedImprovement: ops.ACQF_LOGEI}
-        if len(kinds) != 1 or not kinds <= set(codes):
+        if len(kinds) != 1 or not kinds <= {UpperConfidenceBound, ExpectedImprovement, LogExpectedImprovement}:
             raise TypeError("the acquisition functions must all be UpperConfidenceBound, all ExpectedImprovement or all "
                             "LogExpectedImprovement")
-        self.acqf = codes[type(afs[0])]
+        self.acqf = afs[0].code
         models = [a.model for a in afs]
         m0 = models[0]
         # the source stacks: one object shared by all studies, or slices of one parent with an equal number of tasks (per-study stacks,
         # model.meta_fit_scamlgp_studies) -- then the pass reads the parent's arrays, study g's tasks from task_base[g]
-        st0 = m0._stack
-        parent = getattr(st0, "parent", None)
-        shared = all(m._stack is st0 for m in models)
-        own = (not shared) and parent is not None and all(getattr(m._stack, "parent", None) is parent and m._stack.T == st0.T for m in models)
+        self.source, self._own = studies.source_stack(models, "the batched acquisition is")
+        self.task_base = self._own.get("task_base")
         for m in models:
-            if not (shared or own) or m.kind != m0.kind or m.T != m0.T:
-                raise ValueError("the studies' models must share one source stack and one kernel family")
-            if m._shard is not None:
-                raise NotImplementedError("the batched acquisition is not implemented for a task-sharded source stack (shard=True)")
             if not m.supports_posterior_grad():
-                raise NotImplementedError("the batched acquisition takes models with 1 <= n <= 96 training (and pending) points, D <= 15 "
-                                          "and at most 64 fantasies")
+                raise NotImplementedError(f"the batched acquisition takes models with 1 <= n <= {studies.MAX_N} training (and pending) points, "
+                                          f"D <= {studies.MAX_D} and at most {studies.MAX_FANTASIES} fantasies")
         self.models, self.kind, self.device = models, m0.kind, m0.device
-        st = m0._stack
-        self.source = parent if own else st0   # whose arrays the source pass reads
-        self.task_base = torch.tensor([m._stack.lo for m in models], dtype=torch.int32).to(m0.device) if own else None
-        self._own = dict(task_base=self.task_base, tasks_per_group=st0.T) if own else {}
-        G, D, dev = len(models), st.D, m0.device
-        ns = [m.n for m in models]
-        n_max, nbm = max(ns), (max(ns) + 15) // 16
+        G, D, dev = len(models), m0._stack.D, m0.device
+        n_max = max(m.n for m in models)
         self.G, self.D, self.n_max = G, D, n_max
         z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)   # noqa: E731
-        self.w, self.active = z(G, st.T), torch.zeros(G, st.T, dtype=torch.uint8, device=dev)
-        self.Xt, self.theta = z(G, n_max, D), z(G, D + 2)
-        self.L, self.Linv_diag, self.alpha = z(G, n_max, n_max), z(G, nbm, 16, 16), z(G, n_max)
+        self.L, self.Linv_diag, self.alpha = z(G, n_max, n_max), z(G, (n_max + 15) // 16, 16, 16), z(G, n_max)
         self.info = torch.zeros(G, dtype=torch.int32, device=dev)
         self._VA = []
         fant = [m.num_fantasies or 1 for m in models]
         self.fantasy = any(m.num_fantasies is not None for m in models)
         self.alpha_f = z(G, n_max, max(fant)) if self.fantasy else None
-        param = lambda a: float(a.beta if self.acqf == ops.ACQF_UCB else a.best_f)   # noqa: E731
         if batched_factors:
             self._factors_batched([m for m in models if m.num_fantasies is None and m._target_factor() is None])
         for g, (af, m) in enumerate(zip(afs, models)):
@@ -536,13 +532,10 @@ class StudiesAcquisition:
             f = m._target_factor()
             if f is None:   # (present after the study's scoring pass; otherwise the model's own path computes and caches it)
                 if m.num_fantasies is not None:
-                    m.fantasy_acqf(m.train_X[:1], self.acqf, param(af))
+                    m.fantasy_acqf(m.train_X[:1], self.acqf, float(af.param))
                 else:
                     m.posterior_with_grad(m.train_X[:1])
                 f = m._target_factor()
-            w_full, act = m._active_tasks()
-            self.w[g], self.active[g] = w_full, act.to(torch.uint8)
-            self.Xt[g, :n], self.theta[g] = m.train_X, m.theta
             self.L[g, :n, :n], self.Linv_diag[g, :(n + 15) // 16] = f["L"][0], f["Linv_diag"][0]
             if m.num_fantasies is not None:
                 self.alpha_f[g, :n, :fant[g]] = f["alpha_f"]
@@ -552,13 +545,10 @@ class StudiesAcquisition:
                     self.alpha_f[g, :n, 0] = f["alpha"][0]
             self.info[g] = f["info"][0]
             self._VA.append(m._train_VA().contiguous())
-        host = lambda vals, dt: torch.tensor(vals, dtype=dt).to(dev)   # noqa: E731
-        self.n_points = host(ns, torch.int32)
-        self.m_all = host([m._m_all_f for m in models], torch.float64)
-        self.s_all = host([m._s_all_f for m in models], torch.float64)
-        self.acqf_param = host([param(a) for a in afs], torch.float64)
-        self.n_fant = host(fant, torch.int32) if self.fantasy else None
-        self.VA_tab = host([v.data_ptr() for v in self._VA], torch.int64)
+        for name, arr in studies.pack(models, self._VA).items():   # w, active, theta, Xt, n_points, m_all, s_all, VA_tab
+            setattr(self, name, arr)
+        self.acqf_param = torch.tensor([float(a.param) for a in afs], dtype=torch.float64).to(dev)
+        self.n_fant = torch.tensor(fant, dtype=torch.int32).to(dev) if self.fantasy else None
 
     @staticmethod
     def _factors_batched(models: Sequence[ScaMLGP]):
@@ -573,15 +563,9 @@ class StudiesAcquisition:
                 take.append((m, prob))
         if not take:
             return [], None
-        batch = ops.TargetFitBatch([p for _, p in take])
-        act = [m._active_tasks() for m, _ in take]
-        f = ops.target_factors_batched(batch, torch.stack([a[0] for a in act]), torch.stack([a[1] for a in act]).to(torch.uint8),
-                                       torch.stack([m.theta for m, _ in take]))
+        f = ops.target_factors_batched(ops.TargetFitBatch([p for _, p in take]), *studies.pack_parameters([m for m, _ in take]))
         for g, (m, _) in enumerate(take):
-            n, nb = m.n, (m.n + 15) // 16
-            m._keep_target_factor(dict(L=f["L"][g:g + 1, :n, :n].contiguous(), alpha=f["alpha"][g:g + 1, :n].contiguous(),
-                                       quad=f["quad"][g:g + 1], logdet=f["logdet"][g:g + 1], info=f["info"][g:g + 1],
-                                       jitter=f["jitter"][g:g + 1], Linv_diag=f["Linv_diag"][g:g + 1, :nb].contiguous()))
+            m._keep_target_factor(studies.factor_slice(f, g, m.n))
         return [m for m, _ in take], f
 
     def score(self, X: torch.Tensor, group_per_strip: torch.Tensor, want_posterior: bool = False) -> Dict[str, torch.Tensor]:
@@ -626,6 +610,17 @@ class StudiesAcquisition:
         """(sum counts,) int32 on the device: study s's index ``counts[s]`` times -- the ``group`` of a batch that lists the studies'
         points one study after the other."""
         return torch.repeat_interleave(torch.arange(self.G, dtype=torch.int32), torch.as_tensor(list(counts))).to(self.device)
+
+    def strip_table(self, tables: Sequence[torch.Tensor]):
+        """``score``'s X for the studies' candidate tables ``tables[s]`` (M_s, D) on the host: each padded to whole strips of 16 with a point
+        of the box, whose values are dropped.  Returns (X (16 sum strips, D) on the host, strips per study -- ``group_of(strips)`` is
+        ``score``'s ``group_per_strip`` --, the first row of every study's table in X)."""
+        strips = [(t.shape[0] + 15) // 16 for t in tables]
+        first = [16 * sum(strips[:s]) for s in range(len(tables))]
+        X = torch.full((16 * sum(strips), self.D), 0.5, dtype=torch.float64)
+        for t, o in zip(tables, first):
+            X[o:o + t.shape[0]] = t
+        return X, strips, first
 
     def evaluate(self, X: torch.Tensor, group: torch.Tensor, want_grad: bool = True, want_posterior: bool = False) -> Dict[str, torch.Tensor]:
         """dict(value (Mq,), grad (Mq, D) or None, mu, var (Mq,) or None) at X (Mq, D), point q scored by study ``group[q]`` (int32, on the

@@ -15,6 +15,9 @@ _lib.emul_blocked_plan.argtypes = [ctypes.c_int] * 5 + [_LL, ctypes.c_int, ctype
 
 LDS_LIMIT = int(_lib.emul_lds_limit())
 LINV_TARGET_WORKGROUPS = int(_lib.emul_linv_target_workgroups())
+_limits = (_LL * 3)()
+_lib.emul_studies_limits(_limits)
+STUDIES_MAX_N, STUDIES_MAX_D, STUDIES_MAX_FANTASIES = (int(v) for v in _limits)   # csrc/gp_studies_acqf.h
 
 FitPlan = namedtuple("FitPlan", "variant nb wu block lds_doubles")
 BlockedPlan = namedtuple("BlockedPlan", "path t8 parts lds_coop flag_bytes need nt solve_small_d rounds lds_solve lds_syrk")

@@ -42,6 +42,13 @@ void emul_posterior_plan(int N, int D, long long* out2) {
   out2[1] = p.xl;
 }
 
+// the studies' limits (csrc/gp_studies_acqf.h): training + pending points, input dimensions, fantasies
+void emul_studies_limits(long long* out3) {
+  out3[0] = scaml::STUDIES_ACQF_MAX_N;
+  out3[1] = scaml::STUDIES_ACQF_MAX_D;
+  out3[2] = scaml::STUDIES_FANTASY_MAX_F;
+}
+
 int emul_strip_solve_waves(int np) { return scaml::strip_solve_waves(np); }
 int emul_linv_groups(int T, int nb, int waves) { return scaml::linv_groups(T, nb, waves); }
 

@@ -3,6 +3,8 @@ at 256 CUs (the MI355X) and again at 64 -- nothing in the rules may have a CU co
 inverse-factor split.  csrc/scaml_host.cpp launches from these very functions, so a rule that moves fails here and nowhere silently:
 the helpers that name the instance a case exercises (tests/_fit_bounds.py, tests/_failpath_cases.py, tests/_target_fit_bounds.py) ask
 the same plans."""
+from types import SimpleNamespace
+
 import pytest
 
 from tests import _dispatch as DP
@@ -14,6 +16,35 @@ FIT = {0: (0, 2, 1, 128), 1: (1, 4, 3, 256), 2: (2, 8, 3, 256), 3: (3, 16, 7, 51
 def test_constants():
     assert DP.LDS_LIMIT == 160 * KIB
     assert DP.LINV_TARGET_WORKGROUPS == 256
+
+
+def test_python_studies_limits_are_the_headers():
+    """scamlgp_amd/studies.py restates csrc/gp_studies_acqf.h's limits for the Python layer (the stack's N: tests/test_studies_acqf_gpu.py)."""
+    from scamlgp_amd import studies
+
+    assert (studies.MAX_N, studies.MAX_D, studies.MAX_FANTASIES) == (DP.STUDIES_MAX_N, DP.STUDIES_MAX_D, DP.STUDIES_MAX_FANTASIES)
+
+
+def _model(n=8, D=2, N=32, num_fantasies=None, device="cuda"):
+    """What ``studies.takes`` reads of a ScaMLGP."""
+    return SimpleNamespace(n=n, num_fantasies=num_fantasies, device=SimpleNamespace(type=device), _stack=SimpleNamespace(D=D, N=N))
+
+
+def test_studies_predicate_at_its_edges():
+    from scamlgp_amd.studies import takes
+
+    # the model as it stands: 1 <= n <= 96 (its stack's N does not bound n), D <= 15, N <= 512, on the GPU, at most 64 fantasies
+    assert [takes(_model(n=n)) for n in (0, 1, 96, 97)] == [False, True, True, False]
+    assert [takes(_model(D=D)) for D in (15, 16)] == [True, False]
+    assert [takes(_model(N=N)) for N in (512, 513)] == [True, False]
+    assert takes(_model(n=40, N=32)) and not takes(_model(device="cpu"))
+    assert [takes(_model(num_fantasies=F)) for F in (None, 1, 64, 65)] == [True, True, True, False]
+    # an ordinary model still to be conditioned on p points with F fantasies: n + p <= 96 and <= N, 1 <= F <= 64
+    assert [takes(_model(n=n, N=128), p, 4) for n, p in ((0, 1), (1, 1), (95, 1), (96, 1), (90, 6), (90, 7))] == [False, True, True, False, True, False]
+    assert [takes(_model(n=30, N=32), p, 4) for p in (2, 3)] == [True, False]
+    assert [takes(_model(n=8), 1, F) for F in (0, 1, 64, 65)] == [False, True, True, False]
+    assert [takes(_model(n=8, D=D), 1, 4) for D in (15, 16)] == [True, False]
+    assert not takes(_model(n=8, num_fantasies=4), 1, 4) and not takes(_model(n=8, device="cpu"), 1, 4)   # (a fantasy model is not conditioned further)
 
 
 # ---- fused fit / POTRF ---------------------------------------------------------------------------------------------

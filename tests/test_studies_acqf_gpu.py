@@ -20,7 +20,7 @@ import pytest
 import torch
 
 from oracle import gp_oracle as O
-from scamlgp_amd import hyper, model as M, ops, synthetic, utils
+from scamlgp_amd import _lib, hyper, model as M, ops, studies, synthetic, utils
 from scamlgp_amd.bo import GraphedAcquisition
 
 pytestmark = pytest.mark.gpu
@@ -189,6 +189,7 @@ def test_grouped_pass_equals_ungrouped(device):
         # the covariance block is summed in a fixed order on both sides
         assert torch.equal(cov[:, :m.n][:, :, rows], ref["cov"].reshape(st.T, m.n, rows.numel(), 16))
     assert not bool(out["mu"][:, 5].any()) and not bool(out["var"][:, 5].any())
+    assert studies.MAX_STACK_N == _lib.lib.scaml_posterior_max_n()   # the pass's limit on the stack's N, as the Python layer states it
 
 
 def test_graph_replay_equals_eager(device):
