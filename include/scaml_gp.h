@@ -329,6 +329,57 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
                                   const double* theta, int n, int M, int F, int D, int kind, double* value, double* grad, void* stream);
 
 /*
+ * (5g), (7p) JOINT q-point Monte-Carlo acquisition (qEI, qUCB) with exact input gradients: B batches X_b = (x_1 .. x_q) of query points
+ * that are scored -- and moved by the optimiser -- together, Mq = B q points in all (botorch's optimize_acqf(q = ...) on a
+ * Monte-Carlo acquisition function over the joint posterior; scamlgp_amd.ScaMLGP.joint_acqf, utils.qExpectedImprovement /
+ * qUpperConfidenceBound, ScaMLGPBOLoop.suggest_batch).
+ * scaml_posterior_linv_grad_joint_f64 (5g): (5d) with q more rows in the covariance block of every strip.  VQ (T, N, Mq): the V of ALL
+ *   Mq query points from one value pass (5c) that keeps V;  cov (T, Ma + q, Mq * 16).  Rows a < Ma of strip j are (5d)'s (against the
+ *   leading points Xa / VA); row Ma + r is the covariance of x_j with its batch mate x_{b q + r}, b = j / q (V: column b q + r of VQ,
+ *   coordinates: Xq[b q + r]): column 16 j the covariance, columns 16 j + 1 + d its derivative with respect to x_j WITH THE MATE HELD
+ *   FIXED -- the row of the point itself (r = j mod q) therefore holds var and half of var's derivative.  mu, var as (5d) (may be NULL).
+ *   Ma >= 1, Mq a multiple of q; NULL Xa / VA / VQ / cov, q < 1: SCAML_E_BADARG.  q <= scaml_qacqf_max_q() = 8, Ma + q <= 96,
+ *   Ma + q <= N, D <= 15 and (5d)'s limits: SCAML_E_TOOLARGE beyond them.  Everything is checked before the first HIP call.
+ * scaml_target_qacqf_f64 (7p): per batch, from the value path's outputs as (7f) takes them (Knq, Z (n, Mq), alpha (n), mean_q, var_q
+ *   (Mq), m_all, s_all, info) and the weighted task sums (6') of (5g) as (7f) takes those of (5d) (cov_g (n + q, Mq * 16), mu_g, var_g
+ *   (Mq * 16)):
+ *     mu_j  = m + s (mean_q[j] + Knq[:, j] . alpha)
+ *     S_jk  = P_jk - Knq[:, j] . Z[:, k],  P_jj = var_q[j],  P_jk = cov_g[n + k][16 j] / s^2 + os_t k_t(x_j, x_k),  Sigma = s^2 S
+ *             (no observation noise)
+ *     C C^T = Sigma + jitter I;  the ladder 0, 1e-8, 1e-7, 1e-6 of psd_safe_cholesky: an attempt fails on a pivot <= 0 or not finite,
+ *             after the fourth failure info_out[b] = 1 and the batch's outputs are NaN.  The jitter is a constant for the gradient.
+ *     f_s   = mu + C eps_s with the caller's base samples eps = base_samples (S, q), shared by all batches
+ *     acqf SCAML_ACQF_EI  (acqf_param = best_f): a_s = max_j max(best_f - f_sj, 0)          (minimisation, as everywhere)
+ *     acqf SCAML_ACQF_UCB (acqf_param = beta):   a_s = max_j (-mu_j + sqrt(beta pi / 2) |(C eps_s)_j|)
+ *     value[b] = (1/S) sum_s a_s
+ *   Every other code -- 17 (LogEI) and 0x10 among them -- is SCAML_E_BADARG here: a joint LogEI is not defined.
+ *   grad (Mq, D) or NULL: d value[b] / d x_j for the q points of batch b.  Sub-gradients: the arg-max is the lowest j that attains the
+ *   maximum; max(., 0) and |.| have slope 0 at 0.  Adjoint: mubar and Cbar summed over the samples, Phi = tril(C^T Cbar) with its
+ *   diagonal halved, Sigmabar = sym(C^-T Phi C^-1), Sbar = s^2 Sigmabar, mbar = s mubar; then
+ *     grad_j = mbar_j dm_j/dx_j + Sbar_jj dvar_q[j]/dx_j + 2 sum_{k != j} Sbar_jk dP_jk/dx_j - (dKnq[:, j]/dx_j)^T (2 sum_k Sbar_jk Z[:, k])
+ *   and the sum over the training points is contracted once per query point against mbar_j alpha - 2 sum_k Sbar_jk Z[:, k], as (7f)
+ *   does with its abar.  jitter_used (B) or NULL: the rung that passed.  info_out (B) int32 or NULL.
+ *   One workgroup per batch; the q x q work is done in LDS, the samples are dealt to the threads, every sum over the samples is formed
+ *   by one thread in a fixed order: no atomics, the outputs are a pure function of the inputs (two calls agree bit for bit).
+ *   Non-finite values: a query point with a NaN / infinite coordinate, or a NaN anywhere in its batch's inputs, gives NaN in that
+ *   batch's value and in all q rows of its grad; other batches are not affected.  info[0] != 0 (the target's factorisation failed):
+ *   every output is NaN (info_out 1).
+ *   Limits: 1 <= q <= scaml_qacqf_max_q() = 8, 1 <= S <= scaml_qacqf_max_samples() = 512, n + q <= 96, D <= 15: SCAML_E_TOOLARGE
+ *   beyond them; n < 1, Mq not a multiple of q, a NULL input or value, s_all <= 0, an unknown kind: SCAML_E_BADARG (first).  Mq == 0
+ *   enqueues nothing.  No host synchronisation.
+ */
+int scaml_qacqf_max_q(void);
+int scaml_qacqf_max_samples(void);
+int scaml_posterior_linv_grad_joint_f64(const double* Xq, const double* Xa, const double* X, const double* theta, const double* Linv,
+                                        const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points,
+                                        const double* VA, const double* VQ, int T, int N, int Mq, int Ma, int q, int D, int kind, double* mu,
+                                        double* var, double* cov, unsigned flags, void* stream);
+int scaml_target_qacqf_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q, double m_all,
+                           double s_all, const int32_t* info, const double* cov_g, const double* mu_g, const double* var_g, const double* Xt,
+                           const double* Xq, const double* theta, const double* base_samples, int acqf, double acqf_param, int n, int Mq, int q,
+                           int S, int D, int kind, double* value, double* grad, double* jitter_used, int32_t* info_out, void* stream);
+
+/*
  * (7o) The acquisition function of M given posteriors, elementwise: A[i] and its partial derivatives Amu[i] = dA / dmu, Av[i] = dA / dv
  * at (mu[i], var[i]) (original units), i = 0 .. M-1, one thread per element -- the statement (7f), (7g), (7i) and (7k) evaluate
  * (sa_acquisition of csrc/gp_studies_formulas.h), with their clamps.  acqf: SCAML_ACQF_UCB (acqf_param = beta), SCAML_ACQF_EI or

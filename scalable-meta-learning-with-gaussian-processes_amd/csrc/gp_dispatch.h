@@ -10,6 +10,7 @@
 #include "gp_posterior_params.h"
 #include "gp_target_params.h"
 #include "gp_studies_condition.h"
+#include "gp_qacqf.h"
 
 namespace scaml {
 
@@ -198,5 +199,12 @@ constexpr StudiesConditionPlan studies_condition_block_plan(int G, int n_max, in
 constexpr StudiesConditionPlan studies_fantasy_condition_plan(int G, int n_max, int F_max) {
   return {(unsigned)G, (unsigned)STUDIES_CONDITION_THREADS, sc_fantasy_lds_doubles(n_max, F_max)};
 }
+
+// ---- joint q-point acquisition (7p): a workgroup per batch -----------------------------------------------------------------------
+struct QAcqfPlan {
+  unsigned grid, block;
+  size_t lds_doubles;   // more than LDS_LIMIT: the shape is too large
+};
+constexpr QAcqfPlan qacqf_plan(int B, int n, int q, int S) { return {(unsigned)B, (unsigned)QACQF_THREADS, qa_lds_doubles(n, q, S)}; }
 
 }  // namespace scaml

@@ -146,17 +146,26 @@ __global__ __launch_bounds__(256) void gp_posterior_kernel(PosteriorParams p) {
 // for the Ma leading points x_a (p.Xa: the target's training inputs) -- everything botorch's optimize_acqf differentiates through
 // model.posterior for (HOT LOOP #4; scamlgp/utils.py:215-224).  Outputs are (T, Mq, 16) / (T, Ma, Mq * 16): M = 16 Mq.
 // The argument block of gp_posterior_linv_kernel: PosteriorParams, or PosteriorGroupedParams (the same block first, then the groups)
-template <bool GROUPED>
+template <bool GROUPED, bool JOINT = false>
 struct PosteriorArgs {
   using type = PosteriorParams;
   static __device__ __forceinline__ const PosteriorParams& base(const type& a) { return a; }
   static __device__ __forceinline__ PosteriorGroupArgs ga(const type&) { return PosteriorGroupArgs{}; }
+  static __device__ __forceinline__ PosteriorJointArgs ja(const type&) { return PosteriorJointArgs{}; }
 };
 template <>
-struct PosteriorArgs<true> {
+struct PosteriorArgs<true, false> {
   using type = PosteriorGroupedParams;
   static __device__ __forceinline__ const PosteriorParams& base(const type& a) { return a.base; }
   static __device__ __forceinline__ const PosteriorGroupArgs& ga(const type& a) { return a.ga; }
+  static __device__ __forceinline__ PosteriorJointArgs ja(const type&) { return PosteriorJointArgs{}; }
+};
+template <>
+struct PosteriorArgs<false, true> {
+  using type = PosteriorJointParams;
+  static __device__ __forceinline__ const PosteriorParams& base(const type& a) { return a.base; }
+  static __device__ __forceinline__ PosteriorGroupArgs ga(const type&) { return PosteriorGroupArgs{}; }
+  static __device__ __forceinline__ const PosteriorJointArgs& ja(const type& a) { return a.ja; }
 };
 
 // GROUPED (the lock-step acquisition of many BO studies, scaml_posterior_linv_grad_grouped_f64): the query points are divided among G
@@ -173,12 +182,20 @@ struct PosteriorArgs<true> {
 // and added in wave order by one thread per column instead of with LDS float atomics, whose order of arrival differs from run to run:
 // mu and var are then a pure function of the inputs, like cov, and an optimisation does not depend on how its rounds are chunked.  An
 // instantiation of its own: the other passes keep their instruction streams.
-template <int KIND, bool COV, bool GRAD, bool GROUPED = false, bool OWN = false, bool DET = false>
-__global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename PosteriorArgs<GROUPED>::type pp) {
+// JOINT (scaml_posterior_linv_grad_joint_f64, (5g)): the Mq query points come in batches of q that move TOGETHER (a joint q-point
+// acquisition function).  The covariance block of strip j (query point j, batch b = j / q) has q more rows: row Ma + r is the covariance
+// of x_j with its batch mate x_{b q + r}, whose V is column b q + r of VQ (T, N, Mq) -- the value pass's V at the same query points -- and
+// whose coordinates are Xq[b q + r].  Column 0 is the covariance, columns 1 + d its derivative with respect to x_j with the mate held
+// fixed; the row of the point itself (r = j mod q) therefore carries var and HALF of var's derivative.  Two sites differ: the operand
+// fetch of the covariance tiles and the coordinates of the epilogue.  An instantiation of its own, like OWN and DET.
+template <int KIND, bool COV, bool GRAD, bool GROUPED = false, bool OWN = false, bool DET = false, bool JOINT = false>
+__global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename PosteriorArgs<GROUPED, JOINT>::type pp) {
+  using Args = PosteriorArgs<GROUPED, JOINT>;
+  static_assert(!JOINT || (COV && GRAD && !GROUPED), "batch mates belong to the ungrouped GRAD pass with its covariance block");
   static_assert(!GROUPED || COV, "the grouped pass comes with its covariance block");
   static_assert(!DET || (GROUPED && GRAD), "the ordered sums are built for the grouped GRAD pass");
   static_assert(!OWN || GROUPED, "per-group source tasks belong to the grouped pass");
-  const PosteriorParams& p = PosteriorArgs<GROUPED>::base(pp);
+  const PosteriorParams& p = Args::base(pp);
   // eight waves share one K_*^T strip (the row blocks are dealt 8 ways: twice the waves per byte of LDS to hide the L^-1 segment loads)
   constexpr int NW = 8;
   extern __shared__ double lds[];
@@ -192,8 +209,8 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
   int grp = 0;
   int src = task;   // the source task read; `task` stays the slot of the outputs and of a group's VA
   if (GROUPED) {
-    grp = PosteriorArgs<GROUPED>::ga(pp).group[strip];
-    if (grp < 0 || grp >= PosteriorArgs<GROUPED>::ga(pp).G) {   // a padding row: zeros, nothing of any group is read
+    grp = Args::ga(pp).group[strip];
+    if (grp < 0 || grp >= Args::ga(pp).G) {   // a padding row: zeros, nothing of any group is read
       if (threadIdx.x < 16) {
         if (p.mu) p.mu[(size_t)task * M + 16 * strip + threadIdx.x] = 0.0;
         if (p.var) p.var[(size_t)task * M + 16 * strip + threadIdx.x] = 0.0;
@@ -203,8 +220,8 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
     if (OWN) {
       // slot `task` of this group is source task task_base[grp] + task (uniform per workgroup: a scalar load, as the group's count and
       // V pointer are); a source task outside the arrays is a padding row like the one above
-      src = (int)((unsigned)PosteriorArgs<GROUPED>::ga(pp).task_base[grp] + (unsigned)task);
-      if ((unsigned)src >= (unsigned)PosteriorArgs<GROUPED>::ga(pp).Tsrc) {
+      src = (int)((unsigned)Args::ga(pp).task_base[grp] + (unsigned)task);
+      if ((unsigned)src >= (unsigned)Args::ga(pp).Tsrc) {
         if (threadIdx.x < 16) {
           if (p.mu) p.mu[(size_t)task * M + 16 * strip + threadIdx.x] = 0.0;
           if (p.var) p.var[(size_t)task * M + 16 * strip + threadIdx.x] = 0.0;
@@ -348,9 +365,11 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
   constexpr int MAXAS = COV ? 6 : 1;   // at most 96 leading query points (the target's training points)
   // the leading points of the covariance block: their count and V (GROUPED: this strip's group's; p.Ma is then Ma_max, the row count
   // of cov, which the host checked against the LDS strip)
-  const int Ma = GROUPED ? PosteriorArgs<GROUPED>::ga(pp).count(grp, p.Ma) : p.Ma;
-  const double* VAp = GROUPED ? PosteriorArgs<GROUPED>::ga(pp).VA_tab[grp] : p.VA;
-  const int nas = (COV && VAp) ? (Ma + 15) / 16 : 0;
+  const int Ma = GROUPED ? Args::ga(pp).count(grp, p.Ma) : p.Ma;
+  const double* VAp = GROUPED ? Args::ga(pp).VA_tab[grp] : p.VA;
+  // JOINT: the rows of the covariance block are the Ma leading points and then the q points of this strip's batch
+  const int jq = JOINT ? Args::ja(pp).q : 0, Mt = Ma + jq, mate0 = JOINT ? (strip / jq) * jq : 0;
+  const int nas = (COV && VAp) ? (Mt + 15) / 16 : 0;
   d4_t cacc[MAXAS];
 #pragma unroll
   for (int as = 0; as < MAXAS; ++as) cacc[as] = d4_t{0.0, 0.0, 0.0, 0.0};
@@ -358,6 +377,8 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
     double var_part = 0.0;
     const bool n_even = (N & 1) == 0;
     const double* VAg = VAp ? VAp + (size_t)task * N * Ma : nullptr;
+    const int Mqj = M / 16;   // (JOINT: the row stride of VQ)
+    const double* VQg = JOINT ? Args::ja(pp).VQ + (size_t)task * N * Mqj + mate0 : nullptr;
     for (int it = 0;; ++it) {
       const int kb = (it & 1) ? (it + 1) * NW - 1 - wave : it * NW + wave;
       if (kb >= NB) {
@@ -393,7 +414,12 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
               const int row = 16 * kb + lq + 4 * m;
-              va[m] = (row < n && ac < Ma) ? VAg[(size_t)row * Ma + ac] : 0.0;
+              if (JOINT) {   // a leading point's column of VA, or a batch mate's column of VQ: one load either way
+                const double* src = ac < Ma ? VAg + (size_t)row * Ma + ac : VQg + (size_t)row * Mqj + (ac - Ma);
+                va[m] = (row < n && ac < Mt) ? *src : 0.0;
+              } else {
+                va[m] = (row < n && ac < Ma) ? VAg[(size_t)row * Ma + ac] : 0.0;
+              }
             }
 #pragma unroll
             for (int m = 0; m < 4; ++m) cacc[as] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[m], vb[m], cacc[as], 0, 0, 0);
@@ -451,15 +477,19 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
       __syncthreads();
     }
     // the Ma leading points: the head of the query list (the caller put the target's training points first), or p.Xa
-    const double* Xap = GROUPED ? PosteriorArgs<GROUPED>::ga(pp).Xa + (size_t)grp * p.Ma * D : p.Xa;
+    const double* Xap = GROUPED ? Args::ga(pp).Xa + (size_t)grp * p.Ma * D : p.Xa;
     const double* Xqg = Xap ? Xap : p.Xq + (p.xq_per_task ? (size_t)task * M * D : 0);
     for (int e = tid; e < nas * 256; e += blockDim.x) {
       const int as = e >> 8, g = (e >> 6) & 3, ln = e & 63;
       const int a = 16 * as + (ln >> 4) + 4 * g, c = ln & 15, qcc = 16 * strip + c;
-      if (a < Ma && qcc < M) {
+      if (a < Mt && qcc < M) {
+        // (JOINT, a row past the leading points: batch mate a - Ma of this strip's point)
+        const bool mate = JOINT && a >= Ma;
+        const double* xab = mate ? p.Xq + (p.xq_per_task ? (size_t)task * (M / 16) * D : 0) : Xqg;
+        const size_t xa0 = mate ? (size_t)(mate0 + a - Ma) * D : (size_t)a * D;
         double d2 = 0.0;
         for (int d = 0; d < D; ++d) {
-          const double df = Xqg[(size_t)a * D + d] * invl[d] - xqs[d * 16 + c];
+          const double df = (JOINT ? xab[xa0 + d] : Xqg[(size_t)a * D + d]) * invl[d] - xqs[d * 16 + c];
           d2 = __builtin_fma(df, df, d2);
         }
         double kv;
@@ -468,12 +498,12 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
           if (c - 1 < D) {
             double k0, dk;
             kernel_and_slope_scaled<KIND>(d2, os, exptab, k0, dk);
-            kv = 2.0 * dk * (xqs[(c - 1) * 16 + c] - Xqg[(size_t)a * D + c - 1] * invl[c - 1]) * invl[c - 1];
+            kv = 2.0 * dk * (xqs[(c - 1) * 16 + c] - (JOINT ? xab[xa0 + c - 1] : Xqg[(size_t)a * D + c - 1]) * invl[c - 1]) * invl[c - 1];
           }
         } else {
           kv = os * kernel_from_sqdist<KIND>(d2, exptab);
         }
-        p.cov[((size_t)task * p.Ma + a) * M + qcc] = ys * ys * (kv - cb[e]) + (nq[c] - nq[c]);   // (NaN for a non-finite query, as above)
+        p.cov[((size_t)task * (JOINT ? Mt : p.Ma) + a) * M + qcc] = ys * ys * (kv - cb[e]) + (nq[c] - nq[c]);   // (NaN for a non-finite query, as above)
       }
     }
   }
@@ -752,3 +782,5 @@ template __global__ void scaml::gp_posterior_linv_kernel<0, true, false, true>(s
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, false, true>(scaml::PosteriorGroupedParams);
 template __global__ void scaml::gp_posterior_linv_kernel<0, true, false, true, true>(scaml::PosteriorGroupedParams);   // (5f')
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, false, true, true>(scaml::PosteriorGroupedParams);
+template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, false, false, false, true>(scaml::PosteriorJointParams);   // (5g)
+template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, false, false, false, true>(scaml::PosteriorJointParams);

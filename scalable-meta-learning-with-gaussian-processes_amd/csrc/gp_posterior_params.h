@@ -61,6 +61,18 @@ struct PosteriorGroupedParams {
   PosteriorGroupArgs ga;
 };
 
+// The joint GRAD pass (scaml_posterior_linv_grad_joint_f64): the query points move in batches of q; the covariance block of a strip
+// gets q more rows, against the strip's batch mates.  In `base`: Ma = the leading points alone, cov has Ma + q rows.
+struct PosteriorJointArgs {
+  const double* VQ;   // (T, N, Mq) the V of all query points, from the value pass
+  int q;              // points per batch; Mq is a multiple of it
+  int pad_;
+};
+struct PosteriorJointParams {
+  PosteriorParams base;
+  PosteriorJointArgs ja;
+};
+
 struct PosteriorCovParams {
   const double* Xq;     // (M, D)
   const double* theta;  // (T, D+2)

@@ -70,6 +70,7 @@ struct Module {
   hipFunction_t tgt_assemble[2] = {}, tgt_finish = nullptr, tgt_fit = nullptr, tgt_fit_batched = nullptr, tgt_grad[2] = {};
   hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {};   // value only; value + gradient per kind
   hipFunction_t acqf_transform = nullptr;                          // the elementwise acquisition of given posteriors (7o)
+  hipFunction_t post_linv_grad_joint[2] = {}, tgt_qacqf = nullptr;   // joint q-point acquisition: the GRAD pass with batch mates (5g), qEI / qUCB (7p)
   hipFunction_t post_linv_grouped[2] = {}, tgt_acqf_batched = nullptr;   // lock-step studies: grouped GRAD pass, batched acquisition
   hipFunction_t post_linv_grouped_own[2] = {};                           // the grouped pass with per-group source tasks
   hipFunction_t post_linv_grouped_det[2] = {}, post_linv_grouped_det_own[2] = {};   // the GRAD grouped pass with ordered sums: (7l)'s rounds
@@ -95,15 +96,17 @@ struct Module {
     std::vector<KernelRow> rows = {
         {post, "_ZN5scaml19gp_posterior_kernelILi%dEEEvNS_15PosteriorParamsE", kLdsLimit, {K}},
         {post_cov, "_ZN5scaml23gp_posterior_cov_kernelILi%dEEEvNS_18PosteriorCovParamsE", 0, {K}},
-        {post_linv, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb0ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_cov, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped_det, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit - kOrderedSumsLds, {K}},   // (static LDS: the waves' shares)
-        {post_linv_grouped_det_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1ELb1EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit - kOrderedSumsLds, {K}},   // (static LDS: the waves' shares)
-        {post_linv_grouped_val, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped_val_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EE4typeE", kLdsLimit, {K}},
+        {post_linv, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
+        {post_linv_cov, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_det, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit - kOrderedSumsLds, {K}},   // (static LDS: the waves' shares)
+        {post_linv_grouped_det_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit - kOrderedSumsLds, {K}},   // (static LDS: the waves' shares)
+        {post_linv_grouped_val, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_val_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grad_joint, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0ELb0ELb1EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
+        {&tgt_qacqf, "scaml_target_qacqf_kernel", kLdsLimit, {}},
         {&tgt_acqf_batched, "scaml_target_acqf_batched_kernel", kLdsLimit, {}},
         {&tgt_score_batched, "scaml_target_score_batched_kernel", kLdsLimit, {}},
         {&tgt_fantasy_acqf_batched, "scaml_target_fantasy_acqf_batched_kernel", kLdsLimit, {}},
@@ -592,6 +595,34 @@ int scaml_posterior_linv_grad_f64(const double* Xq, const double* Xa, const doub
                                mu, var, nullptr, Ma > 0 ? cov : nullptr, flags, stream, true, Xa);
 }
 
+// (5g) (5d) for query points that move in batches of q: q more covariance rows per strip, against the strip's batch mates
+int scaml_qacqf_max_q(void) { return scaml::QACQF_MAX_Q; }
+int scaml_qacqf_max_samples(void) { return scaml::QACQF_MAX_SAMPLES; }
+
+int scaml_posterior_linv_grad_joint_f64(const double* Xq, const double* Xa, const double* X, const double* theta, const double* Linv,
+                                        const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points,
+                                        const double* VA, const double* VQ, int T, int N, int Mq, int Ma, int q, int D, int kind, double* mu,
+                                        double* var, double* cov, unsigned flags, void* stream) {
+  if (T < 0 || N < 1 || Mq < 0 || Ma < 1 || q < 1 || D < 1 || Mq % q != 0) return SCAML_E_BADARG;
+  if (!Xq || !Xa || !X || !theta || !Linv || !alpha || !VA || !VQ || !cov) return SCAML_E_BADARG;
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (flags & SCAML_POST_MEAN_ONLY) return SCAML_E_BADARG;
+  if (D > 15 || q > scaml::QACQF_MAX_Q || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
+  if (N > scaml_posterior_max_n()) return SCAML_E_TOOLARGE;
+  if (Ma + q > scaml::QACQF_MAX_ROWS || Ma + q > N) return SCAML_E_TOOLARGE;   // six 16-row strips of the covariance block, staged in the N x 16 LDS strip
+  const size_t lds = scaml::posterior_linv_lds_doubles(N, D) * sizeof(double);
+  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (T == 0 || Mq == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  const int M = 16 * Mq;
+  scaml::PosteriorJointParams p{{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N, M, D, 0,
+                                 (flags & SCAML_POST_XQ_PER_TASK) ? 1 : 0, 0, VA, cov, Ma, 0, Xa},
+                                {VQ, q, 0}};
+  const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * (unsigned)Mq;   // XCD-aware (task, strip) map inside the kernel, a strip per query point
+  return launch(m->post_linv_grad_joint[kind], dim3(blocks), 512, lds, stream, "gp_posterior_linv_joint", p);
+}
+
 // ---- (4) gradient of the marginal log-likelihood ------------------------------------------------
 long long scaml_mll_backward_workspace_doubles(int T, int N, int D) {
   const long long nb = (N + 15) / 16;
@@ -696,6 +727,27 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
                              value, grad, n, M, F, grad ? D : 0, acqf, 0};
   // one wave per query point
   return launch(grad ? m->tgt_fantasy_grad[kind] : m->tgt_fantasy, dim3((unsigned)M), 64, 0, stream, "target_fantasy_acqf", p);
+}
+
+// ---- (7p) joint q-point Monte-Carlo acquisition, qEI / qUCB, and its input gradient: a workgroup per batch (csrc/gp_qacqf.hip) ----
+int scaml_target_qacqf_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q, double m_all,
+                           double s_all, const int32_t* info, const double* cov_g, const double* mu_g, const double* var_g, const double* Xt,
+                           const double* Xq, const double* theta, const double* base_samples, int acqf, double acqf_param, int n, int Mq, int q,
+                           int S, int D, int kind, double* value, double* grad, double* jitter_used, int32_t* info_out, void* stream) {
+  if (n < 1 || Mq < 0 || q < 1 || S < 1 || D < 1 || Mq % q != 0) return SCAML_E_BADARG;
+  if (!Knq || !Z || !alpha || !mean_q || !var_q || !cov_g || !mu_g || !var_g || !Xt || !Xq || !theta || !base_samples || !value) return SCAML_E_BADARG;
+  if (!scaml::qa_acqf_valid(acqf)) return SCAML_E_BADARG;   // (a joint LogEI is not defined: 17 and 0x10 are refused like 2)
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (!(s_all > 0.0)) return SCAML_E_BADARG;
+  if (q > scaml::QACQF_MAX_Q || S > scaml::QACQF_MAX_SAMPLES || n + q > scaml::QACQF_MAX_ROWS || D > scaml::QACQF_MAX_D) return SCAML_E_TOOLARGE;
+  const scaml::QAcqfPlan plan = scaml::qacqf_plan(Mq / q, n, q, S);
+  if (plan.lds_doubles * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (Mq == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  scaml::QAcqfParams p{Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples, acqf_param,
+                       value, grad, jitter_used, info_out, n, Mq, q, S, D, kind, acqf, 0};
+  return launch(m->tgt_qacqf, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "target_qacqf", p);
 }
 
 // ---- (7o) the acquisition value and chain-rule factors of M given posteriors, elementwise (csrc/gp_acqf_transform.hip) ----------

@@ -96,6 +96,13 @@ SIGNATURES = {
     "scaml_posterior_linv_grad_f64": (_i, [_dp] * 10 + [_i] * 6 + [_dp, _dp, _dp, _u, c_void_p]),
     "scaml_target_posterior_grad_f64": (_i, [_dp] * 8 + [_f, _dp, _i, _i, _i, _i, _dp, _dp, c_void_p]),
     "scaml_target_fantasy_acqf_f64": (_i, [_dp] * 5 + [_f, _f, _f, _dp, _i, _f] + [_dp] * 6 + [_i] * 5 + [_dp, _dp, c_void_p]),
+    "scaml_qacqf_max_q": (_i, []),
+    "scaml_qacqf_max_samples": (_i, []),
+    # (5g) (5d)'s arrays with VQ after VA; T, N, Mq, Ma, q, D, kind; mu, var, cov, flags
+    "scaml_posterior_linv_grad_joint_f64": (_i, [_dp] * 11 + [_i] * 7 + [_dp, _dp, _dp, _u, c_void_p]),
+    # (7p) Knq, Z, alpha, mean_q, var_q; m_all, s_all; info; cov_g, mu_g, var_g, Xt, Xq, theta, base_samples; acqf, acqf_param;
+    # n, Mq, q, S, D, kind; value, grad, jitter_used, info_out
+    "scaml_target_qacqf_f64": (_i, [_dp] * 5 + [_f, _f, _dp] + [_dp] * 7 + [_i, _f] + [_i] * 6 + [_dp] * 4 + [c_void_p]),
     # (7o) mu, var; acqf_param, M, acqf; A, Amu, Av
     "scaml_acqf_transform_f64": (_i, [_dp, _dp, _f, _i, _i, _dp, _dp, _dp, c_void_p]),
     # (5e) Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points; T, N, Mq, G, Ma_max, D, kind; mu, var, cov

@@ -32,6 +32,7 @@ from . import hyper
 from . import studies as _studies
 from .model import ScaMLGP, SourceGP, fantasize_studies
 from .utils import ExpectedImprovement, LogExpectedImprovement, StudiesAcquisition, UpperConfidenceBound, capture_graph, fit_targets_batched, optimize_marginal_likelihood
+from .utils import qExpectedImprovement, qUpperConfidenceBound
 
 
 class OptimizerNotReady(RuntimeError):
@@ -99,7 +100,10 @@ def acqf_pick_initial_conditions(vals: torch.Tensor, num_restarts: int, generato
 def acqf_local_optimization(af: Callable[[torch.Tensor], torch.Tensor], x0: torch.Tensor, max_iter: int = 50, fd_step: float = 1e-4,
                             graph_device: Optional[torch.device] = None, analytic_grad: bool = True) -> torch.Tensor:
     """Stage 2 of ``optimize_acqf``: ONE box-constrained scipy L-BFGS-B run over the R starts jointly (the summed acquisition value);
-    returns the end points (R, dim) inside [0, 1]^dim."""
+    returns the end points (R, dim) inside [0, 1]^dim.  x0 (R, q, dim): R q-batches of a joint acquisition function, one run over the
+    R q dim variables on its ``value_and_grad``; the end points are (R, q, dim)."""
+    if x0.dim() == 3:
+        return _joint_local_optimization(af, x0, max_iter)
     R, dim = x0.shape
     eye = torch.eye(dim, dtype=torch.float64)
     analytic = analytic_grad and hasattr(af, "value_and_grad") and getattr(getattr(af, "model", None), "supports_posterior_grad", lambda: False)()
@@ -134,6 +138,33 @@ def acqf_local_optimization(af: Callable[[torch.Tensor], torch.Tensor], x0: torc
     return torch.from_numpy(np.clip(res.x, 0.0, 1.0)).reshape(R, dim)
 
 
+def _joint_local_optimization(af, x0: torch.Tensor, max_iter: int) -> torch.Tensor:
+    """``acqf_local_optimization`` for R q-batches x0 (R, q, dim): exact gradients of the joint Monte-Carlo value (fixed base samples)."""
+    R, q, dim = x0.shape
+
+    def fun(zv: np.ndarray):
+        v, g = af.value_and_grad(torch.from_numpy(zv).reshape(R, q, dim))
+        out = torch.cat([v.reshape(-1), g.reshape(-1)]).detach().cpu()   # one device -> host copy per evaluation
+        f = float(out[:R].sum())
+        if not math.isfinite(f):
+            return float("inf"), np.zeros_like(zv)
+        return -f, -torch.nan_to_num(out[R:]).numpy()
+
+    res = scipy.optimize.minimize(fun, x0.reshape(-1).numpy(), jac=True, method="L-BFGS-B", bounds=[(0.0, 1.0)] * (R * q * dim),
+                                  options=dict(maxiter=max_iter))
+    return torch.from_numpy(np.clip(res.x, 0.0, 1.0)).reshape(R, q, dim)
+
+
+def _optimize_acqf_joint(af, dim: int, q: int, raw_samples: int, num_restarts: int, max_iter: int, generator: Optional[torch.Generator], eta: float):
+    """``optimize_acqf`` for q > 1: ``raw_samples`` random q-batches, the Boltzmann pick over batches, one L-BFGS-B run over the
+    R q dim variables, the best end batch.  Returns (X (q, dim), value)."""
+    cand = torch.rand(raw_samples, q, dim, dtype=torch.float64, generator=generator)
+    vals = af(cand).detach().cpu()
+    best0, picks = acqf_pick_initial_conditions(vals, num_restarts, generator, eta)
+    xs = acqf_local_optimization(af, cand[picks], max_iter)
+    return acqf_final_choice(cand, vals, best0, xs, af(xs))
+
+
 def acqf_final_choice(cand: torch.Tensor, vals: torch.Tensor, best0: int, xs: torch.Tensor, fin: torch.Tensor):
     """Stage 3 of ``optimize_acqf``: the best end point (``fin`` = the acquisition values at ``xs``, re-scored), unless the best raw
     candidate is better.  Returns (x (dim,), value)."""
@@ -146,8 +177,12 @@ def acqf_final_choice(cand: torch.Tensor, vals: torch.Tensor, best0: int, xs: to
 
 def optimize_acqf(af: Callable[[torch.Tensor], torch.Tensor], dim: int, raw_samples: int = 1024, num_restarts: int = 10,
                   max_iter: int = 50, generator: Optional[torch.Generator] = None, fd_step: float = 1e-4,
-                  eta: float = 2.0, graph_device: Optional[torch.device] = None, analytic_grad: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Maximise ``af`` over [0, 1]^dim; returns (x_best (dim,), af(x_best)).  botorch's ``optimize_acqf`` recipe:
+                  eta: float = 2.0, graph_device: Optional[torch.device] = None, analytic_grad: bool = True, q: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Maximise ``af`` over [0, 1]^dim; returns (x_best (dim,), af(x_best)).  ``q`` > 1: ``af`` is a joint acquisition function
+    (``utils.qExpectedImprovement`` / ``qUpperConfidenceBound``) over batches of q points, ``raw_samples`` counts q-batches, the Boltzmann
+    pick is over batches, the L-BFGS-B run is over R q dim variables and the result is (X_best (q, dim), af(X_best)).  The joint route
+    always runs on the exact gradients of ``af.value_and_grad``, evaluated eagerly: ``fd_step``, ``graph_device`` and ``analytic_grad``
+    belong to the single-point route and are not read with q > 1.  botorch's ``optimize_acqf`` recipe:
     ``raw_samples`` random candidates -> ``num_restarts`` initial conditions (the best candidate plus a Boltzmann sample
     of the rest, ``initialize_q_batch``) -> ONE box-constrained L-BFGS-B run over all starts jointly (the summed
     acquisition value, which is separable over the starts: botorch's ``gen_candidates_scipy`` does the same) -> the
@@ -158,6 +193,10 @@ def optimize_acqf(af: Callable[[torch.Tensor], torch.Tensor], dim: int, raw_samp
     once and replayed per L-BFGS-B step (``GraphedAcquisition``).  The three stages are functions of their own
     (``acqf_initial_conditions``, ``acqf_local_optimization``, ``acqf_final_choice``): ``ScaMLGPBOStudies`` runs the middle one for
     all its studies at once."""
+    if q != 1:
+        if int(q) < 1:
+            raise ValueError("q must be a positive integer")
+        return _optimize_acqf_joint(af, dim, int(q), raw_samples, num_restarts, max_iter, generator, eta)
     cand, vals, best0, x0 = acqf_initial_conditions(af, dim, raw_samples, num_restarts, generator, eta)
     xs = acqf_local_optimization(af, x0, max_iter, fd_step, graph_device, analytic_grad)
     return acqf_final_choice(cand, vals, best0, xs, af(xs))
@@ -168,14 +207,16 @@ class ScaMLGPBOLoop:
                  num_restarts_log_likelihood: int = 5, raw_samples: int = 1024, num_restarts: int = 10, af_max_iter: int = 50,
                  gp_likelihood: Optional[hyper.GaussianLikelihood] = None, gp_kernel: Optional[hyper.ScaleKernel] = None,
                  seed: Optional[int] = None, use_graph: bool = True, max_pending_evaluations: Optional[int] = None,
-                 num_fantasies: int = 16):
-        """``max_pending_evaluations``: None (default) -- strictly suggest -> report, no bookkeeping; an integer k -- ``suggest()``
+                 num_fantasies: int = 16, num_mc_samples: int = 128):
+        """``num_mc_samples``: base samples of the joint acquisition function of ``suggest_batch``.
+        ``max_pending_evaluations``: None (default) -- strictly suggest -> report, no bookkeeping; an integer k -- ``suggest()``
         records its point in ``pending`` until it is reported, raises OptimizerNotReady while k points are pending, and builds the
         acquisition function on ``num_fantasies`` fantasies of the pending outcomes (ScaMLGP.fantasize, base samples from ``gen``)."""
         if max_pending_evaluations is not None and int(max_pending_evaluations) < 1:
             raise ValueError("max_pending_evaluations must be None or a positive integer")
         self.max_pending_evaluations = None if max_pending_evaluations is None else int(max_pending_evaluations)
         self.num_fantasies = int(num_fantasies)
+        self.num_mc_samples = int(num_mc_samples)
         self.pending = torch.empty(0, dim, dtype=torch.float64)
         self.source_gps, self.dim = source_gps, dim
         self.acquisition, self.beta = acquisition, beta
@@ -255,6 +296,42 @@ class ScaMLGPBOLoop:
         if k is not None:
             self.pending = torch.cat([self.pending, x.reshape(1, -1)], 0)
         return x
+
+    def joint_acquisition_function(self, q: int):
+        """The joint Monte-Carlo acquisition function of ``suggest_batch``: qUCB for ``acquisition="ucb"``, qEI for ``"ei"`` (best_f: the
+        incumbent over the observed values); its base samples come from ``gen``."""
+        if self.acquisition == "logei":
+            raise ValueError("a joint LogEI is not defined: suggest_batch takes acquisition='ucb' or 'ei'")
+        if self.acquisition == "ei":
+            Yf = self.Y[torch.isfinite(self.Y)]
+            if Yf.numel() == 0:
+                raise ValueError("EI needs at least one evaluation")
+            return qExpectedImprovement(self.model, float(Yf.min()), self.num_mc_samples, self.gen, q=q)
+        return qUpperConfidenceBound(self.model, self.beta, self.num_mc_samples, self.gen, q=q)
+
+    def suggest_batch(self, q: int) -> torch.Tensor:
+        """q points for q parallel workers, optimised AGAINST EACH OTHER: the maximiser (q, D) of the joint Monte-Carlo acquisition
+        function over batches of q points (botorch's optimize_acqf(q = ...)), where q calls of ``suggest()`` condition every point on
+        fantasies of the ones before it.  With ``max_pending_evaluations=k``: q <= k, and all q points become pending; with points
+        already pending it raises (a joint acquisition function on a fantasy model is not defined here).  ``report(x (q, D), y (q,))``
+        takes the results."""
+        q, k = int(q), self.max_pending_evaluations
+        if q < 1:
+            raise ValueError("suggest_batch takes q >= 1")
+        if self.acquisition not in ("ucb", "ei"):
+            raise ValueError("a joint LogEI is not defined: suggest_batch takes acquisition='ucb' or 'ei'")
+        if self.pending.shape[0] > 0:
+            raise NotImplementedError("suggest_batch with evaluations pending: the joint acquisition function is not defined on a fantasy model")
+        if k is not None and q > k:
+            raise ValueError(f"suggest_batch({q}) exceeds max_pending_evaluations={k}")
+        self.model.eval()
+        af = self.joint_acquisition_function(q)
+        # (the joint route for every q, q = 1 included: optimize_acqf(q=1) is the single-point path of the analytic functions)
+        X, _ = _optimize_acqf_joint(af, self.dim, q, self.raw_samples, self.num_restarts, self.af_max_iter, self.gen, 2.0)
+        X = X.reshape(q, self.dim)
+        if k is not None:
+            self.pending = torch.cat([self.pending, X], 0)
+        return X
 
     def run(self, objective: Callable[[torch.Tensor], float], n_steps: int):
         for _ in range(n_steps):

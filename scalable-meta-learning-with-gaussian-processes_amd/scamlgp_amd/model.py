@@ -996,6 +996,84 @@ class ScaMLGP:
         xall = torch.cat([self.train_X, Xq], 0)
         return cov_s, mean_s, var_s, xall, cov_g, mu_g, var_g
 
+    def joint_acqf(self, X: torch.Tensor, acqf: int, acqf_param: float, base_samples: torch.Tensor, want_grad: bool = False):
+        """The joint Monte-Carlo acquisition function of B batches of q points, X (B, q, D): qEI (``acqf`` ops.ACQF_EI, acqf_param =
+        best_f) or qUCB (ops.ACQF_UCB, beta) over the JOINT posterior of each batch, reparameterised with ``base_samples`` (S, q)
+        -- (value (B,), d value / d X (B, q, D) or None).  The value pass at the B q points keeps their V; the joint GRAD pass
+        (scaml_posterior_linv_grad_joint_f64) adds, per point, the covariances with its batch mates and their input derivatives; the
+        weighted task sums, the assemble and Z = Knn^-1 Knq are those of ``posterior_with_grad`` (the training block's factor is cached);
+        then ONE launch of scaml_target_qacqf_f64 factors every batch's q x q posterior covariance, draws the samples, evaluates the
+        utility and carries the adjoint back through the factor to the inputs: no (B, S, q) tensor reaches memory."""
+        out = self.joint_acqf_full(X, acqf, acqf_param, base_samples, want_grad)
+        return out["value"], out["grad"]
+
+    def joint_acqf_full(self, X: torch.Tensor, acqf: int, acqf_param: float, base_samples: torch.Tensor, want_grad: bool = False) -> dict:
+        """``joint_acqf`` with the kernel's per-batch status: dict(value (B,), grad (B, q, D) or None, jitter (B,) -- the rung of the
+        ladder 0, 1e-8, 1e-7, 1e-6 that made the batch's covariance positive definite --, info (B,) int32 -- 1: none did, the batch is
+        NaN)."""
+        if acqf not in (ops.ACQF_UCB, ops.ACQF_EI):   # (before anything is launched; the kernel refuses the same codes)
+            raise ValueError("the joint acquisition function takes ops.ACQF_UCB or ops.ACQF_EI: a joint LogEI is not defined")
+        kw = self.joint_acqf_inputs(X, base_samples)
+        B, q, D = kw.pop("shape")
+        if B == 0:
+            return dict(value=kw["Xq"].new_empty((0,)), grad=kw["Xq"].new_empty((0, q, D)) if want_grad else None,
+                        jitter=kw["Xq"].new_empty((0,)), info=torch.empty(0, dtype=torch.int32, device=self.device))
+        out = ops.target_qacqf(acqf=acqf, acqf_param=acqf_param, want_grad=want_grad, **kw)
+        out["grad"] = out["grad"].reshape(B, q, D) if want_grad else None
+        return out
+
+    def joint_acqf_inputs(self, X: torch.Tensor, base_samples: torch.Tensor) -> dict:
+        """Everything of ``joint_acqf`` in front of the acquisition kernel, for X (B, q, D): the keyword arguments of
+        ``ops.target_qacqf`` by name (Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples,
+        kind) and ``shape`` = (B, q, D).  They do not depend on the acquisition code or its parameter."""
+        if self.num_fantasies is not None:
+            raise NotImplementedError("the joint acquisition function is not defined on a fantasy model")
+        if self._shard is not None:
+            raise NotImplementedError("the joint acquisition function takes an unsharded source stack")
+        if not self.supports_posterior_grad():
+            raise NotImplementedError(f"the joint acquisition function needs {studies.LIMITS}")
+        st, f = self._stack, self._stack.fit
+        X = torch.as_tensor(X, dtype=torch.float64).to(self.device)
+        if X.dim() != 3 or X.shape[-1] != st.D:
+            raise ValueError("joint_acqf takes X (B, q, D)")
+        B, q, D = X.shape
+        n = self.n
+        base_samples = torch.as_tensor(base_samples, dtype=torch.float64).to(self.device)
+        if base_samples.dim() != 2 or base_samples.shape[1] != q or base_samples.shape[0] < 1:
+            raise ValueError("base_samples must be (S, q)")
+        if q > ops.qacqf_max_q() or base_samples.shape[0] > ops.qacqf_max_samples():
+            raise NotImplementedError(f"the joint acquisition kernel takes q <= {ops.qacqf_max_q()} and at most {ops.qacqf_max_samples()} samples")
+        if n + q > studies.MAX_N or n + q > st.N:
+            raise NotImplementedError(f"the joint acquisition function needs n + q <= {min(studies.MAX_N, st.N)}")
+        Xq = X.reshape(B * q, D).contiguous()
+        if B == 0:
+            return dict(Xq=Xq, shape=(B, q, D))
+        Mq = B * q
+        w_full, active = self._active_tasks()
+        mu_t, cov_tt, var_t = self._train_prior()
+        VQ = ops.source_posteriors(Xq, st.X, st.theta, st.kind, f["L"], f["Linv_diag"], f["alpha"], st.y_mean, st.y_std, n_points=st.n_points,
+                                   want_var=False, keep_V=True, Linv=f["Linv"])["V"]
+        g = ops.source_posteriors_grad_joint(Xq, q, self.train_X, st.X, st.theta, st.kind, f["Linv"], f["alpha"], self._train_VA(), VQ,
+                                             st.y_mean, st.y_std, st.n_points)
+        mu_g, cov_g = ops.weighted_prior_reduce(g["mu"].reshape(st.T, Mq * 16), g["cov"], w_full, active)
+        var_g = ops.weighted_task_sum(g["var"].reshape(st.T, Mq * 16), w_full, 2, active)
+        mu_g, cov_g, var_g = sdist.fused_allreduce([mu_g, cov_g, var_g], self._shard)
+        # the value columns of the training rows next to the training block: the joint prior the target GP's value path takes
+        cov_s = torch.cat([cov_tt, cov_g[:n].reshape(n, Mq, 16)[:, :, 0]], 1)
+        mean_s = torch.cat([mu_t, mu_g.reshape(Mq, 16)[:, 0]])
+        var_s = torch.cat([var_t, var_g.reshape(Mq, 16)[:, 0]])
+        xall = torch.cat([self.train_X, Xq], 0)
+        theta = self.theta
+        factor = self._target_factor()
+        if factor is not None and "alpha_f" not in factor:   # (cached by posterior(): one target vector, its alpha is the one column)
+            factor = dict(factor, alpha_f=factor["alpha"][0].unsqueeze(-1))
+        blk = ops.target_fantasy_block(cov_s, mean_s, var_s, xall, theta, self.train_targets.unsqueeze(0), self._m_all_f, self._s_all_f,
+                                       self.kind, factor=factor)
+        self._keep_target_factor(blk["factor"])
+        return dict(Knq=blk["Knq"], Z=blk["Z"], alpha=blk["factor"]["alpha"][0], mean_q=blk["mean_q"], var_q=blk["var_q"], m_all=self._m_all_f,
+                    s_all=self._s_all_f, info=blk["info"], cov_g=cov_g, mu_g=mu_g, var_g=var_g, Xt=self.train_X, Xq=Xq, theta=theta,
+                    base_samples=base_samples, kind=self.kind, shape=(B, q, D))
+
     def fantasy_acqf(self, X: torch.Tensor, acqf: int, acqf_param: float, want_grad: bool = False):
         """The acquisition function of a fantasy model, averaged over its fantasies, at X (M, D): (value (M,), d value / d X (M, D) or
         None).  ``acqf``: ops.ACQF_UCB (acqf_param = beta), ops.ACQF_EI or ops.ACQF_LOGEI (acqf_param = best_f).  The source pass at cat(X', Xq), the

@@ -673,6 +673,95 @@ def target_fantasy_acqf(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor,
     return value, grad
 
 
+def qacqf_max_q() -> int:
+    """Points per batch of the joint acquisition kernels (5g) / (7p)."""
+    return int(_lib.lib.scaml_qacqf_max_q())
+
+
+def qacqf_max_samples() -> int:
+    """Base samples the joint acquisition kernel (7p) takes."""
+    return int(_lib.lib.scaml_qacqf_max_samples())
+
+
+def source_posteriors_grad_joint(Xq: torch.Tensor, q: int, Xa: torch.Tensor, X: torch.Tensor, theta: torch.Tensor, kind: int, Linv: torch.Tensor,
+                                 alpha: torch.Tensor, VA: torch.Tensor, VQ: torch.Tensor, y_mean: Optional[torch.Tensor] = None,
+                                 y_std: Optional[torch.Tensor] = None, n_points: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """``source_posteriors_grad`` for query points Xq (Mq, D) that move in batches of ``q`` (Mq a multiple of q): one launch of
+    scaml_posterior_linv_grad_joint_f64 (5g).  cov is (T, Ma + q, Mq * 16): rows a < Ma against the leading points Xa (Ma, D) / VA
+    (T, N, Ma), row Ma + r of query point j's strip against its batch mate (j // q) * q + r -- the covariance in column 0, its
+    derivative with respect to x_j (mate held fixed) in columns 1 .. D.  VQ (T, N, Mq): the V of the query points themselves
+    (``source_posteriors(Xq, ..., keep_V=True, Linv=Linv)["V"]``).  Returns dict(mu (T, Mq, 16), var (T, Mq, 16), cov)."""
+    T, N, D = X.shape
+    Mq, q = int(Xq.shape[0]), int(q)
+    if q < 1 or Mq % q:
+        raise ValueError("the query points come in batches of q: Mq must be a multiple of q >= 1")
+    X = _check(X, "X")
+    Xq = _check(Xq, "Xq", (Mq, D))
+    theta = _check(theta, "theta", (T, D + 2))
+    Linv = _check(Linv, "Linv", (T, N, N))
+    alpha = _check(alpha, "alpha", (T, N))
+    Ma = int(VA.shape[-1])
+    VA = _check(VA, "VA", (T, N, Ma))
+    Xa = _check(Xa, "Xa", (Ma, D))
+    VQ = _check(VQ, "VQ", (T, N, Mq))
+    y_mean = _opt(y_mean, "y_mean", (T,))
+    y_std = _opt(y_std, "y_std", (T,))
+    n_points = _opt(n_points, "n_points", (T,), torch.int32)
+    dev = X.device
+    with torch.cuda.device(dev):
+        mu = _empty(dev, T, Mq, 16)
+        var = _empty(dev, T, Mq, 16)
+        cov = _empty(dev, T, Ma + q, Mq * 16)
+        rc = _lib.lib.scaml_posterior_linv_grad_joint_f64(_ptr(Xq), _ptr(Xa), _ptr(X), _ptr(theta), _ptr(Linv), _ptr(alpha), _ptr(y_mean),
+                                                          _ptr(y_std), _ptr(n_points), _ptr(VA), _ptr(VQ), T, N, Mq, Ma, q, D, int(kind),
+                                                          _ptr(mu), _ptr(var), _ptr(cov), 0, _stream_handle())
+    _lib.check_rc(rc, "scaml_posterior_linv_grad_joint_f64")
+    return dict(mu=mu, var=var, cov=cov)
+
+
+def target_qacqf(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor, mean_q: torch.Tensor, var_q: torch.Tensor, m_all: float, s_all: float,
+                 info: Optional[torch.Tensor], cov_g: torch.Tensor, mu_g: torch.Tensor, var_g: torch.Tensor, Xt: torch.Tensor, Xq: torch.Tensor,
+                 theta: torch.Tensor, base_samples: torch.Tensor, acqf: int, acqf_param: float, kind: int = KIND_RBF,
+                 want_grad: bool = True) -> Dict[str, torch.Tensor]:
+    """The joint Monte-Carlo acquisition of B = Mq / q batches of q points, qEI (``acqf`` ACQF_EI, acqf_param = best_f) or qUCB
+    (ACQF_UCB, beta), over the joint posterior of each batch, with its exact input gradient: one launch of scaml_target_qacqf_f64 (7p).
+    Knq, Z (n, Mq), alpha (n,), mean_q, var_q (Mq,) from the value path (``target_fantasy_block``); cov_g (n + q, Mq * 16), mu_g, var_g
+    (Mq * 16) the weighted sums of ``source_posteriors_grad_joint``; base_samples (S, q) standard-normal draws shared by all batches.
+    Returns dict(value (B,), grad (Mq, D) or None, jitter (B,), info (B,) int32)."""
+    n, Mq = Knq.shape
+    S, q = base_samples.shape
+    D = int(Xq.shape[1])
+    if q < 1 or Mq % q:
+        raise ValueError("Mq must be a multiple of q = base_samples.shape[1]")
+    B = Mq // q
+    Knq = _check(Knq, "Knq", (n, Mq))
+    Z = _check(Z, "Z", (n, Mq))
+    alpha = _check(alpha, "alpha", (n,))
+    mean_q = _check(mean_q, "mean_q", (Mq,))
+    var_q = _check(var_q, "var_q", (Mq,))
+    cov_g = _check(cov_g.reshape(n + q, -1), "cov_g", (n + q, Mq * 16))
+    mu_g = _check(mu_g.reshape(-1), "mu_g", (Mq * 16,))
+    var_g = _check(var_g.reshape(-1), "var_g", (Mq * 16,))
+    Xt = _check(Xt, "Xt", (n, D))
+    Xq = _check(Xq, "Xq", (Mq, D))
+    theta = _check(theta, "theta", (D + 2,))
+    base_samples = _check(base_samples, "base_samples", (S, q))
+    if info is not None:
+        info = _check(info.reshape(-1)[:1], "info", (1,), torch.int32)
+    dev = Knq.device
+    with torch.cuda.device(dev):
+        value = _empty(dev, B)
+        grad = _empty(dev, Mq, D) if want_grad else None
+        jitter = _empty(dev, B)
+        info_out = _empty(dev, B, dtype=torch.int32)
+        rc = _lib.lib.scaml_target_qacqf_f64(_ptr(Knq), _ptr(Z), _ptr(alpha), _ptr(mean_q), _ptr(var_q), float(m_all), float(s_all), _ptr(info),
+                                             _ptr(cov_g), _ptr(mu_g), _ptr(var_g), _ptr(Xt), _ptr(Xq), _ptr(theta), _ptr(base_samples),
+                                             int(acqf), float(acqf_param), n, Mq, q, S, D, int(kind), _ptr(value), _ptr(grad), _ptr(jitter),
+                                             _ptr(info_out), _stream_handle())
+    _lib.check_rc(rc, "scaml_target_qacqf_f64")
+    return dict(value=value, grad=grad, jitter=jitter, info=info_out)
+
+
 def _source_pass_grouped(value: bool, Xq, group, Xa, n_points_a, VA_tab, X, theta, kind, Linv, alpha, y_mean, y_std, n_points, task_base,
                          tasks_per_group, cov_out) -> Dict[str, torch.Tensor]:
     """The grouped source pass behind ``source_posteriors_grad_grouped`` (``value`` False: 16 columns per query point, ``group`` per query

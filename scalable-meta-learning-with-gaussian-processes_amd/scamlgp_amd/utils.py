@@ -463,6 +463,76 @@ class LogExpectedImprovement(_AnalyticAcquisition):
         return A, Amu.unsqueeze(-1) * dmu + Av.unsqueeze(-1) * dvar
 
 
+class _JointAcquisition:
+    """What qEI and qUCB share: a Monte-Carlo acquisition function over the JOINT posterior of the q points of a batch (botorch's
+    qExpectedImprovement / qUpperConfidenceBound under optimize_acqf(q = ...)), evaluated by ``ScaMLGP.joint_acqf``.  The base samples
+    are drawn ONCE at construction with ``torch.randn`` from ``generator`` -- (num_samples, 8), of which a batch of q points reads the
+    leading q columns -- and stay fixed: the function is deterministic, as L-BFGS-B needs it.  ``q`` is fixed by the ``q`` argument
+    or by the first batch."""
+
+    def __init__(self, model: ScaMLGP, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None):
+        if model.num_fantasies is not None:
+            raise NotImplementedError("the joint acquisition functions are not defined on a fantasy model")
+        if not 1 <= num_samples <= ops.qacqf_max_samples():
+            raise ValueError(f"num_samples must be within 1 .. {ops.qacqf_max_samples()}")
+        self.model, self.num_samples = model, int(num_samples)
+        # (num_samples, max q) draws, once; a batch of q points reads the leading q columns
+        self._eps = torch.randn(self.num_samples, ops.qacqf_max_q(), dtype=torch.float64, generator=generator).to(model.device)
+        self.q, self.base_samples = None, None
+        if q is not None:
+            self._draw(int(q))
+
+    def _draw(self, q: int) -> None:
+        if not 1 <= q <= ops.qacqf_max_q():
+            raise ValueError(f"q must be within 1 .. {ops.qacqf_max_q()}")
+        self.q, self.base_samples = q, self._eps[:, :q].contiguous()
+
+    def _batches(self, X: torch.Tensor) -> torch.Tensor:
+        X = torch.as_tensor(X, dtype=torch.float64)
+        if X.dim() == 2:   # one batch (q, D); with q = 1, M single points (M, D), as the analytic functions read a flat list
+            X = X.unsqueeze(1) if self.q == 1 else X.unsqueeze(0)
+        if X.dim() != 3:
+            raise ValueError("a joint acquisition function takes X (B, q, D)")
+        if self.q is None:
+            self._draw(int(X.shape[1]))
+        if X.shape[1] != self.q:
+            raise ValueError(f"this acquisition function was drawn for q = {self.q}, got q = {X.shape[1]}")
+        return X
+
+    def __call__(self, X: torch.Tensor) -> torch.Tensor:
+        X = self._batches(X)
+        # (in chunks of at most 256 points: the pass keeps 16 columns per point and covariance row, for every task)
+        step = max(1, 256 // self.q)
+        vals = [self.model.joint_acqf(X[i:i + step], self.code, self.param, self.base_samples)[0] for i in range(0, X.shape[0], step)]
+        return torch.cat(vals) if vals else X.new_empty((0,))
+
+    def value_and_grad(self, X: torch.Tensor):
+        """(value (B,), d value / d X (B, q, D)), the exact gradient of the Monte-Carlo estimate at the fixed base samples."""
+        return self.model.joint_acqf(self._batches(X), self.code, self.param, self.base_samples, want_grad=True)
+
+
+class qExpectedImprovement(_JointAcquisition):
+    """botorch qExpectedImprovement (minimisation): (1/S) sum_s max_j max(best_f - f_sj, 0) over S joint posterior samples of the batch."""
+
+    code = ops.ACQF_EI
+    param = property(lambda self: self.best_f)
+
+    def __init__(self, model: ScaMLGP, best_f: float, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None):
+        super().__init__(model, num_samples, generator, q)
+        self.best_f = float(best_f)
+
+
+class qUpperConfidenceBound(_JointAcquisition):
+    """botorch qUpperConfidenceBound (minimisation): (1/S) sum_s max_j (-mu_j + sqrt(beta pi / 2) |f_sj - mu_j|)."""
+
+    code = ops.ACQF_UCB
+    param = property(lambda self: self.beta)
+
+    def __init__(self, model: ScaMLGP, beta: float = 9.0, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None):
+        super().__init__(model, num_samples, generator, q)
+        self.beta = float(beta)
+
+
 class StudiesAcquisition:
     """The acquisition functions of S ScaMLGP models on ONE source stack (or on slices of one: see below), evaluated together: ``value_and_grad(X, group)`` is two
     library launches whatever S is -- the grouped GRAD source pass (``ops.source_posteriors_grad_grouped``: a query point's covariance

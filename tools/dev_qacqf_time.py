@@ -1,0 +1,185 @@
+"""Cost of the joint q-point acquisition at configs[4] shapes (T = 32 Hartmann-6 sources of N = 512 points, D = 6, n = 80 target
+points) with q = 4, 10 batches and S = 128 base samples, qEI.
+
+In one process, the sides of each comparison interleaved, median of 5 with min .. max:
+  1. one joint evaluation (value + gradient), split into the value pass that keeps V, the joint GRAD pass (5g), the weighted
+     reductions, the target's value path (assemble / cached factor / solve) and the acquisition kernel (7p);
+  2. (5g) against the (5d) route over the same batches: per batch one launch with the batch's V concatenated behind VA;
+  3. suggest_batch(4) against four successive suggest() calls with max_pending_evaluations = 4 and 16 fantasies.
+Host clock around work that ends in a device synchronise.
+
+  python tools/dev_qacqf_time.py [--out FILE] [--no-suggest]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "scalable-meta-learning-with-gaussian-processes_amd"))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from scamlgp_amd import model as M, ops, synthetic  # noqa: E402
+from scamlgp_amd.bo import ScaMLGPBOLoop  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--out", default=None)
+ap.add_argument("--no-suggest", action="store_true", help="skip the suggest_batch / suggest comparison")
+args = ap.parse_args()
+
+T, N, D, n, q, B, S, REPS = 32, 512, 6, 80, 4, 10, 128, 5
+dev = torch.device("cuda:0")
+lines = []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def sync_time(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def interleaved(variants, reps=REPS, warmup=2):
+    for fn in variants.values():
+        for _ in range(warmup):
+            fn()
+    times = {k: [] for k in variants}
+    for _ in range(reps):
+        for k, fn in variants.items():
+            times[k].append(sync_time(fn))
+    return times
+
+
+def report(times, unit=1e6, name="us"):
+    for k, v in times.items():
+        say(f"{k:44s} median {unit * statistics.median(v):10.1f} {name}  (min {unit * min(v):10.1f} .. max {unit * max(v):10.1f}, {len(v)} reps)")
+
+
+d = synthetic.hartmann6_task_stack(T, N, seed=0)
+stack = M.SourceGPStack(list(range(T)), [torch.from_numpy(d["X"][t]) for t in range(T)],
+                        [torch.from_numpy(d["Y"][t]).unsqueeze(-1) for t in range(T)], kind=1, device=dev)
+rng = np.random.default_rng(0)
+stack.set_theta(torch.from_numpy(np.concatenate([0.6 + 0.8 * rng.uniform(size=(T, D)), 0.5 + rng.uniform(size=(T, 1)),
+                                                 1e-3 + 5e-3 * rng.uniform(size=(T, 1))], 1)))
+stack.refresh()
+gps = {tid: M.SourceGP(stack, i) for i, tid in enumerate(stack.task_ids)}
+g = torch.Generator().manual_seed(1)
+obj = lambda x: synthetic.hartmann6(np.asarray(x, dtype=np.float64).reshape(-1, D))   # noqa: E731
+Xt = torch.rand(n, D, dtype=torch.float64, generator=g)
+yt = torch.from_numpy(obj(Xt.numpy())).unsqueeze(-1)
+model = M.ScaMLGP(Xt, yt, gps).eval()
+model.weights = torch.from_numpy(0.01 + 0.1 * rng.uniform(size=T))
+best_f = float(yt.min())
+X = torch.rand(B, q, D, dtype=torch.float64, generator=g).to(dev)
+eps = torch.randn(S, q, dtype=torch.float64, generator=g).to(dev)
+Mq = B * q
+Xq = X.reshape(Mq, D).contiguous()
+say(f"configs[4] shapes: T={T} N={N} D={D} n={n}; q={q}, {B} batches, S={S} base samples, qEI")
+
+# ---- 1. one joint evaluation and its parts --------------------------------------------------------------------------------------
+f = stack.fit
+src = (stack.X, stack.theta, stack.kind)
+w_full, active = model._active_tasks()
+mu_t, cov_tt, var_t = model._train_prior()
+VA = model._train_VA()
+held = {}
+
+
+def value_pass():
+    held["VQ"] = ops.source_posteriors(Xq, *src, f["L"], f["Linv_diag"], f["alpha"], stack.y_mean, stack.y_std, n_points=stack.n_points,
+                                       want_var=False, keep_V=True, Linv=f["Linv"])["V"]
+
+
+def joint_pass():
+    held["g"] = ops.source_posteriors_grad_joint(Xq, q, model.train_X, *src, f["Linv"], f["alpha"], VA, held["VQ"], stack.y_mean, stack.y_std,
+                                                 stack.n_points)
+
+
+def reductions():
+    gg = held["g"]
+    mu_g, cov_g = ops.weighted_prior_reduce(gg["mu"].reshape(T, Mq * 16), gg["cov"], w_full, active)
+    var_g = ops.weighted_task_sum(gg["var"].reshape(T, Mq * 16), w_full, 2, active)
+    held.update(mu_g=mu_g, cov_g=cov_g, var_g=var_g)
+
+
+def value_path():
+    cov_s = torch.cat([cov_tt, held["cov_g"][:n].reshape(n, Mq, 16)[:, :, 0]], 1)
+    mean_s = torch.cat([mu_t, held["mu_g"].reshape(Mq, 16)[:, 0]])
+    var_s = torch.cat([var_t, held["var_g"].reshape(Mq, 16)[:, 0]])
+    xall = torch.cat([model.train_X, Xq], 0)
+    held["blk"] = ops.target_fantasy_block(cov_s, mean_s, var_s, xall, model.theta, model.train_targets.unsqueeze(0), model._m_all_f,
+                                           model._s_all_f, model.kind, factor=held.get("factor"))
+    held["factor"] = held["blk"]["factor"]
+
+
+def acqf_kernel():
+    b = held["blk"]
+    held["out"] = ops.target_qacqf(b["Knq"], b["Z"], b["factor"]["alpha"][0], b["mean_q"], b["var_q"], model._m_all_f, model._s_all_f, b["info"],
+                                   held["cov_g"], held["mu_g"], held["var_g"], model.train_X, Xq, model.theta, eps, ops.ACQF_EI, best_f,
+                                   model.kind, True)
+
+
+for fn in (value_pass, joint_pass, reductions, value_path, acqf_kernel):
+    fn()
+say("-- one joint evaluation (value + gradient)")
+report(interleaved({
+    "whole evaluation (ScaMLGP.joint_acqf)": lambda: model.joint_acqf(X, ops.ACQF_EI, best_f, eps, want_grad=True),
+    "  value pass, V kept (5c)": value_pass,
+    "  joint GRAD pass (5g)": joint_pass,
+    "  weighted reductions (6')": reductions,
+    "  value path: assemble, cached factor, solve": value_path,
+    "  acquisition kernel (7p)": acqf_kernel,
+}))
+
+# ---- 2. (5g) against the concatenated (5d) route ----------------------------------------------------------------------------------
+VQ = held["VQ"]
+
+
+def concat_route():
+    for b in range(B):
+        sl = slice(b * q, (b + 1) * q)
+        ops.source_posteriors_grad(Xq[sl], torch.cat([model.train_X, Xq[sl]]), *src, f["Linv"], f["alpha"], stack.y_mean, stack.y_std,
+                                   stack.n_points, torch.cat([VA, VQ[:, :, sl]], -1).contiguous())
+
+
+say("-- the joint GRAD pass against (5d) with the batch's V concatenated behind VA, one launch per batch")
+t2 = interleaved({"(5g), one launch for all batches": joint_pass, f"(5d) route, {B} launches + {B} copies of V": concat_route})
+report(t2)
+
+# ---- 3. suggest_batch(4) against four suggest() calls -------------------------------------------------------------------------------
+if not args.no_suggest:
+    def loop():
+        lp = ScaMLGPBOLoop(gps, dim=D, acquisition="ei", num_restarts_log_likelihood=1, seed=0, max_pending_evaluations=q, num_fantasies=16,
+                           num_mc_samples=S)
+        lp.record(Xt, yt.squeeze(-1))
+        lp.model.weights = model.weights.clone()
+        return lp
+
+    lp_a, lp_b = loop(), loop()
+
+    def batch():
+        lp_a.pending = lp_a.pending[:0]
+        lp_a.suggest_batch(q)
+
+    def successive():
+        lp_b.pending = lp_b.pending[:0]
+        for _ in range(q):
+            lp_b.suggest()
+
+    say(f"-- {q} points: suggest_batch({q}) against {q} successive suggest() calls (max_pending_evaluations={q}, 16 fantasies)")
+    report(interleaved({f"suggest_batch({q})": batch, f"{q} x suggest()": successive}, warmup=1), unit=1e3, name="ms")
+
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
