@@ -380,6 +380,39 @@ int scaml_target_qacqf_f64(const double* Knq, const double* Z, const double* alp
                            int S, int D, int kind, double* value, double* grad, double* jitter_used, int32_t* info_out, void* stream);
 
 /*
+ * (7q) (7p) with p EVALUATIONS PENDING (botorch's X_pending): every batch is its q moving points followed by the same p pending
+ * points Xp (p, D); the joint vector has Q = q + p entries (moving first, pending point k at index q + k), the utility's maximum runs
+ * over all Q of them, base_samples is (S, q + p), and only the q moving points get a gradient (grad (Mq, D)): a pending point is held
+ * fixed.  scamlgp_amd.ScaMLGP.joint_acqf(X_pending=...), utils.qExpectedImprovement / qUpperConfidenceBound(X_pending=...),
+ * ScaMLGPBOLoop(joint_pending="joint").suggest_batch.
+ * The pending points are the same in every batch, so they are LEADING points of (5g), not batch mates: call (5g) with
+ * Xa = cat(Xt, Xp), VA = cat(V_train, V_pending), Ma = n + p.  The source pass then keeps B q strips, and cov_g is
+ * (n + p + q, Mq * 16): rows a < n the training points, rows n + k pending point k, rows n + p + r batch mate r.
+ *   Zp (n, p) = Knn^-1 Knp;  mu_p (p), Sigma_pp (p, p): the target posterior of the pending points among themselves, original units,
+ *   no observation noise (they do not depend on the batch: computed once per pending set).
+ *   mu_j, S_jk for j, k < q: (7p)'s, the mate rows read at n + p + k.
+ *   S_{j, q+k} = cov_g[n + k][16 j] / s^2 + os_t k_t(x_j, xp_k) - Knq[:, j] . Zp[:, k],  Sigma = s^2 S   (j < q)
+ *   the pending block of Sigma and mu: Sigma_pp (its lower triangle is read) and mu_p as given.
+ *   The ladder, f = mu + C eps, qEI / qUCB, the lowest-index arg-max and the adjoint (mubar, Cbar, Phi, Sigmabar) are (7p)'s at Q.
+ *   grad_j = (7p)'s terms + 2 sum_k Sbar_{j,q+k} dP_{j,q+k}/dx_j (the source part from columns 16 j + 1 + d of row n + k, the target
+ *   kernel's slope against xp_k), and the weight vector on dKnq[:, j] is
+ *   mbar_j alpha - 2 sum_{k<q} Sbar_jk Z[:, k] - 2 sum_{k<p} Sbar_{j,q+k} Zp[:, k].  The pending rows of mbar and Sbar are not used.
+ *   One workgroup of 256 threads per batch, the Q x Q work in LDS, every sum over the samples by one thread in (7p)'s fixed order: no
+ *   atomics, two calls agree bit for bit, and with p == 0 the outputs are (7p)'s bits (Xp, Zp, mu_p, Sigma_pp may be NULL then).
+ *   Non-finite values: a NaN / infinite coordinate of a moving point turns its batch NaN (value and its q rows of grad) as in (7p);
+ *   a NaN anywhere in Xp, Zp, mu_p or Sigma_pp turns EVERY batch NaN, the pending set being shared.  info[0] != 0 as in (7p).
+ *   Limits: 1 <= q, 0 <= p, q + p <= scaml_qacqf_max_q() = 8, n + p + q <= 96, S <= 512, D <= 15: SCAML_E_TOOLARGE beyond them;
+ *   (7p)'s bad arguments, p < 0, or a NULL Xp / Zp / mu_p / Sigma_pp with p > 0: SCAML_E_BADARG (first).  Mq == 0 enqueues nothing.
+ *   No host synchronisation.
+ */
+int scaml_target_qacqf_pending_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q,
+                                   double m_all, double s_all, const int32_t* info, const double* cov_g, const double* mu_g,
+                                   const double* var_g, const double* Xt, const double* Xq, const double* theta, const double* base_samples,
+                                   const double* Xp, const double* Zp, const double* mu_p, const double* Sigma_pp, int acqf,
+                                   double acqf_param, int n, int Mq, int q, int p, int S, int D, int kind, double* value, double* grad,
+                                   double* jitter_used, int32_t* info_out, void* stream);
+
+/*
  * (7o) The acquisition function of M given posteriors, elementwise: A[i] and its partial derivatives Amu[i] = dA / dmu, Av[i] = dA / dv
  * at (mu[i], var[i]) (original units), i = 0 .. M-1, one thread per element -- the statement (7f), (7g), (7i) and (7k) evaluate
  * (sa_acquisition of csrc/gp_studies_formulas.h), with their clamps.  acqf: SCAML_ACQF_UCB (acqf_param = beta), SCAML_ACQF_EI or

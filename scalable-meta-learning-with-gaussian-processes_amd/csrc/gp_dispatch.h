@@ -206,5 +206,9 @@ struct QAcqfPlan {
   size_t lds_doubles;   // more than LDS_LIMIT: the shape is too large
 };
 constexpr QAcqfPlan qacqf_plan(int B, int n, int q, int S) { return {(unsigned)B, (unsigned)QACQF_THREADS, qa_lds_doubles(n, q, S)}; }
+// ... with p evaluations pending (7q): still a workgroup per batch of q moving points
+constexpr QAcqfPlan qacqf_pending_plan(int B, int n, int q, int p, int S) {
+  return {(unsigned)B, (unsigned)QACQF_THREADS, qa_pending_lds_doubles(n, q, p, S)};
+}
 
 }  // namespace scaml

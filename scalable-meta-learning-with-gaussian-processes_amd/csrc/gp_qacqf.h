@@ -20,6 +20,13 @@
 // would sit in scratch memory).  The samples are dealt to the threads; what a sample adds to mubar, Cbar and the value is recorded in
 // LDS and summed by ONE thread per entry over four fixed chunks of the sample axis, ascending: no atomics, no cross-wave reduction, so
 // the result is a pure function of the inputs, whatever the number of threads, and the host build computes what the device computes.
+//
+// With p evaluations pending ((7q), qa_batch<true>) the joint vector is the q moving points followed by the p pending ones, Q = q + p,
+// the same pending points in every batch.  They are LEADING points of (5g) (rows n + k of cov_g, in front of the mates' rows n + p + r), so
+//   S_{j, q+k} = cov_g[n + k][16 j] / s^2 + os k_t(x_j, xp_k) - Knq[:, j] . Zp[:, k]     (Zp = Knn^-1 Knp),    Sigma = s^2 S
+// and the pending block of Sigma and mu is given (Sigma_pp, mu_p: they do not depend on the batch).  The tail runs at Q; a pending point
+// is held fixed, so the gradient of moving point j gains 2 sum_k Sbar_{j,q+k} dP_{j,q+k}/dx_j and its weight vector on dKnq[:, j] the
+// term -2 sum_k Sbar_{j,q+k} Zp[:, k].  The pending rows of mbar and Sbar are not read.
 #pragma once
 #include "gp_studies_formulas.h"   // SA_DEV / SA_SYNC, sa_kernel_and_slope, the acquisition codes
 
@@ -59,6 +66,19 @@ struct QAcqfParams {
   int n, Mq, q, S, D, kind, acqf, pad_;
 };
 
+// (7q): the pending set, shared by all batches.  In QAcqfParams then: cov_g (n + p + q, Mq * 16), base_samples (S, q + p).
+struct QAcqfPending {
+  const double* Xp;         // (p, D)
+  const double* Zp;         // (n, p) Knn^-1 Knp
+  const double* mu_p;       // (p)    target posterior mean of the pending points, original units
+  const double* Sigma_pp;   // (p, p) ... and their covariance among themselves, no observation noise
+  int p, pad_;
+};
+struct QAcqfPendingParams {
+  QAcqfParams a;
+  QAcqfPending pe;
+};
+
 // ---- LDS of the tail, in doubles (8 x 8 matrices with row stride 8, whatever q) -----------------------------------------------------
 //   Sigma | mu [8] | C | C^-1 | Cbar, then Phi C^-1 | mubar [8] | Phi, then C^-T Phi C^-1 | Sigmabar | out [8] | part [4][80] |
 //   eps [S][q] | a, wm, wc, j* [4][S]
@@ -68,6 +88,10 @@ constexpr int QA_OUT_VALUE = 0, QA_OUT_JITTER = 1, QA_OUT_INFO = 2;
 constexpr size_t qa_tail_lds_doubles(int q, int S) { return (size_t)QA_EPS + (size_t)S * (size_t)(q + 4); }
 // ... and of a whole batch: the tail, then  Knq [n][8] | Z [n][8] | U, SL [2][8][n + q] | bad [8]
 constexpr size_t qa_lds_doubles(int n, int q, int S) { return qa_tail_lds_doubles(q, S) + 16 * (size_t)n + 16 * (size_t)(n + q) + 8; }
+// ... and with p pending points: the tail at q + p, Knq | Z as above, U, SL [2][8][n + p + q] | bad [8] | Zp [n][8]
+constexpr size_t qa_pending_lds_doubles(int n, int q, int p, int S) {
+  return qa_tail_lds_doubles(q + p, S) + 16 * (size_t)n + 16 * (size_t)(n + p + q) + 8 + 8 * (size_t)n;
+}
 
 // Everything from "Sigma, mu given" onwards, by `nthr` cooperating threads: t[QA_SG] (both triangles; only the lower one is read) and
 // t[QA_MU] hold the joint posterior of the q points, entries past q are zero.  Leaves value, jitter and info in t[QA_OUT], mubar in
@@ -255,9 +279,13 @@ SA_DEV void qa_tail(double* t, int q, int S, int acqf, double par, const double*
 }
 
 // Batch b of the call by `nthr` cooperating threads; `lds`: qa_lds_doubles(n, q, S).  (Every branch up to a barrier is uniform over
-// the workgroup.)
-SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr) {
-  const int n = p.n, q = p.q, S = p.S, D = p.D, Mq = p.Mq, R = n + q;
+// the workgroup.)  PEND: (7q), `pe.p` pending points behind the q moving ones; `lds`: qa_pending_lds_doubles(n, q, p, S).  Without
+// PEND `pe` is not read and P below is the constant 0: (7p) as it was, instruction for instruction (a wrapper around the template
+// instead of the default argument reorders three instructions of that kernel; tools/dev_isa_diff.py).
+template <bool PEND = false>
+SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr, const QAcqfPending& pe = QAcqfPending{}) {
+  const int P = PEND ? pe.p : 0;
+  const int n = p.n, q = p.q, S = p.S, D = p.D, Mq = p.Mq, R = n + P + q, Q = q + P;
   const size_t q0 = (size_t)b * q, W = (size_t)Mq * 16;
   const double nan = NAN;
   if (p.info && p.info[0] != 0) {   // the target's training block was not positive definite even with jitter
@@ -271,11 +299,12 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
     return;
   }
   double* t = lds;
-  double* Kq = lds + qa_tail_lds_doubles(q, S);   // [a][8]
+  double* Kq = lds + qa_tail_lds_doubles(Q, S);   // [a][8]
   double* Zq = Kq + (size_t)n * 8;                // [a][8]
   double* U = Zq + (size_t)n * 8;                 // [j][R]: the weight of row a in point j's gradient, / s^2
   double* SL = U + (size_t)8 * R;                 // [j][R]: that weight times 2 os dk_t / d(d2)
-  double* badp = SL + (size_t)8 * R;
+  double* badp = SL + (size_t)8 * R;              // [0] the batch's coordinates, [1 .. 7] shares of the pending set's arrays
+  double* Zpl = badp + 8;                         // [a][8] (PEND)
   const double s = p.s_all, s2 = s * s, inv_s2 = 1.0 / s2;
   const double os = p.theta[D];
 
@@ -284,13 +313,36 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
     Kq[a * 8 + j] = p.Knq[(size_t)a * Mq + q0 + j];
     Zq[a * 8 + j] = p.Z[(size_t)a * Mq + q0 + j];
   }
+  if constexpr (PEND)
+    for (int e = tid; e < n * P; e += nthr) Zpl[(e / P) * 8 + e % P] = pe.Zp[e];
   SA_SYNC();
   // ---- the joint posterior of the batch: one thread per entry of Sigma (lower triangle, mirrored) and of mu, training points ascending
-  for (int e = tid; e < QA_ENTRIES; e += nthr) {
+  for (int e = tid; e < QA_ENTRIES + (PEND ? 7 : 0); e += nthr) {
     if (e < 64) {
       const int j = e >> 3, k = e & 7;
-      if (j >= q || k >= q) {
+      if (j >= Q || k >= Q) {
         t[QA_SG + e] = 0.0;
+      } else if (PEND && k <= j && j >= q) {
+        // a pending row: against a moving point k the mixed block (the pending point is the ANCHOR of strip k: row n + jp of cov_g),
+        // against a pending one the given Sigma_pp
+        const int jp = j - q;
+        double v;
+        if (k >= q) {
+          v = pe.Sigma_pp[jp * P + (k - q)];
+        } else {
+          double kz = 0.0;
+          for (int a = 0; a < n; ++a) kz = fma(Kq[a * 8 + k], Zpl[a * 8 + jp], kz);
+          double d2 = 0.0;
+          for (int d = 0; d < D; ++d) {
+            const double df = (p.Xq[(q0 + k) * D + d] - pe.Xp[jp * D + d]) / p.theta[d];
+            d2 = fma(df, df, d2);
+          }
+          double k0, dk;
+          sa_kernel_and_slope(p.kind, d2, os, k0, dk);
+          v = s2 * (p.cov_g[(size_t)(n + jp) * W + (q0 + k) * 16] * inv_s2 + k0 + (d2 - d2) - kz);
+        }
+        t[QA_SG + j * 8 + k] = v;
+        t[QA_SG + k * 8 + j] = v;
       } else if (k <= j) {
         double kz = 0.0;
         for (int a = 0; a < n; ++a) kz = fma(Kq[a * 8 + j], Zq[a * 8 + k], kz);
@@ -305,7 +357,7 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
           }
           double k0, dk;
           sa_kernel_and_slope(p.kind, d2, os, k0, dk);
-          prior = p.cov_g[(size_t)(n + k) * W + (q0 + j) * 16] * inv_s2 + k0 + (d2 - d2);
+          prior = p.cov_g[(size_t)(n + P + k) * W + (q0 + j) * 16] * inv_s2 + k0 + (d2 - d2);
         }
         const double v = s2 * (prior - kz);
         t[QA_SG + j * 8 + k] = v;
@@ -319,8 +371,9 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
         for (int a = 0; a < n; ++a) acc = fma(Kq[a * 8 + j], p.alpha[a], acc);
         m = fma(s, acc, p.m_all);
       }
+      if (PEND && j >= q && j < Q) m = pe.mu_p[j - q];
       t[QA_MU + j] = m;
-    } else {
+    } else if (!PEND || e == 72) {
       // a NaN / infinite coordinate anywhere in the batch: sum (x - x) is 0, or NaN then
       double bad = 0.0;
       for (int i = 0; i < q * D; ++i) {
@@ -328,13 +381,24 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
         bad += x - x;
       }
       badp[0] = bad;
+    } else if constexpr (PEND) {
+      // ... or anywhere in the pending set's arrays, which every batch shares: seven threads, every seventh element each
+      const int w = e - QA_ENTRIES, nx = P * D, nz = nx + n * P, nm = nz + P, ns = nm + P * P;
+      double bad = 0.0;
+      for (int i = w; i < ns; i += 7) {
+        const double x = i < nx ? pe.Xp[i] : (i < nz ? pe.Zp[i - nx] : (i < nm ? pe.mu_p[i - nz] : pe.Sigma_pp[i - nm]));
+        bad += x - x;
+      }
+      badp[1 + w] = bad;
     }
   }
   SA_SYNC();
-  qa_tail(t, q, S, p.acqf, p.acqf_param, p.base_samples, tid, nthr);
+  qa_tail(t, Q, S, p.acqf, p.acqf_param, p.base_samples, tid, nthr);
 
   const bool failed = t[QA_OUT + QA_OUT_INFO] != 0.0;
-  const double value = failed ? nan : t[QA_OUT + QA_OUT_VALUE] + badp[0];
+  double value = failed ? nan : t[QA_OUT + QA_OUT_VALUE] + badp[0];
+  if constexpr (PEND)
+    for (int w = 1; w < 8; ++w) value += badp[w];   // (zeros, or NaN)
   if (tid == 0) {
     p.value[b] = value;
     if (p.jitter_used) p.jitter_used[b] = t[QA_OUT + QA_OUT_JITTER];
@@ -356,10 +420,16 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
     if (a < n) {
       double sz = 0.0;
       for (int k = 0; k < q; ++k) sz = fma(Sb[j * 8 + k], Zq[a * 8 + k], sz);
+      if constexpr (PEND)
+        for (int k = 0; k < P; ++k) sz = fma(Sb[j * 8 + q + k], Zpl[a * 8 + k], sz);
       u = s * mb[j] * p.alpha[a] - 2.0 * s2 * sz;
       xa = p.Xt + (size_t)a * D;
-    } else {
+    } else if (PEND && a < n + P) {   // a pending point: held fixed, so only this side of the pair
       const int k = a - n;
+      u = 2.0 * s2 * Sb[j * 8 + q + k];
+      xa = pe.Xp + (size_t)k * D;
+    } else {
+      const int k = a - n - P;
       u = k == j ? 0.0 : 2.0 * s2 * Sb[j * 8 + k];
       xa = p.Xq + (q0 + k) * D;
     }
@@ -382,12 +452,19 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
     const double xjd = p.Xq[(q0 + j) * D + d];
     double acc = fma(mb[j], p.mu_g[col], Sb[j * 8 + j] * p.var_g[col]);
     for (int a = 0; a < R; ++a) {
-      const double xad = a < n ? p.Xt[(size_t)a * D + d] : p.Xq[(q0 + a - n) * D + d];
+      double xad;
+      if (PEND && a >= n && a < n + P) xad = pe.Xp[(size_t)(a - n) * D + d];
+      else xad = a < n ? p.Xt[(size_t)a * D + d] : p.Xq[(q0 + a - n - P) * D + d];
       acc = fma(U[j * R + a], p.cov_g[(size_t)a * W + col], acc);
       acc = fma(SL[j * R + a], (xjd - xad) * il2, acc);
     }
     p.grad[(q0 + j) * D + d] = acc;
   }
+}
+
+// (7q)
+SA_DEV void qa_batch_pending(const QAcqfPendingParams& pp, double* lds, int b, int tid, int nthr) {
+  qa_batch<true>(pp.a, lds, b, tid, nthr, pp.pe);
 }
 
 }  // namespace scaml

@@ -71,6 +71,7 @@ struct Module {
   hipFunction_t tgt_fantasy = nullptr, tgt_fantasy_grad[2] = {};   // value only; value + gradient per kind
   hipFunction_t acqf_transform = nullptr;                          // the elementwise acquisition of given posteriors (7o)
   hipFunction_t post_linv_grad_joint[2] = {}, tgt_qacqf = nullptr;   // joint q-point acquisition: the GRAD pass with batch mates (5g), qEI / qUCB (7p)
+  hipFunction_t tgt_qacqf_pending = nullptr;                         // ... with evaluations pending (7q)
   hipFunction_t post_linv_grouped[2] = {}, tgt_acqf_batched = nullptr;   // lock-step studies: grouped GRAD pass, batched acquisition
   hipFunction_t post_linv_grouped_own[2] = {};                           // the grouped pass with per-group source tasks
   hipFunction_t post_linv_grouped_det[2] = {}, post_linv_grouped_det_own[2] = {};   // the GRAD grouped pass with ordered sums: (7l)'s rounds
@@ -107,6 +108,7 @@ struct Module {
         {post_linv_grouped_val_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
         {post_linv_grad_joint, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0ELb0ELb1EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
         {&tgt_qacqf, "scaml_target_qacqf_kernel", kLdsLimit, {}},
+        {&tgt_qacqf_pending, "scaml_target_qacqf_pending_kernel", kLdsLimit, {}},
         {&tgt_acqf_batched, "scaml_target_acqf_batched_kernel", kLdsLimit, {}},
         {&tgt_score_batched, "scaml_target_score_batched_kernel", kLdsLimit, {}},
         {&tgt_fantasy_acqf_batched, "scaml_target_fantasy_acqf_batched_kernel", kLdsLimit, {}},
@@ -748,6 +750,33 @@ int scaml_target_qacqf_f64(const double* Knq, const double* Z, const double* alp
   scaml::QAcqfParams p{Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples, acqf_param,
                        value, grad, jitter_used, info_out, n, Mq, q, S, D, kind, acqf, 0};
   return launch(m->tgt_qacqf, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "target_qacqf", p);
+}
+
+// ---- (7q) (7p) with p evaluations pending behind every batch: the same workgroup per batch, the joint at q + p ----
+int scaml_target_qacqf_pending_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q,
+                                   double m_all, double s_all, const int32_t* info, const double* cov_g, const double* mu_g,
+                                   const double* var_g, const double* Xt, const double* Xq, const double* theta, const double* base_samples,
+                                   const double* Xp, const double* Zp, const double* mu_p, const double* Sigma_pp, int acqf,
+                                   double acqf_param, int n, int Mq, int q, int p, int S, int D, int kind, double* value, double* grad,
+                                   double* jitter_used, int32_t* info_out, void* stream) {
+  if (n < 1 || Mq < 0 || q < 1 || p < 0 || S < 1 || D < 1 || Mq % q != 0) return SCAML_E_BADARG;
+  if (!Knq || !Z || !alpha || !mean_q || !var_q || !cov_g || !mu_g || !var_g || !Xt || !Xq || !theta || !base_samples || !value) return SCAML_E_BADARG;
+  if (p > 0 && (!Xp || !Zp || !mu_p || !Sigma_pp)) return SCAML_E_BADARG;
+  if (!scaml::qa_acqf_valid(acqf)) return SCAML_E_BADARG;
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (!(s_all > 0.0)) return SCAML_E_BADARG;
+  if (q > scaml::QACQF_MAX_Q || p > scaml::QACQF_MAX_Q || q + p > scaml::QACQF_MAX_Q || S > scaml::QACQF_MAX_SAMPLES ||
+      n > scaml::QACQF_MAX_ROWS || n + p + q > scaml::QACQF_MAX_ROWS || D > scaml::QACQF_MAX_D)
+    return SCAML_E_TOOLARGE;
+  const scaml::QAcqfPlan plan = scaml::qacqf_pending_plan(Mq / q, n, q, p, S);
+  if (plan.lds_doubles * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (Mq == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  scaml::QAcqfPendingParams pp{{Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples, acqf_param,
+                                value, grad, jitter_used, info_out, n, Mq, q, S, D, kind, acqf, 0},
+                               {Xp, Zp, mu_p, Sigma_pp, p, 0}};
+  return launch(m->tgt_qacqf_pending, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "target_qacqf_pending", pp);
 }
 
 // ---- (7o) the acquisition value and chain-rule factors of M given posteriors, elementwise (csrc/gp_acqf_transform.hip) ----------

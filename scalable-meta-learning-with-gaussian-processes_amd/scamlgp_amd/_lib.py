@@ -103,6 +103,8 @@ SIGNATURES = {
     # (7p) Knq, Z, alpha, mean_q, var_q; m_all, s_all; info; cov_g, mu_g, var_g, Xt, Xq, theta, base_samples; acqf, acqf_param;
     # n, Mq, q, S, D, kind; value, grad, jitter_used, info_out
     "scaml_target_qacqf_f64": (_i, [_dp] * 5 + [_f, _f, _dp] + [_dp] * 7 + [_i, _f] + [_i] * 6 + [_dp] * 4 + [c_void_p]),
+    # (7q) (7p)'s arrays, then Xp, Zp, mu_p, Sigma_pp; acqf, acqf_param; n, Mq, q, p, S, D, kind; value, grad, jitter_used, info_out
+    "scaml_target_qacqf_pending_f64": (_i, [_dp] * 5 + [_f, _f, _dp] + [_dp] * 11 + [_i, _f] + [_i] * 7 + [_dp] * 4 + [c_void_p]),
     # (7o) mu, var; acqf_param, M, acqf; A, Amu, Av
     "scaml_acqf_transform_f64": (_i, [_dp, _dp, _f, _i, _i, _dp, _dp, _dp, c_void_p]),
     # (5e) Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points; T, N, Mq, G, Ma_max, D, kind; mu, var, cov

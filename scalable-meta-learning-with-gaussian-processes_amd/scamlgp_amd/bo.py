@@ -207,13 +207,18 @@ class ScaMLGPBOLoop:
                  num_restarts_log_likelihood: int = 5, raw_samples: int = 1024, num_restarts: int = 10, af_max_iter: int = 50,
                  gp_likelihood: Optional[hyper.GaussianLikelihood] = None, gp_kernel: Optional[hyper.ScaleKernel] = None,
                  seed: Optional[int] = None, use_graph: bool = True, max_pending_evaluations: Optional[int] = None,
-                 num_fantasies: int = 16, num_mc_samples: int = 128):
+                 num_fantasies: int = 16, num_mc_samples: int = 128, joint_pending: str = "refuse"):
         """``num_mc_samples``: base samples of the joint acquisition function of ``suggest_batch``.
+        ``joint_pending``: what ``suggest_batch`` does while evaluations are pending -- ``"refuse"`` (default): NotImplementedError;
+        ``"joint"``: the pending points join every batch and are held fixed (botorch's X_pending, ``ScaMLGP.joint_acqf(X_pending=...)``).
         ``max_pending_evaluations``: None (default) -- strictly suggest -> report, no bookkeeping; an integer k -- ``suggest()``
         records its point in ``pending`` until it is reported, raises OptimizerNotReady while k points are pending, and builds the
         acquisition function on ``num_fantasies`` fantasies of the pending outcomes (ScaMLGP.fantasize, base samples from ``gen``)."""
         if max_pending_evaluations is not None and int(max_pending_evaluations) < 1:
             raise ValueError("max_pending_evaluations must be None or a positive integer")
+        if joint_pending not in ("refuse", "joint"):
+            raise ValueError(f"joint_pending must be 'refuse' or 'joint', got {joint_pending!r}")
+        self.joint_pending = joint_pending
         self.max_pending_evaluations = None if max_pending_evaluations is None else int(max_pending_evaluations)
         self.num_fantasies = int(num_fantasies)
         self.num_mc_samples = int(num_mc_samples)
@@ -297,35 +302,40 @@ class ScaMLGPBOLoop:
             self.pending = torch.cat([self.pending, x.reshape(1, -1)], 0)
         return x
 
-    def joint_acquisition_function(self, q: int):
+    def joint_acquisition_function(self, q: int, X_pending: Optional[torch.Tensor] = None):
         """The joint Monte-Carlo acquisition function of ``suggest_batch``: qUCB for ``acquisition="ucb"``, qEI for ``"ei"`` (best_f: the
-        incumbent over the observed values); its base samples come from ``gen``."""
+        incumbent over the observed values); its base samples come from ``gen``.  ``X_pending`` (p, D): evaluations that are running,
+        appended to every batch and held fixed."""
         if self.acquisition == "logei":
             raise ValueError("a joint LogEI is not defined: suggest_batch takes acquisition='ucb' or 'ei'")
         if self.acquisition == "ei":
             Yf = self.Y[torch.isfinite(self.Y)]
             if Yf.numel() == 0:
                 raise ValueError("EI needs at least one evaluation")
-            return qExpectedImprovement(self.model, float(Yf.min()), self.num_mc_samples, self.gen, q=q)
-        return qUpperConfidenceBound(self.model, self.beta, self.num_mc_samples, self.gen, q=q)
+            return qExpectedImprovement(self.model, float(Yf.min()), self.num_mc_samples, self.gen, q=q, X_pending=X_pending)
+        return qUpperConfidenceBound(self.model, self.beta, self.num_mc_samples, self.gen, q=q, X_pending=X_pending)
 
     def suggest_batch(self, q: int) -> torch.Tensor:
         """q points for q parallel workers, optimised AGAINST EACH OTHER: the maximiser (q, D) of the joint Monte-Carlo acquisition
         function over batches of q points (botorch's optimize_acqf(q = ...)), where q calls of ``suggest()`` condition every point on
         fantasies of the ones before it.  With ``max_pending_evaluations=k``: q <= k, and all q points become pending; with points
-        already pending it raises (a joint acquisition function on a fantasy model is not defined here).  ``report(x (q, D), y (q,))``
-        takes the results."""
-        q, k = int(q), self.max_pending_evaluations
+        already pending it raises (a joint acquisition function on a fantasy model is not defined here) unless the loop was built with
+        ``joint_pending="joint"``: then the p pending points join every batch as fixed entries of the joint posterior (q + p <= k, and
+        OptimizerNotReady once p >= k), and only the q new points are optimised.  ``report(x (q, D), y (q,))`` takes the results."""
+        q, k, p = int(q), self.max_pending_evaluations, int(self.pending.shape[0])
         if q < 1:
             raise ValueError("suggest_batch takes q >= 1")
         if self.acquisition not in ("ucb", "ei"):
             raise ValueError("a joint LogEI is not defined: suggest_batch takes acquisition='ucb' or 'ei'")
-        if self.pending.shape[0] > 0:
-            raise NotImplementedError("suggest_batch with evaluations pending: the joint acquisition function is not defined on a fantasy model")
-        if k is not None and q > k:
-            raise ValueError(f"suggest_batch({q}) exceeds max_pending_evaluations={k}")
+        if p > 0 and self.joint_pending != "joint":
+            raise NotImplementedError("suggest_batch with evaluations pending: the joint acquisition function is not defined on a fantasy model "
+                                      "(joint_pending='joint' holds the pending points fixed in every batch instead)")
+        if k is not None and p >= k:
+            raise OptimizerNotReady(f"{p} evaluations are pending (max_pending_evaluations={k}): report one first")
+        if k is not None and q + p > k:
+            raise ValueError(f"suggest_batch({q}) exceeds max_pending_evaluations={k}" + (f" with {p} pending" if p else ""))
         self.model.eval()
-        af = self.joint_acquisition_function(q)
+        af = self.joint_acquisition_function(q, self.pending if p > 0 else None)
         # (the joint route for every q, q = 1 included: optimize_acqf(q=1) is the single-point path of the analytic functions)
         X, _ = _optimize_acqf_joint(af, self.dim, q, self.raw_samples, self.num_restarts, self.af_max_iter, self.gen, 2.0)
         X = X.reshape(q, self.dim)

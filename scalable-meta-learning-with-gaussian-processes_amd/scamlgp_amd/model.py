@@ -996,55 +996,108 @@ class ScaMLGP:
         xall = torch.cat([self.train_X, Xq], 0)
         return cov_s, mean_s, var_s, xall, cov_g, mu_g, var_g
 
-    def joint_acqf(self, X: torch.Tensor, acqf: int, acqf_param: float, base_samples: torch.Tensor, want_grad: bool = False):
+    def joint_acqf(self, X: torch.Tensor, acqf: int, acqf_param: float, base_samples: torch.Tensor, want_grad: bool = False,
+                   X_pending=None):
         """The joint Monte-Carlo acquisition function of B batches of q points, X (B, q, D): qEI (``acqf`` ops.ACQF_EI, acqf_param =
         best_f) or qUCB (ops.ACQF_UCB, beta) over the JOINT posterior of each batch, reparameterised with ``base_samples`` (S, q)
         -- (value (B,), d value / d X (B, q, D) or None).  The value pass at the B q points keeps their V; the joint GRAD pass
         (scaml_posterior_linv_grad_joint_f64) adds, per point, the covariances with its batch mates and their input derivatives; the
         weighted task sums, the assemble and Z = Knn^-1 Knq are those of ``posterior_with_grad`` (the training block's factor is cached);
         then ONE launch of scaml_target_qacqf_f64 factors every batch's q x q posterior covariance, draws the samples, evaluates the
-        utility and carries the adjoint back through the factor to the inputs: no (B, S, q) tensor reaches memory."""
-        out = self.joint_acqf_full(X, acqf, acqf_param, base_samples, want_grad)
+        utility and carries the adjoint back through the factor to the inputs: no (B, S, q) tensor reaches memory.
+
+        ``X_pending`` (p, D), or the dict ``joint_pending`` made of it: evaluations that are running (botorch's X_pending).  They join
+        every batch behind its q points -- ``base_samples`` is (S, q + p), the utility's maximum runs over all q + p joint samples --
+        and stay fixed: value (B,), gradient (B, q, D).  The pending points are the same in every batch, so they ride with the LEADING
+        points of the source pass (Xa = cat(train_X, X_pending), Ma = n + p); the passes still see B q strips and
+        scaml_target_qacqf_pending_f64 puts the (q + p) x (q + p) joint together.  None or p = 0: the path above, unchanged."""
+        out = self.joint_acqf_full(X, acqf, acqf_param, base_samples, want_grad, X_pending)
         return out["value"], out["grad"]
 
-    def joint_acqf_full(self, X: torch.Tensor, acqf: int, acqf_param: float, base_samples: torch.Tensor, want_grad: bool = False) -> dict:
+    def joint_acqf_full(self, X: torch.Tensor, acqf: int, acqf_param: float, base_samples: torch.Tensor, want_grad: bool = False,
+                        X_pending=None) -> dict:
         """``joint_acqf`` with the kernel's per-batch status: dict(value (B,), grad (B, q, D) or None, jitter (B,) -- the rung of the
         ladder 0, 1e-8, 1e-7, 1e-6 that made the batch's covariance positive definite --, info (B,) int32 -- 1: none did, the batch is
         NaN)."""
         if acqf not in (ops.ACQF_UCB, ops.ACQF_EI):   # (before anything is launched; the kernel refuses the same codes)
             raise ValueError("the joint acquisition function takes ops.ACQF_UCB or ops.ACQF_EI: a joint LogEI is not defined")
-        kw = self.joint_acqf_inputs(X, base_samples)
+        kw = self.joint_acqf_inputs(X, base_samples, X_pending)
         B, q, D = kw.pop("shape")
         if B == 0:
             return dict(value=kw["Xq"].new_empty((0,)), grad=kw["Xq"].new_empty((0, q, D)) if want_grad else None,
                         jitter=kw["Xq"].new_empty((0,)), info=torch.empty(0, dtype=torch.int32, device=self.device))
-        out = ops.target_qacqf(acqf=acqf, acqf_param=acqf_param, want_grad=want_grad, **kw)
+        kernel = ops.target_qacqf_pending if "Xp" in kw else ops.target_qacqf
+        out = kernel(acqf=acqf, acqf_param=acqf_param, want_grad=want_grad, **kw)
         out["grad"] = out["grad"].reshape(B, q, D) if want_grad else None
         return out
 
-    def joint_acqf_inputs(self, X: torch.Tensor, base_samples: torch.Tensor) -> dict:
-        """Everything of ``joint_acqf`` in front of the acquisition kernel, for X (B, q, D): the keyword arguments of
-        ``ops.target_qacqf`` by name (Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples,
-        kind) and ``shape`` = (B, q, D).  They do not depend on the acquisition code or its parameter."""
+    def _joint_refusals(self) -> None:
         if self.num_fantasies is not None:
             raise NotImplementedError("the joint acquisition function is not defined on a fantasy model")
         if self._shard is not None:
             raise NotImplementedError("the joint acquisition function takes an unsharded source stack")
         if not self.supports_posterior_grad():
             raise NotImplementedError(f"the joint acquisition function needs {studies.LIMITS}")
+
+    def joint_pending(self, X_pending: torch.Tensor) -> dict:
+        """What ``joint_acqf(..., X_pending=)`` needs of a pending set X_pending (p, D) and what does not depend on the batches: the
+        leading points of the source pass with the pending ones behind the training inputs (Xa (n + p, D), VA (T, N, n + p)), Zp (n, p) =
+        Knn^-1 Knp, and the target posterior of the pending points among themselves in original units without observation noise
+        (mu_p (p,), Sigma_pp (p, p)).  Computed for the model's current weights and hyper-parameters: an acquisition-function object
+        calls this once and passes the dict with every evaluation."""
+        self._joint_refusals()
+        st, f = self._stack, self._stack.fit
+        Xp = torch.as_tensor(X_pending, dtype=torch.float64).to(self.device).reshape(-1, st.D).contiguous()
+        if Xp.shape[0] == 0:
+            return dict(Xp=Xp)
+        n, p = self.n, int(Xp.shape[0])
+        if p >= ops.qacqf_max_q():
+            raise NotImplementedError(f"the joint acquisition kernel takes q + p <= {ops.qacqf_max_q()} points: {p} pending leave no room for a batch")
+        if n + p + 1 > studies.MAX_N or n + p + 1 > st.N:
+            raise NotImplementedError(f"the joint acquisition function needs n + p + q <= {min(studies.MAX_N, st.N)}")
+        Vp = ops.source_posteriors(Xp, st.X, st.theta, st.kind, f["L"], f["Linv_diag"], f["alpha"], st.y_mean, st.y_std, n_points=st.n_points,
+                                   want_var=False, keep_V=True, Linv=f["Linv"])["V"]
+        mvn = self.posterior(Xp).mvn
+        xall = torch.cat([self.train_X, Xp], 0)
+        mean_s, cov_s, var_s = self._source_prior(xall, n, train_first=True)
+        factor = self._target_factor()
+        if factor is not None and "alpha_f" not in factor:
+            factor = dict(factor, alpha_f=factor["alpha"][0].unsqueeze(-1))
+        blk = ops.target_fantasy_block(cov_s, mean_s, var_s, xall, self.theta, self.train_targets.unsqueeze(0), self._m_all_f, self._s_all_f,
+                                       self.kind, factor=factor)
+        return dict(Xp=Xp, Xa=xall, VA=torch.cat([self._train_VA(), Vp], -1).contiguous(), Zp=blk["Z"].contiguous(),
+                    mu_p=mvn.mean.contiguous(), Sigma_pp=mvn.covariance_matrix.contiguous())
+
+    def joint_acqf_inputs(self, X: torch.Tensor, base_samples: torch.Tensor, X_pending=None) -> dict:
+        """Everything of ``joint_acqf`` in front of the acquisition kernel, for X (B, q, D): the keyword arguments of
+        ``ops.target_qacqf`` by name (Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples,
+        kind) and ``shape`` = (B, q, D).  They do not depend on the acquisition code or its parameter.  With p > 0 pending points
+        (``X_pending``: (p, D) or ``joint_pending``'s dict): the keyword arguments of ``ops.target_qacqf_pending`` -- the same names,
+        cov_g with n + p + q rows, base_samples (S, q + p), and Xp, Zp, mu_p, Sigma_pp."""
+        self._joint_refusals()
         st, f = self._stack, self._stack.fit
         X = torch.as_tensor(X, dtype=torch.float64).to(self.device)
         if X.dim() != 3 or X.shape[-1] != st.D:
             raise ValueError("joint_acqf takes X (B, q, D)")
         B, q, D = X.shape
         n = self.n
+        pend = None
+        if X_pending is not None:
+            pend = X_pending if isinstance(X_pending, dict) else self.joint_pending(X_pending)
+            if pend["Xp"].shape[0] == 0:
+                pend = None
+        p = 0 if pend is None else int(pend["Xp"].shape[0])
         base_samples = torch.as_tensor(base_samples, dtype=torch.float64).to(self.device)
-        if base_samples.dim() != 2 or base_samples.shape[1] != q or base_samples.shape[0] < 1:
-            raise ValueError("base_samples must be (S, q)")
+        if base_samples.dim() != 2 or base_samples.shape[1] != q + p or base_samples.shape[0] < 1:
+            raise ValueError("base_samples must be (S, q)" if p == 0 else "base_samples must be (S, q + p)")
         if q > ops.qacqf_max_q() or base_samples.shape[0] > ops.qacqf_max_samples():
             raise NotImplementedError(f"the joint acquisition kernel takes q <= {ops.qacqf_max_q()} and at most {ops.qacqf_max_samples()} samples")
         if n + q > studies.MAX_N or n + q > st.N:
             raise NotImplementedError(f"the joint acquisition function needs n + q <= {min(studies.MAX_N, st.N)}")
+        if p > 0 and q + p > ops.qacqf_max_q():
+            raise NotImplementedError(f"the joint acquisition kernel takes q + p <= {ops.qacqf_max_q()} points, got q = {q} and {p} pending")
+        if p > 0 and (n + p + q > studies.MAX_N or n + p + q > st.N):
+            raise NotImplementedError(f"the joint acquisition function needs n + p + q <= {min(studies.MAX_N, st.N)}")
         Xq = X.reshape(B * q, D).contiguous()
         if B == 0:
             return dict(Xq=Xq, shape=(B, q, D))
@@ -1053,7 +1106,9 @@ class ScaMLGP:
         mu_t, cov_tt, var_t = self._train_prior()
         VQ = ops.source_posteriors(Xq, st.X, st.theta, st.kind, f["L"], f["Linv_diag"], f["alpha"], st.y_mean, st.y_std, n_points=st.n_points,
                                    want_var=False, keep_V=True, Linv=f["Linv"])["V"]
-        g = ops.source_posteriors_grad_joint(Xq, q, self.train_X, st.X, st.theta, st.kind, f["Linv"], f["alpha"], self._train_VA(), VQ,
+        # (pending points are leading points: rows n .. n + p - 1 of every strip's covariance block, in front of the mates' rows)
+        Xa, VA = (self.train_X, self._train_VA()) if pend is None else (pend["Xa"], pend["VA"])
+        g = ops.source_posteriors_grad_joint(Xq, q, Xa, st.X, st.theta, st.kind, f["Linv"], f["alpha"], VA, VQ,
                                              st.y_mean, st.y_std, st.n_points)
         mu_g, cov_g = ops.weighted_prior_reduce(g["mu"].reshape(st.T, Mq * 16), g["cov"], w_full, active)
         var_g = ops.weighted_task_sum(g["var"].reshape(st.T, Mq * 16), w_full, 2, active)
@@ -1070,9 +1125,12 @@ class ScaMLGP:
         blk = ops.target_fantasy_block(cov_s, mean_s, var_s, xall, theta, self.train_targets.unsqueeze(0), self._m_all_f, self._s_all_f,
                                        self.kind, factor=factor)
         self._keep_target_factor(blk["factor"])
-        return dict(Knq=blk["Knq"], Z=blk["Z"], alpha=blk["factor"]["alpha"][0], mean_q=blk["mean_q"], var_q=blk["var_q"], m_all=self._m_all_f,
-                    s_all=self._s_all_f, info=blk["info"], cov_g=cov_g, mu_g=mu_g, var_g=var_g, Xt=self.train_X, Xq=Xq, theta=theta,
-                    base_samples=base_samples, kind=self.kind, shape=(B, q, D))
+        kw = dict(Knq=blk["Knq"], Z=blk["Z"], alpha=blk["factor"]["alpha"][0], mean_q=blk["mean_q"], var_q=blk["var_q"], m_all=self._m_all_f,
+                  s_all=self._s_all_f, info=blk["info"], cov_g=cov_g, mu_g=mu_g, var_g=var_g, Xt=self.train_X, Xq=Xq, theta=theta,
+                  base_samples=base_samples, kind=self.kind, shape=(B, q, D))
+        if pend is not None:
+            kw.update(Xp=pend["Xp"], Zp=pend["Zp"], mu_p=pend["mu_p"], Sigma_pp=pend["Sigma_pp"])
+        return kw
 
     def fantasy_acqf(self, X: torch.Tensor, acqf: int, acqf_param: float, want_grad: bool = False):
         """The acquisition function of a fantasy model, averaged over its fantasies, at X (M, D): (value (M,), d value / d X (M, D) or

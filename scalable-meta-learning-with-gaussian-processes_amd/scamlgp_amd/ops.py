@@ -762,6 +762,62 @@ def target_qacqf(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor, mean_q
     return dict(value=value, grad=grad, jitter=jitter, info=info_out)
 
 
+def target_qacqf_pending(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor, mean_q: torch.Tensor, var_q: torch.Tensor, m_all: float,
+                         s_all: float, info: Optional[torch.Tensor], cov_g: torch.Tensor, mu_g: torch.Tensor, var_g: torch.Tensor,
+                         Xt: torch.Tensor, Xq: torch.Tensor, theta: torch.Tensor, base_samples: torch.Tensor, Xp: torch.Tensor,
+                         Zp: Optional[torch.Tensor], mu_p: Optional[torch.Tensor], Sigma_pp: Optional[torch.Tensor], acqf: int,
+                         acqf_param: float, kind: int = KIND_RBF, want_grad: bool = True) -> Dict[str, torch.Tensor]:
+    """``target_qacqf`` with p = Xp.shape[0] evaluations pending: every batch is its q moving points followed by the same p pending
+    points Xp (p, D), the utility's maximum runs over all q + p joint samples (base_samples (S, q + p)) and only the moving points
+    get a gradient: one launch of scaml_target_qacqf_pending_f64 (7q).  cov_g (n + p + q, Mq * 16): the weighted sums of
+    ``source_posteriors_grad_joint`` called with the pending points behind the training inputs (Ma = n + p).  Zp (n, p) = Knn^-1 Knp;
+    mu_p (p,), Sigma_pp (p, p): the target posterior of the pending points among themselves, original units, no observation noise.
+    p = 0 (Zp, mu_p, Sigma_pp may be None): ``target_qacqf``'s outputs to the bit.
+    Returns dict(value (B,), grad (Mq, D) or None, jitter (B,), info (B,) int32)."""
+    n, Mq = Knq.shape
+    D = int(Xq.shape[1])
+    p = int(Xp.shape[0])
+    S, Q = base_samples.shape
+    q = Q - p
+    if q < 1 or Mq % q:
+        raise ValueError("Mq must be a multiple of q = base_samples.shape[1] - Xp.shape[0] >= 1")
+    B = Mq // q
+    Knq = _check(Knq, "Knq", (n, Mq))
+    Z = _check(Z, "Z", (n, Mq))
+    alpha = _check(alpha, "alpha", (n,))
+    mean_q = _check(mean_q, "mean_q", (Mq,))
+    var_q = _check(var_q, "var_q", (Mq,))
+    cov_g = _check(cov_g.reshape(n + p + q, -1), "cov_g", (n + p + q, Mq * 16))
+    mu_g = _check(mu_g.reshape(-1), "mu_g", (Mq * 16,))
+    var_g = _check(var_g.reshape(-1), "var_g", (Mq * 16,))
+    Xt = _check(Xt, "Xt", (n, D))
+    Xq = _check(Xq, "Xq", (Mq, D))
+    theta = _check(theta, "theta", (D + 2,))
+    base_samples = _check(base_samples, "base_samples", (S, Q))
+    Xp = _check(Xp, "Xp", (p, D))
+    if p > 0:
+        Zp = _check(Zp, "Zp", (n, p))
+        mu_p = _check(mu_p, "mu_p", (p,))
+        Sigma_pp = _check(Sigma_pp, "Sigma_pp", (p, p))
+    else:
+        Xp = Zp = mu_p = Sigma_pp = None
+    if info is not None:
+        info = _check(info.reshape(-1)[:1], "info", (1,), torch.int32)
+    dev = Knq.device
+    with torch.cuda.device(dev):
+        value = _empty(dev, B)
+        grad = _empty(dev, Mq, D) if want_grad else None
+        jitter = _empty(dev, B)
+        info_out = _empty(dev, B, dtype=torch.int32)
+        rc = _lib.lib.scaml_target_qacqf_pending_f64(_ptr(Knq), _ptr(Z), _ptr(alpha), _ptr(mean_q), _ptr(var_q), float(m_all), float(s_all),
+                                                     _ptr(info), _ptr(cov_g), _ptr(mu_g), _ptr(var_g), _ptr(Xt), _ptr(Xq), _ptr(theta),
+                                                     _ptr(base_samples), _ptr(Xp), _ptr(Zp), _ptr(mu_p), _ptr(Sigma_pp), int(acqf),
+                                                     float(acqf_param), n, Mq, q, p, S, D, int(kind), _ptr(value), _ptr(grad), _ptr(jitter),
+                                                     _ptr(info_out), _stream_handle())
+    _lib.check_rc(rc, "scaml_target_qacqf_pending_f64")
+    return dict(value=value, grad=grad, jitter=jitter, info=info_out)
+
+
 def _source_pass_grouped(value: bool, Xq, group, Xa, n_points_a, VA_tab, X, theta, kind, Linv, alpha, y_mean, y_std, n_points, task_base,
                          tasks_per_group, cov_out) -> Dict[str, torch.Tensor]:
     """The grouped source pass behind ``source_posteriors_grad_grouped`` (``value`` False: 16 columns per query point, ``group`` per query

@@ -468,15 +468,25 @@ class _JointAcquisition:
     qExpectedImprovement / qUpperConfidenceBound under optimize_acqf(q = ...)), evaluated by ``ScaMLGP.joint_acqf``.  The base samples
     are drawn ONCE at construction with ``torch.randn`` from ``generator`` -- (num_samples, 8), of which a batch of q points reads the
     leading q columns -- and stay fixed: the function is deterministic, as L-BFGS-B needs it.  ``q`` is fixed by the ``q`` argument
-    or by the first batch."""
+    or by the first batch.
 
-    def __init__(self, model: ScaMLGP, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None):
+    ``X_pending`` (p, D): evaluations that are running (botorch's X_pending).  They are appended to every batch and held fixed: the
+    utility's maximum runs over the q + p joint samples, a batch reads the leading q + p columns of the draws, and the gradient is the
+    q moving points'.  What depends on the pending set alone (``ScaMLGP.joint_pending``) is computed here, once, for the model's
+    parameters as they are now."""
+
+    def __init__(self, model: ScaMLGP, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None,
+                 X_pending: Optional[torch.Tensor] = None):
         if model.num_fantasies is not None:
             raise NotImplementedError("the joint acquisition functions are not defined on a fantasy model")
         if not 1 <= num_samples <= ops.qacqf_max_samples():
             raise ValueError(f"num_samples must be within 1 .. {ops.qacqf_max_samples()}")
         self.model, self.num_samples = model, int(num_samples)
-        # (num_samples, max q) draws, once; a batch of q points reads the leading q columns
+        self.p, self._pending = 0, None
+        if X_pending is not None and torch.as_tensor(X_pending).numel() > 0:
+            self._pending = model.joint_pending(X_pending)
+            self.p = int(self._pending["Xp"].shape[0])
+        # (num_samples, max q) draws, once; a batch of q points reads the leading q (+ p) columns
         self._eps = torch.randn(self.num_samples, ops.qacqf_max_q(), dtype=torch.float64, generator=generator).to(model.device)
         self.q, self.base_samples = None, None
         if q is not None:
@@ -485,7 +495,9 @@ class _JointAcquisition:
     def _draw(self, q: int) -> None:
         if not 1 <= q <= ops.qacqf_max_q():
             raise ValueError(f"q must be within 1 .. {ops.qacqf_max_q()}")
-        self.q, self.base_samples = q, self._eps[:, :q].contiguous()
+        if q + self.p > ops.qacqf_max_q():
+            raise NotImplementedError(f"the joint acquisition kernel takes q + p <= {ops.qacqf_max_q()} points, got q = {q} and {self.p} pending")
+        self.q, self.base_samples = q, self._eps[:, :q + self.p].contiguous()
 
     def _batches(self, X: torch.Tensor) -> torch.Tensor:
         X = torch.as_tensor(X, dtype=torch.float64)
@@ -503,12 +515,13 @@ class _JointAcquisition:
         X = self._batches(X)
         # (in chunks of at most 256 points: the pass keeps 16 columns per point and covariance row, for every task)
         step = max(1, 256 // self.q)
-        vals = [self.model.joint_acqf(X[i:i + step], self.code, self.param, self.base_samples)[0] for i in range(0, X.shape[0], step)]
+        vals = [self.model.joint_acqf(X[i:i + step], self.code, self.param, self.base_samples, X_pending=self._pending)[0]
+                for i in range(0, X.shape[0], step)]
         return torch.cat(vals) if vals else X.new_empty((0,))
 
     def value_and_grad(self, X: torch.Tensor):
         """(value (B,), d value / d X (B, q, D)), the exact gradient of the Monte-Carlo estimate at the fixed base samples."""
-        return self.model.joint_acqf(self._batches(X), self.code, self.param, self.base_samples, want_grad=True)
+        return self.model.joint_acqf(self._batches(X), self.code, self.param, self.base_samples, want_grad=True, X_pending=self._pending)
 
 
 class qExpectedImprovement(_JointAcquisition):
@@ -517,8 +530,9 @@ class qExpectedImprovement(_JointAcquisition):
     code = ops.ACQF_EI
     param = property(lambda self: self.best_f)
 
-    def __init__(self, model: ScaMLGP, best_f: float, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None):
-        super().__init__(model, num_samples, generator, q)
+    def __init__(self, model: ScaMLGP, best_f: float, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None,
+                 X_pending: Optional[torch.Tensor] = None):
+        super().__init__(model, num_samples, generator, q, X_pending)
         self.best_f = float(best_f)
 
 
@@ -528,8 +542,9 @@ class qUpperConfidenceBound(_JointAcquisition):
     code = ops.ACQF_UCB
     param = property(lambda self: self.beta)
 
-    def __init__(self, model: ScaMLGP, beta: float = 9.0, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None):
-        super().__init__(model, num_samples, generator, q)
+    def __init__(self, model: ScaMLGP, beta: float = 9.0, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None,
+                 X_pending: Optional[torch.Tensor] = None):
+        super().__init__(model, num_samples, generator, q, X_pending)
         self.beta = float(beta)
 
 

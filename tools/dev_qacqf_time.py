@@ -9,6 +9,14 @@ In one process, the sides of each comparison interleaved, median of 5 with min .
 Host clock around work that ends in a device synchronise.
 
   python tools/dev_qacqf_time.py [--out FILE] [--no-suggest]
+
+With ``--pending P`` (and ``--q Q``): the same shapes with P evaluations pending, in place of the three comparisons above
+  4. one evaluation (value + gradient of the Q moving points) through the pending route -- the pending points as leading points of the
+     source pass, scaml_target_qacqf_pending_f64 (7q) -- against the same model's concatenated route joint_acqf(cat(X, X_pending)) at
+     q' = Q + P, and the parts of the pending route;
+  5. suggest_batch(2) with 4 evaluations pending (joint_pending="joint") against two successive suggest() calls with 16 fantasies.
+
+  python tools/dev_qacqf_time.py --pending P [--q Q] [--out FILE] [--no-suggest]
 """
 import argparse
 import os
@@ -29,9 +37,11 @@ from scamlgp_amd.bo import ScaMLGPBOLoop  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
 ap.add_argument("--no-suggest", action="store_true", help="skip the suggest_batch / suggest comparison")
+ap.add_argument("--pending", type=int, default=0, help="P evaluations pending: time the pending route against the concatenated one")
+ap.add_argument("--q", type=int, default=4, help="points per batch")
 args = ap.parse_args()
 
-T, N, D, n, q, B, S, REPS = 32, 512, 6, 80, 4, 10, 128, 5
+T, N, D, n, q, B, S, REPS = 32, 512, 6, 80, args.q, 10, 128, 5
 dev = torch.device("cuda:0")
 lines = []
 
@@ -129,6 +139,74 @@ def acqf_kernel():
                                    model.kind, True)
 
 
+def pending_comparison(P):
+    """4. and 5. of the module's text."""
+    Xp = torch.rand(P, D, dtype=torch.float64, generator=g).to(dev)
+    eps_p = torch.randn(S, q + P, dtype=torch.float64, generator=g).to(dev)
+    Xcat = torch.cat([X, Xp.expand(B, P, D)], 1).contiguous()
+    pend = model.joint_pending(Xp)   # (once per pending set, as the acquisition classes do)
+    say(f"-- {P} evaluations pending: B q = {Mq} strips through the passes against B (q + p) = {B * (q + P)}")
+
+    def joint_pass_p():
+        held["g"] = ops.source_posteriors_grad_joint(Xq, q, pend["Xa"], *src, f["Linv"], f["alpha"], pend["VA"], held["VQ"], stack.y_mean,
+                                                     stack.y_std, stack.n_points)
+
+    def acqf_kernel_p():
+        b = held["blk"]
+        held["out"] = ops.target_qacqf_pending(b["Knq"], b["Z"], b["factor"]["alpha"][0], b["mean_q"], b["var_q"], model._m_all_f, model._s_all_f,
+                                               b["info"], held["cov_g"], held["mu_g"], held["var_g"], model.train_X, Xq, model.theta, eps_p,
+                                               pend["Xp"], pend["Zp"], pend["mu_p"], pend["Sigma_pp"], ops.ACQF_EI, best_f, model.kind, True)
+
+    for fn in (value_pass, joint_pass_p, reductions, value_path, acqf_kernel_p):
+        fn()
+    report(interleaved({
+        f"pending route: joint_acqf(X, X_pending), {Mq} strips": lambda: model.joint_acqf(X, ops.ACQF_EI, best_f, eps_p, want_grad=True, X_pending=pend),
+        f"concatenated route: joint_acqf(cat), {B * (q + P)} strips": lambda: model.joint_acqf(Xcat, ops.ACQF_EI, best_f, eps_p, want_grad=True),
+        "  value pass, V kept (5c)": value_pass,
+        "  joint GRAD pass (5g), Ma = n + p": joint_pass_p,
+        "  weighted reductions (6')": reductions,
+        "  value path: assemble, cached factor, solve": value_path,
+        "  acquisition kernel (7q)": acqf_kernel_p,
+        "  (once per pending set: joint_pending)": lambda: model.joint_pending(Xp),
+    }))
+    if args.no_suggest:
+        return
+
+    def loop():
+        lp = ScaMLGPBOLoop(gps, dim=D, acquisition="ei", num_restarts_log_likelihood=1, seed=0, max_pending_evaluations=6, num_fantasies=16,
+                           num_mc_samples=S, joint_pending="joint")
+        lp.record(Xt, yt.squeeze(-1))
+        lp.model.weights = model.weights.clone()
+        return lp
+
+    lp_a, lp_b = loop(), loop()
+    Xp4 = torch.rand(4, D, dtype=torch.float64, generator=g)
+
+    def batch():
+        lp_a.pending = Xp4.clone()
+        lp_a.suggest_batch(2)
+
+    def successive():
+        lp_b.pending = Xp4.clone()
+        for _ in range(2):
+            lp_b.suggest()
+
+    say("-- 2 points with 4 evaluations pending: suggest_batch(2), joint_pending='joint', against 2 successive suggest() calls (16 fantasies)")
+    report(interleaved({"suggest_batch(2), 4 pending": batch, "2 x suggest(), 4 pending": successive}, warmup=1), unit=1e3, name="ms")
+
+
+def finish():
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if args.pending:
+    pending_comparison(args.pending)
+    finish()
+    sys.exit(0)
+
 for fn in (value_pass, joint_pass, reductions, value_path, acqf_kernel):
     fn()
 say("-- one joint evaluation (value + gradient)")
@@ -179,7 +257,4 @@ if not args.no_suggest:
     say(f"-- {q} points: suggest_batch({q}) against {q} successive suggest() calls (max_pending_evaluations={q}, 16 fantasies)")
     report(interleaved({f"suggest_batch({q})": batch, f"{q} x suggest()": successive}, warmup=1), unit=1e3, name="ms")
 
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
+finish()
