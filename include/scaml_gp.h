@@ -413,7 +413,51 @@ int scaml_target_qacqf_pending_f64(const double* Knq, const double* Z, const dou
                                    double* jitter_used, int32_t* info_out, void* stream);
 
 /*
- * (7o) The acquisition function of M given posteriors, elementwise: A[i] and its partial derivatives Amu[i] = dA / dmu, Av[i] = dA / dv
+ * (5h), (7r) The joint acquisition VALUE ONLY: what the scoring stage of a batch optimiser needs of its raw candidates -- no
+ * derivative column is computed or stored anywhere.  scamlgp_amd.ScaMLGP.joint_acqf_value, utils.qExpectedImprovement /
+ * qUpperConfidenceBound(score_mode="value_pass"), ScaMLGPBOLoop(joint_score_mode="value_pass").
+ * Column packing (csrc/gp_qacqf_columns.h): the B batches of q points are laid into strips of 16 columns, whole batches only --
+ *   bps = 16 / q batches per strip (integer division), point j of batch b in column 16 (b / bps) + (b % bps) q + j,
+ *   Mp = scaml_qacqf_value_columns(B, q) = 16 ceil(B / bps) columns (-1 for q outside 1 .. 8 or B < 0).  Dense for q in {1, 2, 4, 8};
+ *   q = 3, 5, 6, 7 leave 1, 1, 4, 2 padding columns per strip, and the last strip is padded behind batch B - 1.
+ * scaml_posterior_linv_cov_joint_f64 (5h): (5c') -- the value pass with its fused covariance block against Ma leading points Xa
+ *   (Ma, D) / VA (T, N, Ma) -- at the PACKED query points Xq (Mp, D), with q more covariance rows: cov (T, Ma + q, Mp).  Rows a < Ma
+ *   are (5c')'s.  Row Ma + r of column c is s_t^2 (os k(x_c, x_mate) - G[mate][c]) with the mate = point r of c's batch and
+ *   G = V^T V the Gram tile of the strip's V with itself, formed on the matrix cores from the V block in its accumulator (V never
+ *   reaches memory); the row of the point itself (r = c's index in its batch) is its variance.  Rows Ma + r of a padding column are
+ *   zeros.  Padding columns of Xq must hold finite coordinates (their mu / var / leading rows are computed like any point's).
+ *   mu, var (T, Mp) or NULL.  Pending evaluations are leading points exactly as in (7q): Xa = cat(Xt, Xp), Ma = n + p.
+ *   Non-finite values: a query point with a NaN / infinite coordinate gives NaN in its own mu, var and column of cov, as in (5c);
+ *   the other columns -- those of its strip included -- are not affected (mate rows that involve it need not show the NaN: (7r)
+ *   tests the batch's coordinates itself).
+ *   T < 0, N < 1, Mp < 0, Ma < 1, B < 0, q < 1, D < 1, a NULL Xq / Xa / X / theta / Linv / alpha / VA / cov, an unknown kind,
+ *   SCAML_POST_MEAN_ONLY, or (q <= 8) Mp != scaml_qacqf_value_columns(B, q): SCAML_E_BADARG (first).  q > 8, Ma + q > 96, Ma + q > N,
+ *   N > scaml_posterior_max_n(): SCAML_E_TOOLARGE.  Everything is checked before the first HIP call.  B == 0 enqueues nothing.
+ * scaml_target_qacqf_value_f64 (7r): (7p) / (7q) without the gradient, for p >= 0 pending points, from the value layout: Knq, Z
+ *   (n, Mp), mean_q, var_q (Mp) and Xq (Mp, D) are read at the batch's columns, and cov_s (n + p + q, Mp) -- the weighted sums (6')
+ *   of (5h) -- replaces cov_g:  P_jk = cov_s[n + p + k][col(b, j)] / s^2 + os_t k_t(x_j, x_k), the mixed block of a pending point k
+ *   from cov_s[n + k][col(b, j)].  mu, Sigma, the ladder, f = mu + C eps, qEI / qUCB and the lowest-index arg-max are (7p)'s / (7q)'s:
+ *   given the same numbers in both layouts value, jitter_used and info_out are those kernels' bit for bit (same sums, same order),
+ *   and two calls agree bit for bit.  base_samples (S, q + p).  Outputs: value (B), jitter_used (B) or NULL, info_out (B) or NULL.
+ *   Non-finite values as (7p) / (7q): a NaN / infinite coordinate of a batch's point or a NaN in its inputs turns that batch NaN;
+ *   a NaN anywhere in Xp, Zp, mu_p or Sigma_pp turns every batch NaN; info[0] != 0 turns everything NaN (info_out 1).
+ *   Limits and refusals are (7q)'s: q + p <= 8, n + p + q <= 96, S <= 512, D <= 15 (SCAML_E_TOOLARGE); its bad arguments, every
+ *   acquisition code but SCAML_ACQF_EI / SCAML_ACQF_UCB, B < 0 or Mp != scaml_qacqf_value_columns(B, q): SCAML_E_BADARG (first).
+ *   One workgroup of 256 threads per batch.  B == 0 enqueues nothing.  No host synchronisation.
+ */
+int scaml_qacqf_value_columns(int B, int q);
+int scaml_posterior_linv_cov_joint_f64(const double* Xq, const double* Xa, const double* X, const double* theta, const double* Linv,
+                                       const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points,
+                                       const double* VA, int T, int N, int Mp, int Ma, int B, int q, int D, int kind, double* mu, double* var,
+                                       double* cov, unsigned flags, void* stream);
+int scaml_target_qacqf_value_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q,
+                                 double m_all, double s_all, const int32_t* info, const double* cov_s, const double* Xq, const double* theta,
+                                 const double* base_samples, const double* Xp, const double* Zp, const double* mu_p, const double* Sigma_pp,
+                                 int acqf, double acqf_param, int n, int Mp, int B, int q, int p, int S, int D, int kind, double* value,
+                                 double* jitter_used, int32_t* info_out, void* stream);
+
+/*
+ * (7o)The acquisition function of M given posteriors, elementwise: A[i] and its partial derivatives Amu[i] = dA / dmu, Av[i] = dA / dv
  * at (mu[i], var[i]) (original units), i = 0 .. M-1, one thread per element -- the statement (7f), (7g), (7i) and (7k) evaluate
  * (sa_acquisition of csrc/gp_studies_formulas.h), with their clamps.  acqf: SCAML_ACQF_UCB (acqf_param = beta), SCAML_ACQF_EI or
  * SCAML_ACQF_EI | SCAML_ACQF_LOG (acqf_param = best_f); anything else is SCAML_E_BADARG.  Amu and Av may be NULL.  The input gradient

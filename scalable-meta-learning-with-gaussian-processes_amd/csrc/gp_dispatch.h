@@ -210,5 +210,18 @@ constexpr QAcqfPlan qacqf_plan(int B, int n, int q, int S) { return {(unsigned)B
 constexpr QAcqfPlan qacqf_pending_plan(int B, int n, int q, int p, int S) {
   return {(unsigned)B, (unsigned)QACQF_THREADS, qa_pending_lds_doubles(n, q, p, S)};
 }
+// ... value only (7r), p >= 0: still a workgroup per batch
+constexpr QAcqfPlan qacqf_value_plan(int B, int n, int q, int p, int S) {
+  return {(unsigned)B, (unsigned)QACQF_THREADS, qa_value_lds_doubles(n, q, p, S)};
+}
+
+// ---- the value-layout joint source pass (5h): a workgroup per (task, strip of 16 packed columns), XCD-aware map inside the kernel ----
+struct PosteriorJointValuePlan {
+  unsigned grid, block;
+  size_t lds_doubles;
+};
+constexpr PosteriorJointValuePlan posterior_jointv_plan(int T, int N, int D, int Mp) {
+  return {(unsigned)(((T + 7) / 8) * 8) * (unsigned)(Mp / 16), 512u, posterior_linv_jointv_lds_doubles(N, D)};
+}
 
 }  // namespace scaml

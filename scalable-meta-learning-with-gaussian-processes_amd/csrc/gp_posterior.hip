@@ -19,6 +19,7 @@
 #include "scaml_common.hpp"
 #include "../../include/scaml_gp.h"
 #include "gp_posterior_params.h"
+#include "gp_qacqf_columns.h"
 
 namespace scaml {
 
@@ -146,26 +147,37 @@ __global__ __launch_bounds__(256) void gp_posterior_kernel(PosteriorParams p) {
 // for the Ma leading points x_a (p.Xa: the target's training inputs) -- everything botorch's optimize_acqf differentiates through
 // model.posterior for (HOT LOOP #4; scamlgp/utils.py:215-224).  Outputs are (T, Mq, 16) / (T, Ma, Mq * 16): M = 16 Mq.
 // The argument block of gp_posterior_linv_kernel: PosteriorParams, or PosteriorGroupedParams (the same block first, then the groups)
-template <bool GROUPED, bool JOINT = false>
+template <bool GROUPED, bool JOINT = false, bool JOINTV = false>
 struct PosteriorArgs {
   using type = PosteriorParams;
   static __device__ __forceinline__ const PosteriorParams& base(const type& a) { return a; }
   static __device__ __forceinline__ PosteriorGroupArgs ga(const type&) { return PosteriorGroupArgs{}; }
   static __device__ __forceinline__ PosteriorJointArgs ja(const type&) { return PosteriorJointArgs{}; }
+  static __device__ __forceinline__ PosteriorJointValueArgs jv(const type&) { return PosteriorJointValueArgs{}; }
 };
 template <>
-struct PosteriorArgs<true, false> {
+struct PosteriorArgs<true, false, false> {
   using type = PosteriorGroupedParams;
   static __device__ __forceinline__ const PosteriorParams& base(const type& a) { return a.base; }
   static __device__ __forceinline__ const PosteriorGroupArgs& ga(const type& a) { return a.ga; }
   static __device__ __forceinline__ PosteriorJointArgs ja(const type&) { return PosteriorJointArgs{}; }
+  static __device__ __forceinline__ PosteriorJointValueArgs jv(const type&) { return PosteriorJointValueArgs{}; }
 };
 template <>
-struct PosteriorArgs<false, true> {
+struct PosteriorArgs<false, true, false> {
   using type = PosteriorJointParams;
   static __device__ __forceinline__ const PosteriorParams& base(const type& a) { return a.base; }
   static __device__ __forceinline__ PosteriorGroupArgs ga(const type&) { return PosteriorGroupArgs{}; }
   static __device__ __forceinline__ const PosteriorJointArgs& ja(const type& a) { return a.ja; }
+  static __device__ __forceinline__ PosteriorJointValueArgs jv(const type&) { return PosteriorJointValueArgs{}; }
+};
+template <>
+struct PosteriorArgs<false, false, true> {
+  using type = PosteriorJointValueParams;
+  static __device__ __forceinline__ const PosteriorParams& base(const type& a) { return a.base; }
+  static __device__ __forceinline__ PosteriorGroupArgs ga(const type&) { return PosteriorGroupArgs{}; }
+  static __device__ __forceinline__ PosteriorJointArgs ja(const type&) { return PosteriorJointArgs{}; }
+  static __device__ __forceinline__ const PosteriorJointValueArgs& jv(const type& a) { return a.jv; }
 };
 
 // GROUPED (the lock-step acquisition of many BO studies, scaml_posterior_linv_grad_grouped_f64): the query points are divided among G
@@ -188,9 +200,17 @@ struct PosteriorArgs<false, true> {
 // whose coordinates are Xq[b q + r].  Column 0 is the covariance, columns 1 + d its derivative with respect to x_j with the mate held
 // fixed; the row of the point itself (r = j mod q) therefore carries var and HALF of var's derivative.  Two sites differ: the operand
 // fetch of the covariance tiles and the coordinates of the epilogue.  An instantiation of its own, like OWN and DET.
-template <int KIND, bool COV, bool GRAD, bool GROUPED = false, bool OWN = false, bool DET = false, bool JOINT = false>
-__global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename PosteriorArgs<GROUPED, JOINT>::type pp) {
-  using Args = PosteriorArgs<GROUPED, JOINT>;
+// JOINTV (scaml_posterior_linv_cov_joint_f64, (5h)): the batches of q in VALUE layout -- a strip holds 16 different query points, whole
+// batches only (csrc/gp_qacqf_columns.h), so a point's batch mates sit in its own strip.  The V block of a row block is at once the A
+// and the B operand of one more tile, the strip's Gram tile G[a][c] = sum_rows V[row][a] V[row][c] (both operands have the lane layout
+// of the accumulator): four more MFMAs per row block, no loads, and V never reaches memory.  Row Ma + r of column c is
+// s^2 (os k(x_c, x_mate) - G[mate][c]) with the mate = point r of c's batch; a padding column gets zeros there.  Column c of V enters
+// row c and column c of G only, so a query point with a NaN coordinate leaves the other batches of its strip alone.  The Gram
+// tile's register image has 256 doubles of its own behind the K_*^T strip.  An instantiation of its own.
+template <int KIND, bool COV, bool GRAD, bool GROUPED = false, bool OWN = false, bool DET = false, bool JOINT = false, bool JOINTV = false>
+__global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename PosteriorArgs<GROUPED, JOINT, JOINTV>::type pp) {
+  using Args = PosteriorArgs<GROUPED, JOINT, JOINTV>;
+  static_assert(!JOINTV || (COV && !GRAD && !GROUPED && !JOINT), "the value-layout batch mates belong to the ungrouped value pass with its covariance block");
   static_assert(!JOINT || (COV && GRAD && !GROUPED), "batch mates belong to the ungrouped GRAD pass with its covariance block");
   static_assert(!GROUPED || COV, "the grouped pass comes with its covariance block");
   static_assert(!DET || (GROUPED && GRAD), "the ordered sums are built for the grouped GRAD pass");
@@ -249,6 +269,7 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
   double* nr = nq + 16;
   double* Ks = nr + NP;
   // End of the carve, Ks + NP * 16: posterior_linv_lds_doubles(N, D) (gp_posterior_params.h) -- change both together.
+  // JOINTV: then the Gram tile's image [256], image number nas of the epilogue (nas <= NB): posterior_linv_jointv_lds_doubles(N, D).
 
   const double* Xg = p.X + (size_t)src * N * D;
   const double* th = p.theta + (size_t)src * (D + 2);
@@ -373,6 +394,8 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
   d4_t cacc[MAXAS];
 #pragma unroll
   for (int as = 0; as < MAXAS; ++as) cacc[as] = d4_t{0.0, 0.0, 0.0, 0.0};
+  [[maybe_unused]] d4_t gacc = {0.0, 0.0, 0.0, 0.0};   // (JOINTV: the strip's Gram tile)
+  const int covrows = JOINT ? Mt : (JOINTV ? Ma + Args::jv(pp).q : p.Ma);   // the row count of cov
   if (!p.mean_only) {
     double var_part = 0.0;
     const bool n_even = (N & 1) == 0;
@@ -425,6 +448,11 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
             for (int m = 0; m < 4; ++m) cacc[as] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[m], vb[m], cacc[as], 0, 0, 0);
           }
         }
+        if constexpr (JOINTV) {
+          // (V^T V)[a][c] of the strip with itself: A[i = lc][k = lq + 4 m] = V[16 kb + lq + 4 m][lc] is the register that is B
+#pragma unroll
+          for (int m = 0; m < 4; ++m) gacc = __builtin_amdgcn_mfma_f64_16x16x4f64(vb[m], vb[m], gacc, 0, 0, 0);
+        }
       }
     }
     var_part = sum_lane_groups(var_part);
@@ -473,6 +501,15 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
             }
           }
         }
+        if constexpr (JOINTV) {
+          d4_t v = gacc;
+          mfma_settle(v);
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            double* dst = cb + nas * 256 + g * 64 + lane;
+            *dst = (w == 0 ? 0.0 : *dst) + v[g];
+          }
+        }
       }
       __syncthreads();
     }
@@ -503,7 +540,28 @@ __global__ __launch_bounds__(512) void gp_posterior_linv_kernel(typename Posteri
         } else {
           kv = os * kernel_from_sqdist<KIND>(d2, exptab);
         }
-        p.cov[((size_t)task * (JOINT ? Mt : p.Ma) + a) * M + qcc] = ys * ys * (kv - cb[e]) + (nq[c] - nq[c]);   // (NaN for a non-finite query, as above)
+        p.cov[((size_t)task * covrows + a) * M + qcc] = ys * ys * (kv - cb[e]) + (nq[c] - nq[c]);   // (NaN for a non-finite query, as above)
+      }
+    }
+    if constexpr (JOINTV) {
+      // the mate rows from the Gram tile's image: element (i, c) is G[i][c]; it is row Ma + r of column c where point i is mate r of
+      // c's batch, nothing otherwise.  A padding column's q mate rows are zeros (written from its first q elements).
+      const int q = Args::jv(pp).q;
+      const double* gb = cb + nas * 256;
+      if (tid < 256) {
+        const int g = tid >> 6, ln = tid & 63, i = (ln >> 4) + 4 * g, c = ln & 15;
+        const size_t col = (size_t)16 * strip + c;
+        if (qav_batch_of(strip, c, q, Args::jv(pp).B) < 0) {
+          if (i < q) p.cov[((size_t)task * covrows + Ma + i) * M + col] = 0.0;
+        } else if (i / q == c / q) {
+          double d2 = 0.0;
+          for (int d = 0; d < D; ++d) {
+            const double df = xqs[d * 16 + i] - xqs[d * 16 + c];
+            d2 = __builtin_fma(df, df, d2);
+          }
+          const double kv = os * kernel_from_sqdist<KIND>(d2, exptab);
+          p.cov[((size_t)task * covrows + Ma + (i - (c / q) * q)) * M + col] = ys * ys * (kv - gb[tid]) + (nq[c] - nq[c]);
+        }
       }
     }
   }
@@ -784,3 +842,5 @@ template __global__ void scaml::gp_posterior_linv_kernel<0, true, false, true, t
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, false, true, true>(scaml::PosteriorGroupedParams);
 template __global__ void scaml::gp_posterior_linv_kernel<0, true, true, false, false, false, true>(scaml::PosteriorJointParams);   // (5g)
 template __global__ void scaml::gp_posterior_linv_kernel<1, true, true, false, false, false, true>(scaml::PosteriorJointParams);
+template __global__ void scaml::gp_posterior_linv_kernel<0, true, false, false, false, false, false, true>(scaml::PosteriorJointValueParams);   // (5h)
+template __global__ void scaml::gp_posterior_linv_kernel<1, true, false, false, false, false, false, true>(scaml::PosteriorJointValueParams);

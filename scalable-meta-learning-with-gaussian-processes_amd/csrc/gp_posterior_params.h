@@ -73,6 +73,18 @@ struct PosteriorJointParams {
   PosteriorJointArgs ja;
 };
 
+// The joint pass in VALUE layout (scaml_posterior_linv_cov_joint_f64, (5h)): a strip holds 16 different query points, the B batches of q
+// packed as csrc/gp_qacqf_columns.h lays them (M = Mp columns); the covariance block gets q more rows, against the column's batch
+// mates, from the Gram tile of the strip's V with itself.  In `base`: Ma = the leading points alone, cov has Ma + q rows.
+struct PosteriorJointValueArgs {
+  int q;   // points per batch
+  int B;   // batches: the columns behind the last one are padding
+};
+struct PosteriorJointValueParams {
+  PosteriorParams base;
+  PosteriorJointValueArgs jv;
+};
+
 struct PosteriorCovParams {
   const double* Xq;     // (M, D)
   const double* theta;  // (T, D+2)
@@ -161,6 +173,9 @@ constexpr size_t posterior_linv_lds_doubles(int N, int D) {
   const size_t d4 = (size_t)((D + 3) & ~3);   // query points, 1 / lengthscale zero-padded to the MFMA k-step
   return 64 + np + d4 + 16 * d4 + 32 + 16 + np + np * 16;
 }
+// ... its JOINTV instantiation (5h): the same carve, then the [256] register image of the strip's Gram tile -- the epilogue lays the
+// ceil(Ma / 16) images of the leading tiles into the K_*^T strip, and with Ma > 16 (np / 16 - 1) one more does not fit there
+constexpr size_t posterior_linv_jointv_lds_doubles(int N, int D) { return posterior_linv_lds_doubles(N, D) + 256; }
 
 // gp_linv_kernel, gp_cho_solve_kernel: one [np][16] strip per wave
 constexpr size_t strip_solve_lds_doubles(int np, int waves) { return (size_t)waves * np * 16; }

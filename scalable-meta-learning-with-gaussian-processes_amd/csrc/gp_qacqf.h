@@ -27,8 +27,15 @@
 // and the pending block of Sigma and mu is given (Sigma_pp, mu_p: they do not depend on the batch).  The tail runs at Q; a pending point
 // is held fixed, so the gradient of moving point j gains 2 sum_k Sbar_{j,q+k} dP_{j,q+k}/dx_j and its weight vector on dKnq[:, j] the
 // term -2 sum_k Sbar_{j,q+k} Zp[:, k].  The pending rows of mbar and Sbar are not read.
+//
+// Value only ((7r), qa_batch<true, true>): the same joint posterior, ladder, samples and sums -- value, jitter and info are (7p)'s /
+// (7q)'s bit for bit given the same numbers -- read from the VALUE layout of (5h): the B batches packed into Mp columns
+// (csrc/gp_qacqf_columns.h; the points of a batch are consecutive columns), Knq, Z (n, Mp), mean_q, var_q (Mp), Xq (Mp, D), and
+// cov_s (n + p + q, Mp) in the place of cov_g, one column per point: P_jk = cov_s[n + p + k][col(b, j)] / s^2 + os k_t(x_j, x_k).
+// Nothing of the gradient is formed or read (mu_g, var_g, Xt and grad are NULL), and U / SL leave the LDS.
 #pragma once
 #include "gp_studies_formulas.h"   // SA_DEV / SA_SYNC, sa_kernel_and_slope, the acquisition codes
+#include "gp_qacqf_columns.h"
 
 namespace scaml {
 
@@ -92,6 +99,8 @@ constexpr size_t qa_lds_doubles(int n, int q, int S) { return qa_tail_lds_double
 constexpr size_t qa_pending_lds_doubles(int n, int q, int p, int S) {
   return qa_tail_lds_doubles(q + p, S) + 16 * (size_t)n + 16 * (size_t)(n + p + q) + 8 + 8 * (size_t)n;
 }
+// ... and of the value-only batch (7r): the tail at q + p, Knq | Z as above, bad [8] | Zp [n][8] -- no U, SL
+constexpr size_t qa_value_lds_doubles(int n, int q, int p, int S) { return qa_tail_lds_doubles(q + p, S) + 16 * (size_t)n + 8 + 8 * (size_t)n; }
 
 // Everything from "Sigma, mu given" onwards, by `nthr` cooperating threads: t[QA_SG] (both triangles; only the lower one is read) and
 // t[QA_MU] hold the joint posterior of the q points, entries past q are zero.  Leaves value, jitter and info in t[QA_OUT], mubar in
@@ -282,11 +291,14 @@ SA_DEV void qa_tail(double* t, int q, int S, int acqf, double par, const double*
 // the workgroup.)  PEND: (7q), `pe.p` pending points behind the q moving ones; `lds`: qa_pending_lds_doubles(n, q, p, S).  Without
 // PEND `pe` is not read and P below is the constant 0: (7p) as it was, instruction for instruction (a wrapper around the template
 // instead of the default argument reorders three instructions of that kernel; tools/dev_isa_diff.py).
-template <bool PEND = false>
+// VAL: (7r), the value layout -- p.Mq is Mp, the batch's first column comes from the column map, a point has ONE column of p.cov_g
+// (which holds cov_s), `lds`: qa_value_lds_doubles(n, q, p, S), and the body ends with the value.
+template <bool PEND = false, bool VAL = false>
 SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr, const QAcqfPending& pe = QAcqfPending{}) {
+  constexpr size_t CS = VAL ? 1 : 16;   // columns of the source sums per query point
   const int P = PEND ? pe.p : 0;
   const int n = p.n, q = p.q, S = p.S, D = p.D, Mq = p.Mq, R = n + P + q, Q = q + P;
-  const size_t q0 = (size_t)b * q, W = (size_t)Mq * 16;
+  const size_t q0 = VAL ? (size_t)qav_column(b, 0, q) : (size_t)b * q, W = (size_t)Mq * CS;
   const double nan = NAN;
   if (p.info && p.info[0] != 0) {   // the target's training block was not positive definite even with jitter
     if (tid == 0) {
@@ -302,8 +314,8 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
   double* Kq = lds + qa_tail_lds_doubles(Q, S);   // [a][8]
   double* Zq = Kq + (size_t)n * 8;                // [a][8]
   double* U = Zq + (size_t)n * 8;                 // [j][R]: the weight of row a in point j's gradient, / s^2
-  double* SL = U + (size_t)8 * R;                 // [j][R]: that weight times 2 os dk_t / d(d2)
-  double* badp = SL + (size_t)8 * R;              // [0] the batch's coordinates, [1 .. 7] shares of the pending set's arrays
+  double* SL = U + (VAL ? 0 : (size_t)8 * R);     // [j][R]: that weight times 2 os dk_t / d(d2)   (VAL: neither is there)
+  double* badp = SL + (VAL ? 0 : (size_t)8 * R);  // [0] the batch's coordinates, [1 .. 7] shares of the pending set's arrays
   double* Zpl = badp + 8;                         // [a][8] (PEND)
   const double s = p.s_all, s2 = s * s, inv_s2 = 1.0 / s2;
   const double os = p.theta[D];
@@ -339,7 +351,7 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
           }
           double k0, dk;
           sa_kernel_and_slope(p.kind, d2, os, k0, dk);
-          v = s2 * (p.cov_g[(size_t)(n + jp) * W + (q0 + k) * 16] * inv_s2 + k0 + (d2 - d2) - kz);
+          v = s2 * (p.cov_g[(size_t)(n + jp) * W + (q0 + k) * CS] * inv_s2 + k0 + (d2 - d2) - kz);
         }
         t[QA_SG + j * 8 + k] = v;
         t[QA_SG + k * 8 + j] = v;
@@ -357,7 +369,7 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
           }
           double k0, dk;
           sa_kernel_and_slope(p.kind, d2, os, k0, dk);
-          prior = p.cov_g[(size_t)(n + P + k) * W + (q0 + j) * 16] * inv_s2 + k0 + (d2 - d2);
+          prior = p.cov_g[(size_t)(n + P + k) * W + (q0 + j) * CS] * inv_s2 + k0 + (d2 - d2);
         }
         const double v = s2 * (prior - kz);
         t[QA_SG + j * 8 + k] = v;
@@ -404,7 +416,7 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
     if (p.jitter_used) p.jitter_used[b] = t[QA_OUT + QA_OUT_JITTER];
     if (p.info_out) p.info_out[b] = failed ? 1 : 0;
   }
-  if (!p.grad) return;
+  if (VAL || !p.grad) return;
   if (value != value) {   // (NaN: uniform over the workgroup, all of them read the same value)
     for (int e = tid; e < q * D; e += nthr) p.grad[q0 * D + e] = nan;
     return;
@@ -465,6 +477,11 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
 // (7q)
 SA_DEV void qa_batch_pending(const QAcqfPendingParams& pp, double* lds, int b, int tid, int nthr) {
   qa_batch<true>(pp.a, lds, b, tid, nthr, pp.pe);
+}
+
+// (7r): value only, from the value layout, p >= 0 pending points
+SA_DEV void qa_batch_value(const QAcqfPendingParams& pp, double* lds, int b, int tid, int nthr) {
+  qa_batch<true, true>(pp.a, lds, b, tid, nthr, pp.pe);
 }
 
 }  // namespace scaml

@@ -72,6 +72,7 @@ struct Module {
   hipFunction_t acqf_transform = nullptr;                          // the elementwise acquisition of given posteriors (7o)
   hipFunction_t post_linv_grad_joint[2] = {}, tgt_qacqf = nullptr;   // joint q-point acquisition: the GRAD pass with batch mates (5g), qEI / qUCB (7p)
   hipFunction_t tgt_qacqf_pending = nullptr;                         // ... with evaluations pending (7q)
+  hipFunction_t post_linv_cov_joint[2] = {}, tgt_qacqf_value = nullptr;   // ... value only: the value-layout pass with batch mates (5h), (7r)
   hipFunction_t post_linv_grouped[2] = {}, tgt_acqf_batched = nullptr;   // lock-step studies: grouped GRAD pass, batched acquisition
   hipFunction_t post_linv_grouped_own[2] = {};                           // the grouped pass with per-group source tasks
   hipFunction_t post_linv_grouped_det[2] = {}, post_linv_grouped_det_own[2] = {};   // the GRAD grouped pass with ordered sums: (7l)'s rounds
@@ -97,18 +98,20 @@ struct Module {
     std::vector<KernelRow> rows = {
         {post, "_ZN5scaml19gp_posterior_kernelILi%dEEEvNS_15PosteriorParamsE", kLdsLimit, {K}},
         {post_cov, "_ZN5scaml23gp_posterior_cov_kernelILi%dEEEvNS_18PosteriorCovParamsE", 0, {K}},
-        {post_linv, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
-        {post_linv_cov, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped_det, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit - kOrderedSumsLds, {K}},   // (static LDS: the waves' shares)
-        {post_linv_grouped_det_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit - kOrderedSumsLds, {K}},   // (static LDS: the waves' shares)
-        {post_linv_grouped_val, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grouped_val_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
-        {post_linv_grad_joint, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0ELb0ELb1EEEvNS_13PosteriorArgsIXT2_EXT5_EE4typeE", kLdsLimit, {K}},
+        {post_linv, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb0ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit, {K}},
+        {post_linv_cov, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grad, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_det, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb0ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit - kOrderedSumsLds, {K}},   // (static LDS: the waves' shares)
+        {post_linv_grouped_det_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb1ELb1ELb1ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit - kOrderedSumsLds, {K}},   // (static LDS: the waves' shares)
+        {post_linv_grouped_val, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb0ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grouped_val_own, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb1ELb1ELb0ELb0ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit, {K}},
+        {post_linv_grad_joint, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb1ELb0ELb0ELb0ELb1ELb0EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit, {K}},
         {&tgt_qacqf, "scaml_target_qacqf_kernel", kLdsLimit, {}},
         {&tgt_qacqf_pending, "scaml_target_qacqf_pending_kernel", kLdsLimit, {}},
+        {post_linv_cov_joint, "_ZN5scaml24gp_posterior_linv_kernelILi%dELb1ELb0ELb0ELb0ELb0ELb0ELb1EEEvNS_13PosteriorArgsIXT2_EXT5_EXT6_EE4typeE", kLdsLimit, {K}},
+        {&tgt_qacqf_value, "scaml_target_qacqf_value_kernel", kLdsLimit, {}},
         {&tgt_acqf_batched, "scaml_target_acqf_batched_kernel", kLdsLimit, {}},
         {&tgt_score_batched, "scaml_target_score_batched_kernel", kLdsLimit, {}},
         {&tgt_fantasy_acqf_batched, "scaml_target_fantasy_acqf_batched_kernel", kLdsLimit, {}},
@@ -777,6 +780,63 @@ int scaml_target_qacqf_pending_f64(const double* Knq, const double* Z, const dou
                                 value, grad, jitter_used, info_out, n, Mq, q, S, D, kind, acqf, 0},
                                {Xp, Zp, mu_p, Sigma_pp, p, 0}};
   return launch(m->tgt_qacqf_pending, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "target_qacqf_pending", pp);
+}
+
+// ---- (5h) the joint source pass in value layout: 16 packed query points per strip, the mates' covariances from the strip's Gram tile ----
+int scaml_qacqf_value_columns(int B, int q) {
+  if (B < 0 || q < 1 || q > scaml::QACQF_MAX_Q || B > (1 << 26)) return -1;
+  return scaml::qav_columns(B, q);
+}
+
+int scaml_posterior_linv_cov_joint_f64(const double* Xq, const double* Xa, const double* X, const double* theta, const double* Linv,
+                                       const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points,
+                                       const double* VA, int T, int N, int Mp, int Ma, int B, int q, int D, int kind, double* mu, double* var,
+                                       double* cov, unsigned flags, void* stream) {
+  if (T < 0 || N < 1 || Mp < 0 || Ma < 1 || B < 0 || q < 1 || D < 1) return SCAML_E_BADARG;
+  if (!Xq || !Xa || !X || !theta || !Linv || !alpha || !VA || !cov) return SCAML_E_BADARG;
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (flags & SCAML_POST_MEAN_ONLY) return SCAML_E_BADARG;
+  if (q <= scaml::QACQF_MAX_Q && B <= (1 << 26) && Mp != scaml::qav_columns(B, q)) return SCAML_E_BADARG;   // (the packing is defined up to q = 8)
+  if (q > scaml::QACQF_MAX_Q || B > (1 << 26)) return SCAML_E_TOOLARGE;
+  if (N > scaml_posterior_max_n()) return SCAML_E_TOOLARGE;
+  if (Ma > scaml::QACQF_MAX_ROWS || Ma + q > scaml::QACQF_MAX_ROWS || Ma + q > N) return SCAML_E_TOOLARGE;   // six 16-row strips of leading points, staged in the N x 16 LDS strip
+  const scaml::PosteriorJointValuePlan plan = scaml::posterior_jointv_plan(T, N, D, Mp);
+  const size_t lds = plan.lds_doubles * sizeof(double);
+  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (T == 0 || B == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  scaml::PosteriorJointValueParams p{{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N, Mp, D, 0,
+                                      (flags & SCAML_POST_XQ_PER_TASK) ? 1 : 0, 0, VA, cov, Ma, 0, Xa},
+                                     {q, B}};
+  return launch(m->post_linv_cov_joint[kind], dim3(plan.grid), plan.block, lds, stream, "gp_posterior_linv_cov_joint", p);
+}
+
+// ---- (7r) (7p) / (7q) value only, from the value layout of (5h): a workgroup per batch (csrc/gp_qacqf_value.hip) ----
+int scaml_target_qacqf_value_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q,
+                                 double m_all, double s_all, const int32_t* info, const double* cov_s, const double* Xq, const double* theta,
+                                 const double* base_samples, const double* Xp, const double* Zp, const double* mu_p, const double* Sigma_pp,
+                                 int acqf, double acqf_param, int n, int Mp, int B, int q, int p, int S, int D, int kind, double* value,
+                                 double* jitter_used, int32_t* info_out, void* stream) {
+  if (n < 1 || Mp < 0 || B < 0 || q < 1 || p < 0 || S < 1 || D < 1) return SCAML_E_BADARG;
+  if (!Knq || !Z || !alpha || !mean_q || !var_q || !cov_s || !Xq || !theta || !base_samples || !value) return SCAML_E_BADARG;
+  if (p > 0 && (!Xp || !Zp || !mu_p || !Sigma_pp)) return SCAML_E_BADARG;
+  if (!scaml::qa_acqf_valid(acqf)) return SCAML_E_BADARG;   // (a joint LogEI is not defined)
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (!(s_all > 0.0)) return SCAML_E_BADARG;
+  if (q <= scaml::QACQF_MAX_Q && B <= (1 << 26) && Mp != scaml::qav_columns(B, q)) return SCAML_E_BADARG;
+  if (q > scaml::QACQF_MAX_Q || p > scaml::QACQF_MAX_Q || q + p > scaml::QACQF_MAX_Q || S > scaml::QACQF_MAX_SAMPLES || B > (1 << 26) ||
+      n > scaml::QACQF_MAX_ROWS || n + p + q > scaml::QACQF_MAX_ROWS || D > scaml::QACQF_MAX_D)
+    return SCAML_E_TOOLARGE;
+  const scaml::QAcqfPlan plan = scaml::qacqf_value_plan(B, n, q, p, S);
+  if (plan.lds_doubles * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
+  if (B == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  scaml::QAcqfPendingParams pp{{Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_s, nullptr, nullptr, nullptr, Xq, theta, base_samples,
+                                acqf_param, value, nullptr, jitter_used, info_out, n, Mp, q, S, D, kind, acqf, 0},
+                               {p > 0 ? Xp : nullptr, p > 0 ? Zp : nullptr, p > 0 ? mu_p : nullptr, p > 0 ? Sigma_pp : nullptr, p, 0}};
+  return launch(m->tgt_qacqf_value, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "target_qacqf_value", pp);
 }
 
 // ---- (7o) the acquisition value and chain-rule factors of M given posteriors, elementwise (csrc/gp_acqf_transform.hip) ----------

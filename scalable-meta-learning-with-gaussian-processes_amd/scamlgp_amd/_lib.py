@@ -105,6 +105,12 @@ SIGNATURES = {
     "scaml_target_qacqf_f64": (_i, [_dp] * 5 + [_f, _f, _dp] + [_dp] * 7 + [_i, _f] + [_i] * 6 + [_dp] * 4 + [c_void_p]),
     # (7q) (7p)'s arrays, then Xp, Zp, mu_p, Sigma_pp; acqf, acqf_param; n, Mq, q, p, S, D, kind; value, grad, jitter_used, info_out
     "scaml_target_qacqf_pending_f64": (_i, [_dp] * 5 + [_f, _f, _dp] + [_dp] * 11 + [_i, _f] + [_i] * 7 + [_dp] * 4 + [c_void_p]),
+    "scaml_qacqf_value_columns": (_i, [_i, _i]),
+    # (5h) Xq, Xa, X, theta, Linv, alpha, y_mean, y_std, n_points, VA; T, N, Mp, Ma, B, q, D, kind; mu, var, cov, flags
+    "scaml_posterior_linv_cov_joint_f64": (_i, [_dp] * 10 + [_i] * 8 + [_dp, _dp, _dp, _u, c_void_p]),
+    # (7r) Knq, Z, alpha, mean_q, var_q; m_all, s_all; info; cov_s, Xq, theta, base_samples, Xp, Zp, mu_p, Sigma_pp; acqf, acqf_param;
+    # n, Mp, B, q, p, S, D, kind; value, jitter_used, info_out
+    "scaml_target_qacqf_value_f64": (_i, [_dp] * 5 + [_f, _f, _dp] + [_dp] * 8 + [_i, _f] + [_i] * 8 + [_dp] * 3 + [c_void_p]),
     # (7o) mu, var; acqf_param, M, acqf; A, Amu, Av
     "scaml_acqf_transform_f64": (_i, [_dp, _dp, _f, _i, _i, _dp, _dp, _dp, c_void_p]),
     # (5e) Xq, group, Xa, n_points_a, VA_tab, X, theta, Linv, alpha, y_mean, y_std, n_points; T, N, Mq, G, Ma_max, D, kind; mu, var, cov

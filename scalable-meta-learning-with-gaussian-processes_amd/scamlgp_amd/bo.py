@@ -207,8 +207,11 @@ class ScaMLGPBOLoop:
                  num_restarts_log_likelihood: int = 5, raw_samples: int = 1024, num_restarts: int = 10, af_max_iter: int = 50,
                  gp_likelihood: Optional[hyper.GaussianLikelihood] = None, gp_kernel: Optional[hyper.ScaleKernel] = None,
                  seed: Optional[int] = None, use_graph: bool = True, max_pending_evaluations: Optional[int] = None,
-                 num_fantasies: int = 16, num_mc_samples: int = 128, joint_pending: str = "refuse"):
+                 num_fantasies: int = 16, num_mc_samples: int = 128, joint_pending: str = "refuse", joint_score_mode: str = "grad_pass"):
         """``num_mc_samples``: base samples of the joint acquisition function of ``suggest_batch``.
+        ``joint_score_mode``: how ``suggest_batch`` scores its raw batches (stage 1) and its end batches (stage 3) -- ``"grad_pass"``
+        (default): through the route of the gradient evaluations; ``"value_pass"``: through the value-only route
+        (``ScaMLGP.joint_acqf_value``, 16 points per strip of the source pass).  Stage 2 runs on the exact gradients either way.
         ``joint_pending``: what ``suggest_batch`` does while evaluations are pending -- ``"refuse"`` (default): NotImplementedError;
         ``"joint"``: the pending points join every batch and are held fixed (botorch's X_pending, ``ScaMLGP.joint_acqf(X_pending=...)``).
         ``max_pending_evaluations``: None (default) -- strictly suggest -> report, no bookkeeping; an integer k -- ``suggest()``
@@ -218,7 +221,9 @@ class ScaMLGPBOLoop:
             raise ValueError("max_pending_evaluations must be None or a positive integer")
         if joint_pending not in ("refuse", "joint"):
             raise ValueError(f"joint_pending must be 'refuse' or 'joint', got {joint_pending!r}")
-        self.joint_pending = joint_pending
+        if joint_score_mode not in ("grad_pass", "value_pass"):
+            raise ValueError(f"joint_score_mode must be 'grad_pass' or 'value_pass', got {joint_score_mode!r}")
+        self.joint_pending, self.joint_score_mode = joint_pending, joint_score_mode
         self.max_pending_evaluations = None if max_pending_evaluations is None else int(max_pending_evaluations)
         self.num_fantasies = int(num_fantasies)
         self.num_mc_samples = int(num_mc_samples)
@@ -312,8 +317,9 @@ class ScaMLGPBOLoop:
             Yf = self.Y[torch.isfinite(self.Y)]
             if Yf.numel() == 0:
                 raise ValueError("EI needs at least one evaluation")
-            return qExpectedImprovement(self.model, float(Yf.min()), self.num_mc_samples, self.gen, q=q, X_pending=X_pending)
-        return qUpperConfidenceBound(self.model, self.beta, self.num_mc_samples, self.gen, q=q, X_pending=X_pending)
+            return qExpectedImprovement(self.model, float(Yf.min()), self.num_mc_samples, self.gen, q=q, X_pending=X_pending,
+                                        score_mode=self.joint_score_mode)
+        return qUpperConfidenceBound(self.model, self.beta, self.num_mc_samples, self.gen, q=q, X_pending=X_pending, score_mode=self.joint_score_mode)
 
     def suggest_batch(self, q: int) -> torch.Tensor:
         """q points for q parallel workers, optimised AGAINST EACH OTHER: the maximiser (q, D) of the joint Monte-Carlo acquisition

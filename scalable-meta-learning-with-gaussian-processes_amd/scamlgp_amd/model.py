@@ -1068,14 +1068,11 @@ class ScaMLGP:
         return dict(Xp=Xp, Xa=xall, VA=torch.cat([self._train_VA(), Vp], -1).contiguous(), Zp=blk["Z"].contiguous(),
                     mu_p=mvn.mean.contiguous(), Sigma_pp=mvn.covariance_matrix.contiguous())
 
-    def joint_acqf_inputs(self, X: torch.Tensor, base_samples: torch.Tensor, X_pending=None) -> dict:
-        """Everything of ``joint_acqf`` in front of the acquisition kernel, for X (B, q, D): the keyword arguments of
-        ``ops.target_qacqf`` by name (Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples,
-        kind) and ``shape`` = (B, q, D).  They do not depend on the acquisition code or its parameter.  With p > 0 pending points
-        (``X_pending``: (p, D) or ``joint_pending``'s dict): the keyword arguments of ``ops.target_qacqf_pending`` -- the same names,
-        cov_g with n + p + q rows, base_samples (S, q + p), and Xp, Zp, mu_p, Sigma_pp."""
+    def _joint_arguments(self, X: torch.Tensor, base_samples: torch.Tensor, X_pending=None):
+        """The arguments of a joint evaluation, checked before anything batch-dependent is launched: X (B, q, D) and base_samples
+        (S, q + p) on the device, and ``joint_pending``'s dict (None with no point pending).  The refusals of ``joint_acqf``."""
         self._joint_refusals()
-        st, f = self._stack, self._stack.fit
+        st = self._stack
         X = torch.as_tensor(X, dtype=torch.float64).to(self.device)
         if X.dim() != 3 or X.shape[-1] != st.D:
             raise ValueError("joint_acqf takes X (B, q, D)")
@@ -1098,6 +1095,18 @@ class ScaMLGP:
             raise NotImplementedError(f"the joint acquisition kernel takes q + p <= {ops.qacqf_max_q()} points, got q = {q} and {p} pending")
         if p > 0 and (n + p + q > studies.MAX_N or n + p + q > st.N):
             raise NotImplementedError(f"the joint acquisition function needs n + p + q <= {min(studies.MAX_N, st.N)}")
+        return X, base_samples, pend
+
+    def joint_acqf_inputs(self, X: torch.Tensor, base_samples: torch.Tensor, X_pending=None) -> dict:
+        """Everything of ``joint_acqf`` in front of the acquisition kernel, for X (B, q, D): the keyword arguments of
+        ``ops.target_qacqf`` by name (Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples,
+        kind) and ``shape`` = (B, q, D).  They do not depend on the acquisition code or its parameter.  With p > 0 pending points
+        (``X_pending``: (p, D) or ``joint_pending``'s dict): the keyword arguments of ``ops.target_qacqf_pending`` -- the same names,
+        cov_g with n + p + q rows, base_samples (S, q + p), and Xp, Zp, mu_p, Sigma_pp."""
+        st, f = self._stack, self._stack.fit
+        X, base_samples, pend = self._joint_arguments(X, base_samples, X_pending)
+        B, q, D = X.shape
+        n = self.n
         Xq = X.reshape(B * q, D).contiguous()
         if B == 0:
             return dict(Xq=Xq, shape=(B, q, D))
@@ -1128,6 +1137,65 @@ class ScaMLGP:
         kw = dict(Knq=blk["Knq"], Z=blk["Z"], alpha=blk["factor"]["alpha"][0], mean_q=blk["mean_q"], var_q=blk["var_q"], m_all=self._m_all_f,
                   s_all=self._s_all_f, info=blk["info"], cov_g=cov_g, mu_g=mu_g, var_g=var_g, Xt=self.train_X, Xq=Xq, theta=theta,
                   base_samples=base_samples, kind=self.kind, shape=(B, q, D))
+        if pend is not None:
+            kw.update(Xp=pend["Xp"], Zp=pend["Zp"], mu_p=pend["mu_p"], Sigma_pp=pend["Sigma_pp"])
+        return kw
+
+    def joint_acqf_value(self, X: torch.Tensor, acqf: int, acqf_param: float, base_samples: torch.Tensor, X_pending=None) -> torch.Tensor:
+        """``joint_acqf``'s value (B,) for X (B, q, D) WITHOUT its gradient, through a route of its own: what the scoring of an
+        optimiser's raw candidates needs.  The batches are packed into strips of 16 columns (``ops.qacqf_value_pack``), the value-layout
+        joint source pass (scaml_posterior_linv_cov_joint_f64) takes 16 points per strip -- the GRAD pass of ``joint_acqf`` one -- and
+        gets the batch mates' covariances from the strip's own Gram tile, then the weighted task sums, the target's value path with the
+        cached factor, and ONE launch of scaml_target_qacqf_value_f64 for all batches.  Same refusals, same ``X_pending`` (the pending
+        points are leading points, ``joint_pending``'s dict is reused as it is), same base samples (S, q + p); the values are
+        ``joint_acqf``'s up to the rounding of the two source passes."""
+        return self.joint_acqf_value_full(X, acqf, acqf_param, base_samples, X_pending)["value"]
+
+    def joint_acqf_value_full(self, X: torch.Tensor, acqf: int, acqf_param: float, base_samples: torch.Tensor, X_pending=None) -> dict:
+        """``joint_acqf_value`` with the kernel's per-batch status: dict(value (B,), jitter (B,), info (B,) int32), as ``joint_acqf_full``."""
+        if acqf not in (ops.ACQF_UCB, ops.ACQF_EI):   # (before anything is launched; the kernel refuses the same codes)
+            raise ValueError("the joint acquisition function takes ops.ACQF_UCB or ops.ACQF_EI: a joint LogEI is not defined")
+        kw = self.joint_acqf_value_inputs(X, base_samples, X_pending)
+        B, q, D = kw.pop("shape")
+        if B == 0:
+            return dict(value=torch.empty(0, dtype=torch.float64, device=self.device), jitter=torch.empty(0, dtype=torch.float64, device=self.device),
+                        info=torch.empty(0, dtype=torch.int32, device=self.device))
+        return ops.target_qacqf_value(acqf=acqf, acqf_param=acqf_param, **kw)
+
+    def joint_acqf_value_inputs(self, X: torch.Tensor, base_samples: torch.Tensor, X_pending=None) -> dict:
+        """Everything of ``joint_acqf_value`` in front of the acquisition kernel, for X (B, q, D): the keyword arguments of
+        ``ops.target_qacqf_value`` by name (Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_s, Xq, theta, base_samples, B, kind --
+        Xq (Mp, D) the packed points, everything with a query axis at its Mp columns -- and Xp, Zp, mu_p, Sigma_pp with points pending)
+        and ``shape`` = (B, q, D)."""
+        st, f = self._stack, self._stack.fit
+        X, base_samples, pend = self._joint_arguments(X, base_samples, X_pending)
+        B, q, D = X.shape
+        n = self.n
+        if B == 0:
+            return dict(shape=(B, q, D))
+        Xq = ops.qacqf_value_pack(X)
+        w_full, active = self._active_tasks()
+        mu_t, cov_tt, var_t = self._train_prior()
+        # (pending points are leading points: rows n .. n + p - 1 of the covariance block, in front of the mates' rows)
+        Xa, VA = (self.train_X, self._train_VA()) if pend is None else (pend["Xa"], pend["VA"])
+        g = ops.source_posteriors_cov_joint(Xq, B, q, Xa, st.X, st.theta, st.kind, f["Linv"], f["alpha"], VA, st.y_mean, st.y_std, st.n_points)
+        mu_v, cov_v = ops.weighted_prior_reduce(g["mu"], g["cov"], w_full, active)
+        var_v = ops.weighted_task_sum(g["var"], w_full, 2, active)
+        # the training rows next to the training block: the joint prior the target GP's value path takes
+        cov_s = torch.cat([cov_tt, cov_v[:n]], 1)
+        mean_s = torch.cat([mu_t, mu_v])
+        var_s = torch.cat([var_t, var_v])
+        xall = torch.cat([self.train_X, Xq], 0)
+        theta = self.theta
+        factor = self._target_factor()
+        if factor is not None and "alpha_f" not in factor:   # (cached by posterior(): one target vector, its alpha is the one column)
+            factor = dict(factor, alpha_f=factor["alpha"][0].unsqueeze(-1))
+        blk = ops.target_fantasy_block(cov_s, mean_s, var_s, xall, theta, self.train_targets.unsqueeze(0), self._m_all_f, self._s_all_f,
+                                       self.kind, factor=factor)
+        self._keep_target_factor(blk["factor"])
+        kw = dict(Knq=blk["Knq"], Z=blk["Z"], alpha=blk["factor"]["alpha"][0], mean_q=blk["mean_q"], var_q=blk["var_q"], m_all=self._m_all_f,
+                  s_all=self._s_all_f, info=blk["info"], cov_s=cov_v, Xq=Xq, theta=theta, base_samples=base_samples, B=B, kind=self.kind,
+                  shape=(B, q, D))
         if pend is not None:
             kw.update(Xp=pend["Xp"], Zp=pend["Zp"], mu_p=pend["mu_p"], Sigma_pp=pend["Sigma_pp"])
         return kw

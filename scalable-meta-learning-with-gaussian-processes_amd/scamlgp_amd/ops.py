@@ -818,6 +818,112 @@ def target_qacqf_pending(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor
     return dict(value=value, grad=grad, jitter=jitter, info=info_out)
 
 
+def qacqf_value_columns(B: int, q: int) -> int:
+    """Mp: the columns B batches of q points take in the value layout of (5h) / (7r) (scaml_qacqf_value_columns: strips of 16 columns,
+    16 // q whole batches each)."""
+    Mp = int(_lib.lib.scaml_qacqf_value_columns(int(B), int(q)))
+    if Mp < 0:
+        raise ValueError(f"the value layout takes B >= 0 batches of 1 <= q <= {qacqf_max_q()} points")
+    return Mp
+
+
+def qacqf_value_column_map(B: int, q: int) -> torch.Tensor:
+    """(B, q) int64: the column of point j of batch b in the value layout, 16 (b // bps) + (b % bps) q + j with bps = 16 // q
+    (csrc/gp_qacqf_columns.h)."""
+    bps = 16 // int(q)
+    b = torch.arange(int(B), dtype=torch.int64).unsqueeze(1)
+    return 16 * (b // bps) + (b % bps) * int(q) + torch.arange(int(q), dtype=torch.int64).unsqueeze(0)
+
+
+def qacqf_value_pack(X: torch.Tensor, fill: float = 0.5) -> torch.Tensor:
+    """X (B, q, D) -> the packed query points (Mp, D) of (5h); padding columns hold ``fill`` (any finite coordinate will do)."""
+    B, q, D = X.shape
+    out = X.new_full((qacqf_value_columns(B, q), D), float(fill))
+    if B > 0:
+        out[qacqf_value_column_map(B, q).reshape(-1).to(X.device)] = X.reshape(B * q, D)
+    return out
+
+
+def source_posteriors_cov_joint(Xq: torch.Tensor, B: int, q: int, Xa: torch.Tensor, X: torch.Tensor, theta: torch.Tensor, kind: int,
+                                Linv: torch.Tensor, alpha: torch.Tensor, VA: torch.Tensor, y_mean: Optional[torch.Tensor] = None,
+                                y_std: Optional[torch.Tensor] = None, n_points: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The source posteriors of B batches of q points in VALUE layout, Xq (Mp, D) packed by ``qacqf_value_pack``: one launch of
+    scaml_posterior_linv_cov_joint_f64 (5h).  cov is (T, Ma + q, Mp): rows a < Ma against the leading points Xa (Ma, D) / VA (T, N, Ma),
+    row Ma + r of a column against point r of its batch (zeros in a padding column) -- 16 points per strip and no derivative columns,
+    where ``source_posteriors_grad_joint`` spends a strip per point.  Returns dict(mu (T, Mp), var (T, Mp), cov)."""
+    T, N, D = X.shape
+    B, q = int(B), int(q)
+    Mp = qacqf_value_columns(B, q)
+    X = _check(X, "X")
+    Xq = _check(Xq, "Xq", (Mp, D))
+    theta = _check(theta, "theta", (T, D + 2))
+    Linv = _check(Linv, "Linv", (T, N, N))
+    alpha = _check(alpha, "alpha", (T, N))
+    Ma = int(VA.shape[-1])
+    VA = _check(VA, "VA", (T, N, Ma))
+    Xa = _check(Xa, "Xa", (Ma, D))
+    y_mean = _opt(y_mean, "y_mean", (T,))
+    y_std = _opt(y_std, "y_std", (T,))
+    n_points = _opt(n_points, "n_points", (T,), torch.int32)
+    dev = X.device
+    with torch.cuda.device(dev):
+        mu = _empty(dev, T, Mp)
+        var = _empty(dev, T, Mp)
+        cov = _empty(dev, T, Ma + q, Mp)
+        rc = _lib.lib.scaml_posterior_linv_cov_joint_f64(_ptr(Xq), _ptr(Xa), _ptr(X), _ptr(theta), _ptr(Linv), _ptr(alpha), _ptr(y_mean),
+                                                         _ptr(y_std), _ptr(n_points), _ptr(VA), T, N, Mp, Ma, B, q, D, int(kind), _ptr(mu),
+                                                         _ptr(var), _ptr(cov), 0, _stream_handle())
+    _lib.check_rc(rc, "scaml_posterior_linv_cov_joint_f64")
+    return dict(mu=mu, var=var, cov=cov)
+
+
+def target_qacqf_value(Knq: torch.Tensor, Z: torch.Tensor, alpha: torch.Tensor, mean_q: torch.Tensor, var_q: torch.Tensor, m_all: float,
+                       s_all: float, info: Optional[torch.Tensor], cov_s: torch.Tensor, Xq: torch.Tensor, theta: torch.Tensor,
+                       base_samples: torch.Tensor, B: int, acqf: int, acqf_param: float, kind: int = KIND_RBF,
+                       Xp: Optional[torch.Tensor] = None, Zp: Optional[torch.Tensor] = None, mu_p: Optional[torch.Tensor] = None,
+                       Sigma_pp: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """``target_qacqf`` / ``target_qacqf_pending`` without the gradient, from the value layout: one launch of
+    scaml_target_qacqf_value_f64 (7r).  Knq, Z (n, Mp), mean_q, var_q (Mp,), Xq (Mp, D) at the packed columns of the B batches;
+    cov_s (n + p + q, Mp) the weighted sums of ``source_posteriors_cov_joint``; base_samples (S, q + p) with p = Xp.shape[0] pending
+    points (Xp None: p = 0).  Returns dict(value (B,), jitter (B,), info (B,) int32): the bits of the gradient kernels' outputs."""
+    n, Mp = Knq.shape
+    D = int(Xq.shape[1])
+    p = 0 if Xp is None else int(Xp.shape[0])
+    S, Q = base_samples.shape
+    q, B = Q - p, int(B)
+    if q < 1 or B < 0 or Mp != qacqf_value_columns(B, q):
+        raise ValueError("Knq must have qacqf_value_columns(B, q) columns, q = base_samples.shape[1] - Xp.shape[0] >= 1")
+    Knq = _check(Knq, "Knq", (n, Mp))
+    Z = _check(Z, "Z", (n, Mp))
+    alpha = _check(alpha, "alpha", (n,))
+    mean_q = _check(mean_q, "mean_q", (Mp,))
+    var_q = _check(var_q, "var_q", (Mp,))
+    cov_s = _check(cov_s, "cov_s", (n + p + q, Mp))
+    Xq = _check(Xq, "Xq", (Mp, D))
+    theta = _check(theta, "theta", (D + 2,))
+    base_samples = _check(base_samples, "base_samples", (S, Q))
+    if p > 0:
+        Xp = _check(Xp, "Xp", (p, D))
+        Zp = _check(Zp, "Zp", (n, p))
+        mu_p = _check(mu_p, "mu_p", (p,))
+        Sigma_pp = _check(Sigma_pp, "Sigma_pp", (p, p))
+    else:
+        Xp = Zp = mu_p = Sigma_pp = None
+    if info is not None:
+        info = _check(info.reshape(-1)[:1], "info", (1,), torch.int32)
+    dev = Knq.device
+    with torch.cuda.device(dev):
+        value = _empty(dev, B)
+        jitter = _empty(dev, B)
+        info_out = _empty(dev, B, dtype=torch.int32)
+        rc = _lib.lib.scaml_target_qacqf_value_f64(_ptr(Knq), _ptr(Z), _ptr(alpha), _ptr(mean_q), _ptr(var_q), float(m_all), float(s_all),
+                                                   _ptr(info), _ptr(cov_s), _ptr(Xq), _ptr(theta), _ptr(base_samples), _ptr(Xp), _ptr(Zp),
+                                                   _ptr(mu_p), _ptr(Sigma_pp), int(acqf), float(acqf_param), n, Mp, B, q, p, S, D, int(kind),
+                                                   _ptr(value), _ptr(jitter), _ptr(info_out), _stream_handle())
+    _lib.check_rc(rc, "scaml_target_qacqf_value_f64")
+    return dict(value=value, jitter=jitter, info=info_out)
+
+
 def _source_pass_grouped(value: bool, Xq, group, Xa, n_points_a, VA_tab, X, theta, kind, Linv, alpha, y_mean, y_std, n_points, task_base,
                          tasks_per_group, cov_out) -> Dict[str, torch.Tensor]:
     """The grouped source pass behind ``source_posteriors_grad_grouped`` (``value`` False: 16 columns per query point, ``group`` per query

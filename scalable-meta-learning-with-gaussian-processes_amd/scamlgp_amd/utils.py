@@ -473,10 +473,23 @@ class _JointAcquisition:
     ``X_pending`` (p, D): evaluations that are running (botorch's X_pending).  They are appended to every batch and held fixed: the
     utility's maximum runs over the q + p joint samples, a batch reads the leading q + p columns of the draws, and the gradient is the
     q moving points'.  What depends on the pending set alone (``ScaMLGP.joint_pending``) is computed here, once, for the model's
-    parameters as they are now."""
+    parameters as they are now.
+
+    ``score_mode``: how ``__call__`` (values only: an optimiser's scoring of raw candidates and of its end points) is evaluated.
+    ``"grad_pass"`` (default): through ``ScaMLGP.joint_acqf``, the route of ``value_and_grad``, a strip of the source pass per point.
+    ``"value_pass"``: through ``ScaMLGP.joint_acqf_value``, 16 points per strip and no derivative columns; the values agree with the
+    default's to the rounding of the two source passes.  ``value_and_grad`` is the same in both modes."""
+
+    SCORE_MODES = ("grad_pass", "value_pass")
+    # __call__ in "value_pass" mode chunks in whole strips so that the source pass's covariance block, T (n + p + q) Mp doubles, stays
+    # within this (StudiesAcquisition.SCORE_COV_CAP_BYTES' figure)
+    SCORE_COV_CAP_BYTES = 256 << 20
 
     def __init__(self, model: ScaMLGP, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None,
-                 X_pending: Optional[torch.Tensor] = None):
+                 X_pending: Optional[torch.Tensor] = None, score_mode: str = "grad_pass"):
+        if score_mode not in self.SCORE_MODES:
+            raise ValueError(f"score_mode must be one of {self.SCORE_MODES}, got {score_mode!r}")
+        self.score_mode = score_mode
         if model.num_fantasies is not None:
             raise NotImplementedError("the joint acquisition functions are not defined on a fantasy model")
         if not 1 <= num_samples <= ops.qacqf_max_samples():
@@ -511,8 +524,20 @@ class _JointAcquisition:
             raise ValueError(f"this acquisition function was drawn for q = {self.q}, got q = {X.shape[1]}")
         return X
 
+    def _value_pass_step(self) -> int:
+        """Batches per call of the value route: whole strips, the covariance block within SCORE_COV_CAP_BYTES (one strip at the least)."""
+        bps = 16 // self.q
+        rows = self.model.n + self.p + self.q
+        strips = int(self.SCORE_COV_CAP_BYTES) // (8 * self.model._stack.T * rows * 16)
+        return max(1, strips) * bps
+
     def __call__(self, X: torch.Tensor) -> torch.Tensor:
         X = self._batches(X)
+        if self.score_mode == "value_pass":
+            step = self._value_pass_step()
+            vals = [self.model.joint_acqf_value(X[i:i + step], self.code, self.param, self.base_samples, X_pending=self._pending)
+                    for i in range(0, X.shape[0], step)]
+            return torch.cat(vals) if vals else X.new_empty((0,))
         # (in chunks of at most 256 points: the pass keeps 16 columns per point and covariance row, for every task)
         step = max(1, 256 // self.q)
         vals = [self.model.joint_acqf(X[i:i + step], self.code, self.param, self.base_samples, X_pending=self._pending)[0]
@@ -531,8 +556,8 @@ class qExpectedImprovement(_JointAcquisition):
     param = property(lambda self: self.best_f)
 
     def __init__(self, model: ScaMLGP, best_f: float, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None,
-                 X_pending: Optional[torch.Tensor] = None):
-        super().__init__(model, num_samples, generator, q, X_pending)
+                 X_pending: Optional[torch.Tensor] = None, score_mode: str = "grad_pass"):
+        super().__init__(model, num_samples, generator, q, X_pending, score_mode)
         self.best_f = float(best_f)
 
 
@@ -543,8 +568,8 @@ class qUpperConfidenceBound(_JointAcquisition):
     param = property(lambda self: self.beta)
 
     def __init__(self, model: ScaMLGP, beta: float = 9.0, num_samples: int = 128, generator: Optional[torch.Generator] = None, q: Optional[int] = None,
-                 X_pending: Optional[torch.Tensor] = None):
-        super().__init__(model, num_samples, generator, q, X_pending)
+                 X_pending: Optional[torch.Tensor] = None, score_mode: str = "grad_pass"):
+        super().__init__(model, num_samples, generator, q, X_pending, score_mode)
         self.beta = float(beta)
 
 

@@ -17,6 +17,15 @@ With ``--pending P`` (and ``--q Q``): the same shapes with P evaluations pending
   5. suggest_batch(2) with 4 evaluations pending (joint_pending="joint") against two successive suggest() calls with 16 fantasies.
 
   python tools/dev_qacqf_time.py --pending P [--q Q] [--out FILE] [--no-suggest]
+
+With ``--score`` (and ``--q Q``, ``--pending P``): the scoring of suggest_batch's 1024 raw batches by the two routes, in place of the above
+  6. af(cand) with score_mode="grad_pass" (ScaMLGP.joint_acqf in chunks of 256 points: the GRAD pass, a strip per point) against
+     score_mode="value_pass" (ScaMLGP.joint_acqf_value: 16 points per strip), and the parts of the value route -- packing, the
+     value-layout joint source pass (5h), the weighted reductions, the target's value path, the acquisition kernel (7r);
+  7. suggest_batch(Q) with P evaluations pending in both modes, each split into its three stages (raw scoring, L-BFGS-B, re-scoring of
+     the end batches), next to Q successive suggest() calls with 16 fantasies.
+
+  python tools/dev_qacqf_time.py --score [--q Q] [--pending P] [--out FILE] [--no-suggest]
 """
 import argparse
 import os
@@ -31,7 +40,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from scamlgp_amd import model as M, ops, synthetic  # noqa: E402
+from scamlgp_amd import bo, model as M, ops, synthetic, utils  # noqa: E402
 from scamlgp_amd.bo import ScaMLGPBOLoop  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -39,6 +48,7 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--no-suggest", action="store_true", help="skip the suggest_batch / suggest comparison")
 ap.add_argument("--pending", type=int, default=0, help="P evaluations pending: time the pending route against the concatenated one")
 ap.add_argument("--q", type=int, default=4, help="points per batch")
+ap.add_argument("--score", action="store_true", help="time the scoring of the raw batches by the grad_pass and value_pass routes")
 args = ap.parse_args()
 
 T, N, D, n, q, B, S, REPS = 32, 512, 6, 80, args.q, 10, 128, 5
@@ -195,12 +205,130 @@ def pending_comparison(P):
     report(interleaved({"suggest_batch(2), 4 pending": batch, "2 x suggest(), 4 pending": successive}, warmup=1), unit=1e3, name="ms")
 
 
+def score_comparison(P):
+    """6. and 7. of the module's text."""
+    RAW = 1024
+    Xp = torch.rand(P, D, dtype=torch.float64, generator=g) if P else None
+    cand = torch.rand(RAW, q, D, dtype=torch.float64, generator=g)
+    afs = {m: utils.qExpectedImprovement(model, best_f, S, torch.Generator().manual_seed(7), q=q, X_pending=Xp, score_mode=m)
+           for m in utils._JointAcquisition.SCORE_MODES}
+    af_v = afs["value_pass"]
+    pend, eps_v = af_v._pending, af_v.base_samples
+    Xc = cand.to(dev)
+    Xa, VAl = (model.train_X, VA) if pend is None else (pend["Xa"], pend["VA"])
+    Mp = ops.qacqf_value_columns(RAW, q)
+    say(f"-- scoring {RAW} raw batches of q={q} with {P} pending: {RAW * q} strips of the GRAD pass against {Mp // 16} of the value-layout pass "
+        f"(covariance block {8e-6 * T * (n + P + q) * Mp:.0f} MB, {-(-RAW // af_v._value_pass_step())} chunk(s))")
+    vg, vv = afs["grad_pass"](cand), af_v(cand)
+    say(f"   the two routes agree to {float((vv - vg).abs().max() / vg.abs().max()):.2e} of max|value|")
+
+    def pack():
+        held["Xq"] = ops.qacqf_value_pack(Xc)
+
+    def source_pass():
+        held["g"] = ops.source_posteriors_cov_joint(held["Xq"], RAW, q, Xa, *src, f["Linv"], f["alpha"], VAl, stack.y_mean, stack.y_std, stack.n_points)
+
+    def reductions_v():
+        gg = held["g"]
+        mu_v, cov_v = ops.weighted_prior_reduce(gg["mu"], gg["cov"], w_full, active)
+        held.update(mu_v=mu_v, cov_v=cov_v, var_v=ops.weighted_task_sum(gg["var"], w_full, 2, active))
+
+    def value_path_v():
+        cov_s = torch.cat([cov_tt, held["cov_v"][:n]], 1)
+        mean_s = torch.cat([mu_t, held["mu_v"]])
+        var_s = torch.cat([var_t, held["var_v"]])
+        xall = torch.cat([model.train_X, held["Xq"]], 0)
+        held["blk"] = ops.target_fantasy_block(cov_s, mean_s, var_s, xall, model.theta, model.train_targets.unsqueeze(0), model._m_all_f,
+                                               model._s_all_f, model.kind, factor=held.get("factor"))
+        held["factor"] = held["blk"]["factor"]
+
+    def acqf_kernel_v():
+        b = held["blk"]
+        kw = {} if pend is None else dict(Xp=pend["Xp"], Zp=pend["Zp"], mu_p=pend["mu_p"], Sigma_pp=pend["Sigma_pp"])
+        held["out"] = ops.target_qacqf_value(b["Knq"], b["Z"], b["factor"]["alpha"][0], b["mean_q"], b["var_q"], model._m_all_f, model._s_all_f,
+                                             b["info"], held["cov_v"], held["Xq"], model.theta, eps_v, RAW, ops.ACQF_EI, best_f, model.kind, **kw)
+
+    for fn in (pack, source_pass, reductions_v, value_path_v, acqf_kernel_v):
+        fn()
+    report(interleaved({
+        "af(cand), score_mode='grad_pass'": lambda: afs["grad_pass"](cand),
+        "af(cand), score_mode='value_pass'": lambda: af_v(cand),
+        "  host -> device copy and packing": lambda: ops.qacqf_value_pack(cand.to(dev)),
+        "  value-layout joint source pass (5h)": source_pass,
+        "  weighted reductions (6')": reductions_v,
+        "  value path: assemble, cached factor, solve": value_path_v,
+        "  acquisition kernel (7r)": acqf_kernel_v,
+    }), unit=1e3, name="ms")
+    if args.no_suggest:
+        return
+
+    def loop(mode):
+        lp = ScaMLGPBOLoop(gps, dim=D, acquisition="ei", num_restarts_log_likelihood=1, seed=0, max_pending_evaluations=8, num_fantasies=16,
+                           num_mc_samples=S, joint_pending="joint", joint_score_mode=mode)
+        lp.record(Xt, yt.squeeze(-1))
+        lp.model.weights = model.weights.clone()
+        lp.model.eval()
+        return lp
+
+    Xp_host = None if Xp is None else Xp.clone()
+    loops = {m: loop(m) for m in utils._JointAcquisition.SCORE_MODES}
+    lp_s = loop("grad_pass")
+    stages = {m: {k: [] for k in ("stage 1: af(raw batches)", "stage 2: L-BFGS-B", "stage 3: af(end batches)")} for m in loops}
+
+    def batch(mode):
+        lp = loops[mode]
+        lp.pending = lp.pending[:0] if Xp_host is None else Xp_host.clone()
+        lp.suggest_batch(q)
+
+    def staged(mode):
+        """suggest_batch's three stages, one device synchronise after each (what bo._optimize_acqf_joint does)."""
+        lp = loops[mode]
+        af = lp.joint_acquisition_function(q, Xp_host)
+        t = [time.perf_counter()]
+        c = torch.rand(lp.raw_samples, q, D, dtype=torch.float64, generator=lp.gen)
+        vals = af(c).detach().cpu()
+        t.append(time.perf_counter())
+        best0, picks = bo.acqf_pick_initial_conditions(vals, lp.num_restarts, lp.gen, 2.0)
+        xs = bo.acqf_local_optimization(af, c[picks], lp.af_max_iter)
+        torch.cuda.synchronize()
+        t.append(time.perf_counter())
+        bo.acqf_final_choice(c, vals, best0, xs, af(xs))
+        t.append(time.perf_counter())
+        for k, a, b in zip(stages[mode], t[:-1], t[1:]):
+            stages[mode][k].append(b - a)
+
+    def successive():
+        lp_s.pending = lp_s.pending[:0] if Xp_host is None else Xp_host.clone()
+        for _ in range(q):
+            lp_s.suggest()
+
+    say(f"-- {q} points with {P} pending: suggest_batch({q}) in both modes against {q} successive suggest() calls (16 fantasies)")
+    variants = {f"suggest_batch({q}), joint_score_mode='{m}'": (lambda m=m: batch(m)) for m in loops}
+    variants[f"{q} x suggest()"] = successive
+    report(interleaved(variants, warmup=1), unit=1e3, name="ms")
+    for m in loops:
+        for _ in range(2):
+            staged(m)
+        for k in stages[m]:
+            stages[m][k].clear()
+    for _ in range(REPS):
+        for m in loops:
+            staged(m)
+    for m in loops:
+        report({f"  '{m}' {k}": v for k, v in stages[m].items()}, unit=1e3, name="ms")
+
+
 def finish():
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
 
+
+if args.score:
+    score_comparison(args.pending)
+    finish()
+    sys.exit(0)
 
 if args.pending:
     pending_comparison(args.pending)
