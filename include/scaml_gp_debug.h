@@ -34,6 +34,12 @@ int scaml_debug_coop_far(int on);
  * would apply, anything else the choice by shape.  Starts from SCAML_TARGET_FIT_NO_MFMA (set: 1).  Returns the previous mode. */
 int scaml_debug_target_fit_path(int mode);
 
+/* scaml_gp_fit_fused_f64 has a switch without a function: the environment variable SCAML_FIT_NO_FULL.  Set (not empty, not "0"),
+ * every call takes the generic instance of its size class, never the full-tile instance of the N <= 256 class (N == 256, no
+ * n_points, L -- when stored -- on a 16-byte boundary).  Unlike the switches above it is read at EVERY launch, so a process runs
+ * both instances on the same input by changing its environment between two calls; changing the environment while another thread
+ * is inside the entry point is a data race of the C library's. */
+
 /* Diagnostic builds only (SCAML_STAMPS): point the device-side stamp buffer at caller memory.  0 ok, SCAML_E_BADARG
  * when the code object has no stamp buffer, SCAML_E_LAUNCH on a HIP error. */
 int scaml_debug_set_stamp_buffer(long long* buf);

@@ -50,6 +50,16 @@ constexpr FitPlan fit_plan(int T, int N, int D, int cus) {
   return {vi, v.nb, v.wu, (unsigned)(v.wu + 1) * 64, fit_lds_doubles(v.nb, v.wu, D)};
 }
 
+// The full-tile instance gp_fit_fused_kernel<16, 7, kind, true> (csrc/gp_fit_fused.hip, FULL): whether a launch of instance
+// <nb, wu> may take it.  Its contract, every clause a compile-time fact inside the kernel: the N <= 256 class with N == 16 nb (no
+// padded rows), no n_points (every point valid), kernel-matrix mode (no given matrix), dense addressing (not a diagonal block of
+// a blocked fit: LD == N), and -- when the call stores L -- an L on a 16-byte boundary (N is even, so every row is then).
+// mode: 0 by arguments, 1 never (the environment variable SCAML_FIT_NO_FULL, csrc/scaml_host.cpp).  l_addr: the L pointer as an
+// integer, read on the host (no device work).
+constexpr bool fit_full_instance(int nb, int wu, int N, bool ragged, bool from_matrix, bool blocked, bool stores_l, size_t l_addr, int mode) {
+  return mode == 0 && nb == 16 && wu == 7 && N == 16 * nb && !ragged && !from_matrix && !blocked && (!stores_l || l_addr % 16 == 0);
+}
+
 // ---- blocked fit (256 < N <= 512, N a multiple of 16) --------------------------------------------------------------------------
 struct BlockedPlan {
   int path;            // 1 the 2 x 2 sequence of launches, 2 the several-CUs-per-task kernel in one launch

@@ -53,6 +53,9 @@
 // Diagnostic build only (python __graft_entry__.py --stamps): update wave 0 and the panel wave of
 // every workgroup accumulate s_memtime deltas per phase into a caller-provided buffer [T][2][16].
 // Never compiled into libscaml_hip.so.
+#ifdef SCAML_FIT_FULL_TU
+#define g_stamp_buf g_stamp_buf_full   // (one buffer pointer per translation unit; scaml_debug_set_stamp_buffer sets both)
+#endif
 __device__ long long* g_stamp_buf = nullptr;
 #define STAMP_DECL long long st_prev = __builtin_amdgcn_s_memtime(), st_acc[16] = {0}
 #define STAMP(i) do { long long st_now = __builtin_amdgcn_s_memtime(); st_acc[i] += st_now - st_prev; st_prev = st_now; } while (0)
@@ -380,8 +383,14 @@ struct FitBlk<true> {
   __device__ __forceinline__ size_t sW(size_t) const { return (size_t)v.stride_W; }
 };
 
-template <int NB, int WU, int KIND, bool BLK>
+// FULL: the full-tile instance of a size class.  The launcher chooses it (fit_full_instance, csrc/gp_dispatch.h) when the call
+// gives n_points == nullptr, N == 16 * NB, A_in == nullptr (kernel-matrix mode), dense addressing (LD == N) and, where L is stored,
+// an L on a 16-byte boundary.  n, N, LD, the mode and the 16-byte store path are then compile-time facts, and every test of them --
+// padded rows, ragged tiles, the given matrix, 8-byte stores -- is gone from the instruction stream.  The arithmetic is the generic
+// instance's, operation for operation.
+template <int NB, int WU, int KIND, bool BLK, bool FULL>
 __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double jitter, const FitBlk<BLK> b) {
+  static_assert(!(FULL && BLK), "the blocked fit addresses L with a leading dimension of its own");
   constexpr int NP = NB * 16;                 // padded matrix order
   constexpr int NT = NB * (NB + 1) / 2;       // lower-triangular tiles
   constexpr int SLOTS = (NT + WU - 1) / WU;   // tiles per update wave
@@ -437,11 +446,14 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   const int lc = lane & 15;   // tile column owned by this lane
   const int lq = lane >> 4;   // tile row group: rows lq + 4 * reg
   // (wave-uniform: the jitter retries read `p` through a pointer, and without this every size derived from D sat in a VGPR there)
-  const int N = __builtin_amdgcn_readfirstlane(p.N), D = __builtin_amdgcn_readfirstlane(p.D);
-  const int LD = b.ldl(N);   // leading dimension of the stored factor (N, or the full size when this is a diagonal block of a blocked fit)
-  int n = p.n_points ? p.n_points[task] : N;
-  n = n < 0 ? 0 : (n > N ? N : n);
-  const bool from_matrix = p.A_in != nullptr;   // POTRF mode: the matrix is given, nothing to evaluate
+  const int N = FULL ? NP : __builtin_amdgcn_readfirstlane(p.N), D = __builtin_amdgcn_readfirstlane(p.D);
+  const int LD = FULL ? NP : b.ldl(N);   // leading dimension of the stored factor (N, or the full size when this is a diagonal block of a blocked fit)
+  int n = NP;
+  if constexpr (!FULL) {
+    n = p.n_points ? p.n_points[task] : N;
+    n = n < 0 ? 0 : (n > N ? N : n);
+  }
+  const bool from_matrix = FULL ? false : p.A_in != nullptr;   // POTRF mode: the matrix is given, nothing to evaluate
   const double* Ag = from_matrix ? p.A_in + (size_t)task * N * N : nullptr;
   const double* Xg = from_matrix ? nullptr : p.X + (size_t)task * b.sx((size_t)N * D);
   const double* yg = p.y ? p.y + (size_t)task * b.sy((size_t)N) : nullptr;
@@ -458,8 +470,12 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   // (the test and the lane mapping are worked out where they are used, from operands the compiler cannot trace back: neither
   //  is kept in a register across the panel loop)
   auto st16 = [&]() {
-    const int bits = opaque_s(__builtin_amdgcn_readfirstlane((int)(((unsigned)(size_t)Lg) | ((unsigned)LD << 3))));
-    return (bits & 15) == 0;
+    if constexpr (FULL) {
+      return true;   // (the launcher looked at the pointer)
+    } else {
+      const int bits = opaque_s(__builtin_amdgcn_readfirstlane((int)(((unsigned)(size_t)Lg) | ((unsigned)LD << 3))));
+      return (bits & 15) == 0;
+    }
   };
   auto lane16 = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
   // The strict upper triangle of L as zeros (on request): tile (c, ti), ti > c, mirrors the lower tile (ti, c).  The
@@ -468,7 +484,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   const bool zfill = Lg && zero_upper;
   auto zero_mirror = [&](int c, int ti) {
     double* mb = Lg + ((size_t)(16 * c) * LD + 16 * ti);   // wave-uniform
-    if (16 * ti + 16 <= n) {                               // interior tile: no per-lane bounds
+    if (FULL || 16 * ti + 16 <= n) {                       // interior tile: no per-lane bounds
       if (st16()) {
         const d2_t z = {0.0, 0.0};
         const int l = lane16(), lane_idx2 = (l >> 3) * LD + 2 * (l & 7);
@@ -512,7 +528,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
     // operations per matrix element.  y into ytil.
     const int D4 = (D + 3) & ~3;
     for (int r = tid; r < NP; r += NTHREADS) {
-      const bool in = r < n;
+      const bool in = FULL || r < n;
       if (!from_matrix) {
         double h = 0.0;
         for (int d = 0; d < D; ++d) {
@@ -590,7 +606,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
       } else {
         // wave-uniform fast path: an off-diagonal tile entirely inside the n valid points needs neither the
         // diagonal term nor the identity padding (saves ~10 VALU instructions per element)
-        if (kr != 0 && 16 * (kj + kr) + 16 <= n) {
+        if (kr != 0 && (FULL || 16 * (kj + kr) + 16 <= n)) {
 #pragma unroll
           for (int g = 0; g < 4; ++g) kt[g] = kernel_from_sqdist_scaled<KIND>(d2[g], kc0, kc1, kc2, exptab);
         } else {
@@ -599,7 +615,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
             const int col = col0 + 4 * g;
             double kv = kernel_from_sqdist_scaled<KIND>(row == col ? 0.0 : d2[g], kc0, kc1, kc2, exptab);
             if (row == col) kv += diag_add;
-            if (row >= n || col >= n) kv = row == col ? 1.0 : 0.0;
+            if (!FULL && (row >= n || col >= n)) kv = row == col ? 1.0 : 0.0;
             kt[g] = kv;
           }
         }
@@ -782,7 +798,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
     // One finished sub-diagonal tile (ti, c): read back from the LDS column buffer in row segments -> HBM.
     auto store_tile = [&](int c, int ti) {
       double* tb = Lg + ((size_t)(16 * ti) * LD + 16 * c);   // tile (ti, c), wave-uniform
-      if (16 * ti + 16 <= n && st16()) {
+      if ((FULL || 16 * ti + 16 <= n) && st16()) {
         // interior tile, rows on 16-byte boundaries: two neighbours of a row per lane (the odd pitch leaves the LDS side
         // at 8-byte alignment: one two-address read per trip), two stores of 8 rows x 128 bytes
         const int l = lane16(), lane_idx2 = (l >> 3) * LD + 2 * (l & 7);
@@ -871,7 +887,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
 #endif
           const int c = j - 2;
           int ti = j - 1;
-          for (; ti + SCAML_STRIP - 1 < NB && 16 * (ti + SCAML_STRIP) <= n; ti += SCAML_STRIP) {
+          for (; ti + SCAML_STRIP - 1 < NB && (FULL || 16 * (ti + SCAML_STRIP) <= n); ti += SCAML_STRIP) {
             if (st16()) {
               const int l = lane16(), lane_idx2 = (l >> 3) * LD + 2 * (l & 7);
               const double* prow = PT + (c % 3) * PANEL + (16 * ti + (l >> 3)) * PP + 2 * (l & 7);
@@ -949,7 +965,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
           for (int g = 0; g < 4; ++g) {
             const int row = 16 * c + lq + 4 * g;
             const double e = lt[4 * g * PP];
-            if (row < n && col < n && (zero_upper || col <= row)) tb[(size_t)g * 4 * LD + lane_idx] = e;
+            if ((FULL || (row < n && col < n)) && (zero_upper || col <= row)) tb[(size_t)g * 4 * LD + lane_idx] = e;
           }
         }
       };
@@ -1103,6 +1119,21 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
 
   // ---- scalars: quad, logdet (panel wave), then alpha by blocked back-substitution
   STAMP(15);
+  // (full-tile instance: the thread's indices are worked out again for the tail, from a copy of threadIdx.x the compiler cannot
+  //  trace back.  Held from the top of the kernel, lane, lc and lq were the three values its register allocation kept in scratch
+  //  across the panel loop -- stores at the kernel's entry, in front of the loop-exit barrier, where the first attempt must not
+  //  touch scratch.)
+  const int lane_top = lane, lc_top = lc, lq_top = lq;
+  {
+  int tid_tail = tid;
+  if constexpr (FULL) {
+    tid_tail = (int)threadIdx.x;
+    asm volatile("" : "+v"(tid_tail));
+  }
+  const int tid = tid_tail;   // (shadows: the tail below sees these four)
+  const int lane = FULL ? (tid_tail & 63) : lane_top;
+  const int lc = FULL ? (lane & 15) : lc_top;
+  const int lq = FULL ? (lane >> 4) : lq_top;
 #if defined(SCAML_STAMPS_PER_PANEL) && !defined(SCAML_STAMPS_ONE_PANEL)
   if (!is_panel) { st_acc[14] = __builtin_amdgcn_s_memtime() - st_prev; }   // loop left (slot 14 = U1(14) never runs... overwritten on purpose)
 #endif
@@ -1275,6 +1306,7 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
       for (int r = tid; r < n; r += NTHREADS) p.alpha[(size_t)task * b.sy((size_t)N) + r] = dl[r];
     }
   }
+  }
   STAMP(10);
 #if defined(SCAML_STAMPS_PER_PANEL) && !defined(SCAML_STAMPS_ONE_PANEL)
   if (!is_panel) { st_acc[15] = __builtin_amdgcn_s_memtime() - st_prev; }   // end of the attempt
@@ -1283,22 +1315,22 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   return fail;
 }
 
-template <int NB, int WU, int KIND, bool BLK>
+template <int NB, int WU, int KIND, bool BLK, bool FULL>
 __device__ __noinline__ int gp_fit_retry(const FitParams& p, const double jitter, const FitBlk<BLK> b) {
-  return gp_fit_attempt<NB, WU, KIND, BLK>(p, jitter, b);
+  return gp_fit_attempt<NB, WU, KIND, BLK, FULL>(p, jitter, b);
 }
 
-template <int NB, int WU, int KIND, bool BLK>
+template <int NB, int WU, int KIND, bool BLK, bool FULL>
 __device__ __forceinline__ void gp_fit_main(const FitParams& p, const FitBlk<BLK> b) {
   // jitter escalation of linear_operator's psd_safe_cholesky, per task, without leaving the GPU
   double jitter = 0.0;
-  int fail = gp_fit_attempt<NB, WU, KIND, BLK>(p, 0.0, b);
+  int fail = gp_fit_attempt<NB, WU, KIND, BLK, FULL>(p, 0.0, b);
 #ifndef SCAML_STAMPS  // (the diagnostic build times the first attempt only)
   if (fail && !(p.flags & SCAML_FIT_NO_RETRY)) {
     const FitParams pc = p;  // only this cold copy has its address taken; `p` stays in the kernarg segment
     for (int attempt = 1; attempt < 4 && fail; ++attempt) {
       jitter = attempt == 1 ? 1e-8 : (attempt == 2 ? 1e-7 : 1e-6);
-      fail = gp_fit_retry<NB, WU, KIND, BLK>(pc, jitter, b);
+      fail = gp_fit_retry<NB, WU, KIND, BLK, FULL>(pc, jitter, b);
     }
   }
 #endif
@@ -1315,25 +1347,30 @@ __device__ __forceinline__ void gp_fit_main(const FitParams& p, const FitBlk<BLK
   }
 }
 
-template <int NB, int WU, int KIND>
+template <int NB, int WU, int KIND, bool FULL>
 __global__ __launch_bounds__((WU + 1) * 64) void gp_fit_fused_kernel(FitParams p) {
-  gp_fit_main<NB, WU, KIND, false>(p, FitBlk<false>{});
+  gp_fit_main<NB, WU, KIND, false, FULL>(p, FitBlk<false>{});
 }
 
 // the same fit in place on a diagonal block of a larger task (strided addressing; tasks may be switched off)
 template <int NB, int WU, int KIND>
 __global__ __launch_bounds__((WU + 1) * 64) void gp_fit_blocked_kernel(FitParams p, FitBlockParams bp) {
   if (bp.active && bp.active[blockIdx.x] == 0) return;   // (jitter rounds: this task is already done)
-  gp_fit_main<NB, WU, KIND, true>(p, FitBlk<true>{bp});
+  gp_fit_main<NB, WU, KIND, true, false>(p, FitBlk<true>{bp});
 }
 
 }  // namespace scaml
 
 // Explicit instantiations: one kernel per padded size class (NB 16-blocks, WU update waves) and
 // kernel kind (see VGPR_CAPS in __graft_entry__.py for the register budgets).
+// The full-tile instances are compiled from csrc/gp_fit_fused_full.hip, which includes this file with SCAML_FIT_FULL_TU
+// defined: a translation unit of their own, because this kernel's register allocation follows everything else that is
+// compiled with it (profiles/full_instance_notes.md: with both in one unit the generic instance measured 0.4-0.7 us slower
+// from the same LLVM IR).
+#ifndef SCAML_FIT_FULL_TU
 #define SCAML_INSTANTIATE(NB, WU)                                                   \
-  template __global__ void scaml::gp_fit_fused_kernel<NB, WU, 0>(scaml::FitParams); \
-  template __global__ void scaml::gp_fit_fused_kernel<NB, WU, 1>(scaml::FitParams); \
+  template __global__ void scaml::gp_fit_fused_kernel<NB, WU, 0, false>(scaml::FitParams); \
+  template __global__ void scaml::gp_fit_fused_kernel<NB, WU, 1, false>(scaml::FitParams); \
   template __global__ void scaml::gp_fit_blocked_kernel<NB, WU, 0>(scaml::FitParams, scaml::FitBlockParams); \
   template __global__ void scaml::gp_fit_blocked_kernel<NB, WU, 1>(scaml::FitParams, scaml::FitBlockParams);
 SCAML_INSTANTIATE(2, 1)
@@ -1341,3 +1378,8 @@ SCAML_INSTANTIATE(4, 3)
 SCAML_INSTANTIATE(8, 3)
 SCAML_INSTANTIATE(8, 7)   // wide variant for N <= 128: one workgroup per CU, used when the tasks do not fill the CUs twice
 SCAML_INSTANTIATE(16, 7)
+#else
+// the full-tile instance (N == 256, every point valid, kernel-matrix mode, dense 16-byte aligned L): the flagship shape
+template __global__ void scaml::gp_fit_fused_kernel<16, 7, 0, true>(scaml::FitParams);
+template __global__ void scaml::gp_fit_fused_kernel<16, 7, 1, true>(scaml::FitParams);
+#endif

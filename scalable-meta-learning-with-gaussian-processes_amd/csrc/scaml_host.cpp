@@ -65,6 +65,7 @@ struct Module {
   hipModule_t mod = nullptr;
   std::atomic<int> num_cus{0};
   FitVariant fit[scaml::FIT_INSTANCES] = {};   // (NB, WU) of each: scaml::fit_instance
+  hipFunction_t fit_full[2] = {};              // the full-tile instance of <16, 7> per kind: scaml::fit_full_instance
   hipFunction_t post[2] = {}, post_cov[2] = {}, post_linv[2] = {}, post_linv_cov[2] = {}, post_linv_grad[2] = {};
   hipFunction_t wsum = nullptr, linv = nullptr, chosolve = nullptr, kmat[2] = {}, mllgrad[2] = {};
   hipFunction_t tgt_assemble[2] = {}, tgt_finish = nullptr, tgt_fit = nullptr, tgt_fit_batched = nullptr, tgt_grad[2] = {};
@@ -146,9 +147,10 @@ struct Module {
     };
     for (int i = 0; i < scaml::FIT_INSTANCES; ++i) {   // the kernels use up to the full 160 KiB of LDS
       const scaml::FitInstance v = scaml::fit_instance(i);
-      rows.push_back({fit[i].fn[0], "_ZN5scaml19gp_fit_fused_kernelILi%dELi%dELi%dEEEvNS_9FitParamsE", kLdsLimit, {{1, {v.nb}}, {1, {v.wu}}, K}});
+      rows.push_back({fit[i].fn[0], "_ZN5scaml19gp_fit_fused_kernelILi%dELi%dELi%dELb0EEEvNS_9FitParamsE", kLdsLimit, {{1, {v.nb}}, {1, {v.wu}}, K}});
       rows.push_back({fit[i].fn[1], "_ZN5scaml21gp_fit_blocked_kernelILi%dELi%dELi%dEEEvNS_9FitParamsENS_14FitBlockParamsE", kLdsLimit, {{1, {v.nb}}, {1, {v.wu}}, K}});
     }
+    rows.push_back({fit_full, "_ZN5scaml19gp_fit_fused_kernelILi16ELi7ELi%dELb1EEEvNS_9FitParamsE", kLdsLimit, {K}});
     for (const KernelRow& r : rows) {
       hipFunction_t* slot = r.slot;
       for (int i = 0; i < r.ax[0].n; ++i) {
@@ -263,6 +265,9 @@ int scaml_debug_set_stamp_buffer(long long* buf) {
   hipDeviceptr_t sym = nullptr;
   size_t bytes = 0;
   if (hipModuleGetGlobal(&sym, &bytes, m->mod, "g_stamp_buf") != hipSuccess) return SCAML_E_BADARG;
+  if (hipMemcpyHtoD(sym, &buf, sizeof(buf)) != hipSuccess) return SCAML_E_LAUNCH;
+  // (the full-tile fit instances are a translation unit of their own, with a pointer of their own)
+  if (hipModuleGetGlobal(&sym, &bytes, m->mod, "g_stamp_buf_full") != hipSuccess) return SCAML_E_BADARG;
   return hipMemcpyHtoD(sym, &buf, sizeof(buf)) == hipSuccess ? 0 : SCAML_E_LAUNCH;
 }
 
@@ -279,7 +284,14 @@ static int fit_common(scaml::FitParams p, int kind, void* stream, const scaml::F
   const size_t lds = plan.lds_doubles * sizeof(double);
   if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
   struct { scaml::FitParams p; scaml::FitBlockParams b; } args{p, blk ? *blk : scaml::FitBlockParams{}};   // (kernarg layout: both 8-byte aligned)
-  return launch(m->fit[plan.variant].fn[blk ? 1 : 0][kind], dim3((unsigned)p.T), plan.block, lds, stream, "gp_fit_fused", args,
+  // the full-tile instance where the arguments satisfy its contract (pointer values only: nothing here touches the device).
+  // SCAML_FIT_NO_FULL (set, not empty, not "0"): never -- read at every launch, so that one process can run both instances on
+  // the same input by changing its environment between two calls (include/scaml_gp_debug.h)
+  const char* no_full = getenv("SCAML_FIT_NO_FULL");
+  const int full_mode = (no_full && no_full[0] && !(no_full[0] == '0' && !no_full[1])) ? 1 : 0;
+  const bool full = scaml::fit_full_instance(plan.nb, plan.wu, p.N, p.n_points != nullptr, p.A_in != nullptr, blk != nullptr,
+                                             (p.flags & SCAML_FIT_STORE_L) != 0, (size_t)p.L, full_mode);
+  return launch(full ? m->fit_full[kind] : m->fit[plan.variant].fn[blk ? 1 : 0][kind], dim3((unsigned)p.T), plan.block, lds, stream, "gp_fit_fused", args,
                 blk ? sizeof(args) : sizeof(p));
 }
 
