@@ -861,6 +861,72 @@ int scaml_studies_fantasy_condition_f64(const double* L, const double* resid, co
                                         const int32_t* info, const double* eps, const int32_t* n_fant, const double* m_all, const double* s_all,
                                         int G, int n_max, int p_max, int F_max, double* alpha_f, double* y_fant, double* mu_p, void* stream);
 
+/*
+ * (7s), (7t) The OPTIMISER of the joint q-point acquisition (5g) / (7p) / (7q) on the device: a box-constrained L-BFGS per start
+ * batch (scamlgp_amd.bo with joint_opt_mode="device"; the default runs scipy L-BFGS-B on the host around every evaluation).  A start
+ * is one batch of q points, P = q D <= scaml_qacqf_opt_max_p() = 128 variables.  The state machine is (7h)'s (csrc/gp_lbfgs_core.h,
+ * the box instance) with two variables per lane (csrc/gp_qacqf_opt.hip: one wave per SLOT, no LDS); every dot product adds variable 0
+ * first, ascending, and no product is contracted, so that, given the same evaluations, the iterates are hyper.batched_lbfgs(bounds=)'s
+ * bit for bit.  It MAXIMISES.
+ *
+ * The slot table.  slots (Bs) int32, distinct entries within [0, B) (NULL: the identity, Bs == B): slot s works on start slots[s].  It
+ * reads value[s] / grad[s, :P], advances state[slots[s]], writes the next trial batch to Xq[s, :P] -- Xq (Bs, q D) IS the (Bs q, D)
+ * array the evaluation kernels read -- and the accepted point, its value and the counters to x / f / stats[slots[s]].  Starts that are
+ * not in the table are not touched.  A start that stops inside a call keeps its slot until the call ends (its row of Xq is its accepted
+ * point, what comes back for it is ignored); the caller reads stats between calls anyway and hands the next call the table of the
+ * starts still running, so that the cost of a round follows them without a live table inside (5g) / (7p).  An entry outside [0, B) is
+ * skipped.
+ *
+ * (7t) scaml_qacqf_opt_step_f64: the step alone, on the caller's evaluation -- a device-side box L-BFGS for ANY function of P <= 128
+ * variables per start.  mode 0: the start x0[slots[s]] projected onto the box is the accepted point and the first trial, the state is
+ * reset.  mode 1: one evaluation (value (Bs), grad (Bs, P), of the maximised function at Xq) is consumed.  mode 2: neither; the outputs
+ * are written again from the state as it is -- the first launch after the table has changed, which puts the trial points in its order.
+ *   x0 (B, P); lo, hi (P): the box, lo <= hi; state (B, scaml_qacqf_opt_step_workspace_bytes(B, P, history) / (8 B)) doubles per start in
+ *   the layout given under (9); x (B, P), f (B) (-inf for a failed start), stats (B, 4) int32 as (7h).  max_iter, history <= 16, max_ls,
+ *   gtol, ftol, c1: as (7h).
+ *   Checks: B, Bs < 0, Bs > B, slots NULL with Bs != B, P < 1, mode, max_iter < 0, max_ls < 1, history outside 1 .. 16, a NULL pointer
+ *   (x0 in mode 0; value, grad in mode 1), gtol < 0 or NaN, c1 <= 0, ftol NaN: SCAML_E_BADARG.  P > 128, B > 2^26: SCAML_E_TOOLARGE (bad
+ *   arguments answer first).  Bs == 0: nothing is enqueued.  One launch, does not synchronise.
+ *
+ * (7s) scaml_qacqf_opt_f64: n_evals rounds enqueued on `stream` with (7h)'s contract -- no graph, nothing is synchronised, every
+ * argument and size checked once before the first launch (SCAML_E_BADARG answers before SCAML_E_TOOLARGE), SCAML_ACQF_OPT_CONTINUE
+ * resumes, B == 0, Bs == 0 or n_evals == 0 enqueues nothing, SCAML_E_LAUNCH from a later round leaves the rounds before it enqueued.
+ * A call opens with the step in mode 0 (mode 2 when it continues) and the training block of the joint prior; a round is then, at
+ * Mq = Bs q points and with the arguments scamlgp_amd.model.ScaMLGP.joint_acqf_inputs hands them: the value pass
+ * scaml_posterior_linv_f64 with V kept, (5g), scaml_weighted_prior_reduce_f64 and scaml_weighted_task_sum_f64, the gather (column 0 of
+ * every point's 16 of mu_g, var_g and of rows a < n of cov_g go behind the training block of mean_s, var_s (n + Mq), cov_s (n, n + Mq),
+ * the points into xall[n:]), scaml_target_assemble_f64, scaml_cho_solve_batched_f64 against the caller's target factor, (7p) -- (7q)
+ * when p > 0 --, the step.
+ *   x0 (B, q D); slots (Bs) or NULL;
+ *   Xa (n + p, D), X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, VA (T, N, n + p): the source stack and the leading points as
+ *       (5g) takes them (the pending points behind the training inputs); w (T), active (T) or NULL: as (6);
+ *   mu_t (n), cov_tt (n, n), var_t (n): the weighted source sums at the training inputs;
+ *   Xt (n, D), theta_t (D + 2), targets (n) standardised, L (n, n), Linv_diag, alpha_t (n), info (1) or NULL: the target GP and the
+ *       factor of its training block as (2) leaves it; m_all, s_all.  info[0] != 0: every start fails at its first evaluation (status 4);
+ *   base_samples (S, q + p); Xp (p, D), Zp (n, p), mu_p (p), Sigma_pp (p, p): as (7q) takes them, read when p > 0;
+ *   acqf, acqf_param: as (7p); lo, hi (q D): the box; the optimiser's options as (7h).
+ *   workspace: scaml_qacqf_opt_workspace_bytes(B, n, p, q, T, N, D, history) bytes (0 for shapes the call does not take), 16-byte
+ *       aligned; it starts with the per-start state, P = q D; the evaluation arrays behind it are packed at the call's Bs.
+ * Limits: those of (5g) / (7p) / (7q) -- q + p <= 8, n + p + q <= 96 and <= N, S <= 512, D <= 15, N <= scaml_posterior_max_n() --,
+ * history <= 16, B <= 2^20.  The evaluations of a round scatter by the source pass's float atomics: between runs and chunkings the
+ * results agree to rounding, not bit for bit.
+ */
+int scaml_qacqf_opt_max_p(void);
+long long scaml_qacqf_opt_step_workspace_bytes(int B, int P, int history);
+long long scaml_qacqf_opt_workspace_bytes(int B, int n, int p, int q, int T, int N, int D, int history);
+int scaml_qacqf_opt_step_f64(const double* value, const double* grad, const int32_t* slots, const double* x0, const double* lo, const double* hi,
+                             int B, int Bs, int P, int mode, int max_iter, int history, int max_ls, double gtol, double ftol, double c1,
+                             double* state, double* Xq, double* x, double* f, int32_t* stats, void* stream);
+int scaml_qacqf_opt_f64(const double* x0, const int32_t* slots, const double* Xa, const double* X, const double* theta_s, const double* Linv,
+                        const double* alpha_s, const double* y_mean, const double* y_std, const int32_t* n_points_s, const double* VA,
+                        const double* w, const uint8_t* active, const double* mu_t, const double* cov_tt, const double* var_t, const double* Xt,
+                        const double* theta_t, const double* targets, const double* L, const double* Linv_diag, const double* alpha_t,
+                        double m_all, double s_all, const int32_t* info, const double* base_samples, const double* Xp, const double* Zp,
+                        const double* mu_p, const double* Sigma_pp, int B, int Bs, int n, int p, int q, int S, int T, int N, int D, int kind_s,
+                        int kind_t, int acqf, double acqf_param, const double* lo, const double* hi, int max_iter, int history, int max_ls,
+                        double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace, long long workspace_bytes, double* x,
+                        double* f, int32_t* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 // gp_lbfgs_core.h -- the L-BFGS state machine of the two device-side optimisers: one wave per problem, one lane per variable, the
-// state in the caller's workspace, one evaluation consumed per call, no LDS.  Two instances:
+// state in the caller's workspace, one evaluation consumed per call, no LDS.  Three instances:
 //   BOX = false   csrc/gp_stack_fit.hip: hyper.batched_lbfgs, the unconstrained fit of the source stack's hyper-parameters
 //   BOX = true    csrc/gp_acqf_opt.h:    hyper._batched_lbfgs_box, the projected optimiser of the acquisition function
+//   BOX = true    csrc/gp_qacqf_opt.h:   the same for the joint q-point acquisition, q D <= 128 variables, two per lane
 // What differs between them (the eight rows of DESIGN.md 4h's table) is an `if constexpr (BOX)` below or the reduction `R` the
 // instance hands in:
 //   R::NV                a lane's variables (i = lane, lane + LBFGS_LANES, ... < P live in arrays of NV entries)
@@ -51,6 +52,11 @@ struct LbfgsResult {
   double f;
   int it, n_eval, status, hist;
 };
+
+// A flag per variable of a lane: a bool where a lane has one variable; an int where it has several -- an array of bools indexed by
+// the loop variable is kept in scratch memory, an array of ints in registers.
+template <int NV> struct LbfgsFlag { typedef int type; };
+template <> struct LbfgsFlag<1> { typedef bool type; };
 
 LBFGS_DEV bool lbfgs_finite(double x) { return x - x == 0.0; }
 // min(max(v, lo), hi) that keeps a NaN
@@ -165,7 +171,7 @@ LBFGS_DEV LbfgsResult lbfgs_advance(double* st, const double* lo, const double* 
     ls = 0;
     // BOX: coordinates held by a bound (at it, and -g points out of the box) take no part in the direction
     double q[R::NV] = {0.0}, gfree[R::NV] = {0.0}, al[LBFGS_HMAX];
-    bool held[R::NV] = {false};
+    typename LbfgsFlag<R::NV>::type held[R::NV] = {};
     LBFGS_FOR(i, P) {
       if constexpr (BOX) held[LBFGS_AT(i)] = (x[i] <= lo[i] && g[i] > 0.0) || (x[i] >= hi[i] && g[i] < 0.0);
       gfree[LBFGS_AT(i)] = held[LBFGS_AT(i)] ? 0.0 : g[i];

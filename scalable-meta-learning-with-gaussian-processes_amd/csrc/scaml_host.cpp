@@ -22,6 +22,7 @@
 #include "gp_stack_fit_params.h"
 #include "gp_studies_acqf.h"   // (argument block and LDS footprint; its arithmetic is not called here)
 #include "gp_acqf_opt.h"       // (argument block and state stride; likewise)
+#include "gp_qacqf_opt.h"      // (likewise: the joint optimiser's step and gather blocks)
 #include "gp_studies_score.h"  // (likewise: the strip scoring kernel's LDS footprint, the train-block arguments)
 #include <math.h>
 
@@ -82,6 +83,7 @@ struct Module {
   hipFunction_t tgt_fantasy_acqf_batched = nullptr, tgt_fantasy_score_batched = nullptr;   // both with pending evaluations (7k)
   hipFunction_t cond_block = nullptr, cond_fantasy = nullptr;   // the batched fantasy set-up of studies with pending evaluations (7m), (7n)
   hipFunction_t blk_round = nullptr, blk_finish = nullptr, coop[2] = {}, stack_step = nullptr, acqf_opt_step = nullptr;
+  hipFunction_t qacqf_opt_step = nullptr, qacqf_opt_gather = nullptr;   // the joint acquisition's optimiser: step (7t), gather of a round (7s)
   hipFunction_t blk_solve[2][2] = {}, blk_syrk[2] = {};   // solve: [kind][D <= 8]
   hipFunction_t mllgrad_fused[4][2][2] = {};   // [size class NBT = 2, 4, 8, 16][kind][LDS-DMA staging]
   hipFunction_t mllgrad_split[2][2][2] = {};   // LDS-DMA staging, [N <= 128 | N <= 256 class][kind][2 | 4 workgroups per task]
@@ -140,6 +142,8 @@ struct Module {
         {coop, "_ZN5scaml18gp_fit_coop_kernelILi%dEEEvNS_13CoopFitParamsE", kLdsLimit, {K}},
         {&stack_step, "scaml_stack_fit_step_kernel", 0, {}},
         {&acqf_opt_step, "scaml_acqf_opt_step_kernel", 0, {}},
+        {&qacqf_opt_step, "scaml_qacqf_opt_step_kernel", 0, {}},
+        {&qacqf_opt_gather, "scaml_qacqf_opt_gather_kernel", 0, {}},
         {&blk_round, "scaml_blocked_round_kernel", 0, {}},
         {&blk_finish, "scaml_blocked_finish_kernel", 0, {}},
         {&blk_solve[0][0], "_ZN5scaml23gp_blocked_solve_kernelILi%dELb%dEEEvNS_16BlockedFitParamsE", kLdsLimit, {K, B}},
@@ -465,15 +469,24 @@ int scaml_posterior_cov_f64(const double* Xq, const double* theta, const double*
 }
 
 // ---- (6) weighted sum over tasks ---------------------------------------------------------------
-int scaml_weighted_task_sum_f64(const double* in, const double* w, const uint8_t* active, int T, long long len,
-                                int power, double* out, void* stream) {
+// (check and launch apart, here and below for every launch of a joint acquisition round: (7s) checks each once and launches it per round)
+static int wsum_check(const double* in, const double* w, int T, long long len, int power, const double* out) {
   if (T < 0 || len < 0 || (power != 1 && power != 2)) return SCAML_E_BADARG;
   if (!in || !w || !out) return SCAML_E_BADARG;
+  return SCAML_OK;
+}
+static int wsum_launch(Module& m, const double* in, const double* w, const uint8_t* active, int T, long long len, int power, double* out,
+                       void* stream) {   // checked, len > 0
+  void* args[] = {(void*)&in, (void*)&w, (void*)&active, (void*)&T, (void*)&len, (void*)&power, (void*)&out};
+  return launch_args(m.wsum, dim3((unsigned)((len + 63) / 64)), 256, stream, "weighted_task_sum", args);
+}
+int scaml_weighted_task_sum_f64(const double* in, const double* w, const uint8_t* active, int T, long long len,
+                                int power, double* out, void* stream) {
+  if (const int rc = wsum_check(in, w, T, len, power, out)) return rc;
   if (len == 0) return SCAML_OK;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
-  void* args[] = {(void*)&in, (void*)&w, (void*)&active, (void*)&T, (void*)&len, (void*)&power, (void*)&out};
-  return launch_args(m->wsum, dim3((unsigned)((len + 63) / 64)), 256, stream, "weighted_task_sum", args);
+  return wsum_launch(*m, in, w, active, T, len, power, out, stream);
 }
 
 // ---- (1) stand-alone kernel matrix ---------------------------------------------------------------
@@ -492,20 +505,27 @@ int scaml_kernel_matrix_f64(const double* X1, const double* X2, const double* th
 }
 
 // ---- batched Cholesky solve ----------------------------------------------------------------------
+static int cho_solve_check(const scaml::ChoSolveParams& p) {
+  if (p.T < 0 || p.N < 1 || p.R < 0) return SCAML_E_BADARG;
+  if (!p.L || !p.Linv_diag || !p.B || !p.Xout) return SCAML_E_BADARG;
+  if (p.N > scaml_posterior_max_n()) return SCAML_E_TOOLARGE;
+  return SCAML_OK;
+}
+static int cho_solve_launch(Module& m, scaml::ChoSolveParams& p, void* stream) {   // a checked, non-empty block
+  const int nb = (p.N + 15) / 16, np = nb * 16, strips = (p.R + 15) / 16;
+  int waves = scaml::strip_solve_waves(np);
+  if (waves > strips) waves = strips;
+  return launch(m.chosolve, dim3((unsigned)((strips + waves - 1) / waves), (unsigned)p.T), (unsigned)waves * 64,
+                scaml::strip_solve_lds_doubles(np, waves) * sizeof(double), stream, "gp_cho_solve", p);
+}
 static int cho_solve_common(const double* L, const double* Linv_diag, const double* B, const int32_t* n_points,
                            int T, int N, int R, double* Xout, int mode, void* stream) {
-  if (T < 0 || N < 1 || R < 0) return SCAML_E_BADARG;
-  if (!L || !Linv_diag || !B || !Xout) return SCAML_E_BADARG;
-  if (N > scaml_posterior_max_n()) return SCAML_E_TOOLARGE;
+  scaml::ChoSolveParams p{L, Linv_diag, B, n_points, Xout, T, N, R, mode};
+  if (const int rc = cho_solve_check(p)) return rc;
   if (T == 0 || R == 0) return SCAML_OK;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
-  const int nb = (N + 15) / 16, np = nb * 16, strips = (R + 15) / 16;
-  int waves = scaml::strip_solve_waves(np);
-  if (waves > strips) waves = strips;
-  scaml::ChoSolveParams p{L, Linv_diag, B, n_points, Xout, T, N, R, mode};
-  return launch(m->chosolve, dim3((unsigned)((strips + waves - 1) / waves), (unsigned)T), (unsigned)waves * 64,
-                scaml::strip_solve_lds_doubles(np, waves) * sizeof(double), stream, "gp_cho_solve", p);
+  return cho_solve_launch(*m, p, stream);
 }
 
 int scaml_cho_solve_batched_f64(const double* L, const double* Linv_diag, const double* B, const int32_t* n_points,
@@ -560,29 +580,41 @@ int scaml_linv_batched_lower_f64(const double* L, const double* Linv_diag, const
   return linv_batched(L, Linv_diag, n_points, T, N, Linv, stream, 1);
 }
 
+// The inverse-factor pass's block (L = Linv; Ma = 0 without VA): the arguments, then the LDS strip, then the launch.
+static int posterior_linv_check(const scaml::PosteriorParams& p, int kind, unsigned flags, bool grad) {
+  if (p.T < 0 || p.N < 1 || p.M < 0 || p.D < 1) return SCAML_E_BADARG;
+  if (!p.Xq || !p.X || !p.theta || !p.L || !p.alpha) return SCAML_E_BADARG;
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (flags & SCAML_POST_MEAN_ONLY) return SCAML_E_BADARG;   // (use scaml_posterior_batched_f64 for that)
+  if (p.N > scaml_posterior_max_n()) return SCAML_E_TOOLARGE;
+  if (p.VA && (!p.cov || p.Ma < 1 || (!grad && p.Ma > p.M))) return SCAML_E_BADARG;
+  if (p.VA && (p.Ma > 96 || p.Ma > p.N)) return SCAML_E_TOOLARGE;      // six 16-point strips of leading query points at most
+  return SCAML_OK;
+}
+static int posterior_linv_fits(const scaml::PosteriorParams& p) {
+  return scaml::posterior_linv_lds_doubles(p.N, p.D) * sizeof(double) > kLdsLimit ? SCAML_E_TOOLARGE : SCAML_OK;
+}
+static int posterior_linv_launch(Module& m, scaml::PosteriorParams& p, int kind, bool grad, void* stream) {   // a checked, non-empty block that fits
+  const size_t lds = scaml::posterior_linv_lds_doubles(p.N, p.D) * sizeof(double);
+  const unsigned strips = (unsigned)((p.M + 15) / 16);
+  const unsigned blocks = (unsigned)(((p.T + 7) / 8) * 8) * strips;   // XCD-aware (task, strip) map inside the kernel
+  return launch(grad ? m.post_linv_grad[kind] : (p.VA ? m.post_linv_cov[kind] : m.post_linv[kind]), dim3(blocks), 512, lds, stream,
+                "gp_posterior_linv", p);
+}
+
 static int posterior_linv_common(const double* Xq, const double* X, const double* theta, const double* Linv, const double* alpha,
                                  const double* y_mean, const double* y_std, const int32_t* n_points, const double* VA, int T, int N,
                                  int M, int Ma, int D, int kind, double* mu, double* var, double* V, double* cov, unsigned flags,
                                  void* stream, bool grad = false, const double* Xa = nullptr) {
-  if (T < 0 || N < 1 || M < 0 || D < 1) return SCAML_E_BADARG;
-  if (!Xq || !X || !theta || !Linv || !alpha) return SCAML_E_BADARG;
-  if (!valid_kind(kind)) return SCAML_E_BADARG;
-  if (flags & SCAML_POST_MEAN_ONLY) return SCAML_E_BADARG;   // (use scaml_posterior_batched_f64 for that)
-  if (N > scaml_posterior_max_n()) return SCAML_E_TOOLARGE;
-  if (VA && (!cov || Ma < 1 || (!grad && Ma > M))) return SCAML_E_BADARG;
-  if (VA && (Ma > 96 || Ma > N)) return SCAML_E_TOOLARGE;      // six 16-point strips of leading query points at most
-  if (T == 0 || M == 0) return SCAML_OK;
-  Module* m = ready();
-  if (!m) return SCAML_E_LAUNCH;
-  const size_t lds = scaml::posterior_linv_lds_doubles(N, D) * sizeof(double);
-  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
   // (x_in_lds = 0: the task's points are MFMA operands read from memory, nothing to stage)
   scaml::PosteriorParams p{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, V, T, N, M, D, 0,
                            (flags & SCAML_POST_XQ_PER_TASK) ? 1 : 0, 0, VA, cov, VA ? Ma : 0, 0, Xa};
-  const unsigned strips = (unsigned)((M + 15) / 16);
-  const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * strips;   // XCD-aware (task, strip) map inside the kernel
-  return launch(grad ? m->post_linv_grad[kind] : (VA ? m->post_linv_cov[kind] : m->post_linv[kind]), dim3(blocks), 512, lds, stream,
-                "gp_posterior_linv", p);
+  if (const int rc = posterior_linv_check(p, kind, flags, grad)) return rc;
+  if (T == 0 || M == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  if (const int rc = posterior_linv_fits(p)) return rc;
+  return posterior_linv_launch(*m, p, kind, grad, stream);
 }
 
 int scaml_posterior_linv_f64(const double* Xq, const double* X, const double* theta, const double* Linv, const double* alpha,
@@ -616,28 +648,44 @@ int scaml_posterior_linv_grad_f64(const double* Xq, const double* Xa, const doub
 int scaml_qacqf_max_q(void) { return scaml::QACQF_MAX_Q; }
 int scaml_qacqf_max_samples(void) { return scaml::QACQF_MAX_SAMPLES; }
 
+// (5g)'s block: base.M = 16 columns per query point (saturated: the check refuses what does not fit), Mq handed on beside it
+static scaml::PosteriorJointParams grad_joint_block(const double* Xq, const double* Xa, const double* X, const double* theta, const double* Linv,
+                                                    const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points,
+                                                    const double* VA, const double* VQ, int T, int N, int Mq, int Ma, int q, int D, double* mu,
+                                                    double* var, double* cov, unsigned flags) {
+  const long long M = 16LL * Mq;
+  return scaml::PosteriorJointParams{{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N,
+                                      M > INT32_MAX ? INT32_MAX : (int)M, D, 0, (flags & SCAML_POST_XQ_PER_TASK) ? 1 : 0, 0, VA, cov, Ma, 0, Xa},
+                                     {VQ, q, 0}};
+}
+static int grad_joint_check(const scaml::PosteriorJointParams& p, int Mq, int kind, unsigned flags) {
+  const scaml::PosteriorParams& b = p.base;
+  const int q = p.ja.q;
+  if (b.T < 0 || b.N < 1 || Mq < 0 || b.Ma < 1 || q < 1 || b.D < 1 || Mq % q != 0) return SCAML_E_BADARG;
+  if (!b.Xq || !b.Xa || !b.X || !b.theta || !b.L || !b.alpha || !b.VA || !p.ja.VQ || !b.cov) return SCAML_E_BADARG;
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (flags & SCAML_POST_MEAN_ONLY) return SCAML_E_BADARG;
+  if (b.D > 15 || q > scaml::QACQF_MAX_Q || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
+  if (b.N > scaml_posterior_max_n()) return SCAML_E_TOOLARGE;
+  if (b.Ma + q > scaml::QACQF_MAX_ROWS || b.Ma + q > b.N) return SCAML_E_TOOLARGE;   // six 16-row strips of the covariance block, staged in the N x 16 LDS strip
+  return posterior_linv_fits(b);
+}
+static int grad_joint_launch(Module& m, scaml::PosteriorJointParams& p, int Mq, int kind, void* stream) {   // a checked, non-empty block
+  const size_t lds = scaml::posterior_linv_lds_doubles(p.base.N, p.base.D) * sizeof(double);
+  const unsigned blocks = (unsigned)(((p.base.T + 7) / 8) * 8) * (unsigned)Mq;   // XCD-aware (task, strip) map inside the kernel, a strip per query point
+  return launch(m.post_linv_grad_joint[kind], dim3(blocks), 512, lds, stream, "gp_posterior_linv_joint", p);
+}
+
 int scaml_posterior_linv_grad_joint_f64(const double* Xq, const double* Xa, const double* X, const double* theta, const double* Linv,
                                         const double* alpha, const double* y_mean, const double* y_std, const int32_t* n_points,
                                         const double* VA, const double* VQ, int T, int N, int Mq, int Ma, int q, int D, int kind, double* mu,
                                         double* var, double* cov, unsigned flags, void* stream) {
-  if (T < 0 || N < 1 || Mq < 0 || Ma < 1 || q < 1 || D < 1 || Mq % q != 0) return SCAML_E_BADARG;
-  if (!Xq || !Xa || !X || !theta || !Linv || !alpha || !VA || !VQ || !cov) return SCAML_E_BADARG;
-  if (!valid_kind(kind)) return SCAML_E_BADARG;
-  if (flags & SCAML_POST_MEAN_ONLY) return SCAML_E_BADARG;
-  if (D > 15 || q > scaml::QACQF_MAX_Q || Mq > (1 << 26)) return SCAML_E_TOOLARGE;
-  if (N > scaml_posterior_max_n()) return SCAML_E_TOOLARGE;
-  if (Ma + q > scaml::QACQF_MAX_ROWS || Ma + q > N) return SCAML_E_TOOLARGE;   // six 16-row strips of the covariance block, staged in the N x 16 LDS strip
-  const size_t lds = scaml::posterior_linv_lds_doubles(N, D) * sizeof(double);
-  if (lds > kLdsLimit) return SCAML_E_TOOLARGE;
+  scaml::PosteriorJointParams p = grad_joint_block(Xq, Xa, X, theta, Linv, alpha, y_mean, y_std, n_points, VA, VQ, T, N, Mq, Ma, q, D, mu, var, cov, flags);
+  if (const int rc = grad_joint_check(p, Mq, kind, flags)) return rc;
   if (T == 0 || Mq == 0) return SCAML_OK;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
-  const int M = 16 * Mq;
-  scaml::PosteriorJointParams p{{Xq, X, theta, Linv, nullptr, alpha, y_mean, y_std, n_points, mu, var, nullptr, T, N, M, D, 0,
-                                 (flags & SCAML_POST_XQ_PER_TASK) ? 1 : 0, 0, VA, cov, Ma, 0, Xa},
-                                {VQ, q, 0}};
-  const unsigned blocks = (unsigned)(((T + 7) / 8) * 8) * (unsigned)Mq;   // XCD-aware (task, strip) map inside the kernel, a strip per query point
-  return launch(m->post_linv_grad_joint[kind], dim3(blocks), 512, lds, stream, "gp_posterior_linv_joint", p);
+  return grad_joint_launch(*m, p, Mq, kind, stream);
 }
 
 // ---- (4) gradient of the marginal log-likelihood ------------------------------------------------
@@ -676,20 +724,28 @@ int scaml_mll_backward_f64(const double* X, const double* theta, const double* L
 }
 
 // ---- target GP: assemble the joint prior block / finish the posterior (a10) -----------------------------------------
+static int target_assemble_check(const scaml::TargetAssembleParams& p, int kind) {
+  if (p.n < 1 || p.M < 0 || p.D < 1) return SCAML_E_BADARG;
+  if (!p.cov_s || !p.mean_s || !p.var_s || !p.Xall || !p.theta || !p.train_targets || !p.Knn || !p.resid) return SCAML_E_BADARG;
+  if (p.M > 0 && (!p.Knq || !p.mean_q || !p.var_q)) return SCAML_E_BADARG;
+  if (!valid_kind(kind)) return SCAML_E_BADARG;
+  if (!(p.s_all > 0.0)) return SCAML_E_BADARG;
+  return SCAML_OK;
+}
+static int target_assemble_launch(Module& m, scaml::TargetAssembleParams& p, int kind, void* stream) {   // a checked block
+  long long elems = (long long)p.n * (p.n + p.M);
+  if (elems < p.M) elems = p.M;
+  return launch(m.tgt_assemble[kind], dim3((unsigned)((elems + 255) / 256)), 256, 0, stream, "target_assemble", p);
+}
+
 int scaml_target_assemble_f64(const double* cov_s, const double* mean_s, const double* var_s, const double* Xall,
                               const double* theta, const double* train_targets, double m_all, double s_all, int n, int M, int D,
                               int kind, double* Knn, double* resid, double* Knq, double* mean_q, double* var_q, void* stream) {
-  if (n < 1 || M < 0 || D < 1) return SCAML_E_BADARG;
-  if (!cov_s || !mean_s || !var_s || !Xall || !theta || !train_targets || !Knn || !resid) return SCAML_E_BADARG;
-  if (M > 0 && (!Knq || !mean_q || !var_q)) return SCAML_E_BADARG;
-  if (!valid_kind(kind)) return SCAML_E_BADARG;
-  if (!(s_all > 0.0)) return SCAML_E_BADARG;
+  scaml::TargetAssembleParams p{cov_s, mean_s, var_s, Xall, theta, train_targets, m_all, s_all, Knn, resid, Knq, mean_q, var_q, n, M, D};
+  if (const int rc = target_assemble_check(p, kind)) return rc;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
-  scaml::TargetAssembleParams p{cov_s, mean_s, var_s, Xall, theta, train_targets, m_all, s_all, Knn, resid, Knq, mean_q, var_q, n, M, D};
-  long long elems = (long long)n * (n + M);
-  if (elems < M) elems = M;
-  return launch(m->tgt_assemble[kind], dim3((unsigned)((elems + 255) / 256)), 256, 0, stream, "target_assemble", p);
+  return target_assemble_launch(*m, p, kind, stream);
 }
 
 int scaml_target_finish_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q,
@@ -747,51 +803,71 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
 }
 
 // ---- (7p) joint q-point Monte-Carlo acquisition, qEI / qUCB, and its input gradient: a workgroup per batch (csrc/gp_qacqf.hip) ----
+static int qacqf_check(const scaml::QAcqfParams& p) {
+  if (p.n < 1 || p.Mq < 0 || p.q < 1 || p.S < 1 || p.D < 1 || p.Mq % p.q != 0) return SCAML_E_BADARG;
+  if (!p.Knq || !p.Z || !p.alpha || !p.mean_q || !p.var_q || !p.cov_g || !p.mu_g || !p.var_g || !p.Xt || !p.Xq || !p.theta || !p.base_samples || !p.value)
+    return SCAML_E_BADARG;
+  if (!scaml::qa_acqf_valid(p.acqf)) return SCAML_E_BADARG;   // (a joint LogEI is not defined: 17 and 0x10 are refused like 2)
+  if (!valid_kind(p.kind)) return SCAML_E_BADARG;
+  if (!(p.s_all > 0.0)) return SCAML_E_BADARG;
+  if (p.q > scaml::QACQF_MAX_Q || p.S > scaml::QACQF_MAX_SAMPLES || p.n + p.q > scaml::QACQF_MAX_ROWS || p.D > scaml::QACQF_MAX_D) return SCAML_E_TOOLARGE;
+  if (scaml::qacqf_plan(p.Mq / p.q, p.n, p.q, p.S).lds_doubles * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
+  return SCAML_OK;
+}
+static int qacqf_launch(Module& m, scaml::QAcqfParams& p, void* stream) {   // a checked, non-empty block
+  const scaml::QAcqfPlan plan = scaml::qacqf_plan(p.Mq / p.q, p.n, p.q, p.S);
+  return launch(m.tgt_qacqf, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "target_qacqf", p);
+}
+
 int scaml_target_qacqf_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q, double m_all,
                            double s_all, const int32_t* info, const double* cov_g, const double* mu_g, const double* var_g, const double* Xt,
                            const double* Xq, const double* theta, const double* base_samples, int acqf, double acqf_param, int n, int Mq, int q,
                            int S, int D, int kind, double* value, double* grad, double* jitter_used, int32_t* info_out, void* stream) {
-  if (n < 1 || Mq < 0 || q < 1 || S < 1 || D < 1 || Mq % q != 0) return SCAML_E_BADARG;
-  if (!Knq || !Z || !alpha || !mean_q || !var_q || !cov_g || !mu_g || !var_g || !Xt || !Xq || !theta || !base_samples || !value) return SCAML_E_BADARG;
-  if (!scaml::qa_acqf_valid(acqf)) return SCAML_E_BADARG;   // (a joint LogEI is not defined: 17 and 0x10 are refused like 2)
-  if (!valid_kind(kind)) return SCAML_E_BADARG;
-  if (!(s_all > 0.0)) return SCAML_E_BADARG;
-  if (q > scaml::QACQF_MAX_Q || S > scaml::QACQF_MAX_SAMPLES || n + q > scaml::QACQF_MAX_ROWS || D > scaml::QACQF_MAX_D) return SCAML_E_TOOLARGE;
-  const scaml::QAcqfPlan plan = scaml::qacqf_plan(Mq / q, n, q, S);
-  if (plan.lds_doubles * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
+  scaml::QAcqfParams p{Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples, acqf_param,
+                       value, grad, jitter_used, info_out, n, Mq, q, S, D, kind, acqf, 0};
+  if (const int rc = qacqf_check(p)) return rc;
   if (Mq == 0) return SCAML_OK;
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
-  scaml::QAcqfParams p{Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples, acqf_param,
-                       value, grad, jitter_used, info_out, n, Mq, q, S, D, kind, acqf, 0};
-  return launch(m->tgt_qacqf, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "target_qacqf", p);
+  return qacqf_launch(*m, p, stream);
 }
 
 // ---- (7q) (7p) with p evaluations pending behind every batch: the same workgroup per batch, the joint at q + p ----
+static int qacqf_pending_check(const scaml::QAcqfPendingParams& pp) {
+  const scaml::QAcqfParams& a = pp.a;
+  const int p = pp.pe.p;
+  if (a.n < 1 || a.Mq < 0 || a.q < 1 || p < 0 || a.S < 1 || a.D < 1 || a.Mq % a.q != 0) return SCAML_E_BADARG;
+  if (!a.Knq || !a.Z || !a.alpha || !a.mean_q || !a.var_q || !a.cov_g || !a.mu_g || !a.var_g || !a.Xt || !a.Xq || !a.theta || !a.base_samples || !a.value)
+    return SCAML_E_BADARG;
+  if (p > 0 && (!pp.pe.Xp || !pp.pe.Zp || !pp.pe.mu_p || !pp.pe.Sigma_pp)) return SCAML_E_BADARG;
+  if (!scaml::qa_acqf_valid(a.acqf)) return SCAML_E_BADARG;
+  if (!valid_kind(a.kind)) return SCAML_E_BADARG;
+  if (!(a.s_all > 0.0)) return SCAML_E_BADARG;
+  if (a.q > scaml::QACQF_MAX_Q || p > scaml::QACQF_MAX_Q || a.q + p > scaml::QACQF_MAX_Q || a.S > scaml::QACQF_MAX_SAMPLES ||
+      a.n > scaml::QACQF_MAX_ROWS || a.n + p + a.q > scaml::QACQF_MAX_ROWS || a.D > scaml::QACQF_MAX_D)
+    return SCAML_E_TOOLARGE;
+  if (scaml::qacqf_pending_plan(a.Mq / a.q, a.n, a.q, p, a.S).lds_doubles * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
+  return SCAML_OK;
+}
+static int qacqf_pending_launch(Module& m, scaml::QAcqfPendingParams& pp, void* stream) {   // a checked, non-empty block
+  const scaml::QAcqfPlan plan = scaml::qacqf_pending_plan(pp.a.Mq / pp.a.q, pp.a.n, pp.a.q, pp.pe.p, pp.a.S);
+  return launch(m.tgt_qacqf_pending, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "target_qacqf_pending", pp);
+}
+
 int scaml_target_qacqf_pending_f64(const double* Knq, const double* Z, const double* alpha, const double* mean_q, const double* var_q,
                                    double m_all, double s_all, const int32_t* info, const double* cov_g, const double* mu_g,
                                    const double* var_g, const double* Xt, const double* Xq, const double* theta, const double* base_samples,
                                    const double* Xp, const double* Zp, const double* mu_p, const double* Sigma_pp, int acqf,
                                    double acqf_param, int n, int Mq, int q, int p, int S, int D, int kind, double* value, double* grad,
                                    double* jitter_used, int32_t* info_out, void* stream) {
-  if (n < 1 || Mq < 0 || q < 1 || p < 0 || S < 1 || D < 1 || Mq % q != 0) return SCAML_E_BADARG;
-  if (!Knq || !Z || !alpha || !mean_q || !var_q || !cov_g || !mu_g || !var_g || !Xt || !Xq || !theta || !base_samples || !value) return SCAML_E_BADARG;
-  if (p > 0 && (!Xp || !Zp || !mu_p || !Sigma_pp)) return SCAML_E_BADARG;
-  if (!scaml::qa_acqf_valid(acqf)) return SCAML_E_BADARG;
-  if (!valid_kind(kind)) return SCAML_E_BADARG;
-  if (!(s_all > 0.0)) return SCAML_E_BADARG;
-  if (q > scaml::QACQF_MAX_Q || p > scaml::QACQF_MAX_Q || q + p > scaml::QACQF_MAX_Q || S > scaml::QACQF_MAX_SAMPLES ||
-      n > scaml::QACQF_MAX_ROWS || n + p + q > scaml::QACQF_MAX_ROWS || D > scaml::QACQF_MAX_D)
-    return SCAML_E_TOOLARGE;
-  const scaml::QAcqfPlan plan = scaml::qacqf_pending_plan(Mq / q, n, q, p, S);
-  if (plan.lds_doubles * sizeof(double) > kLdsLimit) return SCAML_E_TOOLARGE;
-  if (Mq == 0) return SCAML_OK;
-  Module* m = ready();
-  if (!m) return SCAML_E_LAUNCH;
   scaml::QAcqfPendingParams pp{{Knq, Z, alpha, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta, base_samples, acqf_param,
                                 value, grad, jitter_used, info_out, n, Mq, q, S, D, kind, acqf, 0},
                                {Xp, Zp, mu_p, Sigma_pp, p, 0}};
-  return launch(m->tgt_qacqf_pending, dim3(plan.grid), plan.block, plan.lds_doubles * sizeof(double), stream, "target_qacqf_pending", pp);
+  if (const int rc = qacqf_pending_check(pp)) return rc;
+  if (Mq == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  return qacqf_pending_launch(*m, pp, stream);
 }
 
 // ---- (5h) the joint source pass in value layout: 16 packed query points per strip, the mates' covariances from the strip's Gram tile ----
@@ -1477,6 +1553,168 @@ int scaml_studies_fantasy_acqf_opt_f64(const double* x0, const int32_t* group, c
                                   alpha_f, n_points_t, m_all, s_all, info, acqf_param, B, G, n_max, T, N, D, kind_s, kind_t, acqf, lo, hi,
                                   max_iter, history, max_ls, gtol, ftol, c1, n_evals, flags, workspace, x, f, stats, task_base != nullptr, task_base,
                                   Tsrc, stream, &fant);
+}
+
+// ---- (7t) the box L-BFGS step for P <= 128 variables per start with a slot table; (7s) the optimiser of the joint q-point acquisition
+// as rounds of { value pass, (5g), weighted sums, gather, assemble, solve, (7p) / (7q), step } (csrc/gp_qacqf_opt.hip) ----
+namespace {
+int qacqf_opt_step_check(const scaml::QAcqfOptParams& p) {
+  if (p.B < 0 || p.Bs < 0 || p.Bs > p.B || (!p.slots && p.Bs != p.B) || p.P < 1 || p.mode < 0 || p.mode > 2) return SCAML_E_BADARG;
+  if (p.max_iter < 0 || p.max_ls < 1 || p.history < 1 || p.history > scaml::QACQF_OPT_HMAX) return SCAML_E_BADARG;
+  if (!p.lo || !p.hi || !p.state || !p.Xq || !p.x || !p.f || !p.stats) return SCAML_E_BADARG;
+  if ((p.mode == 0 && !p.x0) || (p.mode == 1 && (!p.value || !p.grad))) return SCAML_E_BADARG;
+  if (!(p.gtol >= 0.0) || !(p.c1 > 0.0) || p.ftol != p.ftol) return SCAML_E_BADARG;
+  if (p.P > scaml::QACQF_OPT_MAX_P || p.B > (1 << 26)) return SCAML_E_TOOLARGE;
+  return SCAML_OK;
+}
+int qacqf_opt_step_launch(Module& m, scaml::QAcqfOptParams& p, void* stream) {   // a checked block, Bs > 0
+  return launch(m.qacqf_opt_step, dim3((unsigned)p.Bs), 64, 0, stream, "qacqf_opt_step", p);
+}
+int qacqf_opt_gather_launch(Module& m, scaml::QAcqfOptGatherParams& p, void* stream) {
+  const long long elems = scaml::qo_gather_elems(p);
+  return launch(m.qacqf_opt_gather, dim3((unsigned)((elems + 255) / 256)), 256, 0, stream, "qacqf_opt_gather", p);
+}
+
+struct QAcqfOptLayout {
+  size_t state, Xq, value, grad, mu_v, VQ, mu, var, cov, mu_g, var_g, cov_g, mean_s, var_s, cov_s, xall, Knn, resid, Knq, mean_q, var_q, Z,
+      jitter, info_out, total;
+};
+// sized by all B starts: a call at Bs <= B slots packs its arrays (Mq = Bs * q columns) into the same places
+QAcqfOptLayout qacqf_opt_layout(int B, int n, int p, int q, int T, int N, int D, int history) {
+  const size_t b = (size_t)B, nn = (size_t)n, t = (size_t)T, d = (size_t)D, Mq = b * (size_t)q, rows = nn + (size_t)p + (size_t)q;
+  QAcqfOptLayout l{};
+  size_t o = 0;
+  auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  l.state = take(b * scaml::qacqf_opt_state_doubles(q * D, history) * 8);   // (first: the caller may read the state, include/scaml_gp.h)
+  l.Xq = take(Mq * d * 8);
+  l.value = take(b * 8);
+  l.grad = take(Mq * d * 8);
+  l.mu_v = take(t * Mq * 8);
+  l.VQ = take(t * (size_t)N * Mq * 8);
+  l.mu = take(t * Mq * 16 * 8);
+  l.var = take(t * Mq * 16 * 8);
+  l.cov = take(t * rows * Mq * 16 * 8);
+  l.mu_g = take(Mq * 16 * 8);
+  l.var_g = take(Mq * 16 * 8);
+  l.cov_g = take(rows * Mq * 16 * 8);
+  l.mean_s = take((nn + Mq) * 8);
+  l.var_s = take((nn + Mq) * 8);
+  l.cov_s = take(nn * (nn + Mq) * 8);
+  l.xall = take((nn + Mq) * d * 8);
+  l.Knn = take(nn * nn * 8);
+  l.resid = take(nn * 8);
+  l.Knq = take(nn * Mq * 8);
+  l.mean_q = take(Mq * 8);
+  l.var_q = take(Mq * 8);
+  l.Z = take(nn * Mq * 8);
+  l.jitter = take(b * 8);
+  l.info_out = take(b * 4);
+  l.total = o;
+  return l;
+}
+}  // namespace
+
+int scaml_qacqf_opt_max_p(void) { return scaml::QACQF_OPT_MAX_P; }
+
+long long scaml_qacqf_opt_step_workspace_bytes(int B, int P, int history) {
+  if (B < 0 || B > (1 << 26) || P < 1 || P > scaml::QACQF_OPT_MAX_P || history < 1 || history > scaml::QACQF_OPT_HMAX) return 0;
+  return (long long)B * (long long)scaml::qacqf_opt_state_doubles(P, history) * 8;
+}
+
+long long scaml_qacqf_opt_workspace_bytes(int B, int n, int p, int q, int T, int N, int D, int history) {
+  if (B < 0 || B > (1 << 20) || n < 1 || p < 0 || q < 1 || T < 1 || N < 1 || D < 1 || history < 1 || history > scaml::QACQF_OPT_HMAX) return 0;
+  if (q > scaml::QACQF_MAX_Q || q + p > scaml::QACQF_MAX_Q || n + p + q > scaml::QACQF_MAX_ROWS || n + p + q > N || N > scaml_posterior_max_n() ||
+      D > scaml::QACQF_MAX_D)
+    return 0;
+  return (long long)qacqf_opt_layout(B, n, p, q, T, N, D, history).total;
+}
+
+int scaml_qacqf_opt_step_f64(const double* value, const double* grad, const int32_t* slots, const double* x0, const double* lo, const double* hi,
+                             int B, int Bs, int P, int mode, int max_iter, int history, int max_ls, double gtol, double ftol, double c1,
+                             double* state, double* Xq, double* x, double* f, int32_t* stats, void* stream) {
+  scaml::QAcqfOptParams p{value, grad, slots, x0, lo, hi, state, Xq, x, f, stats, B, Bs, P, mode, max_iter, history, max_ls, 0, gtol, ftol, c1};
+  if (const int rc = qacqf_opt_step_check(p)) return rc;
+  if (Bs == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  return qacqf_opt_step_launch(*m, p, stream);
+}
+
+int scaml_qacqf_opt_f64(const double* x0, const int32_t* slots, const double* Xa, const double* X, const double* theta_s, const double* Linv,
+                        const double* alpha_s, const double* y_mean, const double* y_std, const int32_t* n_points_s, const double* VA,
+                        const double* w, const uint8_t* active, const double* mu_t, const double* cov_tt, const double* var_t, const double* Xt,
+                        const double* theta_t, const double* targets, const double* L, const double* Linv_diag, const double* alpha_t,
+                        double m_all, double s_all, const int32_t* info, const double* base_samples, const double* Xp, const double* Zp,
+                        const double* mu_p, const double* Sigma_pp, int B, int Bs, int n, int p, int q, int S, int T, int N, int D, int kind_s,
+                        int kind_t, int acqf, double acqf_param, const double* lo, const double* hi, int max_iter, int history, int max_ls,
+                        double gtol, double ftol, double c1, int n_evals, unsigned flags, void* workspace, long long workspace_bytes, double* x,
+                        double* f, int32_t* stats, void* stream) {
+  // what is the optimiser's own, and what the workspace layout is sized by
+  if (B < 0 || Bs < 0 || n < 1 || p < 0 || q < 1 || T < 1 || N < 1 || D < 1 || n_evals < 0) return SCAML_E_BADARG;
+  if (!workspace || ((uintptr_t)workspace & 15) || (flags & ~SCAML_ACQF_OPT_CONTINUE)) return SCAML_E_BADARG;
+  if (!mu_t || !cov_tt || !var_t || Bs > B) return SCAML_E_BADARG;
+  const bool sized = B <= (1 << 20) && q <= scaml::QACQF_MAX_Q && p <= scaml::QACQF_MAX_Q && D <= scaml::QACQF_MAX_D && n <= scaml::QACQF_MAX_ROWS &&
+                     N <= scaml_posterior_max_n() && history >= 1 && history <= scaml::QACQF_OPT_HMAX;
+  // (a shape beyond the limits: the checks below refuse it, as SCAML_E_BADARG first if an argument is bad as well; the layout is not needed then)
+  const QAcqfOptLayout lay = sized ? qacqf_opt_layout(B, n, p, q, T, N, D, history) : QAcqfOptLayout{};
+  if (sized && workspace_bytes < (long long)lay.total) return SCAML_E_BADARG;
+  auto ws = [workspace](size_t off) { return (double*)((uintptr_t)workspace + off); };
+  const int P = sized ? q * D : 1, Mq = sized ? Bs * q : 0, Ma = n + p;
+  double *Xq = ws(lay.Xq), *value = ws(lay.value), *grad = ws(lay.grad), *VQ = ws(lay.VQ), *mu = ws(lay.mu), *var = ws(lay.var), *cov = ws(lay.cov);
+  double *mu_g = ws(lay.mu_g), *var_g = ws(lay.var_g), *cov_g = ws(lay.cov_g), *mean_s = ws(lay.mean_s), *var_s = ws(lay.var_s), *cov_s = ws(lay.cov_s);
+  double *xall = ws(lay.xall), *Knq = ws(lay.Knq), *mean_q = ws(lay.mean_q), *var_q = ws(lay.var_q), *Z = ws(lay.Z);
+  // the blocks of a round, in its order
+  scaml::PosteriorParams pv{Xq, X, theta_s, Linv, nullptr, alpha_s, y_mean, y_std, n_points_s, ws(lay.mu_v), nullptr, VQ, T, N, Mq, D, 0, 0, 0,
+                            nullptr, nullptr, 0, 0, nullptr};
+  scaml::PosteriorJointParams pj = grad_joint_block(Xq, Xa, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, VA, VQ, T, N, Mq, Ma, q, D, mu, var, cov, 0);
+  const long long len = 16LL * Mq, len_cov = (long long)(Ma + q) * len;
+  scaml::QAcqfOptGatherParams pg{mu_g, var_g, cov_g, Xq, mu_t, var_t, cov_tt, Xt, mean_s, var_s, cov_s, xall, n, Mq, D, 0};
+  scaml::TargetAssembleParams pa{cov_s, mean_s, var_s, xall, theta_t, targets, m_all, s_all, ws(lay.Knn), ws(lay.resid), Knq, mean_q, var_q, n, Mq, D};
+  scaml::ChoSolveParams pc{L, Linv_diag, Knq, nullptr, Z, 1, n, Mq, 0};
+  scaml::QAcqfPendingParams pq{{Knq, Z, alpha_t, mean_q, var_q, m_all, s_all, info, cov_g, mu_g, var_g, Xt, Xq, theta_t, base_samples, acqf_param,
+                                value, grad, ws(lay.jitter), (int32_t*)ws(lay.info_out), n, Mq, q, S, D, kind_t, acqf, 0},
+                               {Xp, Zp, mu_p, Sigma_pp, p, 0}};
+  scaml::QAcqfOptParams po{value, grad, slots, x0, lo, hi, ws(lay.state), Xq, x, f, stats, B, Bs, P, 1, max_iter, history, max_ls, 0, gtol, ftol, c1};
+  if (!x0) return SCAML_E_BADARG;   // (the step's own check asks for it at a reset only; a continued call is handed the same arguments)
+  // every block's SCAML_E_BADARG before any block's SCAML_E_TOOLARGE
+  const int rcs[] = {qacqf_opt_step_check(po),
+                     posterior_linv_check(pv, kind_s, 0, false),
+                     grad_joint_check(pj, Mq, kind_s, 0),
+                     wsum_check(mu, w, T, len, 1, mu_g),
+                     target_assemble_check(pa, kind_t),
+                     cho_solve_check(pc),
+                     p > 0 ? qacqf_pending_check(pq) : qacqf_check(pq.a)};
+  for (const int rc : rcs)
+    if (rc == SCAML_E_BADARG) return SCAML_E_BADARG;
+  for (const int rc : rcs)
+    if (rc != SCAML_OK) return SCAML_E_TOOLARGE;
+  if (!sized || posterior_linv_fits(pv) != SCAML_OK) return SCAML_E_TOOLARGE;
+  if (B == 0 || Bs == 0 || n_evals == 0) return SCAML_OK;
+  Module* m = ready();
+  if (!m) return SCAML_E_LAUNCH;
+  int rc = SCAML_OK;
+  // the start of a call: the trial points of the slots (from a reset, or again from the state: the table may have changed) and the
+  // training block of the joint prior at this call's row width
+  po.mode = (flags & SCAML_ACQF_OPT_CONTINUE) ? 2 : 0;
+  if ((rc = qacqf_opt_step_launch(*m, po, stream)) != SCAML_OK) return rc;
+  po.mode = 1;
+  pg.left = 1;
+  if ((rc = qacqf_opt_gather_launch(*m, pg, stream)) != SCAML_OK) return rc;
+  pg.left = 0;
+  for (int r = 0; r < n_evals; ++r) {
+    // (Arguments and sizes were checked above, once; only a failing launch can end the call here, with the rounds before it enqueued.)
+    if ((rc = posterior_linv_launch(*m, pv, kind_s, false, stream)) != SCAML_OK) return rc;
+    if ((rc = grad_joint_launch(*m, pj, Mq, kind_s, stream)) != SCAML_OK) return rc;
+    if ((rc = wsum_launch(*m, mu, w, active, T, len, 1, mu_g, stream)) != SCAML_OK) return rc;
+    if ((rc = wsum_launch(*m, cov, w, active, T, len_cov, 2, cov_g, stream)) != SCAML_OK) return rc;
+    if ((rc = wsum_launch(*m, var, w, active, T, len, 2, var_g, stream)) != SCAML_OK) return rc;
+    if ((rc = qacqf_opt_gather_launch(*m, pg, stream)) != SCAML_OK) return rc;
+    if ((rc = target_assemble_launch(*m, pa, kind_t, stream)) != SCAML_OK) return rc;
+    if ((rc = cho_solve_launch(*m, pc, stream)) != SCAML_OK) return rc;
+    if ((rc = p > 0 ? qacqf_pending_launch(*m, pq, stream) : qacqf_launch(*m, pq.a, stream)) != SCAML_OK) return rc;
+    if ((rc = qacqf_opt_step_launch(*m, po, stream)) != SCAML_OK) return rc;
+  }
+  return SCAML_OK;
 }
 
 }  // extern "C"

@@ -155,6 +155,16 @@ SIGNATURES = {
     "scaml_studies_condition_block_f64": (_i, [_dp] * 12 + [_i] * 6 + [_dp] * 3 + [c_void_p]),
     # (7n) L, resid, mean_p, n_points, n_obs, info, eps, n_fant, m_all, s_all; G, n_max, p_max, F_max; alpha_f, y_fant, mu_p
     "scaml_studies_fantasy_condition_f64": (_i, [_dp] * 10 + [_i] * 4 + [_dp] * 3 + [c_void_p]),
+    "scaml_qacqf_opt_max_p": (_i, []),
+    "scaml_qacqf_opt_step_workspace_bytes": (_ll, [_i] * 3),
+    "scaml_qacqf_opt_workspace_bytes": (_ll, [_i] * 8),
+    # (7t) value, grad, slots, x0, lo, hi; B, Bs, P, mode, max_iter, history, max_ls; gtol, ftol, c1; state, Xq, x, f, stats
+    "scaml_qacqf_opt_step_f64": (_i, [_dp] * 6 + [_i] * 7 + [_f] * 3 + [_dp] * 5 + [c_void_p]),
+    # (7s) x0, slots; Xa, 8 source-stack arrays, VA; w, active; mu_t, cov_tt, var_t; Xt, theta_t, targets, L, Linv_diag, alpha_t; m_all, s_all;
+    # info, base_samples, Xp, Zp, mu_p, Sigma_pp; B, Bs, n, p, q, S, T, N, D, kind_s, kind_t, acqf; acqf_param; lo, hi; max_iter, history, max_ls;
+    # gtol, ftol, c1; n_evals, flags; workspace, workspace_bytes; x, f, stats
+    "scaml_qacqf_opt_f64": (_i, [_dp] * 22 + [_f, _f] + [_dp] * 6 + [_i] * 12 + [_f] + [_dp, _dp] + [_i] * 3 + [_f] * 3 + [_i, _u]
+                            + [_dp, _ll] + [_dp] * 3 + [c_void_p]),
     "scaml_debug_target_fit_path": (_i, [_i]),
     "scaml_debug_blocked_fit_path": (_i, [_i]),
     "scaml_debug_coop_far": (_i, [_i]),

@@ -97,12 +97,25 @@ def acqf_pick_initial_conditions(vals: torch.Tensor, num_restarts: int, generato
     return best0, picks
 
 
+JOINT_OPT_MODES = ("scipy", "device")
+
+
+def _check_joint_opt_mode(mode: str) -> str:
+    if mode not in JOINT_OPT_MODES:
+        raise ValueError(f"joint_opt_mode must be 'scipy' or 'device', got {mode!r}")
+    return mode
+
+
 def acqf_local_optimization(af: Callable[[torch.Tensor], torch.Tensor], x0: torch.Tensor, max_iter: int = 50, fd_step: float = 1e-4,
-                            graph_device: Optional[torch.device] = None, analytic_grad: bool = True) -> torch.Tensor:
+                            graph_device: Optional[torch.device] = None, analytic_grad: bool = True, joint_opt_mode: str = "scipy") -> torch.Tensor:
     """Stage 2 of ``optimize_acqf``: ONE box-constrained scipy L-BFGS-B run over the R starts jointly (the summed acquisition value);
     returns the end points (R, dim) inside [0, 1]^dim.  x0 (R, q, dim): R q-batches of a joint acquisition function, one run over the
-    R q dim variables on its ``value_and_grad``; the end points are (R, q, dim)."""
+    R q dim variables on its ``value_and_grad``; the end points are (R, q, dim).  ``joint_opt_mode="device"`` (q-batches only): R
+    independent box L-BFGS runs enqueued on the device instead (``_joint_device_optimization``)."""
+    _check_joint_opt_mode(joint_opt_mode)
     if x0.dim() == 3:
+        if joint_opt_mode == "device":
+            return _joint_device_optimization(af, x0, max_iter)["x"]
         return _joint_local_optimization(af, x0, max_iter)
     R, dim = x0.shape
     eye = torch.eye(dim, dtype=torch.float64)
@@ -155,12 +168,35 @@ def _joint_local_optimization(af, x0: torch.Tensor, max_iter: int) -> torch.Tens
     return torch.from_numpy(np.clip(res.x, 0.0, 1.0)).reshape(R, q, dim)
 
 
-def _optimize_acqf_joint(af, dim: int, q: int, raw_samples: int, num_restarts: int, max_iter: int, generator: Optional[torch.Generator], eta: float):
+def _joint_device_optimization(af, x0: torch.Tensor, max_iter: int, evals_per_call: Optional[int] = None) -> dict:
+    """Stage 2 for R q-batches x0 (R, q, dim) on the device: ``af.optimize`` (``utils._JointAcquisition.optimize``, scaml_qacqf_opt_f64)
+    -- R independent box L-BFGS runs, not scipy's one run over the sum; the host twin is ``hyper.batched_lbfgs`` on
+    ``af.value_and_grad``.  Returns its dict with x (R, q, dim) and f (R,) on the host: f is the value AT x, so no re-scoring follows."""
+    if not callable(getattr(af, "optimize", None)):
+        raise TypeError(f"joint_opt_mode='device' needs an acquisition function with an optimize method "
+                        f"(utils.qExpectedImprovement, utils.qUpperConfidenceBound), got {type(af).__name__}")
+    res = dict(af.optimize(x0, max_iter, evals_per_call=evals_per_call))
+    res["x"] = res["x"].detach().cpu().clamp(0.0, 1.0).reshape(x0.shape)
+    res["f"] = res["f"].detach().cpu()
+    return res
+
+
+def _optimize_acqf_joint(af, dim: int, q: int, raw_samples: int, num_restarts: int, max_iter: int, generator: Optional[torch.Generator], eta: float,
+                         joint_opt_mode: str = "scipy", info: Optional[dict] = None):
     """``optimize_acqf`` for q > 1: ``raw_samples`` random q-batches, the Boltzmann pick over batches, one L-BFGS-B run over the
-    R q dim variables, the best end batch.  Returns (X (q, dim), value)."""
+    R q dim variables, the best end batch.  Returns (X (q, dim), value).  ``joint_opt_mode="device"``: stage 2 runs on the device and
+    its values at the end batches stand for stage 3's re-scoring call; stage 2 draws nothing from ``generator`` in either mode.
+    ``info`` (a dict): receives n_eval, n_calls, evals_per_start and status of the device run."""
+    _check_joint_opt_mode(joint_opt_mode)
     cand = torch.rand(raw_samples, q, dim, dtype=torch.float64, generator=generator)
     vals = af(cand).detach().cpu()
     best0, picks = acqf_pick_initial_conditions(vals, num_restarts, generator, eta)
+    if joint_opt_mode == "device":
+        res = _joint_device_optimization(af, cand[picks], max_iter)
+        if info is not None:
+            stats = torch.as_tensor(res["stats"])
+            info.update(n_eval=int(res["n_eval"]), n_calls=int(res["n_calls"]), evals_per_start=stats[:, 1].tolist(), status=stats[:, 2].tolist())
+        return acqf_final_choice(cand, vals, best0, res["x"], res["f"])
     xs = acqf_local_optimization(af, cand[picks], max_iter)
     return acqf_final_choice(cand, vals, best0, xs, af(xs))
 
@@ -177,8 +213,10 @@ def acqf_final_choice(cand: torch.Tensor, vals: torch.Tensor, best0: int, xs: to
 
 def optimize_acqf(af: Callable[[torch.Tensor], torch.Tensor], dim: int, raw_samples: int = 1024, num_restarts: int = 10,
                   max_iter: int = 50, generator: Optional[torch.Generator] = None, fd_step: float = 1e-4,
-                  eta: float = 2.0, graph_device: Optional[torch.device] = None, analytic_grad: bool = True, q: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Maximise ``af`` over [0, 1]^dim; returns (x_best (dim,), af(x_best)).  ``q`` > 1: ``af`` is a joint acquisition function
+                  eta: float = 2.0, graph_device: Optional[torch.device] = None, analytic_grad: bool = True, q: int = 1,
+                  joint_opt_mode: str = "scipy") -> Tuple[torch.Tensor, torch.Tensor]:
+    """Maximise ``af`` over [0, 1]^dim; returns (x_best (dim,), af(x_best)).  ``joint_opt_mode`` (read with q > 1 only): ``"scipy"``
+    (default) or ``"device"`` -- stage 2 of the joint route enqueued on the device (``af.optimize``).  ``q`` > 1: ``af`` is a joint acquisition function
     (``utils.qExpectedImprovement`` / ``qUpperConfidenceBound``) over batches of q points, ``raw_samples`` counts q-batches, the Boltzmann
     pick is over batches, the L-BFGS-B run is over R q dim variables and the result is (X_best (q, dim), af(X_best)).  The joint route
     always runs on the exact gradients of ``af.value_and_grad``, evaluated eagerly: ``fd_step``, ``graph_device`` and ``analytic_grad``
@@ -193,10 +231,11 @@ def optimize_acqf(af: Callable[[torch.Tensor], torch.Tensor], dim: int, raw_samp
     once and replayed per L-BFGS-B step (``GraphedAcquisition``).  The three stages are functions of their own
     (``acqf_initial_conditions``, ``acqf_local_optimization``, ``acqf_final_choice``): ``ScaMLGPBOStudies`` runs the middle one for
     all its studies at once."""
+    _check_joint_opt_mode(joint_opt_mode)
     if q != 1:
         if int(q) < 1:
             raise ValueError("q must be a positive integer")
-        return _optimize_acqf_joint(af, dim, int(q), raw_samples, num_restarts, max_iter, generator, eta)
+        return _optimize_acqf_joint(af, dim, int(q), raw_samples, num_restarts, max_iter, generator, eta, joint_opt_mode)
     cand, vals, best0, x0 = acqf_initial_conditions(af, dim, raw_samples, num_restarts, generator, eta)
     xs = acqf_local_optimization(af, x0, max_iter, fd_step, graph_device, analytic_grad)
     return acqf_final_choice(cand, vals, best0, xs, af(xs))
@@ -207,8 +246,13 @@ class ScaMLGPBOLoop:
                  num_restarts_log_likelihood: int = 5, raw_samples: int = 1024, num_restarts: int = 10, af_max_iter: int = 50,
                  gp_likelihood: Optional[hyper.GaussianLikelihood] = None, gp_kernel: Optional[hyper.ScaleKernel] = None,
                  seed: Optional[int] = None, use_graph: bool = True, max_pending_evaluations: Optional[int] = None,
-                 num_fantasies: int = 16, num_mc_samples: int = 128, joint_pending: str = "refuse", joint_score_mode: str = "grad_pass"):
+                 num_fantasies: int = 16, num_mc_samples: int = 128, joint_pending: str = "refuse", joint_score_mode: str = "grad_pass",
+                 joint_opt_mode: str = "scipy"):
         """``num_mc_samples``: base samples of the joint acquisition function of ``suggest_batch``.
+        ``joint_opt_mode``: where ``suggest_batch`` optimises its picked batches (stage 2) -- ``"scipy"`` (default): one scipy L-BFGS-B
+        run over all of them on the host; ``"device"``: an independent box L-BFGS per batch enqueued on the device
+        (scaml_qacqf_opt_f64), whose values at the end batches stand for the re-scoring call of stage 3.  ``last_suggest_info`` (None
+        before the first ``suggest_batch``) then reports n_eval, n_calls, evals_per_start and status; with ``"scipy"`` it is ``{}``.
         ``joint_score_mode``: how ``suggest_batch`` scores its raw batches (stage 1) and its end batches (stage 3) -- ``"grad_pass"``
         (default): through the route of the gradient evaluations; ``"value_pass"``: through the value-only route
         (``ScaMLGP.joint_acqf_value``, 16 points per strip of the source pass).  Stage 2 runs on the exact gradients either way.
@@ -224,6 +268,8 @@ class ScaMLGPBOLoop:
         if joint_score_mode not in ("grad_pass", "value_pass"):
             raise ValueError(f"joint_score_mode must be 'grad_pass' or 'value_pass', got {joint_score_mode!r}")
         self.joint_pending, self.joint_score_mode = joint_pending, joint_score_mode
+        self.joint_opt_mode = _check_joint_opt_mode(joint_opt_mode)
+        self.last_suggest_info: Optional[dict] = None
         self.max_pending_evaluations = None if max_pending_evaluations is None else int(max_pending_evaluations)
         self.num_fantasies = int(num_fantasies)
         self.num_mc_samples = int(num_mc_samples)
@@ -343,7 +389,9 @@ class ScaMLGPBOLoop:
         self.model.eval()
         af = self.joint_acquisition_function(q, self.pending if p > 0 else None)
         # (the joint route for every q, q = 1 included: optimize_acqf(q=1) is the single-point path of the analytic functions)
-        X, _ = _optimize_acqf_joint(af, self.dim, q, self.raw_samples, self.num_restarts, self.af_max_iter, self.gen, 2.0)
+        info: dict = {}
+        X, _ = _optimize_acqf_joint(af, self.dim, q, self.raw_samples, self.num_restarts, self.af_max_iter, self.gen, 2.0, self.joint_opt_mode, info)
+        self.last_suggest_info = info
         X = X.reshape(q, self.dim)
         if k is not None:
             self.pending = torch.cat([self.pending, X], 0)

@@ -1141,6 +1141,46 @@ class ScaMLGP:
             kw.update(Xp=pend["Xp"], Zp=pend["Zp"], mu_p=pend["mu_p"], Sigma_pp=pend["Sigma_pp"])
         return kw
 
+    def joint_acqf_opt_inputs(self, base_samples: torch.Tensor, X_pending=None) -> dict:
+        """What the device optimiser of the joint acquisition (``ops.QAcqfOpt``, scaml_qacqf_opt_f64) is handed and what does not depend
+        on the round: the arguments of ``joint_acqf_inputs``' launches by the C signature's names -- the source stack and the leading
+        points (Xa, X, theta_s, Linv, alpha_s, y_mean, y_std, n_points_s, VA), w, active, the weighted source sums at the training
+        inputs (mu_t, cov_tt, var_t), the target GP and the factor of its training block (Xt, theta_t, targets, L, Linv_diag, alpha_t,
+        m_all, s_all, info), base_samples (S, q + p), kind_s, kind_t and, with p > 0 points pending (``X_pending``: (p, D) or
+        ``joint_pending``'s dict), Xp, Zp, mu_p, Sigma_pp.  ``joint_acqf``'s refusals; the target factor of the current weights and
+        hyper-parameters is computed here if no evaluation has cached it yet."""
+        st, f = self._stack, self._stack.fit
+        base_samples = torch.as_tensor(base_samples, dtype=torch.float64)
+        if base_samples.dim() != 2:
+            raise ValueError("base_samples must be (S, q + p)")
+        pend = X_pending
+        if X_pending is not None and not isinstance(X_pending, dict):
+            self._joint_refusals()
+            pend = self.joint_pending(X_pending)
+        p = 0 if pend is None else int(pend["Xp"].shape[0])
+        q = int(base_samples.shape[1]) - p
+        if q < 1:
+            raise ValueError("base_samples must be (S, q + p) with q >= 1")
+        # (the refusals of a joint evaluation, on an empty set of batches of this q)
+        _, base_samples, pend = self._joint_arguments(torch.empty(0, q, st.D, dtype=torch.float64), base_samples, pend)
+        w_full, active = self._active_tasks()
+        mu_t, cov_tt, var_t = self._train_prior()
+        theta = self.theta
+        factor = self._target_factor()
+        if factor is None:
+            factor = ops.target_fantasy_block(cov_tt, mu_t, var_t, self.train_X, theta, self.train_targets.unsqueeze(0), self._m_all_f,
+                                              self._s_all_f, self.kind)["factor"]
+            self._keep_target_factor(factor)
+        Xa, VA = (self.train_X, self._train_VA()) if pend is None else (pend["Xa"], pend["VA"])
+        kw = dict(Xa=Xa, X=st.X, theta_s=st.theta, Linv=f["Linv"], alpha_s=f["alpha"], y_mean=st.y_mean, y_std=st.y_std, n_points_s=st.n_points,
+                  VA=VA, w=w_full, active=active.to(torch.uint8), mu_t=mu_t, cov_tt=cov_tt, var_t=var_t, Xt=self.train_X, theta_t=theta,
+                  targets=self.train_targets, L=factor["L"], Linv_diag=factor["Linv_diag"], alpha_t=factor["alpha"][0],
+                  m_all=self._m_all_f, s_all=self._s_all_f, info=factor["info"].reshape(-1)[:1], base_samples=base_samples,
+                  kind_s=st.kind, kind_t=self.kind)
+        if pend is not None:
+            kw.update(Xp=pend["Xp"], Zp=pend["Zp"], mu_p=pend["mu_p"], Sigma_pp=pend["Sigma_pp"])
+        return kw
+
     def joint_acqf_value(self, X: torch.Tensor, acqf: int, acqf_param: float, base_samples: torch.Tensor, X_pending=None) -> torch.Tensor:
         """``joint_acqf``'s value (B,) for X (B, q, D) WITHOUT its gradient, through a route of its own: what the scoring of an
         optimiser's raw candidates needs.  The batches are packed into strips of 16 columns (``ops.qacqf_value_pack``), the value-layout

@@ -1693,6 +1693,134 @@ def studies_acqf_opt(arrays, B: int, G: int, n_max: int, T: int, N: int, D: int,
     return StudiesAcqfOpt(arrays, B, G, n_max, T, N, D, kind_s, kind_t, acqf, lo, hi, max_iter, **options).run(evals_per_call)
 
 
+# ---- (7s), (7t) the optimiser of the joint q-point acquisition enqueued on the device --------------------------------------------
+# rounds enqueued between two reads of the status: DESIGN 4t.  A start that has stopped leaves the evaluation kernels at the next chunk
+# boundary (the caller's slot table), so the smaller chunk wins where the columns of tools/dev_qacqf_time.py --opt --sweep agree.
+QACQF_OPT_EVALS_PER_CALL = 4
+
+
+def qacqf_opt_max_p() -> int:
+    """Variables per start (q * D) of the joint acquisition's optimiser step."""
+    return int(_lib.lib.scaml_qacqf_opt_max_p())
+
+
+def qacqf_opt_step(state: torch.Tensor, mode: int, lo: torch.Tensor, hi: torch.Tensor, Xq: torch.Tensor, x: torch.Tensor, f: torch.Tensor,
+                   stats: torch.Tensor, x0: Optional[torch.Tensor] = None, value: Optional[torch.Tensor] = None,
+                   grad: Optional[torch.Tensor] = None, slots: Optional[torch.Tensor] = None, max_iter: int = 50, history: int = 10,
+                   max_ls: int = ACQF_OPT_MAX_LS, gtol: float = 1e-5, ftol: float = 2.2e-9, c1: float = 1e-4) -> None:
+    """One launch of scaml_qacqf_opt_step_f64 (7t), in place: a box L-BFGS step of B starts of P <= 128 variables that MAXIMISES.
+    ``state`` (B, studies_acqf_opt_state_doubles(P, history)); ``mode`` 0 resets from ``x0`` (B, P), 1 consumes ``value`` (Bs,) /
+    ``grad`` (Bs, P) -- the function at ``Xq`` (Bs, P), which then receives the next trial points --, 2 writes the outputs again for a
+    changed ``slots`` (Bs,) int32 table (None: the identity).  ``x`` (B, P), ``f`` (B,), ``stats`` (B, 4) int32 are addressed by start."""
+    B, P = x.shape
+    Bs = B if slots is None else int(slots.shape[0])
+    state = _check(state, "state", (B, _lbfgs_state_doubles(P, int(history))))
+    lo, hi = _check(lo, "lo", (P,)), _check(hi, "hi", (P,))
+    Xq, x, f = _check(Xq, "Xq", (Bs, P)), _check(x, "x", (B, P)), _check(f, "f", (B,))
+    stats = _check(stats, "stats", (B, 4), torch.int32)
+    x0 = _opt(x0, "x0", (B, P))
+    value, grad = _opt(value, "value", (Bs,)), _opt(grad, "grad", (Bs, P))
+    slots = _opt(slots, "slots", (Bs,), torch.int32)
+    with torch.cuda.device(state.device):
+        rc = _lib.lib.scaml_qacqf_opt_step_f64(_ptr(value), _ptr(grad), _ptr(slots), _ptr(x0), _ptr(lo), _ptr(hi), B, Bs, P, int(mode),
+                                               int(max_iter), int(history), int(max_ls), float(gtol), float(ftol), float(c1), _ptr(state),
+                                               _ptr(Xq), _ptr(x), _ptr(f), _ptr(stats), _stream_handle())
+    _lib.check_rc(rc, "scaml_qacqf_opt_step_f64")
+
+
+class QAcqfOpt:
+    """One optimisation of ``scaml_qacqf_opt_f64`` (7s): the checked arguments, the workspace and the outputs, so that the rounds can be
+    enqueued in chunks (``enqueue``; the first call resets, the later ones continue).  ``arrays``: the round-independent device arrays
+    by the C signature's names, as ``ScaMLGP.joint_acqf_opt_inputs`` returns them (Xa, X, theta_s, Linv, alpha_s, y_mean, y_std,
+    n_points_s, VA, w, active, mu_t, cov_tt, var_t, Xt, theta_t, targets, L, Linv_diag, alpha_t, info, base_samples and, with points
+    pending, Xp, Zp, mu_p, Sigma_pp; the floats m_all, s_all; the ints kind_s, kind_t).  ``x0`` (B, q, D): the start batches.
+    ``slots``: the starts the next call works on (all of them after construction); ``run`` rebuilds it from the starts still running
+    after every status read, so that a stopped start costs the evaluation kernels nothing from the next call on."""
+
+    def __init__(self, arrays: Dict, x0: torch.Tensor, acqf: int, acqf_param: float, lo: torch.Tensor, hi: torch.Tensor, max_iter: int,
+                 history: int = 10, max_ls: int = ACQF_OPT_MAX_LS, gtol: float = 1e-5, ftol: float = 2.2e-9, c1: float = 1e-4):
+        if x0.dim() != 3:
+            raise ValueError("x0 must be (B, q, D)")
+        B, q, D = (int(v) for v in x0.shape)
+        f64, i32 = torch.float64, torch.int32
+        a = dict(arrays)
+        X = _check(a["X"], "X")
+        T, N, _ = X.shape
+        n = int(a["Xt"].shape[0])
+        S, Q = (int(v) for v in a["base_samples"].shape)
+        p = Q - q
+        if p < 0 or (p > 0) != (a.get("Xp") is not None):
+            raise ValueError("base_samples must be (S, q + p) with p = Xp.shape[0] pending points")
+        nbm = (n + 15) // 16
+        spec = [("Xa", (n + p, D), f64), ("X", (T, N, D), f64), ("theta_s", (T, D + 2), f64), ("Linv", (T, N, N), f64), ("alpha_s", (T, N), f64),
+                ("y_mean", (T,), f64), ("y_std", (T,), f64), ("n_points_s", (T,), i32), ("VA", (T, N, n + p), f64), ("w", (T,), f64),
+                ("active", (T,), torch.uint8), ("mu_t", (n,), f64), ("cov_tt", (n, n), f64), ("var_t", (n,), f64), ("Xt", (n, D), f64),
+                ("theta_t", (D + 2,), f64), ("targets", (n,), f64), ("L", (1, n, n), f64), ("Linv_diag", (1, nbm, 16, 16), f64),
+                ("alpha_t", (n,), f64)]
+        tail = [("info", (1,), i32), ("base_samples", (S, Q), f64), ("Xp", (p, D), f64), ("Zp", (n, p), f64), ("mu_p", (p,), f64),
+                ("Sigma_pp", (p, p), f64)]
+        self._keep = [_opt(a.get(name), name, shape, dt) for name, shape, dt in spec + tail]
+        self._head = [_ptr(t) for t in self._keep[:len(spec)]]
+        self._tail = [_ptr(t) for t in self._keep[len(spec):]]
+        self._scale = (float(a["m_all"]), float(a["s_all"]))
+        self._shape = (n, p, q, S, T, N, D, int(a["kind_s"]), int(a["kind_t"]), int(acqf))
+        self._param = float(acqf_param)
+        self._dims = (B, q, D)
+        self._opts = (int(max_iter), int(history), int(max_ls), float(gtol), float(ftol), float(c1))
+        P = q * D
+        self.x0 = _check(x0.reshape(B, P), "x0", (B, P))
+        self.lo, self.hi = _check(lo, "lo", (P,)), _check(hi, "hi", (P,))
+        dev = self.x0.device
+        self.device, self.n_calls, self.n_eval, self.live = dev, 0, 0, []
+        self.budget = 1 + int(max_iter) * int(max_ls)
+        with torch.cuda.device(dev):
+            self.x, self.f = _empty(dev, B, P), _empty(dev, B)
+            self.stats = torch.zeros((B, 4), dtype=i32, device=dev)
+            self.nbytes = int(_lib.lib.scaml_qacqf_opt_workspace_bytes(B, n, p, q, T, N, D, int(history)))
+            if self.nbytes == 0:
+                raise ValueError("scaml_qacqf_opt_f64: problem size exceeds kernel limits")
+            self.ws = _empty(dev, max(self.nbytes, 16), dtype=torch.uint8)
+            self.slots = torch.arange(B, dtype=i32, device=dev)
+
+    def enqueue(self, n_evals: int) -> None:
+        B = self._dims[0]
+        Bs = int(self.slots.shape[0])
+        with torch.cuda.device(self.device):
+            rc = _lib.lib.scaml_qacqf_opt_f64(_ptr(self.x0), _ptr(self.slots), *self._head, *self._scale, *self._tail, B, Bs, *self._shape,
+                                              self._param, _ptr(self.lo), _ptr(self.hi), *self._opts, int(n_evals),
+                                              _lib.ACQF_OPT_CONTINUE if self.n_calls else 0, _ptr(self.ws), self.nbytes, _ptr(self.x),
+                                              _ptr(self.f), _ptr(self.stats), _stream_handle())
+        _lib.check_rc(rc, "scaml_qacqf_opt_f64")
+        self.n_calls += 1
+        self.n_eval += int(n_evals)
+        self.live.append(Bs)
+
+    def run(self, evals_per_call: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Every call enqueues ``evals_per_call`` rounds for the starts in ``slots``, then the status column is read -- the only
+        synchronisation --, the stopped starts leave the table and the optimisation continues while a start is still running (at most
+        ``1 + max_iter * max_ls`` evaluations: then every start has stopped).  Returns dict(x (B, q, D), f (B,) the acquisition value
+        there, stats (B, 4) int32 [iterations, evaluations, status, pairs] on the host, n_eval rounds enqueued, n_calls, live: the
+        slots of every call)."""
+        per_call = int(evals_per_call or QACQF_OPT_EVALS_PER_CALL)
+        if per_call < 1:
+            raise ValueError("evals_per_call must be positive")
+        host = self.stats.cpu()
+        while self._dims[0] > 0 and self.n_eval < self.budget:
+            self.enqueue(min(per_call, self.budget - self.n_eval))
+            host = self.stats.cpu()
+            running = torch.nonzero(host[:, 2] == 0).flatten()
+            if running.numel() == 0:
+                break
+            self.slots = running.to(torch.int32).to(self.device)
+        B, q, D = self._dims
+        return dict(x=self.x.reshape(B, q, D), f=self.f, stats=host, n_eval=self.n_eval, n_calls=self.n_calls, live=list(self.live))
+
+    def state(self) -> torch.Tensor:
+        """(B, studies_acqf_opt_state_doubles(q * D, history)): the per-start state that opens the workspace (a view)."""
+        B, q, D = self._dims
+        return _lbfgs_state(self.ws, B, q * D, self._opts[1])
+
+
 def raise_if_not_psd(info: torch.Tensor) -> None:
     """Host-side check of the per-task status (one device->host sync)."""
     if bool((info < 0).any()):

@@ -548,6 +548,22 @@ class _JointAcquisition:
         """(value (B,), d value / d X (B, q, D)), the exact gradient of the Monte-Carlo estimate at the fixed base samples."""
         return self.model.joint_acqf(self._batches(X), self.code, self.param, self.base_samples, want_grad=True, X_pending=self._pending)
 
+    def optimize(self, x0: torch.Tensor, max_iter: int, evals_per_call: Optional[int] = None, **options) -> dict:
+        """Maximise the function over [0, 1]^D from every batch of x0 (R, q, D) ON THE DEVICE (``ops.QAcqfOpt``, scaml_qacqf_opt_f64):
+        R independent box L-BFGS runs whose rounds -- the launches of ``value_and_grad`` and the optimiser step -- are enqueued
+        ``evals_per_call`` at a time without the host; between calls the status is read and the stopped starts leave the evaluation.
+        The host twin is ``hyper.batched_lbfgs(fun, x0.reshape(R, q D), bounds=(0, 1))`` on ``value_and_grad``.  ``options``: history,
+        max_ls, gtol, ftol, c1.  Returns dict(x (R, q, D), f (R,) the value AT x (-inf for a start whose first evaluation is not
+        finite), stats (R, 4) int32 on the host [iterations, evaluations, status, pairs], n_eval rounds enqueued, n_calls, live: the
+        starts evaluated by each call)."""
+        X = self._batches(x0)
+        R, q, D = X.shape
+        dev = self.model.device
+        kw = self.model.joint_acqf_opt_inputs(self.base_samples, self._pending)
+        lo, hi = torch.zeros(q * D, dtype=torch.float64, device=dev), torch.ones(q * D, dtype=torch.float64, device=dev)
+        opt = ops.QAcqfOpt(kw, X.to(dev).contiguous(), self.code, self.param, lo, hi, int(max_iter), **options)
+        return opt.run(evals_per_call)
+
 
 class qExpectedImprovement(_JointAcquisition):
     """botorch qExpectedImprovement (minimisation): (1/S) sum_s max_j max(best_f - f_sj, 0) over S joint posterior samples of the batch."""

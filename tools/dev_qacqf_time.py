@@ -26,6 +26,15 @@ With ``--score`` (and ``--q Q``, ``--pending P``): the scoring of suggest_batch'
      the end batches), next to Q successive suggest() calls with 16 fantasies.
 
   python tools/dev_qacqf_time.py --score [--q Q] [--pending P] [--out FILE] [--no-suggest]
+
+With ``--opt`` (and ``--q Q``, ``--pending P``, ``--sweep 1,2,4,8,16``): suggest_batch's optimiser, in place of the above
+  8. suggest_batch(Q) with P evaluations pending with joint_opt_mode="scipy" (the yardstick: its code path is the one every other
+     comparison here times) and "device" (scaml_qacqf_opt_f64), in both joint_score_modes, next to Q successive suggest() calls; then
+     the stages from the same raw batches and picks -- stage 2 by both optimisers -- with the device run's rounds, evaluations per
+     start and live slots per call;
+  9. with ``--sweep``: stage 2 on the device by evals_per_call.
+
+  python tools/dev_qacqf_time.py --opt [--q Q] [--pending P] [--sweep 1,2,4,8,16] [--out FILE]
 """
 import argparse
 import os
@@ -49,6 +58,8 @@ ap.add_argument("--no-suggest", action="store_true", help="skip the suggest_batc
 ap.add_argument("--pending", type=int, default=0, help="P evaluations pending: time the pending route against the concatenated one")
 ap.add_argument("--q", type=int, default=4, help="points per batch")
 ap.add_argument("--score", action="store_true", help="time the scoring of the raw batches by the grad_pass and value_pass routes")
+ap.add_argument("--opt", action="store_true", help="time suggest_batch's stage 2 on the host (scipy) and on the device (joint_opt_mode)")
+ap.add_argument("--sweep", default="", help="with --opt: evals_per_call values of the device optimiser to compare, e.g. 1,2,4,8,16")
 args = ap.parse_args()
 
 T, N, D, n, q, B, S, REPS = 32, 512, 6, 80, args.q, 10, 128, 5
@@ -318,12 +329,105 @@ def score_comparison(P):
         report({f"  '{m}' {k}": v for k, v in stages[m].items()}, unit=1e3, name="ms")
 
 
+def opt_comparison(P, sweep):
+    """8. and 9. of the module's text."""
+    Xp_host = torch.rand(P, D, dtype=torch.float64, generator=g) if P else None
+
+    def loop(score, opt):
+        lp = ScaMLGPBOLoop(gps, dim=D, acquisition="ei", num_restarts_log_likelihood=1, seed=0, max_pending_evaluations=8, num_fantasies=16,
+                           num_mc_samples=S, joint_pending="joint", joint_score_mode=score, joint_opt_mode=opt)
+        lp.record(Xt, yt.squeeze(-1))
+        lp.model.weights = model.weights.clone()
+        lp.model.eval()
+        return lp
+
+    scores = utils._JointAcquisition.SCORE_MODES
+    loops = {(s, o): loop(s, o) for s in scores for o in bo.JOINT_OPT_MODES}
+    lp_s = loop("grad_pass", "scipy")
+
+    def batch(key):
+        lp = loops[key]
+        lp.pending = lp.pending[:0] if Xp_host is None else Xp_host.clone()
+        lp.suggest_batch(q)
+
+    def successive():
+        lp_s.pending = lp_s.pending[:0] if Xp_host is None else Xp_host.clone()
+        for _ in range(q):
+            lp_s.suggest()
+
+    say(f"-- {q} points with {P} pending, {loops[scores[0], 'scipy'].num_restarts} starts, af_max_iter {loops[scores[0], 'scipy'].af_max_iter}: "
+        f"suggest_batch({q}) with stage 2 on the host ('scipy') and on the device, against {q} successive suggest() calls (16 fantasies)")
+    variants = {f"suggest_batch({q}), '{s}', joint_opt_mode='{o}'": (lambda k=(s, o): batch(k)) for (s, o) in loops}
+    variants[f"{q} x suggest()"] = successive
+    report(interleaved(variants, warmup=1), unit=1e3, name="ms")
+    for (s, o), lp in loops.items():
+        if o == "device":
+            i = lp.last_suggest_info
+            say(f"   '{s}' device run of the last call: {i['n_eval']} rounds in {i['n_calls']} calls, evaluations per start {i['evals_per_start']}, "
+                f"status {i['status']}")
+
+    # the stages, from the same raw batches and picks: stage 2 by both optimisers, stage 3 as the 'scipy' mode runs it
+    names = ("stage 1: af(raw batches)", "stage 2: scipy L-BFGS-B", "stage 2: device", "stage 3: af(end batches) ('scipy' only)")
+    stages = {s: {k: [] for k in names} for s in scores}
+    last = {}
+
+    def staged(s):
+        lp = loops[s, "scipy"]
+        af = lp.joint_acquisition_function(q, Xp_host)
+        t = [time.perf_counter()]
+        c = torch.rand(lp.raw_samples, q, D, dtype=torch.float64, generator=lp.gen)
+        vals = af(c).detach().cpu()
+        t.append(time.perf_counter())
+        best0, picks = bo.acqf_pick_initial_conditions(vals, lp.num_restarts, lp.gen, 2.0)
+        t[-1] = time.perf_counter()
+        xs = bo.acqf_local_optimization(af, c[picks], lp.af_max_iter)
+        torch.cuda.synchronize()
+        t.append(time.perf_counter())
+        res = bo._joint_device_optimization(af, c[picks], lp.af_max_iter)
+        torch.cuda.synchronize()
+        t.append(time.perf_counter())
+        fin = af(xs).detach().cpu()
+        t.append(time.perf_counter())
+        for k, a, b in zip(stages[s], t[:-1], t[1:]):
+            stages[s][k].append(b - a)
+        last[s] = (res, float(fin.max()), float(res["f"].max()), af, c[picks])
+
+    for s in scores:
+        for _ in range(2):
+            staged(s)
+        for k in stages[s]:
+            stages[s][k].clear()
+    for _ in range(REPS):
+        for s in scores:
+            staged(s)
+    for s in scores:
+        report({f"  '{s}' {k}": v for k, v in stages[s].items()}, unit=1e3, name="ms")
+        res, best_scipy, best_dev = last[s][:3]
+        say(f"   '{s}' last repetition: best end value, scipy {best_scipy:.9f}, device {best_dev:.9f}; device: {res['n_eval']} rounds in "
+            f"{res['n_calls']} calls, live slots per call {res['live']}, evaluations per start {res['stats'][:, 1].tolist()}, "
+            f"status {res['stats'][:, 2].tolist()}")
+    if sweep:
+        af, x0 = last[scores[0]][3:]
+        max_iter = loops[scores[0], "scipy"].af_max_iter
+        say(f"-- stage 2 on the device by evals_per_call (the same starts; default {ops.QACQF_OPT_EVALS_PER_CALL})")
+        out = {}
+        report(interleaved({f"  evals_per_call {k:3d}": (lambda k=k: out.__setitem__(k, bo._joint_device_optimization(af, x0, max_iter, evals_per_call=k)))
+                            for k in sweep}), unit=1e3, name="ms")
+        for k in sweep:
+            say(f"   evals_per_call {k:3d}: {out[k]['n_eval']} rounds in {out[k]['n_calls']} calls, live slots per call {out[k]['live']}")
+
+
 def finish():
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
 
+
+if args.opt:
+    opt_comparison(args.pending, [int(v) for v in args.sweep.split(",")] if args.sweep else [])
+    finish()
+    sys.exit(0)
 
 if args.score:
     score_comparison(args.pending)
