@@ -361,9 +361,13 @@ int scaml_target_fantasy_acqf_f64(const double* Knq, const double* Z, const doub
  *   does with its abar.  jitter_used (B) or NULL: the rung that passed.  info_out (B) int32 or NULL.
  *   One workgroup per batch; the q x q work is done in LDS, the samples are dealt to the threads, every sum over the samples is formed
  *   by one thread in a fixed order: no atomics, the outputs are a pure function of the inputs (two calls agree bit for bit).
- *   Non-finite values: a query point with a NaN / infinite coordinate, or a NaN anywhere in its batch's inputs, gives NaN in that
- *   batch's value and in all q rows of its grad; other batches are not affected.  info[0] != 0 (the target's factorisation failed):
- *   every output is NaN (info_out 1).
+ *   Non-finite values: a query point with a NaN / infinite coordinate, or a NaN in anything the batch's VALUE reads (its columns of
+ *   Knq, Z, mean_q, var_q, a value column 16 j of a mate row), gives NaN in that batch's value and in all q rows of its grad -- where
+ *   it enters Sigma, the ladder fails on it (jitter NaN, info_out 1); other batches are not affected.  A NaN base sample is shared: the value and
+ *   the gradient of EVERY batch are NaN (jitter and info_out are the factor's).  A NaN that only the gradient reads -- a derivative
+ *   column 16 j + 1 + d of mu_g, var_g or any row of cov_g -- leaves value, jitter and info_out finite and gives NaN in EVERY entry of
+ *   point j's row of grad, never in some of them (a select where the row is stored: finite inputs keep their bits); the other rows
+ *   are not affected.  info[0] != 0 (the target's factorisation failed): every output is NaN (info_out 1).
  *   Limits: 1 <= q <= scaml_qacqf_max_q() = 8, 1 <= S <= scaml_qacqf_max_samples() = 512, n + q <= 96, D <= 15: SCAML_E_TOOLARGE
  *   beyond them; n < 1, Mq not a multiple of q, a NULL input or value, s_all <= 0, an unknown kind: SCAML_E_BADARG (first).  Mq == 0
  *   enqueues nothing.  No host synchronisation.

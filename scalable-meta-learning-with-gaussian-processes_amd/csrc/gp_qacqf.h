@@ -457,6 +457,7 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
     SL[j * R + a] = 2.0 * u * dk;
   }
   SA_SYNC();
+  double* gl = t + QA_PART;   // [q][D], at most 120 doubles: the chunk sums are spent
   for (int e = tid; e < q * D; e += nthr) {
     const int j = e / D, d = e - j * D;
     const size_t col = (q0 + j) * 16 + 1 + d;
@@ -470,7 +471,16 @@ SA_DEV void qa_batch(const QAcqfParams& p, double* lds, int b, int tid, int nthr
       acc = fma(U[j * R + a], p.cov_g[(size_t)a * W + col], acc);
       acc = fma(SL[j * R + a], (xjd - xad) * il2, acc);
     }
-    p.grad[(q0 + j) * D + d] = acc;
+    gl[e] = acc;
+  }
+  SA_SYNC();
+  // a NaN in ONE derivative column of mu_g / var_g / cov_g reaches one entry only, next to a finite value: every entry of that point's
+  // gradient is NaN where the results are stored, the rule of (7f) (a select: finite inputs stay bit for bit what they were)
+  for (int e = tid; e < q * D; e += nthr) {
+    const int j = e / D;
+    bool bad = false;
+    for (int d = 0; d < D; ++d) bad = bad || gl[j * D + d] != gl[j * D + d];
+    p.grad[q0 * D + e] = bad ? nan : gl[e];
   }
 }
 

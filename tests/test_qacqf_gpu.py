@@ -8,6 +8,8 @@ acquisition kernel (scaml_target_qacqf_f64, (7p)), ScaMLGP.joint_acqf, the acqui
        as tests/test_posterior_grad_gpu.py).  The reference itself is held to cond(Sigma) <= 1e4 and to a margin of 1e-6
        sqrt(max Sigma_jj) between every sample's two best entries and from the kinks (tests/_qacqf_ref.py); the seeds were picked
        on the CPU so that both hold.  Measured worst ratios: profiles/qacqf_notes.md.
+  The kernel's own arithmetic is held to an a-priori per-element fp64 bound, on planted arrays at the shape edges, by
+  tests/test_qacqf_bounds_gpu.py (tests/_qacqf_bounds.py; figures in profiles/qacqf_bounds_notes.md).
 
 Shapes: T = 3 with one pruned weight, ragged n_points (32, 20, 17) at N = 32; D in {2, 15}; q in {1, 2, 3, 8}; B in {1, 5};
 n in {1, 17}, and n = 88 with q = 8 on a T = 2, N = 96 stack (Ma + q = 96, the last row of the covariance block); S in {1, 300, 512};

@@ -9,6 +9,8 @@ ScaMLGPBOLoop(joint_pending="joint").suggest_batch.
   is held to cond(Sigma) <= 1e4 on the (q + p)-point joint and to the margin of 1e-6 sqrt(max Sigma_jj) of every sample from a tie
   and from a kink (tests/_qacqf_ref.py), every batch of every case, both codes; the seed was picked on the CPU so that both hold.
   Measured worst ratios: profiles/qacqf_pending_notes.md.
+  The kernel's own arithmetic is held to an a-priori per-element fp64 bound, on planted arrays at the shape edges, by
+  tests/test_qacqf_bounds_gpu.py (tests/_qacqf_bounds.py; figures in profiles/qacqf_bounds_notes.md).
 
 Shapes: T = 3 with one pruned weight, ragged n_points (32, 20, 17) at N = 32; D in {2, 15}; (q, p) in {(2, 1), (1, 7), (3, 5), (4, 4),
 (7, 1), (1, 1)}; B in {1, 3, 5}; n in {1, 17}, and n = 88 with (3, 5) on a T = 2, N = 96 stack (n + p + q = 96, the last row of the

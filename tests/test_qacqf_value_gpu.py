@@ -9,6 +9,8 @@ ScaMLGP.joint_acqf_value, score_mode="value_pass" of the acquisition classes and
   Against torch autograd through the ORACLE on the CPU in fp64: _close's rule, rtol 1e-4 and atol 1e-4 max|ref|.  The reference is held
   to cond(Sigma) <= 1e4 and to the tie and kink margins (tests/_qacqf_ref.py) on every batch of every case, both codes, at seed 1.
   Measured worst ratios: profiles/qacqf_value_notes.md.
+  The kernel's own arithmetic is held to an a-priori per-element fp64 bound, on planted arrays at the shape edges, by
+  tests/test_qacqf_bounds_gpu.py (tests/_qacqf_bounds.py; figures in profiles/qacqf_bounds_notes.md).
 
 Shapes, by where the packing and the extra tile can go wrong (bps = 16 // q batches per strip):
   (32, 20, 17) D 2  n 17 B 6  q 3 p 0   bps 5, one padding column, the second strip holds one batch; N = 32 with nas = NB: the extra image
