@@ -34,6 +34,13 @@ int scaml_debug_coop_far(int on);
  * would apply, anything else the choice by shape.  Starts from SCAML_TARGET_FIT_NO_MFMA (set: 1).  Returns the previous mode. */
 int scaml_debug_target_fit_path(int mode);
 
+/* scaml_posterior_linv_grad_grouped_f64 / _own_f64 ((5e), (5e')): 1 launch the instance with ordered sums -- the one the rounds of
+ * scaml_studies_fantasy_acqf_opt_f64 run, whose mu / var do not depend on the order in which the waves finish -- under that entry
+ * point's limit (SCAML_E_TOOLARGE where the strip and the waves' shares do not fit the LDS together); anything else the default
+ * instance.  The value-mode passes (5f) / (5f') have no such instance and are not affected.  Starts from
+ * SCAML_GROUPED_ORDERED_SUMS (set: 1).  Returns the previous value. */
+int scaml_debug_grouped_ordered_sums(int mode);
+
 /* scaml_gp_fit_fused_f64 has a switch without a function: the environment variable SCAML_FIT_NO_FULL.  Set (not empty, not "0"),
  * every call takes the generic instance of its size class, never the full-tile instance of the N <= 256 class (N == 256, no
  * n_points, L -- when stored -- on a 16-byte boundary).  Unlike the switches above it is read at EVERY launch, so a process runs

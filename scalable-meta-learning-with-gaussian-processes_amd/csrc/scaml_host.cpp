@@ -247,6 +247,7 @@ struct DevSwitches {
   std::atomic<int> blocked_fit_last{0};   // which one the last call took (1 / 2)
   std::atomic<int> coop_far{getenv("SCAML_COOP_FAR") != nullptr};   // A/B / tests: write-through payload stores even when a task's workgroups share an XCD
   std::atomic<int> target_fit_path{getenv("SCAML_TARGET_FIT_NO_MFMA") ? 1 : 0};   // 0 by shape, 1 column-by-column elimination only
+  std::atomic<int> grouped_ordered{getenv("SCAML_GROUPED_ORDERED_SUMS") ? 1 : 0};   // tests: 1 (5e) / (5e') launch the instance with ordered sums
 } g_dev;
 constexpr auto kRelaxed = std::memory_order_relaxed;
 }  // namespace
@@ -263,6 +264,7 @@ int scaml_debug_blocked_fit_path(int mode) {
 }
 int scaml_debug_target_fit_path(int mode) { return g_dev.target_fit_path.exchange(mode == 1 ? 1 : 0, kRelaxed); }
 int scaml_debug_force_two_launch_grad(int mode) { return g_dev.grad_path.exchange(mode == 1 ? 1 : (mode == 2 ? 2 : 0), kRelaxed); }
+int scaml_debug_grouped_ordered_sums(int mode) { return g_dev.grouped_ordered.exchange(mode == 1 ? 1 : 0, kRelaxed); }
 int scaml_debug_set_stamp_buffer(long long* buf) {
   Module* m = ready();
   if (!m) return SCAML_E_LAUNCH;
@@ -987,9 +989,12 @@ int grouped_launch(Module& m, scaml::PosteriorGroupedParams& p, int kind, bool v
 }
 int grouped_run(scaml::PosteriorGroupedParams p, int kind, bool value, bool own, void* stream) {
   if (const int rc = grouped_check(p, kind, value, own)) return rc;
+  // scaml_debug_grouped_ordered_sums: (5e) / (5e') through the instance with ordered sums, under (7l)'s LDS limit (its static shares)
+  const bool ordered = !value && g_dev.grouped_ordered.load(kRelaxed) == 1;
+  if (ordered && scaml::posterior_linv_lds_doubles(p.base.N, p.base.D) * sizeof(double) > kLdsLimit - kOrderedSumsLds) return SCAML_E_TOOLARGE;
   if (p.base.T == 0 || p.base.M == 0 || p.ga.G == 0) return SCAML_OK;
   Module* m = ready();
-  return m ? grouped_launch(*m, p, kind, value, stream) : SCAML_E_LAUNCH;
+  return m ? grouped_launch(*m, p, kind, value, stream, ordered) : SCAML_E_LAUNCH;
 }
 
 // The studies' acquisition block (csrc/gp_studies_acqf.h).  `strips`: (7i), the value layout, a workgroup per strip of 16 candidates

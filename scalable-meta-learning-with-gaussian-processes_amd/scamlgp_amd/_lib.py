@@ -169,6 +169,7 @@ SIGNATURES = {
     "scaml_debug_blocked_fit_path": (_i, [_i]),
     "scaml_debug_coop_far": (_i, [_i]),
     "scaml_debug_force_two_launch_grad": (_i, [_i]),
+    "scaml_debug_grouped_ordered_sums": (_i, [_i]),
     "scaml_debug_set_stamp_buffer": (_i, [c_void_p]),
 }
 

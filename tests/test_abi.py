@@ -29,7 +29,7 @@ def test_exported_functions_are_exactly_the_two_headers():
     """No more and no fewer: every scaml_* function the library exports is declared in scaml_gp.h or scaml_gp_debug.h.
     (The only other scaml_* exports are the two data objects of the embedded code object, which the build emits.)"""
     debug = _declared_symbols("scaml_gp_debug.h")
-    assert len(debug) == 5 and all(name.startswith("scaml_debug_") for name in debug)
+    assert len(debug) == 6 and all(name.startswith("scaml_debug_") for name in debug)
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     exported = {(kind, name) for _, kind, name in (line.split() for line in out.splitlines() if len(line.split()) == 3)
                 if name.startswith("scaml_")}
