@@ -4,7 +4,11 @@ the input sets that module lists: the shape edges of the three phases, both fami
 tails, info, the refusals, the non-finite-query rule, the F = 1 cross-check against the finish and the target gradient, and the real
 pipeline.  scaml_target_acqf_batched_f64's value is held to the transform bound alone, from its own mu_out / var_out.  Every output
 buffer holds a sentinel and one guard row more than the call may write.  Each test prints the largest error / bound and bound /
-scale seen so far (profiles/fantasy_bounds_notes.md records them)."""
+scale seen so far (profiles/fantasy_bounds_notes.md records them).
+
+The batched acquisition's check here sees only the transform from the kernel's own mu_out / var_out.  The full bound of that kernel
+body -- the task sums, the solve, the posterior and the gradient of all four entry points of sa_block -- lives in
+tests/_studies_bounds.py and is held by tests/test_studies_bounds.py / tests/test_studies_bounds_gpu.py."""
 import numpy as np
 import pytest
 import torch

@@ -12,7 +12,11 @@ from torch autograd through the oracle by at most 2.1e-14.
 Stacks: the c5r-shaped one of tests/test_studies_gpu.py (Hartmann-6, T = 2, N = 64, Matern-5/2) with n = (1, 16, 17, 40); the
 ragged golden stack (T = 4, N = 48, per-task counts 48 / 17 / 1 / 33) with an RBF target kernel, where a study's n is bounded by the
 stack's N = 48 (the GRAD pass keeps the covariance tiles in the task's LDS strip: Ma <= N); and n = 96, the kernels' limit, on a
-Hartmann-6 stack of N = 96 with an RBF target kernel."""
+Hartmann-6 stack of N = 96 with an RBF target kernel.
+
+The 1e-10 here is a max-norm tolerance between two sets of kernels.  The per-element fp64 bound of the kernel body itself
+(sa_block of csrc/gp_studies_acqf.h: value, grad, mu_out, var_out against a long-double reference) lives in
+tests/_studies_bounds.py and is held by tests/test_studies_bounds.py / tests/test_studies_bounds_gpu.py."""
 import os
 
 import numpy as np
