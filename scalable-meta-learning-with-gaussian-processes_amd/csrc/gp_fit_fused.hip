@@ -119,6 +119,18 @@ __device__ __forceinline__ void store16(double* q, d2_t v) {
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(q), "v"(v) : "memory");
 }
 
+// The same with the address split into a wave-uniform base and a per-lane 32-bit byte offset (full-tile build: the lane's
+// offset inside a tile is worked out once, the tile's own offset is a scalar add), both row groups of a tile in one
+// statement: rows 0..7 at `off`, rows 8..15 at `off8`.
+// s_nop 4: a vector-memory instruction must not read an SGPR within five wait states of a VALU write to it, and the compiler,
+// which cannot see into asm, puts none in front of it -- where its register allocation keeps `base` in the lanes of a VGPR it
+// restores the pair with v_readlane right here (the diagnostic build did, and stored through a stale address).
+__device__ __forceinline__ void store16x2_zero(double* base, unsigned off, unsigned off8) {
+  const d2_t z = {0.0, 0.0};
+  asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %2, %3 sc1\n\tglobal_store_dwordx4 %1, %2, %3 sc1\n\ts_nop 1"
+               ::"v"(off), "v"(off8), "v"(z), "s"(base) : "memory");
+}
+
 __device__ __forceinline__ int opaque_s(int v) {
   asm volatile("" : "+s"(v));  // keeps per-slot address arithmetic from being hoisted out of the panel loop
   return v;
@@ -411,7 +423,10 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
   double* LT = CR + 2 * 256;
   constexpr int REGION_A = 3 * PANEL + (NB + 2) * 16 * PP + 4 * 256;
   // (during the build: xsT, then up to 24 tile images written by the panel wave, see PANEL_BUILDS)
-  const int XROWS = ((p.D + 3) & ~3) + 4;   // staged point stack: D rounded up to the MFMA k-step + 4 tail rows
+  // (full-tile instance: from a wave-uniform D, as below -- in the jitter retries the LDS carve derived from it otherwise sits in
+  //  VGPRs from here to the tail, one of them in scratch)
+  const int Dx = FULL ? __builtin_amdgcn_readfirstlane(p.D) : p.D;
+  const int XROWS = ((Dx + 3) & ~3) + 4;   // staged point stack: D rounded up to the MFMA k-step + 4 tail rows
   const int buildA = XROWS * NP + ((WU == 7 && NB == 16) ? 24 * 256 : 0);
   const int regionA = (buildA > REGION_A) ? buildA : REGION_A;
   // Early chain: while xsT and the tile images end in front of WAll, the panel wave's outputs of steps 0 and 1 (W_0, W_1, LT) and
@@ -698,6 +713,56 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
       dst[lane] = kt[0]; dst[64 + lane] = kt[1]; dst[128 + lane] = kt[2]; dst[192 + lane] = kt[3];
       sync_arrive(cnt, lane);
     };
+    // Full-tile build: the lane's share of every address of the build, once per attempt.  A tile adds a wave-uniform byte
+    // offset: 128 * block inside a row of xsT (NP doubles per row), 2048 * image inside KT, the tile's origin inside L.
+    //   fbA  xsT + lq * NP + lc          operand rows of both sides; + D4 * NP: the tail row of the A side
+    //   fbB  xsT + (lq ^ 1) * NP + lc    + D4 * NP: the tail row of the B side
+    //   fbZ  (lane >> 3) * LD + 2 * (lane & 7): this lane's 16 bytes of a tile of L, rows 0..7 (rows 8..15: + 8 * LD)
+    // (opaque: kept in registers, not worked out again per tile)
+    unsigned fbA = 0, fbB = 0, fbZ = 0;
+    double* Lz = Lg;   // the task's L as the scalar base of the zero stores (made wave-uniform by hand: the jitter retries hold it in VGPRs)
+    if constexpr (FULL) {
+      Lz = (double*)(((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)((size_t)Lg >> 32)) << 32) |
+                     (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(size_t)Lg));
+      fbA = lds_addr(xsT) + (unsigned)(lq * NP + lc) * 8u;
+      fbB = lds_addr(xsT) + (unsigned)((lq ^ 1) * NP + lc) * 8u;
+      fbZ = (unsigned)((lane >> 3) * LD + 2 * (lane & 7)) * 8u;
+      asm volatile("" : "+v"(fbA), "+v"(fbB), "+v"(fbZ));
+    }
+    // tile_dist of the full-tile build: oa, ob = byte offsets 128 * kj, 128 * (kj + kr) of the two sides' points
+    auto tile_dist_full = [&](unsigned oa, unsigned ob) -> d4_t {
+      const unsigned tailo = (unsigned)D4 * (NP * 8u);
+      const lds_f64_t* pa = lds_ptr(fbA + oa);
+      const lds_f64_t* pb = lds_ptr(fbA + ob);
+      const lds_f64_t* qa = lds_ptr(fbA + (oa + tailo));
+      const lds_f64_t* qb = lds_ptr(fbB + (ob + tailo));
+      d4_t d2 = {0.0, 0.0, 0.0, 0.0};
+      const double ta = qa[0], tb = qb[0];
+      double ca = pa[0], cb = pb[0];
+      for (int m = 4; m < D4; m += 4) {
+        const double na = pa[m * NP], nb = pb[m * NP];
+        d2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ca, cb, d2, 0, 0, 1);
+        ca = na; cb = nb;
+      }
+      d2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ca, cb, d2, 0, 0, 1);
+      d2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ta, tb, d2, 0, 0, 1);
+      return d2;
+    };
+    // zero_mirror of the full-tile build: the mirror of tile (kj + kr, kj) starts 16 kj rows down and ob bytes into the row
+    auto zero_mirror_full = [&](int kj, unsigned ob) {
+      const unsigned o = fbZ + ((unsigned)(16 * kj) * (LD * 8u) + ob);
+      store16x2_zero(Lz, o, o + 8u * LD * 8u);
+    };
+    // One place decides between the two: the full-tile instance takes the addresses from the lane parts above, every other
+    // instance works them out per tile as before.
+    auto tile_dist_of = [&](int kj, int kr) -> d4_t {
+      if constexpr (FULL) return tile_dist_full(128u * (unsigned)kj, 128u * (unsigned)(kj + kr));
+      else return tile_dist(kj, kr);
+    };
+    auto zero_mirror_of = [&](int kj, int kr) {
+      if constexpr (FULL) zero_mirror_full(kj, 128u * (unsigned)(kj + kr));
+      else zero_mirror(kj, kj + kr);
+    };
     if (!is_panel) {
       int kj = 0, kr = wave;  // column / row-in-column of the current slot's tile
       // (issuing the distances of the next tile ahead of the evaluation of this one was tried: no gain, the
@@ -707,14 +772,14 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
         while (kj < NB && kr >= NB - kj) { kr -= NB - kj; ++kj; }                                  \
         if (kj < NB) {                                                                             \
           double kt[4];                                                                            \
-          tile_eval(kj, kr, tile_dist(kj, kr), kt);                                                \
+          tile_eval(kj, kr, tile_dist_of(kj, kr), kt);                                             \
           TILE_SET(r0, r1, r2, r3, r4, r5, r6, r7, kt[0], kt[1], kt[2], kt[3]);                    \
           if (early) {                                                                             \
             if (S == 0 && wave == 0) park_early(DG, cntE, kt);                   /* D_0 */         \
             if (NB > 1 && S == 1 / WU && wave == 1 % WU) park_early(CR + 256, cntE + 1, kt);   /* R_1 = tile 1 */  \
             if (NB > 1 && S == NB / WU && wave == NB % WU) park_early(DG + 256, cntE + 1, kt); /* D_1 = tile off(1) */ \
           }                                                                                        \
-          if (zfill && kr != 0) zero_mirror(kj, kj + kr);                                          \
+          if (zfill && kr != 0) zero_mirror_of(kj, kr);                                            \
           kr += WU;                                                                                \
         }                                                                                          \
       }
@@ -724,6 +789,12 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
       // The panel wave: its tile images, and between two of them (early chain) step 0 as soon as D_0 is parked, step 1 as
       // soon as R_1 and D_1 are; what is left of the two steps after the last image waits for its tiles here.
       constexpr int NIMG = PANEL_BUILDS ? 6 * 4 : 0;
+      // an image's place, KT + 256 idx + lane -- full-tile instance: the lane's part once, opaque like the ones above
+      unsigned fbK = 0;
+      if constexpr (FULL) {
+        fbK = lds_addr(KT) + (unsigned)lane * 8u;
+        asm volatile("" : "+v"(fbK));
+      }
       int jdone = early ? 0 : JE, next = 0;
       while (next < NIMG || jdone < JE) {
         if (jdone < JE) {
@@ -745,10 +816,15 @@ __device__ __forceinline__ int gp_fit_attempt(const FitParams& p, const double j
         int kj = 0, kr = t;
         while (kr >= NB - kj) { kr -= NB - kj; ++kj; }
         double kt[4];
-        tile_eval(kj, kr, tile_dist(kj, kr), kt);
-        double* img = KT + idx * 256 + lane;
-        img[0] = kt[0]; img[64] = kt[1]; img[128] = kt[2]; img[192] = kt[3];
-        if (zfill && kr != 0) zero_mirror(kj, kj + kr);
+        tile_eval(kj, kr, tile_dist_of(kj, kr), kt);
+        if constexpr (FULL) {
+          lds_f64_t* img = lds_ptr(fbK + (unsigned)idx * 2048u);
+          img[0] = kt[0]; img[64] = kt[1]; img[128] = kt[2]; img[192] = kt[3];
+        } else {
+          double* img = KT + idx * 256 + lane;
+          img[0] = kt[0]; img[64] = kt[1]; img[128] = kt[2]; img[192] = kt[3];
+        }
+        if (zfill && kr != 0) zero_mirror_of(kj, kr);
       }
     }
 #ifdef SCAML_STAMPS
